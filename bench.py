@@ -9,11 +9,14 @@ stream; all K renders and K gathers happen inside the timed region.  Rays are *u
 shadow + reflection + refraction casts, counted by the kernels' counting variant in an untimed pass (the count is
 deterministic).  Total work is fixed as N grows -> "strong" scaling.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload config2|config3|...] [--inflight F] [--no-cpu-baseline] [--no-pmc]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload config2|config3|...] [--inflight F] [--dump-outputs DIR]
+                  [--full [--no-cpu-baseline] [--no-pmc] [--no-one-shot] [--extra-workloads W,...]]
 
 `--gpus N` with N > 1 starts the N ranks itself (a child `python -m torch.distributed.run --nproc-per-node N bench.py ...`,
 started before this process touches a GPU) unless it already runs under torch.distributed.run (WORLD_SIZE set), as the
-driver launches it.  Rank 0 prints ONE JSON line:
+driver launches it.  A plain run sets up, warms up, times the K steps and prints the headline; `--dump-outputs DIR` writes
+the frame of the last timed step to DIR/rgb.npy first (float64; over 64 MB a seeded pixel sample, see dump_outputs).  Everything
+below `ms_per_step` is measured with `--full` only.  Rank 0 prints ONE JSON line:
 
   value / ms_per_step   whole-job unique rays of K frames / wall time of the timed region (barrier + synchronize on both sides)
   roofline              bound "hbm": algorithmic bytes per frame that go through the memory system (device.algorithmic_bytes:
@@ -393,9 +396,31 @@ class Runtime:
         return DeviceRenderer(self.backend, world, cam, device=self.local_rank, _cpu_standin=self.standin)
 
 
+DUMP_BYTES = 64 * 10 ** 6     # --dump-outputs budget, all files together
+
+
+def dump_outputs(d, frame):
+    """--dump-outputs: the frame the timed path delivered in its last step -> d/rgb.npy ((vsize, hsize, 3) float64, the layout
+    rtc_render hands a caller).  A frame larger than the budget (4K: 199 MB) is sampled instead: a fixed, seeded set of pixels ->
+    d/rgb_sample.npy ((n, 3) float64) and their row-major pixel indices -> d/rgb_sample_pixel.npy (float64, exact below 2^53)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    if frame.nbytes <= DUMP_BYTES - 4096:
+        np.save(os.path.join(d, "rgb.npy"), frame)
+        return
+    flat = frame.reshape(-1, 3)
+    n = min(flat.shape[0], (DUMP_BYTES // 2) // (flat.itemsize * 4))
+    idx = np.sort(np.random.default_rng(12345).choice(flat.shape[0], size=n, replace=False))
+    np.save(os.path.join(d, "rgb_sample.npy"), flat[idx])
+    np.save(os.path.join(d, "rgb_sample_pixel.npy"), idx.astype(np.float64))
+
+
 # ---------------------------------------------------------------------------------------------------------------------
-def measure(args, rtm, dist, workload, fuel, steps, warmup, F, rank, world_size, rehearse, want_pmc, want_cpu, partition="bands"):
-    """One workload on this process group.  Returns the dict of measurements (rank 0: complete; other ranks: partial)."""
+def measure(args, rtm, dist, workload, fuel, steps, warmup, F, rank, world_size, rehearse, want_pmc, want_cpu, partition="bands", full=True,
+            keep_frame=False):
+    """One workload on this process group.  Returns the dict of measurements (rank 0: complete; other ranks: partial).  full=False:
+    the timed frames and what the headline needs (unique rays per frame, the device path), nothing measured after them.
+    keep_frame: rank 0's result holds the frame its timed path delivered in the last step (host float64, (vsize, hsize, 3))."""
     import numpy as np
     from raytracer_challenge_amd.device import algorithmic_bytes
     from raytracer_challenge_amd.parallel import FrameGatherer, FrameRoundGatherer
@@ -477,6 +502,16 @@ def measure(args, rtm, dist, workload, fuel, steps, warmup, F, rank, world_size,
     if world_size > 1:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el.item())
+    frame = None
+    if keep_frame and rank == 0 and steps > 0:
+        # N = 1: the tile of the last step; N > 1: the last frame gathered to rank 0 (bands: de-interleaved; frames: rank 0's frame)
+        img = fg.image if world_size > 1 else fg.tiles[(steps - 1) % F][: H * V * 3].view(V, H, 3)
+        frame = img.detach().cpu().numpy().copy()
+    res = {"workload": workload, "desc": desc, "H": H, "V": V, "fuel": fuel, "steps": steps, "warmup": warmup, "elapsed": elapsed, "rays_total": rays_total,
+           "path": path, "counters": cst, "n_lights": nw.n_lights, "primitives": nw.primitive_count, "info": dr.info(), "F": F,
+           "partition": "frames" if frames_mode else "bands", "ingest": ingest, "frame": frame}
+    if not full:
+        return res
 
     # untimed: the frame's own device time, one frame at a time (what rocprofv3's per-kernel durations add up to): HIP events on
     # the scene's stream around n_seq sequential launches
@@ -489,10 +524,7 @@ def measure(args, rtm, dist, workload, fuel, steps, warmup, F, rank, world_size,
     dr.check()
     seq_ms = dr.elapsed_ms(2, 3) / n_seq
     timed_tile = fg.tiles[0].clone()
-
-    res = {"workload": workload, "desc": desc, "H": H, "V": V, "fuel": fuel, "steps": steps, "warmup": warmup, "elapsed": elapsed, "rays_total": rays_total,
-           "seq_ms": seq_ms, "path": path, "counters": cst, "n_lights": nw.n_lights, "primitives": nw.primitive_count, "info": dr.info(), "F": F,
-           "partition": "frames" if frames_mode else "bands", "ingest": ingest}
+    res["seq_ms"] = seq_ms
     if rank != 0 or args.pmc_child:
         return res
     alg = algorithmic_bytes(cst, path["path"], nw.primitive_count, lds_tables=dr.info().get("wavefront_lds_bytes_per_block", 0) > 0)
@@ -578,6 +610,12 @@ def main():
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--one-shot-child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--no-one-shot", action="store_true", help="skip the one-shot (fresh process, one render) measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: sequential device time + roofline, PMC passes, host-pixel calls, CPU baseline "
+                         "+ parity, one-shot children, further workloads, the band partition beside the frame partition (without it: the timed "
+                         "steps and the headline line only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the frame the timed path computed in its last step to DIR/rgb.npy (float64; a seeded pixel sample if over 64 MB)")
     args = ap.parse_args()
     if args.fuel is None:
         args.fuel = default_fuel(args.workload)
@@ -616,7 +654,7 @@ def main():
         args.no_pmc = True
 
     if args.pmc_child:  # profiled by the parent's rocprofv3: the frames of the workload, nothing else
-        measure(args, rtm, dist, args.workload, args.fuel, args.steps, args.warmup, 1, 0, 1, False, False, False)
+        measure(args, rtm, dist, args.workload, args.fuel, args.steps, args.warmup, 1, 0, 1, False, False, False, full=True)
         return
 
     F = max(1, args.inflight)
@@ -626,9 +664,12 @@ def main():
     if partition == "frames" and args.steps < world_size:
         partition = "bands"   # fewer frames than GPUs: nothing to deal out
     m = measure(args, rtm, dist, args.workload, args.fuel, args.steps, args.warmup, F, rank, world_size, rehearse,
-                want_pmc=not args.no_pmc, want_cpu=not args.no_cpu_baseline, partition=partition)
+                want_pmc=not args.no_pmc, want_cpu=not args.no_cpu_baseline, partition=partition, full=args.full,
+                keep_frame=bool(args.dump_outputs))
+    if rank == 0 and args.dump_outputs and m["frame"] is not None:
+        dump_outputs(args.dump_outputs, m["frame"])
     band = None
-    if world_size > 1 and m["partition"] == "frames":
+    if args.full and world_size > 1 and m["partition"] == "frames":
         # the north-star partition beside it: every frame cut into bands over the ranks (what a single frame's latency gets from N GPUs)
         band = measure(args, rtm, dist, args.workload, args.fuel, max(2, min(args.steps, 60)), min(args.warmup, 3), F, rank, world_size, rehearse,
                        want_pmc=False, want_cpu=False, partition="bands")
@@ -650,10 +691,9 @@ def main():
                        "unique_rays_per_frame": m["rays_total"], "rays_per_pixel": m["rays_total"] / (H * V),
                        "ray_count": "rays of the reference's de-duplicated ray tree (device counters = the oracle's); on the one-kernel path a shadow ray "
                                     "towards a light behind the surface is counted and answered without a traversal (DESIGN.md 4.13)"},
-            "roofline": m["roofline"],
             "accelerator": dict(m["info"], ingest=m["ingest"]),
         }
-        for k in ("valu", "parity", "cpu_baseline", "ms_per_step_incl_d2h", "host_pixels"):
+        for k in ("roofline", "valu", "parity", "cpu_baseline", "ms_per_step_incl_d2h", "host_pixels"):
             if k in m:
                 out[k] = m[k]
         if band is not None:
@@ -661,9 +701,9 @@ def main():
                                      "ms_per_step": band["elapsed"] / band["steps"] * 1e3, "parity": band.get("parity"),
                                      "note": "the same job with every frame cut into 8-row bands over the ranks (one gather per frame): what ONE frame's latency gets "
                                              "from N GPUs; its per-rank share is latency-bound (DESIGN.md section 6)"}
-        if world_size == 1 and not args.no_one_shot and not standin:
+        if args.full and world_size == 1 and not args.no_one_shot and not standin:
             out["one_shot"] = one_shot_measure()
-        if world_size == 1:
+        if args.full and world_size == 1:
             for name in [w for w in args.extra_workloads.split(",") if w and w != args.workload]:
                 fuel2 = default_fuel(name)
                 e = measure(args, rtm, dist, name, fuel2, args.steps, args.warmup, F, 0, 1, False,

@@ -4,7 +4,7 @@ mkdir -p gpurun_out
 WL=${1:-config2}; shift
 : > gpurun_out/ab.txt
 for so in raytracer_challenge_amd/csrc/variants/*.so; do
-  RTC_AMD_LIB=$PWD/$so timeout -k 10 150 python3 bench.py --workload $WL --steps 60 --warmup 3 --no-cpu-baseline --no-pmc --extra-workloads "" "$@" 2>/dev/null | python3 -c "
+  RTC_AMD_LIB=$PWD/$so timeout -k 10 150 python3 bench.py --full --workload $WL --steps 60 --warmup 3 --no-cpu-baseline --no-pmc --extra-workloads "" "$@" 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -3,7 +3,7 @@
 VAR=$1; VALS=$2; WL=${3:-config2}; shift; shift; shift
 mkdir -p gpurun_out
 for v in $VALS; do
-  env $VAR=$v timeout -k 10 200 python3 bench.py --workload $WL --steps 60 --warmup 3 --no-cpu-baseline --no-pmc --extra-workloads "" "$@" 2>/dev/null | python3 -c "
+  env $VAR=$v timeout -k 10 200 python3 bench.py --full --workload $WL --steps 60 --warmup 3 --no-cpu-baseline --no-pmc --extra-workloads "" "$@" 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

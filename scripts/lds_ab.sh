@@ -3,7 +3,7 @@
 for k in 4 1; do
   for v in 1 0; do
     for wl in ${WLS:-config2 config3}; do
-      RTC_KERNEL=$k RTC_WF_LDS=$v RTC_K1_LDS=$v timeout -k 10 150 python3 bench.py --workload $wl --steps 60 --warmup 3 --inflight 1 --no-cpu-baseline --no-pmc --extra-workloads "" 2>/dev/null | python3 -c "
+      RTC_KERNEL=$k RTC_WF_LDS=$v RTC_K1_LDS=$v timeout -k 10 150 python3 bench.py --full --workload $wl --steps 60 --warmup 3 --inflight 1 --no-cpu-baseline --no-pmc --extra-workloads "" 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,5 +1,5 @@
 for so in raytracer_challenge_amd/csrc/variants/*.so; do
-  RTC_AMD_LIB=$PWD/$so timeout -k 10 300 python3 bench.py --steps 50 --inflight 1 --no-cpu-baseline --extra-workloads "" 2>/dev/null | python3 -c "
+  RTC_AMD_LIB=$PWD/$so timeout -k 10 300 python3 bench.py --full --steps 50 --inflight 1 --no-cpu-baseline --extra-workloads "" 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

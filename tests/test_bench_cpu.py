@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -24,7 +26,7 @@ def run_bench(*argv, env_extra=None):
 
 def test_bench_gpus_2_launches_its_own_ranks():
     """`python bench.py --gpus 2` with WORLD_SIZE unset: two ranks are started by bench.py itself, rank 0 prints the one line."""
-    j = run_bench("--gpus", "2", "--workload", "smoke", "--steps", "3", "--warmup", "1", "--no-cpu-baseline")
+    j = run_bench("--gpus", "2", "--workload", "smoke", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline")
     assert j["n_gpus"] == 2 and j["steps"] == 3 and j["warmup"] == 1
     # the N-rank line proves its frame too: gathered rows == the whole frame rendered by one rank
     assert j["parity"]["gathered_frame_equals_single_gpu_frame"] is True and j["parity"]["pixels"] == 64 * 36
@@ -33,19 +35,19 @@ def test_bench_gpus_2_launches_its_own_ranks():
     assert "STAND-IN" in j["data"]
     assert j["config"]["partition"].startswith("bands") and "band_partition" not in j     # 3 frames < 2 N: every frame cut into bands
     # enough frames queued (>= 2 N): whole frames round-robin over the ranks, the band partition measured beside it
-    f = run_bench("--gpus", "2", "--workload", "smoke", "--steps", "5", "--warmup", "1", "--no-cpu-baseline")
+    f = run_bench("--gpus", "2", "--workload", "smoke", "--steps", "5", "--warmup", "1", "--full", "--no-cpu-baseline")
     assert f["config"]["partition"].startswith("frames") and f["steps"] == 5 and f["n_gpus"] == 2
     assert f["parity"]["gathered_frame_equals_single_gpu_frame"] is True
     assert f["band_partition"]["parity"]["gathered_frame_equals_single_gpu_frame"] is True and f["band_partition"]["value"] > 0
     assert f["config"]["unique_rays_per_frame"] == j["config"]["unique_rays_per_frame"]
-    one = run_bench("--gpus", "1", "--workload", "smoke", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--extra-workloads", "")
+    one = run_bench("--gpus", "1", "--workload", "smoke", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--extra-workloads", "")
     # same frame, same unique rays, whatever the partition
     assert one["config"]["unique_rays_per_frame"] == j["config"]["unique_rays_per_frame"]
     assert one["config"]["frames_in_flight"] == j["config"]["frames_in_flight"]
 
 
 def test_bench_line_contract_fields_single_rank():
-    j = run_bench("--workload", "smoke", "--steps", "2", "--warmup", "1", "--extra-workloads", "")
+    j = run_bench("--workload", "smoke", "--steps", "2", "--warmup", "1", "--full", "--extra-workloads", "")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
               "roofline", "cpu_baseline", "parity", "ms_per_step_incl_d2h"):
         assert k in j, k
@@ -63,3 +65,42 @@ def test_bench_line_contract_fields_single_rank():
     assert j["cpu_baseline"]["kind"] == "port" and j["cpu_baseline"]["cores"] >= 1
     p = j["parity"]
     assert p["primary_hit_mismatches"] == 0 and p["max_abs_drgb"] <= 1e-5 and p["pixels"] > 0 and p["timed_frame_equals_checked_frame"]
+
+
+def test_plain_run_is_the_headline_and_dumps_the_last_frame(tmp_path):
+    """Without --full: the contract keys and nothing measured after the timed steps; --dump-outputs writes the frame of the last timed
+    step, the same bits as a whole-frame render of the workload, at N = 1 and gathered from N = 2 ranks."""
+    from emu_lib import emu
+    import bench
+    one, two = tmp_path / "n1", tmp_path / "n2"
+    j = run_bench("--workload", "smoke", "--steps", "4", "--warmup", "0", "--dump-outputs", str(one))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "config"):
+        assert k in j, k
+    assert j["steps"] == 4 and j["warmup"] == 0 and j["value"] > 0 and j["ms_per_step"] > 0 and j["dtype"] == "f64" and j["higher_is_better"] is True
+    for k in ("roofline", "valu", "parity", "cpu_baseline", "host_pixels", "ms_per_step_incl_d2h", "one_shot", "config3", "band_partition"):
+        assert k not in j, k
+    assert "secondary" not in j["config"]
+    cam, world, _ = bench.make_workload("smoke")
+    want, _ = emu().render(emu().build_world(world), cam, bench.default_fuel("smoke"), want_hits=False)
+    got = np.load(one / "rgb.npy")
+    assert got.dtype == np.float64 and got.shape == (cam.vsize, cam.hsize, 3)
+    assert np.array_equal(got.reshape(-1, 3), want)
+    f = run_bench("--gpus", "2", "--workload", "smoke", "--steps", "5", "--warmup", "1", "--dump-outputs", str(two))
+    assert f["n_gpus"] == 2 and f["steps"] == 5 and "parity" not in f and "band_partition" not in f
+    assert np.array_equal(np.load(two / "rgb.npy"), got)
+
+
+def test_dump_outputs_samples_a_frame_over_the_budget(tmp_path, monkeypatch):
+    """A frame larger than the budget (4K f64: 199 MB of 64 MB) is written as a fixed seeded pixel sample, the same pixels on every
+    run (here at a budget of 1 MB)."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 10 ** 6)
+    frame = np.arange(360 * 640 * 3, dtype=np.float64).reshape(360, 640, 3)
+    bench.dump_outputs(str(tmp_path / "a"), frame)
+    bench.dump_outputs(str(tmp_path / "b"), frame)
+    assert not (tmp_path / "a" / "rgb.npy").exists()
+    px, rgb = np.load(tmp_path / "a" / "rgb_sample_pixel.npy"), np.load(tmp_path / "a" / "rgb_sample.npy")
+    assert px.dtype == np.float64 and rgb.dtype == np.float64 and rgb.shape == (px.size, 3) and px.size > 0
+    assert np.array_equal(rgb, frame.reshape(-1, 3)[px.astype(np.int64)])
+    assert np.array_equal(px, np.load(tmp_path / "b" / "rgb_sample_pixel.npy"))
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in os.listdir(tmp_path / "a")) <= bench.DUMP_BYTES
