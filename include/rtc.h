@@ -31,7 +31,8 @@ enum {
                               pattern with more than RTC_MAX_PATTERN_DEPTH colour frames on one path (below); a launch
                               whose CSG intersection slab would exceed RTC_CSG_MAX_BYTES (16 GiB: a subtree with more
                               than 32 possible intersections gets that many rows per thread); a material whose
-                              refractive_index is not in (1e-70, 1e70); more than 64 lights; fuel above 16 */
+                              refractive_index is not in (1e-70, 1e70); more than 64 lights (an area light is one); an area
+                              light with more than 16 steps along a side; fuel above 16 */
   RTC_ERR_DEVICE = 3,      /* HIP failure / no device                                                   */
   RTC_ERR_NAN = 4          /* a NaN intersection t reached a sort the reference's comparator would run on: a list
                               of two or more entries of one World::intersect or CSG child list; the reference
@@ -94,6 +95,34 @@ typedef struct rtc_light {
   double intensity[3];
   double origin[3];
 } rtc_light;
+
+/* Either kind of light, for rtc_scene_create_ex / rtc_multi_create_ex.  The reference knows point lights only; the area light is
+ * the rectangular light of the book's first bonus chapter ("Rendering soft shadows"), defined here as follows.
+ *   RTC_LIGHT_POINT: intensity, corner = the origin; the other fields are ignored.  Exactly an rtc_light.
+ *   RTC_LIGHT_AREA:  N = usteps * vsteps samples.  Cells uc = uvec / usteps, vc = vvec / vsteps (componentwise, f64).  Sample
+ *     k = v * usteps + u (v outer, u inner) lies at p_k = (corner + uc * (u + ju)) + vc * (v + jv), componentwise, one rounding per
+ *     operation.  Without RTC_LIGHT_JITTER ju = jv = 0.5 (the cell centres); with it they come from rtc_area_jitter
+ *     (csrc/device_scene.h): h = m(m(m(m(light) ^ bits(x)) ^ bits(y)) ^ bits(z)) over the light's index in the list and the
+ *     shading point's over_point (x, y, z) -- the shadow rays' origin --, ju = (m(h ^ 2k) >> 11) * 2^-53,
+ *     jv = (m(h ^ (2k + 1)) >> 11) * 2^-53, m = SplitMix64's finaliser.  Deterministic: no state, nothing of the pixel or launch.
+ *     Each sample adds exactly the reference's point-light term (World::is_shadowed + Shape::lighting, src/world.rs:26-82,
+ *     src/shape.rs:429-462) for a light at p_k of intensity intensity / N (one f64 division), the N terms in k order: for the
+ *     surface colour an area light is N point lights.  The reflected and refracted colour of a hit is added once per LIGHT
+ *     (src/world.rs:58-79), and an area light is one light: once, not once per sample.
+ * Limits: usteps == 0 or vsteps == 0 is RTC_ERR_INVALID; usteps > 16 or vsteps > 16 is RTC_ERR_UNSUPPORTED.  An area light counts as
+ * one of the 64 lights a scene may have.  rtc_stats.rays_shadow counts one ray per sample. */
+enum { RTC_LIGHT_POINT = 0, RTC_LIGHT_AREA = 1 };
+enum { RTC_LIGHT_JITTER = 1u };
+#define RTC_AREA_MAX_STEPS 16
+typedef struct rtc_light_ex {
+  int32_t kind;     /* RTC_LIGHT_* */
+  uint32_t usteps, vsteps;
+  uint32_t flags;   /* RTC_LIGHT_JITTER */
+  double intensity[3];
+  double corner[3]; /* point lights: the origin */
+  double uvec[3];
+  double vvec[3];
+} rtc_light_ex;
 
 /* The Element tree (src/shape.rs:31-34, :181-185) in DFS pre-order.  A group node carries the world-space
  * bounding box the reference computed for it (Element::composite + propagate_inverses; NaN/inf included,
@@ -166,6 +195,11 @@ int rtc_device_count(void);
 /* Flatten-once upload: validates, builds the results-neutral accelerator (BVH over each group's bounded
  * primitive children) and copies SoA buffers to HBM on `device`. */
 int rtc_scene_create(const rtc_scene_desc* desc, int device, rtc_scene** out);
+/* Same, with the scene's lights given as n rtc_light_ex records (point and area lights in any order; the order is the scene's light
+ * order) in place of desc->lights: desc->n_lights must be 0 (RTC_ERR_INVALID otherwise).  A scene whose list holds point lights only
+ * is exactly the rtc_scene_create scene (same kernels, same bits); one with an area light renders with kernel instantiations of its
+ * own on both device paths.  Every render entry point takes either. */
+int rtc_scene_create_ex(const rtc_scene_desc* desc, const rtc_light_ex* lights, uint32_t n_lights, int device, rtc_scene** out);
 void rtc_scene_destroy(rtc_scene*);
 /* Size in bytes of the scene's device buffers (accelerator included). */
 uint64_t rtc_scene_device_bytes(const rtc_scene*);
@@ -219,6 +253,8 @@ uint64_t rtc_band_rows_owned(uint64_t vsize, uint32_t band_rows, uint32_t band_f
  * One process per GPU + RCCL (bench.py, raytracer_challenge_amd/parallel.py) is the other way to use N GPUs; both partition alike. */
 typedef struct rtc_multi rtc_multi;
 int rtc_multi_create(const rtc_scene_desc* desc, const int* devices, int n_devices, rtc_multi** out);
+/* Same with the lights of rtc_scene_create_ex. */
+int rtc_multi_create_ex(const rtc_scene_desc* desc, const rtc_light_ex* lights, uint32_t n_lights, const int* devices, int n_devices, rtc_multi** out);
 void rtc_multi_destroy(rtc_multi*);
 int rtc_multi_device_count(const rtc_multi*);
 /* Rows per band of the partition (default 8; 1 = single rows interleaved).  Waits for queued frames. */

@@ -78,6 +78,11 @@ void rtw_element_release(rtw_element*);
 
 rtw_world* rtw_world_create(void);
 int rtw_world_add_light(rtw_world*, const double intensity[3], const double origin[3]); /* src/light.rs:5-8 */
+/* An area light (include/rtc.h rtc_light_ex; not in the reference): usteps x vsteps samples over the rectangle corner + [0, uvec] x
+ * [0, vvec], jittered when jitter != 0.  Lights keep the order they were added in, point and area alike.  Product library only (the
+ * oracle restates the reference, which has none); rendering such a world needs rtc_scene_create_ex. */
+int rtw_world_add_area_light(rtw_world*, const double intensity[3], const double corner[3], const double uvec[3], uint32_t usteps,
+                             const double vvec[3], uint32_t vsteps, int jitter);
 int rtw_world_add_element(rtw_world*, rtw_element*);                                    /* consumes */
 uint64_t rtw_world_primitive_count(const rtw_world*);
 void rtw_world_release(rtw_world*);

@@ -13,7 +13,7 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from .scene import (FUEL, GEOMETRY, GROUP_KINDS, JITTER_KINDS, MIXTURE_KINDS, Camera, Element, Material, Pattern, World)
+from .scene import (FUEL, GEOMETRY, GROUP_KINDS, JITTER_KINDS, MIXTURE_KINDS, AreaLight, Camera, Element, Material, Pattern, World)
 
 HIT_DTYPE = np.dtype([("t", "<f8"), ("prim", "<i4"), ("push_idx", "<i4")])
 
@@ -97,6 +97,11 @@ class Backend:
             fn = getattr(lib, name)  # AttributeError = missing export: fail loudly
             fn.restype, fn.argtypes = res, args
         self.name = lib.rtw_backend().decode()
+        # area lights: the product library's extension of rtw.h (the oracle restates the reference, which has none)
+        self.has_area_lights = hasattr(lib, "rtw_world_add_area_light")
+        if self.has_area_lights:
+            lib.rtw_world_add_area_light.restype = i
+            lib.rtw_world_add_area_light.argtypes = [vp, dp, dp, dp, C.c_uint32, dp, C.c_uint32, i]
 
     # ---- errors
     def _err(self) -> str:
@@ -166,6 +171,13 @@ class Backend:
         try:
             for l in world.lights:
                 inten = (C.c_double * 3)(l.intensity.r, l.intensity.g, l.intensity.b)
+                if isinstance(l, AreaLight):
+                    if not self.has_area_lights:
+                        raise RtwError("area lights need librtc_amd.so (backend %r has no rtw_world_add_area_light)" % self.name)
+                    v3 = lambda v: (C.c_double * 3)(*v[:3])  # noqa: E731
+                    self._check(lib.rtw_world_add_area_light(w, inten, v3(l.corner), v3(l.uvec), int(l.usteps), v3(l.vvec), int(l.vsteps),
+                                                             1 if l.jitter else 0), "add_area_light")
+                    continue
                 org = (C.c_double * 3)(*l.origin[:3])
                 self._check(lib.rtw_world_add_light(w, inten, org), "add_light")
             for e in world.elements:

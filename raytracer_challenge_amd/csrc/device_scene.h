@@ -155,7 +155,7 @@ struct DScene {
   const double* mat;         // n_materials x 8 {ambient, diffuse, specular, shininess, reflective, transparency, refractive_index, -}
   const int32_t* mat_pattern;
   const DPat* pats;
-  const double* lights;      // n_lights x {intensity rgb, origin xyz}
+  const double* lights;      // n_lights x {intensity rgb, origin xyz}; scenes with an area light (has_area): n_lights x RTC_ALIGHT doubles
   int32_t n_ops, n_prims, n_lights;
   int32_t all_cast_shadow;   // 1: every primitive casts a shadow -> shadow rays may stop at any hit
   int32_t has_mesh;          // 1: the program contains an OP_MESH
@@ -189,6 +189,8 @@ struct DScene {
   // array lengths, for the traversal guards (a bad index retires the lane and raises DStats.guard instead of faulting)
   int32_t bvh_stack;  // entries each lane's traversal stack needs for this scene's trees (LDS is sized from it at launch)
   int32_t n_bvh, n_items, n_mtri, n_quirk, n_qitem, n_qcell, n_groups, n_qgrids;
+  int32_t has_area;   // 1: some light is an area light: `lights` holds RTC_ALIGHT doubles per light and the area kernels render the scene
+  int32_t pad_area;
 };
 
 // Which pixels a launch covers.
@@ -249,6 +251,26 @@ static inline RTC_HD unsigned long long rtc_hit_hash_base(unsigned long long t_b
 static inline RTC_HD unsigned long long rtc_hit_hash(unsigned long long base, int depth, int kind) {
   return rtc_mix64(base ^ ((unsigned long long)(((unsigned)depth << 8) | (unsigned)kind) + 1ull) * 0xD6E8FEB86659FD93ull);
 }
+
+// Jittered area-light samples (include/rtc.h rtc_light_ex): a counter-based hash of the light's index and the shading point's
+// over_point, so both device paths (and a test that knows the hit point) draw the same offsets.  m = SplitMix64's finaliser.
+static inline RTC_HD unsigned long long rtc_splitmix64(unsigned long long z) {
+  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull; z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+  return z ^ (z >> 31);
+}
+static inline RTC_HD unsigned long long rtc_area_hash(int light, double x, double y, double z) {
+  unsigned long long bx, by, bz;
+  __builtin_memcpy(&bx, &x, 8); __builtin_memcpy(&by, &y, 8); __builtin_memcpy(&bz, &z, 8);
+  return rtc_splitmix64(rtc_splitmix64(rtc_splitmix64(rtc_splitmix64((unsigned long long)(uint32_t)light) ^ bx) ^ by) ^ bz);
+}
+// offset in [0, 1) of draw j (2k: ju of sample k, 2k + 1: jv): 53 bits, exact in f64
+static inline RTC_HD double rtc_area_jitter(unsigned long long h, unsigned j) {
+  return (double)(rtc_splitmix64(h ^ (unsigned long long)j) >> 11) * 0x1.0p-53;
+}
+// Light records of scenes with an area light (DScene.has_area; the area kernels read them): RTC_ALIGHT doubles per light,
+// {intensity (area: / N) rgb, corner xyz, uc xyz, vc xyz, usteps, vsteps, kind (1 area, 0 point), area: jitter (0 / 1), point: its light
+// grid (index among the scene's point lights; scene_build.hpp build_arrays_ex)}.  Point-light-only scenes keep {intensity, origin}.
+#define RTC_ALIGHT 16
 
 // Wavefront path (rtc_device.hpp / rtc_kernels.hip, wf_* kernels): rays of one bounce level live in a queue; per level a traversal launch
 // (closest hits of the level + shadow rays and lighting of the previous level) and a shading launch (hit state, pattern

@@ -1414,6 +1414,79 @@ __device__ __forceinline__ Ray slot_ray(const DPixelMap& pm, const DCamera& cam,
 
 }  // namespace
 
+// Area lights (include/rtc.h rtc_light_ex; DScene.has_area: RTC_ALIGHT doubles per light): World::shade_hit's per-light terms
+// (src/world.rs:50-82, src/shape.rs:429-462) for every light of the scene, an area light's samples in k order, each exactly a point
+// light at p_k of intensity / N.  Shadow ray and Phong terms are fused per sample, so the wavefront shadow role keeps no per-light
+// shadow bits and nothing but the running sums lives across the traversals beyond what the point-light code keeps.  Point lights
+// keep their light grids (Trav.light = the grid their record names; scene_build.hpp builds grids for the point lights only); sample
+// rays walk the BVH (-1).
+// BEHIND: the one-kernel path's light_is_behind shortcut, per sample (its ambient-only term has the bits of the general case).
+// The one-kernel and the wavefront area kernels both run this function: same bits on both paths.
+template <int FEAT, bool KOPS, bool LDSC, bool BEHIND>
+__device__ __forceinline__ void shade_lights_area(const DScene& S, double px, double py, double pz, double nx, double ny, double nz, double ex, double ey,
+                                                  double ez, double cr, double cg, double cb, double ambient, double diffuse, double specular, double shininess,
+                                                  Counters& C, int* stack, int stride, unsigned& n_shadow, const LdsScene& Ls, double& sr, double& sg,
+                                                  double& sb) {
+  for (int l = 0; l < S.n_lights; l++) {
+    const double* LG = S.lights + RTC_ALIGHT * l;
+    const bool area = LG[14] != 0.0, jitter = area && LG[15] != 0.0;
+    const int us = (int)LG[12];
+    const int ns = area ? us * (int)LG[13] : 1;
+    const unsigned long long h = jitter ? rtc_area_hash(l, px, py, pz) : 0ull;
+#pragma unroll 1
+    for (int k = 0; k < ns; k++) {
+      double lx = LG[3], ly = LG[4], lz = LG[5];
+      if (area) {  // p_k = (corner + uc (u + ju)) + vc (v + jv), one rounding per operation
+        const int u = k % us, v = k / us;
+        const double ju = jitter ? rtc_area_jitter(h, 2u * (unsigned)k) : 0.5, jv = jitter ? rtc_area_jitter(h, 2u * (unsigned)k + 1u) : 0.5;
+        const double fu = (double)u + ju, fv = (double)v + jv;
+        lx = (LG[3] + LG[6] * fu) + LG[9] * fv;
+        ly = (LG[4] + LG[7] * fu) + LG[10] * fv;
+        lz = (LG[5] + LG[8] * fu) + LG[11] * fv;
+      }
+      const double vx = lx - px, vy = ly - py, vz = lz - pz;
+      n_shadow++;
+      if (BEHIND && light_is_behind(S, vx, vy, vz, nx, ny, nz)) {  // ambient term only, in the expression of the general case
+        const double lr = (cr * LG[0]) * ambient, lg = (cg * LG[1]) * ambient, lb = (cb * LG[2]) * ambient;
+        sr += (lr + 0.0) + 0.0; sg += (lg + 0.0) + 0.0; sb += (lb + 0.0) + 0.0;
+        continue;
+      }
+      const double distance = sqrt(vx * vx + vy * vy + vz * vz);
+      Ray sray;
+      sray.ox = px; sray.oy = py; sray.oz = pz;
+      sray.dx = vx / distance; sray.dy = vy / distance; sray.dz = vz / distance;
+      Trav Sh;
+      reset_closest(Sh, S.all_cast_shadow ? MODE_SHADOW_ANY : MODE_SHADOW_CLOSEST);
+      if (S.all_cast_shadow) { Sh.thi = distance; Sh.unordered = 1; }
+      Sh.light = area ? -1 : (int)LG[15]; Sh.c1_t = distance;
+      if (S.all_cast_shadow) traverse<FEAT, KOPS, MODE_SHADOW_ANY, LDSC>(S, sray, Sh, C, stack, stride, Ls);
+      else traverse<FEAT, KOPS, MODE_SHADOW_CLOSEST, LDSC>(S, sray, Sh, C, stack, stride, Ls);
+      nan_commit(Sh, C);
+      bool shadowed;
+      if (S.all_cast_shadow) shadowed = Sh.shadowed != 0;
+      else shadowed = (Sh.best_prim != 0x7fffffff) && (S.prims[Sh.best_prim].flags & 1u) && (Sh.best_t < distance);
+      const double er = cr * LG[0], eg = cg * LG[1], eb = cb * LG[2];  // effective_color
+      const double lr = er * ambient, lg = eg * ambient, lb = eb * ambient;
+      // light vector: (p_k - point).normalize() -- the shadow ray's direction
+      const double ldn = sray.dx * nx + sray.dy * ny + sray.dz * nz;
+      double dr = 0.0, dg = 0.0, db = 0.0, pr = 0.0, pg = 0.0, pb = 0.0;
+      if (!shadowed && ldn >= 0.0) {
+        dr = er * diffuse * ldn; dg = eg * diffuse * ldn; db = eb * diffuse * ldn;
+        // reflect = (-light).reflect(normal)
+        const double mlx = -sray.dx, mly = -sray.dy, mlz = -sray.dz;
+        const double d2 = 2.0 * (mlx * nx + mly * ny + mlz * nz);
+        const double rfx = mlx - nx * d2, rfy = mly - ny * d2, rfz = mlz - nz * d2;
+        const double rde = rfx * ex + rfy * ey + rfz * ez;
+        if (rde > 0.0) {
+          const double f = specular_factor(rde, shininess, specular);
+          pr = LG[0] * specular * f; pg = LG[1] * specular * f; pb = LG[2] * specular * f;
+        }
+      }
+      sr += (lr + dr) + pr; sg += (lg + dg) + pg; sb += (lb + db) + pb;
+    }
+  }
+}
+
 // One-kernel path: one lane walks one pixel's whole ray tree (closest pass, shading, shadow passes, pending children); the wave
 // ends with its slowest pixel.  (A persistent variant whose lanes took the next work id from a global counter was measured at
 // -4 % / +14 % and removed in round 2.)
@@ -1425,7 +1498,8 @@ __device__ __forceinline__ Ray slot_ray(const DPixelMap& pm, const DCamera& cam,
 // LEAN: for scenes whose patterns are all Plain colours and whose materials never both reflect and refract (DScene.all_plain,
 // no_glass_mirror: the teapot scenes) — no pattern-tree walk is compiled in and the pending-ray stack has one (unused) entry: 80 B of
 // scratch per lane instead of 1 648 (config 3 -3 %, config 4 -4 %: profiles/r3_partition_probe.txt).
-template <bool COUNT, int FEAT, bool KOPS, int WAVES = 0, bool LEAN = false>
+// AREA: scenes with an area light (DScene.has_area): the lights are shaded by shade_lights_area.  Point-light scenes never run it.
+template <bool COUNT, int FEAT, bool KOPS, int WAVES = 0, bool LEAN = false, bool AREA = false>
 __global__ void __launch_bounds__(RTC_BLOCK, WAVES ? WAVES : ((FEAT >= 2 && RTC_WAVES_PER_SIMD < 2) ? 2 : RTC_WAVES_PER_SIMD)) rtc_trace_kernel(DScene S, DCamera cam, DPixelMap pm, int fuel0, double* __restrict__ rgb, double* __restrict__ hit_t,
                                                         int* __restrict__ hit_prim, int* __restrict__ hit_k, DStats* __restrict__ stats) {
   RTC_LDS_STACK(lds_stack);
@@ -1524,6 +1598,10 @@ __global__ void __launch_bounds__(RTC_BLOCK, WAVES ? WAVES : ((FEAT >= 2 && RTC_
         DIAG_REGION(2);
         // World::shade_hit (src/world.rs:50-82): per light, shadow test + Phong (src/shape.rs:429-462)
         double sr = 0.0, sg = 0.0, sb = 0.0;
+        if constexpr (AREA) {
+          shade_lights_area<FEAT, KOPS, false, true>(S, st.px, st.py, st.pz, st.nx, st.ny, st.nz, st.ex, st.ey, st.ez, cr, cg, cb, ambient, diffuse, specular,
+                                                     shininess, C, stack, stride, n_shadow, LdsScene{}, sr, sg, sb);
+        } else
         for (int l = 0; l < S.n_lights; l++) {
           DIAG_LOOP(5);
           const double* LG = S.lights + 6 * l;
@@ -1834,6 +1912,32 @@ __device__ __forceinline__ void wf_shadow_rec(const DScene& S, const DCamera& ca
   DIAG_SPAN_END(5);
 }
 
+// The shadow role for scenes with an area light (wf_ts<..., AREA>): the record's whole state is loaded first and every sample's shadow
+// ray is followed by its Phong terms (shade_lights_area), where wf_shadow_rec keeps one shadow bit per light.
+template <int FEAT, bool KOPS, bool LDSC>
+__device__ __forceinline__ void wf_shadow_rec_area(const DScene& S, const DCamera& cam, const DPixelMap& pm, const DWave& W, const WorkMap& wm, int level, unsigned s,
+                                                   int* stack, int stride, Counters& C, unsigned& n_shadow, const LdsScene& L) {
+  const size_t cap = W.cap;
+  double* cb = W.contrib + (size_t)level * 3 * cap;
+  const double* r = W.sr;
+  const int node = W.sr_node[s];
+  double ex, ey, ez, weight;
+  if (level == 0) {
+    uint64_t q = 0;
+    (void)work_to_slot(wm, (unsigned)node, q);
+    const Ray pr = slot_ray(pm, cam, q);
+    ex = -pr.dx; ey = -pr.dy; ez = -pr.dz; weight = 1.0;
+  } else {
+    const double* rq = W.rq[level & 1];
+    ex = -rq[3 * cap + node]; ey = -rq[4 * cap + node]; ez = -rq[5 * cap + node]; weight = rq[6 * cap + node];
+  }
+  const double* M = S.mat + 8 * W.sr_mat[s];
+  double sr = 0.0, sg = 0.0, sb = 0.0;
+  shade_lights_area<FEAT, KOPS, LDSC, false>(S, r[s], r[cap + s], r[2 * cap + s], r[3 * cap + s], r[4 * cap + s], r[5 * cap + s], ex, ey, ez, r[6 * cap + s],
+                                             r[7 * cap + s], r[8 * cap + s], M[0], M[1], M[2], M[3], C, stack, stride, n_shadow, L, sr, sg, sb);
+  cb[node] = weight * sr; cb[cap + node] = weight * sg; cb[2 * cap + node] = weight * sb;
+}
+
 // Traversal kernel of the wavefront path: the closest-hit pass of level `tl` and the shadow + lighting pass of level `sl`
 // (either may be -1) as ONE launch, so the two independent passes fill the chip together.  Work is handed out in chunks of
 // RTC_WF_CHUNK items from per-XCD counters (block b belongs to XCD b % 8 and takes chunks b % 8, b % 8 + 8, ...): trace
@@ -1848,7 +1952,8 @@ __device__ __forceinline__ void wf_shadow_rec(const DScene& S, const DCamera& ca
 #ifndef RTC_LDS_BLOCK
 #define RTC_LDS_BLOCK (256 * RTC_WF_TS_WAVES)  // LDSC kernels: one block per CU with all the waves the register budget allows
 #endif
-template <bool COUNT, int FEAT, bool KOPS, bool LDSC = false>
+// AREA: scenes with an area light (DScene.has_area): the shadow role is wf_shadow_rec_area.
+template <bool COUNT, int FEAT, bool KOPS, bool LDSC = false, bool AREA = false>
 __global__ void __launch_bounds__(LDSC ? RTC_LDS_BLOCK : RTC_BLOCK, FEAT <= RTC_WF_TS_WAVES_MAXFEAT ? RTC_WF_TS_WAVES : 2) wf_ts(DScene S, DCamera cam, DPixelMap pm, DWave W, int tl, int sl, unsigned n0, int slot, int fuel_left,
                                                                      double* __restrict__ hit_t, int* __restrict__ hit_prim, int* __restrict__ hit_k, DStats* __restrict__ stats) {
   RTC_LDS_STACK(lds_stack);
@@ -1899,7 +2004,8 @@ __global__ void __launch_bounds__(LDSC ? RTC_LDS_BLOCK : RTC_BLOCK, FEAT <= RTC_
         const unsigned s = base + o + (unsigned)lane;
         if (s < ns) {
           DIAG_SPAN_BEGIN();
-          wf_shadow_rec<FEAT, KOPS, LDSC>(S, cam, pm, W, wm, sl, s, stack, stride, C, n_shadow, L);
+          if constexpr (AREA) wf_shadow_rec_area<FEAT, KOPS, LDSC>(S, cam, pm, W, wm, sl, s, stack, stride, C, n_shadow, L);
+          else wf_shadow_rec<FEAT, KOPS, LDSC>(S, cam, pm, W, wm, sl, s, stack, stride, C, n_shadow, L);
           DIAG_SPAN_END(7);
         }
       }

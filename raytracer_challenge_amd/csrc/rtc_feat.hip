@@ -8,6 +8,8 @@
 //   4         3: + CSG                                             memory
 //   5         2: per-primitive gates                               kernel arguments (round 3: grouped scenes on the fast path — scalar op
 //                                                                  fetches, LDS-resident tables, three waves per SIMD)
+//   6         3, area lights (AREA: DScene.has_area)               memory (serves every scene with an area light)
+//   7         1, area lights                                       kernel arguments (area-light scenes variants 0 and 1 would serve)
 // Exports rtc_launch_trace_v<N> / rtc_launch_wf_ts_v<N> for the dispatchers in rtc_kernels.hip.
 #if defined(RTC_VARIANT) && RTC_VARIANT == 5 && !defined(RTC_WF_TS_WAVES_MAXFEAT)
 #define RTC_WF_TS_WAVES_MAXFEAT 2   // this variant's traversal kernel at three waves per SIMD like variants 0 and 1
@@ -18,7 +20,7 @@
 #endif
 
 #ifndef RTC_VARIANT
-#error "compile with -DRTC_VARIANT=0..4"
+#error "compile with -DRTC_VARIANT=0..7"
 #endif
 #ifndef RTC_CAT
 #define RTC_CAT2(a, b) a##b
@@ -26,6 +28,12 @@
 #endif
 #undef RTC_V_FEAT
 #undef RTC_V_KOPS
+#undef RTC_V_AREA
+#if RTC_VARIANT >= 6
+#define RTC_V_AREA 1
+#else
+#define RTC_V_AREA 0
+#endif
 #if RTC_VARIANT == 0
 #define RTC_V_FEAT 0
 #define RTC_V_KOPS true
@@ -38,9 +46,12 @@
 #elif RTC_VARIANT == 3
 #define RTC_V_FEAT 2
 #define RTC_V_KOPS false
-#elif RTC_VARIANT == 4
+#elif RTC_VARIANT == 4 || RTC_VARIANT == 6
 #define RTC_V_FEAT 3
 #define RTC_V_KOPS false
+#elif RTC_VARIANT == 7
+#define RTC_V_FEAT 1
+#define RTC_V_KOPS true
 #else
 #define RTC_V_FEAT 2
 #define RTC_V_KOPS true
@@ -54,6 +65,12 @@
 
 void RTC_CAT(rtc_launch_trace_v, RTC_VARIANT)(bool count, int waves, unsigned grid, hipStream_t stream, const DScene& S, const DCamera& cam, const DPixelMap& pm, int fuel, double* rgb,
                                               double* hit_t, int* hit_prim, int* hit_k, DStats* stats) {
+#if RTC_V_AREA
+  // area-light scenes: one build per counting mode (no 3-wave or lean build)
+  (void)waves;
+  if (count) hipLaunchKernelGGL((rtc_trace_kernel<true, RTC_V_FEAT, RTC_V_KOPS, 0, false, true>), dim3(grid), dim3(RTC_BLOCK), rtc_stack_bytes(S), stream, S, cam, pm, fuel, rgb, hit_t, hit_prim, hit_k, stats);
+  else hipLaunchKernelGGL((rtc_trace_kernel<false, RTC_V_FEAT, RTC_V_KOPS, 0, false, true>), dim3(grid), dim3(RTC_BLOCK), rtc_stack_bytes(S), stream, S, cam, pm, fuel, rgb, hit_t, hit_prim, hit_k, stats);
+#else
 #if RTC_VARIANT == 1 || RTC_VARIANT == 2
   // mesh scenes larger than the L2s: the 3-waves-per-SIMD build (see rtc_trace_kernel)
   if (waves == 3 && !count) {
@@ -70,12 +87,18 @@ void RTC_CAT(rtc_launch_trace_v, RTC_VARIANT)(bool count, int waves, unsigned gr
 #endif
   if (count) hipLaunchKernelGGL((rtc_trace_kernel<true, RTC_V_FEAT, RTC_V_KOPS>), dim3(grid), dim3(RTC_BLOCK), rtc_stack_bytes(S), stream, S, cam, pm, fuel, rgb, hit_t, hit_prim, hit_k, stats);
   else hipLaunchKernelGGL((rtc_trace_kernel<false, RTC_V_FEAT, RTC_V_KOPS>), dim3(grid), dim3(RTC_BLOCK), rtc_stack_bytes(S), stream, S, cam, pm, fuel, rgb, hit_t, hit_prim, hit_k, stats);
+#endif
 }
 
 void RTC_CAT(rtc_launch_wf_ts_v, RTC_VARIANT)(bool count, unsigned grid, hipStream_t stream, const DScene& S, const DCamera& cam, const DPixelMap& pm, const DWave& W, int tl, int sl,
                                               unsigned n0, int slot, int fuel_left, double* hit_t, int* hit_prim, int* hit_k, DStats* stats) {
+#if RTC_V_AREA
+  if (count) hipLaunchKernelGGL((wf_ts<true, RTC_V_FEAT, RTC_V_KOPS, false, true>), dim3(grid), dim3(RTC_BLOCK), rtc_stack_bytes(S), stream, S, cam, pm, W, tl, sl, n0, slot, fuel_left, hit_t, hit_prim, hit_k, stats);
+  else hipLaunchKernelGGL((wf_ts<false, RTC_V_FEAT, RTC_V_KOPS, false, true>), dim3(grid), dim3(RTC_BLOCK), rtc_stack_bytes(S), stream, S, cam, pm, W, tl, sl, n0, slot, fuel_left, hit_t, hit_prim, hit_k, stats);
+#else
   if (count) hipLaunchKernelGGL((wf_ts<true, RTC_V_FEAT, RTC_V_KOPS>), dim3(grid), dim3(RTC_BLOCK), rtc_stack_bytes(S), stream, S, cam, pm, W, tl, sl, n0, slot, fuel_left, hit_t, hit_prim, hit_k, stats);
   else hipLaunchKernelGGL((wf_ts<false, RTC_V_FEAT, RTC_V_KOPS>), dim3(grid), dim3(RTC_BLOCK), rtc_stack_bytes(S), stream, S, cam, pm, W, tl, sl, n0, slot, fuel_left, hit_t, hit_prim, hit_k, stats);
+#endif
 }
 
 #ifndef RTC_EMU
@@ -118,7 +141,7 @@ bool RTC_CAT(rtc_launch_wf_ts_lds_v, RTC_VARIANT)(bool count, unsigned grid, uns
 // resident waves per CU of this variant's traversal kernel (the persistent grid of the wavefront path)
 int RTC_CAT(rtc_wf_ts_blocks_per_cu_v, RTC_VARIANT)(unsigned lds_bytes) {
   int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, wf_ts<false, RTC_V_FEAT, RTC_V_KOPS>, RTC_BLOCK, lds_bytes) != hipSuccess || nb <= 0) nb = 8;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, wf_ts<false, RTC_V_FEAT, RTC_V_KOPS, false, (bool)RTC_V_AREA>, RTC_BLOCK, lds_bytes) != hipSuccess || nb <= 0) nb = 8;
   return nb;
 }
 #endif

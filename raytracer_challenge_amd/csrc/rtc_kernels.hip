@@ -15,6 +15,14 @@
   bool rtc_launch_wf_ts_lds_v##N(bool count, unsigned grid, unsigned lds_bytes, hipStream_t stream, const DScene& S, const DCamera& cam, const DPixelMap& pm,   \
                                  const DWave& W, int tl, int sl, unsigned n0, int slot, int fuel_left, double* hit_t, int* hit_prim, int* hit_k, DStats* stats);
 RTC_VARIANT_DECL(0) RTC_VARIANT_DECL(1) RTC_VARIANT_DECL(2) RTC_VARIANT_DECL(3) RTC_VARIANT_DECL(4) RTC_VARIANT_DECL(5)
+#ifndef RTC_EMU
+RTC_VARIANT_DECL(6) RTC_VARIANT_DECL(7)  // area-light scenes (the CPU emulator has no entry point that creates one)
+#define RTC_AREA_CASES(call)   \
+  case 6: call(6); break;      \
+  case 7: call(7); break;
+#else
+#define RTC_AREA_CASES(call)
+#endif
 #undef RTC_VARIANT_DECL
 #ifdef RTC_EMU
 // the CPU emulator (tests/cpu_emu) compiles everything as one translation unit
@@ -41,6 +49,8 @@ RTC_VARIANT_DECL(0) RTC_VARIANT_DECL(1) RTC_VARIANT_DECL(2) RTC_VARIANT_DECL(3) 
 // kernel variant a scene needs (rtc_feat.hip): its feature level (rtc_device.hpp, visit_prim) and where its program lives
 static int rtc_variant(const DScene& S) {
   const int feat = S.has_csg ? 3 : (S.has_groups == 2 ? 2 : (S.has_groups ? 1 : 0));
+  // scenes with an area light: the AREA builds of the kernel-argument variants 0 / 1, or of the most general one (4) for the rest
+  if (S.has_area) return (feat <= 1 && S.n_kops > 0) ? 7 : 6;
   if (feat <= 1 && S.n_kops > 0) return feat;
   if (feat == 2 && S.n_kops > 0) return 5;
   return feat <= 1 ? 2 : feat + 1;
@@ -230,6 +240,9 @@ static void launch_wf_ts(int v, bool count, unsigned grid, hipStream_t stream, c
     case 2: rtc_launch_wf_ts_v2(count, grid, stream, S, cam, pm, W, tl, sl, n0, slot, fuel_left, hit_t, hit_prim, hit_k, stats); break;
     case 3: rtc_launch_wf_ts_v3(count, grid, stream, S, cam, pm, W, tl, sl, n0, slot, fuel_left, hit_t, hit_prim, hit_k, stats); break;
     case 5: rtc_launch_wf_ts_v5(count, grid, stream, S, cam, pm, W, tl, sl, n0, slot, fuel_left, hit_t, hit_prim, hit_k, stats); break;
+#define RTC_CALL(N) rtc_launch_wf_ts_v##N(count, grid, stream, S, cam, pm, W, tl, sl, n0, slot, fuel_left, hit_t, hit_prim, hit_k, stats)
+    RTC_AREA_CASES(RTC_CALL)
+#undef RTC_CALL
     default: rtc_launch_wf_ts_v4(count, grid, stream, S, cam, pm, W, tl, sl, n0, slot, fuel_left, hit_t, hit_prim, hit_k, stats); break;
   }
 }
@@ -261,6 +274,9 @@ unsigned rtc_wavefront_grid(const DScene& S, int n_cu) {
     case 2: per_cu = rtc_wf_ts_blocks_per_cu_v2(lds); break;
     case 3: per_cu = rtc_wf_ts_blocks_per_cu_v3(lds); break;
     case 5: per_cu = rtc_wf_ts_blocks_per_cu_v5(lds); break;
+#define RTC_CALL(N) per_cu = rtc_wf_ts_blocks_per_cu_v##N(lds)
+    RTC_AREA_CASES(RTC_CALL)
+#undef RTC_CALL
     default: per_cu = rtc_wf_ts_blocks_per_cu_v4(lds); break;
   }
   return (unsigned)std::max(1, n_cu * per_cu);
@@ -386,6 +402,9 @@ void rtc_launch_trace(const DScene& S, const DCamera& cam, const DPixelMap& pm, 
     case 2: rtc_launch_trace_v2(count, waves, grid, stream, S, cam, pm, fuel, rgb, hit_t, hit_prim, hit_k, stats); break;
     case 3: rtc_launch_trace_v3(count, waves, grid, stream, S, cam, pm, fuel, rgb, hit_t, hit_prim, hit_k, stats); break;
     case 5: rtc_launch_trace_v5(count, waves, grid, stream, S, cam, pm, fuel, rgb, hit_t, hit_prim, hit_k, stats); break;
+#define RTC_CALL(N) rtc_launch_trace_v##N(count, waves, grid, stream, S, cam, pm, fuel, rgb, hit_t, hit_prim, hit_k, stats)
+    RTC_AREA_CASES(RTC_CALL)
+#undef RTC_CALL
     default: rtc_launch_trace_v4(count, waves, grid, stream, S, cam, pm, fuel, rgb, hit_t, hit_prim, hit_k, stats); break;
   }
 }

@@ -453,7 +453,11 @@ int rtc_device_count(void) {
   return n;
 }
 
-int rtc_scene_create(const rtc_scene_desc* desc, int device, rtc_scene** out) {
+}  // extern "C"
+
+namespace {
+// rtc_scene_create (ex == false) and rtc_scene_create_ex (ex == true: the lights are `lx`, desc->lights must be empty)
+int scene_create(const rtc_scene_desc* desc, bool ex, const rtc_light_ex* lx, uint32_t n_lx, int device, rtc_scene** out) {
   if (!desc || !out) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
   *out = nullptr;
   int ndev = 0;
@@ -469,7 +473,8 @@ int rtc_scene_create(const rtc_scene_desc* desc, int device, rtc_scene** out) {
   const char* dbe = std::getenv("RTC_DEVICE_BVH");
   const bool device_bvh = !(dbe && dbe[0] == '0');
   const size_t device_min = (dbe && dbe[0] == '1') ? 4096 : 100000;
-  int rc = rtb::build_arrays(*desc, &H, &err, device_bvh ? rtc_bvh_build_device : nullptr, device_min);
+  int rc = ex ? rtb::build_arrays_ex(*desc, lx, n_lx, &H, &err, device_bvh ? rtc_bvh_build_device : nullptr, device_min)
+              : rtb::build_arrays(*desc, &H, &err, device_bvh ? rtc_bvh_build_device : nullptr, device_min);
   if (rc != RTC_OK) return rtc_fail(rc, err);
   const bool timing = std::getenv("RTC_TIMING") != nullptr;
   const auto t_up0 = std::chrono::steady_clock::now();
@@ -526,6 +531,7 @@ int rtc_scene_create(const rtc_scene_desc* desc, int device, rtc_scene** out) {
     d.kqgrid = hv.kqgrid;
     d.n_bvh = hv.n_bvh; d.n_items = hv.n_items; d.n_mtri = hv.n_mtri; d.n_quirk = hv.n_quirk;
     d.n_qitem = hv.n_qitem; d.n_qcell = hv.n_qcell; d.n_groups = hv.n_groups; d.n_qgrids = hv.n_qgrids;
+    d.has_area = hv.has_area;
   }
   s->n_prims_total = desc->n_prims;
   for (uint32_t i = 0; i < desc->n_prims; i++) {
@@ -574,6 +580,14 @@ int rtc_scene_create(const rtc_scene_desc* desc, int device, rtc_scene** out) {
   }
   *out = s.release();
   return RTC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rtc_scene_create(const rtc_scene_desc* desc, int device, rtc_scene** out) { return scene_create(desc, false, nullptr, 0, device, out); }
+int rtc_scene_create_ex(const rtc_scene_desc* desc, const rtc_light_ex* lights, uint32_t n_lights, int device, rtc_scene** out) {
+  return scene_create(desc, true, lights, n_lights, device, out);
 }
 
 void rtc_scene_destroy(rtc_scene* s) {
@@ -1008,13 +1022,14 @@ int render_multi(rtc_multi* m, const rtc_camera* cam, int32_t fuel, double* rgb_
 }
 }  // namespace
 
-int rtc_multi_create(const rtc_scene_desc* desc, const int* devices, int n_devices, rtc_multi** out) {
+namespace {
+int multi_create(const rtc_scene_desc* desc, bool ex, const rtc_light_ex* lx, uint32_t n_lx, const int* devices, int n_devices, rtc_multi** out) {
   if (!desc || !devices || !out || n_devices <= 0) return rtc_fail(RTC_ERR_INVALID, "NULL argument / no devices");
   *out = nullptr;
   std::unique_ptr<rtc_multi> m(new rtc_multi());
   for (int k = 0; k < n_devices; k++) {
     rtc_scene* s = nullptr;
-    int rc = rtc_scene_create(desc, devices[k], &s);
+    int rc = scene_create(desc, ex, lx, n_lx, devices[k], &s);
     if (rc != RTC_OK) { rtc_multi_destroy(m.release()); return rc; }
     m->scenes.push_back(s);
     m->tiles.push_back(nullptr);
@@ -1045,6 +1060,12 @@ int rtc_multi_create(const rtc_scene_desc* desc, const int* devices, int n_devic
   }
   *out = m.release();
   return RTC_OK;
+}
+}  // namespace
+
+int rtc_multi_create(const rtc_scene_desc* desc, const int* devices, int n_devices, rtc_multi** out) { return multi_create(desc, false, nullptr, 0, devices, n_devices, out); }
+int rtc_multi_create_ex(const rtc_scene_desc* desc, const rtc_light_ex* lights, uint32_t n_lights, const int* devices, int n_devices, rtc_multi** out) {
+  return multi_create(desc, true, lights, n_lights, devices, n_devices, out);
 }
 
 void rtc_multi_destroy(rtc_multi* m) {

@@ -16,6 +16,10 @@
 
 using namespace rth;
 
+// Weak: the CPU emulator of the kernels (tests/cpu_emu) links this file without the _ex entry point; a world with an area light then
+// fails to render with a message instead of the whole library failing to load.
+extern "C" int rtc_scene_create_ex(const rtc_scene_desc*, const rtc_light_ex*, uint32_t, int, rtc_scene**) __attribute__((weak));
+
 struct rtw_pattern { PatRef p; };
 struct rtw_element { std::unique_ptr<Elem> e; };
 struct rtw_world {
@@ -23,6 +27,7 @@ struct rtw_world {
   rtc_scene* scene = nullptr;  // cached flatten+upload; dropped on edit
   int device = 0;
   std::unique_ptr<Flat> flat;  // rtw_world_flatten_desc: the arrays behind the descriptor it handed out
+  std::vector<rtc_light_ex> lights_ex;  // every light in order (point and area) once an area light was added; empty otherwise
   ~rtw_world() { if (scene) rtc_scene_destroy(scene); }
 };
 
@@ -51,7 +56,13 @@ static int ensure_scene(rtw_world* w) {
     rtc_scene_desc d = f.desc();
     if (timing) std::fprintf(stderr, "[rtc-timing] %-28s %.3f s\n", "flatten (host mirror -> desc)", since(t0));
     const auto t1 = std::chrono::steady_clock::now();
-    rc = rtc_scene_create(&d, w->device, &w->scene);
+    if (!w->lights_ex.empty()) {  // area lights: the light list replaces the descriptor's point lights
+      if (!rtc_scene_create_ex) return fail("area lights need rtc_scene_create_ex (librtc_amd.so)");
+      d.n_lights = 0; d.lights = nullptr;
+      rc = rtc_scene_create_ex(&d, w->lights_ex.data(), (uint32_t)w->lights_ex.size(), w->device, &w->scene);
+    } else {
+      rc = rtc_scene_create(&d, w->device, &w->scene);
+    }
     if (timing) std::fprintf(stderr, "[rtc-timing] %-28s %.3f s\n", "rtc_scene_create (all of it)", since(t1));
   }
   if (timing) std::fprintf(stderr, "[rtc-timing] %-28s %.3f s\n", "flatten + create + frees", since(t0));
@@ -160,6 +171,36 @@ int rtw_world_add_light(rtw_world* w, const double i[3], const double o[3]) {
   std::memcpy(l.intensity, i, sizeof(l.intensity));
   std::memcpy(l.origin, o, sizeof(l.origin));
   w->w.lights.push_back(l);
+  if (!w->lights_ex.empty()) {
+    rtc_light_ex x{};
+    x.kind = RTC_LIGHT_POINT;
+    std::memcpy(x.intensity, i, sizeof(x.intensity));
+    std::memcpy(x.corner, o, sizeof(x.corner));
+    w->lights_ex.push_back(x);
+  }
+  if (w->scene) { rtc_scene_destroy(w->scene); w->scene = nullptr; }
+  return 0;
+}
+int rtw_world_add_area_light(rtw_world* w, const double i[3], const double corner[3], const double uvec[3], uint32_t usteps, const double vvec[3], uint32_t vsteps,
+                             int jitter) {
+  if (w->lights_ex.empty()) {  // the point lights added so far, in order
+    for (const Light& p : w->w.lights) {
+      rtc_light_ex x{};
+      x.kind = RTC_LIGHT_POINT;
+      std::memcpy(x.intensity, p.intensity, sizeof(x.intensity));
+      std::memcpy(x.corner, p.origin, sizeof(x.corner));
+      w->lights_ex.push_back(x);
+    }
+  }
+  rtc_light_ex x{};
+  x.kind = RTC_LIGHT_AREA;
+  x.usteps = usteps; x.vsteps = vsteps;
+  x.flags = jitter ? RTC_LIGHT_JITTER : 0u;
+  std::memcpy(x.intensity, i, sizeof(x.intensity));
+  std::memcpy(x.corner, corner, sizeof(x.corner));
+  std::memcpy(x.uvec, uvec, sizeof(x.uvec));
+  std::memcpy(x.vvec, vvec, sizeof(x.vvec));
+  w->lights_ex.push_back(x);
   if (w->scene) { rtc_scene_destroy(w->scene); w->scene = nullptr; }
   return 0;
 }
@@ -208,7 +249,13 @@ int rtw_make_camera(const rtw_camera* cam, rtc_camera* out) {
   return 0;
 }
 // Flatten only (no device): sizes of the arrays a Rust shim would hand to rtc_scene_create.  Works without a GPU.
+// A world with an area light has no such descriptor: its lights are an rtc_light_ex list for rtc_scene_create_ex, which these two
+// helpers do not hand out, and a descriptor without them would render a different scene.  Both refuse such a world.
+static int refuse_area(const rtw_world* w) {
+  return w->lights_ex.empty() ? 0 : fail("flatten: the world has area lights; its lights are an rtc_light_ex list for rtc_scene_create_ex, not desc->lights");
+}
 int rtw_world_flatten_counts(rtw_world* w, uint32_t counts[8]) {
+  if (refuse_area(w)) return 1;
   Flat f;
   Flattener fl(f);
   if (!fl.run(w->w)) return fail("flatten: " + f.error);
@@ -221,6 +268,7 @@ int rtw_world_flatten_counts(rtw_world* w, uint32_t counts[8]) {
 // Flatten only (no device): the descriptor a Rust shim would hand to rtc_scene_create; its arrays live in the world handle until
 // the next call / the world's release.  Works without a GPU (tests compare it with a foreign flattener's output).
 int rtw_world_flatten_desc(rtw_world* w, rtc_scene_desc* out) {
+  if (refuse_area(w)) return 1;
   w->flat.reset(new Flat());
   Flattener fl(*w->flat);
   if (!fl.run(w->w)) return fail("flatten: " + w->flat->error);

@@ -654,6 +654,8 @@ struct HostArrays {
   std::vector<double> lights;
   mutable int backface_cached = -1;  // view(): the magnitude scan behind DScene.backface_skip, done once
   int32_t n_lights = 0, all_cast_shadow = 1, bvh_depth = 0, bvh_stack = 8, csg_max_hits = 0, built_on_device = 0;
+  int32_t has_area = 0;    // lights holds RTC_ALIGHT doubles per light (build_arrays_ex)
+  int32_t area_bounded = 1;  // every area light's sample positions lie below 1e30 in magnitude (the back-face scan's condition)
   double quirk_reach2 = 0.0, abvh_frame[4] = {0, 0, 0, 0};  // see DScene
 
   // Shape::normal (src/shape.rs:419-427) of a plane — local normal vector(0, 1, 0), src/shape.rs:896 — exactly as the device's
@@ -759,9 +761,10 @@ struct HostArrays {
         }
         return true;
       };
-      if (backface_cached < 0) backface_cached = (bounded(xf_inv) && not_flat(xf_inv) && bounded(tri_geo) && bounded(lights)) ? 1 : 0;
+      if (backface_cached < 0) backface_cached = (bounded(xf_inv) && not_flat(xf_inv) && bounded(tri_geo) && bounded(lights) && area_bounded) ? 1 : 0;
       d.backface_skip = on ? backface_cached : 0;
     }
+    d.has_area = has_area;
     d.has_recs = 0;
     for (size_t i = 0; i < ops.size(); i++) {
       const DOp& o = ops[i];
@@ -906,6 +909,68 @@ inline int build_arrays(const rtc_scene_desc& D, HostArrays* H, std::string* err
     if (timing) std::fprintf(stderr, "[rtc-timing]   %zu intersection records for %u primitives\n", H->pisect.size(), D.n_prims);
     lap("intersection records");
   }
+  return RTC_OK;
+}
+
+// desc + a list of point / area lights (include/rtc.h rtc_light_ex) in place of desc.lights.  A list of point lights only builds
+// exactly what build_arrays builds for the same lights as rtc_light records.  With an area light, program and accelerator are built
+// with the POINT lights of the list alone, so light grids (sized by their count) exist for them only: grid g belongs to the g-th point
+// light, which its record names; area-light samples move with the shading point and walk the BVH.  `lights` then holds the
+// RTC_ALIGHT-double records the area kernels read, every light in list order (device_scene.h).
+inline int build_arrays_ex(const rtc_scene_desc& D, const rtc_light_ex* L, uint32_t n, HostArrays* H, std::string* err, bvh::DeviceBuildFn device_build = nullptr,
+                           size_t device_build_min = 4096) {
+  if (D.n_lights != 0) { *err = "rtc_scene_create_ex: desc->n_lights must be 0 (the light list replaces desc->lights)"; return RTC_ERR_INVALID; }
+  if (n > 0 && !L) { *err = "rtc_scene_create_ex: lights is NULL"; return RTC_ERR_INVALID; }
+  bool area = false;
+  for (uint32_t i = 0; i < n; i++) {
+    if (L[i].kind != RTC_LIGHT_POINT && L[i].kind != RTC_LIGHT_AREA) { *err = "light " + std::to_string(i) + ": unknown kind"; return RTC_ERR_INVALID; }
+    if (L[i].kind != RTC_LIGHT_AREA) continue;
+    if (L[i].usteps == 0 || L[i].vsteps == 0) { *err = "area light " + std::to_string(i) + ": usteps and vsteps must be at least 1"; return RTC_ERR_INVALID; }
+    area = true;
+  }
+  for (uint32_t i = 0; i < n; i++)
+    if (L[i].kind == RTC_LIGHT_AREA && (L[i].usteps > RTC_AREA_MAX_STEPS || L[i].vsteps > RTC_AREA_MAX_STEPS)) {
+      *err = "area light " + std::to_string(i) + ": more than 16 steps along a side";
+      return RTC_ERR_UNSUPPORTED;
+    }
+  if (n > 64) { *err = "more than 64 lights (an area light is one)"; return RTC_ERR_UNSUPPORTED; }
+  std::vector<rtc_light> pts;  // all lights (no area light) or the point lights alone, in list order
+  pts.reserve(n);
+  for (uint32_t i = 0; i < n; i++) {
+    if (area && L[i].kind == RTC_LIGHT_AREA) continue;
+    rtc_light p;
+    std::memcpy(p.intensity, L[i].intensity, sizeof(p.intensity));
+    std::memcpy(p.origin, L[i].corner, sizeof(p.origin));
+    pts.push_back(p);
+  }
+  rtc_scene_desc D2 = D;
+  D2.n_lights = (uint32_t)pts.size();
+  D2.lights = pts.empty() ? nullptr : pts.data();
+  const int rc = build_arrays(D2, H, err, device_build, device_build_min);
+  if (rc != RTC_OK || !area) return rc;
+  H->has_area = 1;
+  H->n_lights = (int32_t)n;
+  uint32_t grid = 0;  // index among the point lights = the light grid of a point light
+  H->lights.assign((size_t)n * RTC_ALIGHT, 0.0);
+  for (uint32_t i = 0; i < n; i++) {
+    const rtc_light_ex& l = L[i];
+    double* q = &H->lights[(size_t)i * RTC_ALIGHT];
+    const bool a = l.kind == RTC_LIGHT_AREA;
+    const double N = a ? (double)l.usteps * (double)l.vsteps : 1.0;
+    for (int c = 0; c < 3; c++) {
+      q[c] = a ? l.intensity[c] / N : l.intensity[c];
+      q[3 + c] = l.corner[c];
+      q[6 + c] = a ? l.uvec[c] / (double)l.usteps : 0.0;
+      q[9 + c] = a ? l.vvec[c] / (double)l.vsteps : 0.0;
+      // every sample lies within |corner| + usteps |uc| + vsteps |vc| (plus roundings): the back-face scan's bound
+      if (a && !(std::fabs(l.corner[c]) + (double)l.usteps * std::fabs(q[6 + c]) + (double)l.vsteps * std::fabs(q[9 + c]) < 1e30)) H->area_bounded = 0;
+    }
+    q[12] = a ? (double)l.usteps : 1.0;
+    q[13] = a ? (double)l.vsteps : 1.0;
+    q[14] = a ? 1.0 : 0.0;
+    q[15] = a ? ((l.flags & RTC_LIGHT_JITTER) ? 1.0 : 0.0) : (double)grid++;
+  }
+  H->backface_cached = -1;  // (build_arrays' own view() scanned the corners only)
   return RTC_OK;
 }
 

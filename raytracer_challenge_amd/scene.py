@@ -268,8 +268,27 @@ class PointLight:  # src/light.rs:5-8
     origin: Vec4
 
 
+@dataclass(frozen=True)
+class AreaLight:
+    """Rectangular area light (the book's first bonus chapter; not in the reference): ``usteps x vsteps`` samples over
+    ``corner + [0, uvec] x [0, vvec]``, at the cell centres or, with ``jitter``, at hashed offsets inside the cells.  Each sample
+    shades like a PointLight of ``intensity / (usteps * vsteps)``; reflections and refractions count the light once.  The exact
+    rules are in include/rtc.h (rtc_light_ex).  Rendered by the HIP library only."""
+    intensity: Color
+    corner: Vec4
+    uvec: Vec4
+    usteps: int
+    vvec: Vec4
+    vsteps: int
+    jitter: bool = False
+
+    @property
+    def samples(self) -> int:
+        return self.usteps * self.vsteps
+
+
 @dataclass
-class World:  # src/world.rs:12-15
+class World:  # src/world.rs:12-15; lights: PointLight and AreaLight in any order (the order is kept)
     lights: List[PointLight] = field(default_factory=list)
     elements: List[Element] = field(default_factory=list)
 

@@ -72,6 +72,26 @@ pub struct RtcLight {
     pub origin: [f64; 3],
 }
 
+// include/rtc.h rtc_light_ex: a point or an area light (not in the reference) for rtc_scene_create_ex / rtc_multi_create_ex
+#[allow(dead_code)]
+pub const RTC_LIGHT_POINT: i32 = 0;
+#[allow(dead_code)]
+pub const RTC_LIGHT_AREA: i32 = 1;
+#[allow(dead_code)]
+pub const RTC_LIGHT_JITTER: u32 = 1;
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtcLightEx {
+    pub kind: i32, // RTC_LIGHT_POINT / RTC_LIGHT_AREA
+    pub usteps: u32,
+    pub vsteps: u32,
+    pub flags: u32, // RTC_LIGHT_JITTER
+    pub intensity: [f64; 3],
+    pub corner: [f64; 3], // point lights: the origin
+    pub uvec: [f64; 3],
+    pub vvec: [f64; 3],
+}
+
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct RtcNode {
@@ -153,10 +173,15 @@ extern "C" {
     fn rtc_last_error() -> *const c_char;
     fn rtc_device_count() -> c_int;
     fn rtc_scene_create(desc: *const RtcSceneDesc, device: c_int, out: *mut *mut RtcScene) -> c_int;
+    #[allow(dead_code)] // area lights: the list replaces desc.lights (desc.n_lights = 0)
+    fn rtc_scene_create_ex(desc: *const RtcSceneDesc, lights: *const RtcLightEx, n_lights: u32, device: c_int, out: *mut *mut RtcScene) -> c_int;
     fn rtc_scene_destroy(scene: *mut RtcScene);
     fn rtc_render(scene: *mut RtcScene, camera: *const RtcCamera, fuel: i32, pixel_indices: *const u64, first: u64, n: u64,
                   rgb: *mut f64, hits: *mut RtcHit, stats: *mut RtcStats) -> c_int;
     fn rtc_multi_create(desc: *const RtcSceneDesc, devices: *const c_int, n_devices: c_int, out: *mut *mut RtcMulti) -> c_int;
+    #[allow(dead_code)]
+    fn rtc_multi_create_ex(desc: *const RtcSceneDesc, lights: *const RtcLightEx, n_lights: u32, devices: *const c_int, n_devices: c_int,
+                           out: *mut *mut RtcMulti) -> c_int;
     fn rtc_multi_destroy(multi: *mut RtcMulti);
     fn rtc_render_multi(multi: *mut RtcMulti, camera: *const RtcCamera, fuel: i32, rgb: *mut f64, stats: *mut RtcStats) -> c_int;
     #[allow(dead_code)] // Color::clamp'ed pixels (what Image::ppm writes): 3 bytes per pixel cross xGMI instead of 24

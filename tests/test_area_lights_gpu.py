@@ -1,0 +1,336 @@
+"""Area lights (include/rtc.h rtc_light_ex) on an MI355X, both device paths.  The oracle restates the reference, which has no area
+lights, so the semantics are pinned through identities it can check: an unjittered area light shades like its N sample points as
+point lights of intensity / N; a degenerate one (uvec = vvec = 0) like one point light at its corner, reflections and refractions
+counted once per light; a jittered one like the numpy restatement of the hash (test_area_lights_cpu.py) with the oracle deciding
+each sample's shadow."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+
+import cases
+import foreign_flattener as ff
+from parity import assert_parity
+from raytracer_challenge_amd import scenes
+from raytracer_challenge_amd.device import RtcStatsC
+from raytracer_challenge_amd.image import Image
+from raytracer_challenge_amd.scene import (AreaLight, Camera, Color, Element, Material, Matrix, Pattern, PointLight, ShapeArgs, Vector, World)
+from test_area_lights_cpu import area_hash, equivalent_point_lights, sample_positions
+
+pytestmark = pytest.mark.gpu
+PATHS = ["1", "4"]
+vp = C.c_void_p
+
+
+class RtcLightEx(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("usteps", C.c_uint32), ("vsteps", C.c_uint32), ("flags", C.c_uint32), ("intensity", C.c_double * 3),
+                ("corner", C.c_double * 3), ("uvec", C.c_double * 3), ("vvec", C.c_double * 3)]
+
+
+def bind(lib):
+    lib.rtc_last_error.restype = C.c_char_p
+    for name, args in (("rtc_scene_create", [C.POINTER(ff.RtcSceneDesc), C.c_int, C.POINTER(vp)]),
+                       ("rtc_scene_create_ex", [C.POINTER(ff.RtcSceneDesc), C.POINTER(RtcLightEx), C.c_uint32, C.c_int, C.POINTER(vp)]),
+                       ("rtc_multi_create_ex", [C.POINTER(ff.RtcSceneDesc), C.POINTER(RtcLightEx), C.c_uint32, C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]),
+                       ("rtc_render", [vp, C.POINTER(ff.RtcCamera), C.c_int32, vp, C.c_uint64, C.c_uint64, vp, vp, C.POINTER(RtcStatsC)]),
+                       ("rtc_render_hit_digest", [vp, C.POINTER(ff.RtcCamera), C.c_int32, vp, C.c_uint64, C.c_uint64, vp]),
+                       ("rtc_render_rgb8", [vp, C.POINTER(ff.RtcCamera), C.c_int32, vp, C.POINTER(RtcStatsC)]),
+                       ("rtc_quantize", [vp, vp, C.c_uint64, vp]),
+                       ("rtc_render_multi", [vp, C.POINTER(ff.RtcCamera), C.c_int32, vp, C.POINTER(RtcStatsC)])):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = args
+    lib.rtc_scene_destroy.restype = None
+    lib.rtc_scene_destroy.argtypes = [vp]
+    lib.rtc_multi_destroy.restype = None
+    lib.rtc_multi_destroy.argtypes = [vp]
+    return lib
+
+
+def ex_lights(lights):
+    arr = (RtcLightEx * max(1, len(lights)))()
+    for r, l in zip(arr, lights):
+        r.intensity = (C.c_double * 3)(l.intensity.r, l.intensity.g, l.intensity.b)
+        if isinstance(l, AreaLight):
+            r.kind, r.usteps, r.vsteps, r.flags = 1, l.usteps, l.vsteps, 1 if l.jitter else 0
+            r.corner, r.uvec, r.vvec = (C.c_double * 3)(*l.corner[:3]), (C.c_double * 3)(*l.uvec[:3]), (C.c_double * 3)(*l.vvec[:3])
+        else:
+            r.kind, r.corner = 0, (C.c_double * 3)(*l.origin[:3])
+    return arr
+
+
+def geometry_desc(world):
+    """The foreign flattener's descriptor of the world's elements, with no lights (the _ex list carries them)."""
+    flat = ff.flatten(World([], world.elements))
+    return flat, flat.desc()
+
+
+def render_scene(lib, scene, cam, fuel):
+    rc = ff.make_camera(cam)
+    n = cam.hsize * cam.vsize
+    rgb, hits, dig = np.empty((n, 3)), np.empty(n, dtype=[("t", "<f8"), ("prim", "<i4"), ("push_idx", "<i4")]), np.empty(n, dtype=np.uint64)
+    st = RtcStatsC()
+    assert lib.rtc_render(scene, C.byref(rc), fuel, None, 0, n, rgb.ctypes.data, hits.ctypes.data, C.byref(st)) == 0, lib.rtc_last_error()
+    assert lib.rtc_render_hit_digest(scene, C.byref(rc), fuel, None, 0, n, dig.ctypes.data) == 0, lib.rtc_last_error()
+    return rgb, hits, dig, st
+
+
+def matte(rgb, **kw):
+    return Material(pattern=Pattern.plain(Color(*rgb)), **kw)
+
+
+def penumbra_world(jit=False):
+    """Matte floor, spheres and a cube under area lights of 2x2, 3x1 and 4x4 samples mixed with point lights."""
+    P, V = Vector.point, Vector.vector
+    floor = Element.plane(ShapeArgs(material=matte((0.9, 0.9, 0.85), specular=0.1)))
+    s1 = Element.sphere(ShapeArgs(transform=Matrix.translation(0.0, 1.0, 0.0), material=matte((0.9, 0.3, 0.2), specular=0.4, shininess=50.0)))
+    s2 = Element.sphere(ShapeArgs(transform=Matrix.translation(1.6, 0.5, -1.0) * Matrix.scaling(0.5, 0.5, 0.5), material=matte((0.2, 0.5, 0.9))))
+    cube = Element.cube(ShapeArgs(transform=Matrix.translation(-1.7, 0.6, 0.3) * Matrix.scaling(0.6, 0.6, 0.6), material=matte((0.3, 0.8, 0.3))))
+    lights = [PointLight(Color(0.3, 0.3, 0.3), P(-6.0, 8.0, -6.0)),
+              AreaLight(Color(0.8, 0.8, 0.7), P(-1.0, 4.0, -2.0), V(2.0, 0.0, 0.0), 2, V(0.0, 0.0, 2.0), 2, jit),
+              AreaLight(Color(0.4, 0.5, 0.6), P(2.0, 3.0, -3.0), V(1.5, 0.0, 0.0), 3, V(0.0, 1.0, 0.0), 1, jit),
+              PointLight(Color(0.2, 0.1, 0.1), P(5.0, 6.0, -4.0)),
+              AreaLight(Color(0.5, 0.5, 0.5), P(-3.0, 5.0, 1.0), V(3.0, 0.0, 0.0), 4, V(0.0, 0.0, 3.0), 4, jit)]
+    return World(lights, [floor, s1, s2, cube])
+
+
+def camera(w, h):
+    return Camera.new(w, h, 1.0, Camera.transform(Vector.point(0.0, 3.0, -7.0), Vector.point(0.0, 0.7, 0.0), Vector.vector(0.0, 1.0, 0.0)))
+
+
+def expand(world):
+    """Every (unjittered) area light replaced by its N sample points as point lights of intensity / N, in place."""
+    out = []
+    for i, l in enumerate(world.lights):
+        out.extend(equivalent_point_lights(l, i) if isinstance(l, AreaLight) else [l])
+    return World(out, world.elements)
+
+
+def degenerate(world, n=2):
+    """Each point light as an area light of n x n samples all at its origin (uvec = vvec = 0)."""
+    z = Vector.vector(0.0, 0.0, 0.0)
+    return World([AreaLight(l.intensity, l.origin, z, n, z, n) for l in world.lights], world.elements)
+
+
+def mirror_world():
+    """Fuzz-style mirror scene: reflective floor, mirror and glass spheres on a seeded layout, one light."""
+    rng = np.random.default_rng(7)
+    els = [Element.plane(ShapeArgs(material=Material(pattern=Pattern.checkers(Matrix.id(), Pattern.plain(Color(0.9, 0.9, 0.9)), Pattern.plain(Color(0.2, 0.2, 0.25))),
+                                                     reflective=0.5)))]
+    for i in range(10):
+        x, z, r = rng.uniform(-3, 3), rng.uniform(-2, 3), rng.uniform(0.3, 0.8)
+        kind = i % 3
+        mat = (Material(pattern=Pattern.plain(Color(0.1, 0.1, 0.1)), reflective=0.95, specular=1.0, shininess=300.0) if kind == 0 else
+               Material(pattern=Pattern.plain(Color(0.05, 0.05, 0.1)), reflective=0.9, transparency=0.9, refractive_index=1.5, diffuse=0.1) if kind == 1 else
+               matte(tuple(rng.uniform(0.2, 1.0, 3)), reflective=0.2))
+        els.append(Element.sphere(ShapeArgs(transform=Matrix.translation(x, r, z) * Matrix.scaling(r, r, r), material=mat)))
+    return World([PointLight(Color(1.0, 1.0, 0.95), Vector.point(-4.0, 7.0, -5.0))], els)
+
+
+# ---- 1. matte scenes: an unjittered area light is its N sample points --------------------------------------------------------------
+@pytest.mark.parametrize("path", PATHS)
+def test_area_lights_are_their_sample_points(hip, orc, path, monkeypatch):
+    monkeypatch.setenv("RTC_KERNEL", path)
+    world, cam = penumbra_world(), camera(120, 90)
+    ref = orc.render_with_digest(orc.build_world(expand(world)), cam, 5)
+    err = assert_parity(hip, orc, world, cam, 5, label="penumbrae path %s" % path, ref=ref)
+    print("path %s: max |dRGB| vs the expanded point-light world = %.3e" % (path, err))
+    # the penumbrae are there: the 25 point terms differ from the 5 lights' corners
+    corners = World([PointLight(l.intensity, l.corner) if isinstance(l, AreaLight) else l for l in world.lights], world.elements)
+    assert np.abs(hip.render(hip.build_world(world), cam, 5)[0] - orc.render(orc.build_world(corners), cam, 5)[0]).max() > 1e-2
+
+
+# ---- 2. glass and mirrors: reflected / refracted colour once per light, not per sample ----------------------------------------------
+@pytest.mark.parametrize("path", PATHS)
+def test_secondary_rays_once_per_area_light(hip, orc, path, monkeypatch):
+    monkeypatch.setenv("RTC_KERNEL", path)
+    cam, glass = scenes.chapter11_glass_air_bubble(80, 80)
+    for name, world, c in (("glass_air_bubble", glass, cam), ("mirrors", mirror_world(), camera(96, 64))):
+        ref = orc.render_with_digest(orc.build_world(world), c, 5)
+        assert_parity(hip, orc, degenerate(world), c, 5, label="%s path %s" % (name, path), ref=ref)
+
+
+# ---- 1 + 2 on scenes whose program is not a short kernel-argument one -------------------------------------------------------------
+def around(world, n=2, size=1.0):
+    """Each point light as an unjittered n x n area light of size x size units centred on it (in the xz plane)."""
+    P, V = Vector.point, Vector.vector
+    return World([AreaLight(l.intensity, P(l.origin[0] - 0.5 * size, l.origin[1], l.origin[2] - 0.5 * size), V(size, 0.0, 0.0), n, V(0.0, 0.0, size), n)
+                  for l in world.lights], world.elements)
+
+
+@pytest.mark.parametrize("name", ["csg_scene", "synthetic_cones_grouped", "teapot_low"])
+@pytest.mark.parametrize("path", PATHS)
+def test_area_lights_on_csg_grouped_and_mesh_scenes(hip, orc, path, name, monkeypatch):
+    """The two oracle identities on scenes the area kernels of variant 6 serve (feature level 3, program in memory: CSG, per-primitive
+    group gates) and on a mesh: degenerate lights against the point-light world at fuel 5, and 2x2 lights against their sample points
+    at fuel 0.  (These scenes reflect and refract: the expanded world has N point lights per area light and would add the secondary
+    colour N times -- the once-per-light rule -- so the sample-point identity holds for the surface colour alone, i.e. without bounces.)"""
+    monkeypatch.setenv("RTC_KERNEL", path)
+    cam, world = cases.SMALL_CASES[name]()
+    ref = orc.render_with_digest(orc.build_world(world), cam, 5)
+    assert_parity(hip, orc, degenerate(world), cam, 5, label="%s degenerate path %s" % (name, path), ref=ref)
+    soft = around(world)
+    ref = orc.render_with_digest(orc.build_world(expand(soft)), cam, 0)
+    assert_parity(hip, orc, soft, cam, 0, label="%s 2x2 path %s" % (name, path), ref=ref)
+
+
+# ---- 3. jitter, exactly -------------------------------------------------------------------------------------------------------------
+def phong(color, mat, inten, light_pos, over, normal, eye, shadowed):
+    """Shape::lighting (src/shape.rs:429-462) in the device's operation order."""
+    v = [light_pos[i] - over[i] for i in range(3)]
+    dist = math.sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2])
+    lv = [x / dist for x in v]
+    eff = [color[i] * inten[i] for i in range(3)]
+    amb = [e * mat.ambient for e in eff]
+    ldn = lv[0] * normal[0] + lv[1] * normal[1] + lv[2] * normal[2]
+    dif, spe = [0.0] * 3, [0.0] * 3
+    if not shadowed and ldn >= 0.0:
+        dif = [e * mat.diffuse * ldn for e in eff]
+        ml = [-x for x in lv]
+        d2 = 2.0 * (ml[0] * normal[0] + ml[1] * normal[1] + ml[2] * normal[2])
+        rf = [ml[i] - normal[i] * d2 for i in range(3)]
+        rde = rf[0] * eye[0] + rf[1] * eye[1] + rf[2] * eye[2]
+        if rde > 0.0:
+            f = rde ** mat.shininess
+            spe = [inten[i] * mat.specular * f for i in range(3)]
+    return [(amb[i] + dif[i]) + spe[i] for i in range(3)], dist, lv
+
+
+@pytest.mark.parametrize("occluder", [False, True])
+@pytest.mark.parametrize("path", PATHS)
+def test_jittered_samples_exactly(hip, orc, path, occluder, monkeypatch):
+    monkeypatch.setenv("RTC_KERNEL", path)
+    mat = Material(pattern=Pattern.plain(Color(0.9, 0.8, 0.7)), ambient=0.1, diffuse=0.7, specular=0.3, shininess=20.0)
+    els = [Element.plane(ShapeArgs(material=mat))]
+    if occluder:
+        els.append(Element.sphere(ShapeArgs(transform=Matrix.translation(0.2, 1.5, 0.1) * Matrix.scaling(0.6, 0.6, 0.6))))
+    pl = PointLight(Color(0.2, 0.25, 0.3), Vector.point(-4.0, 6.0, -3.0))
+    al = AreaLight(Color(1.0, 0.9, 0.8), Vector.point(-1.0, 4.0, -1.0), Vector.vector(2.0, 0.0, 0.0), 4, Vector.vector(0.0, 0.0, 2.0), 4, True)
+    world = World([pl, al], els)
+    rng = np.random.default_rng(11)
+    o = np.column_stack([rng.uniform(-2, 2, 96), np.full(96, 3.0), rng.uniform(-2, 2, 96)])
+    d = np.column_stack([rng.uniform(-2.5, 2.5, 96), np.zeros(96), rng.uniform(-2.5, 2.5, 96)]) - o
+    d /= np.sqrt((d * d).sum(1))[:, None]
+    rgb, hits = hip.color_at(hip.build_world(world), np.hstack([o, d]), 0)
+    on_plane = np.flatnonzero(hits["prim"] == 0)
+    assert on_plane.size >= 48
+    nw_o = orc.build_world(World([pl], els))
+    n = float(al.samples)
+    inten_n = [al.intensity.r / n, al.intensity.g / n, al.intensity.b / n]
+    normal, n_shadowed, worst = (0.0, 1.0, 0.0), 0, 0.0
+    for i in on_plane:
+        t = hits["t"][i]
+        point = o[i] + d[i] * t                                   # src/ray.rs:10-12
+        over = point + np.array(normal) * 1e-5                    # src/intersection.rs:54-65
+        eye = (-d[i][0], -d[i][1], -d[i][2])
+        lights = [(list(pl.origin[:3]), [pl.intensity.r, pl.intensity.g, pl.intensity.b])]
+        lights += [(list(p), inten_n) for p in sample_positions(al, 1, tuple(over))]
+        assert area_hash(1, *over) != 0
+        # World::is_shadowed from the oracle: the nearest hit along over -> p below the distance to p
+        rays, dists = [], []
+        for pos, _ in lights:
+            v = [pos[k] - over[k] for k in range(3)]
+            dist = math.sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2])
+            rays.append(list(over) + [x / dist for x in v])
+            dists.append(dist)
+        _, sh = orc.color_at(nw_o, np.array(rays), 0)
+        shadowed = (sh["prim"] >= 0) & (sh["t"] < np.array(dists))
+        n_shadowed += int(shadowed.sum())
+        want = [0.0, 0.0, 0.0]
+        for (pos, inten), s in zip(lights, shadowed):
+            term, _, _ = phong((0.9, 0.8, 0.7), mat, inten, pos, over, normal, eye, bool(s))
+            want = [want[k] + term[k] for k in range(3)]
+        worst = max(worst, float(np.abs(rgb[i] - np.array(want)).max()))
+    assert worst <= 1e-12, worst
+    assert (n_shadowed > 0) == occluder
+    print("path %s occluder %s: %d plane hits, %d shadowed samples, max |dRGB| = %.3e" % (path, occluder, on_plane.size, n_shadowed, worst))
+
+
+def test_jittered_1080p_frame_is_identical_on_both_paths(hip, monkeypatch):
+    world, cam = penumbra_world(jit=True), camera(1920, 1080)
+    frames = []
+    for path in ("1", "4", "4"):
+        monkeypatch.setenv("RTC_KERNEL", path)
+        frames.append(hip.render(hip.build_world(world), cam, 5, want_hits=False)[0])
+    assert np.array_equal(frames[0], frames[1]) and np.array_equal(frames[1], frames[2])
+    monkeypatch.delenv("RTC_KERNEL")
+    assert np.array_equal(hip.render(hip.build_world(world), cam, 5, want_hits=False)[0], frames[0])
+
+
+# ---- 4. the _ex entry point with point lights only is rtc_scene_create ---------------------------------------------------------------
+@pytest.mark.parametrize("path", PATHS)
+def test_create_ex_with_point_lights_is_create(hip, path, monkeypatch):
+    monkeypatch.setenv("RTC_KERNEL", path)
+    lib = bind(hip.lib)
+    for name in ("nested_glass", "synthetic_cones_grouped", "csg_scene"):
+        cam, world = cases.SMALL_CASES[name]()
+        flat = ff.flatten(world)
+        desc = flat.desc()
+        a, b = vp(), vp()
+        assert lib.rtc_scene_create(C.byref(desc), 0, C.byref(a)) == 0, lib.rtc_last_error()
+        gflat, gdesc = geometry_desc(world)
+        lx = ex_lights(world.lights)
+        assert lib.rtc_scene_create_ex(C.byref(gdesc), lx, len(world.lights), 0, C.byref(b)) == 0, lib.rtc_last_error()
+        ra, rb = render_scene(lib, a, cam, 5), render_scene(lib, b, cam, 5)
+        lib.rtc_scene_destroy(a)
+        lib.rtc_scene_destroy(b)
+        assert np.array_equal(ra[0].view(np.uint64), rb[0].view(np.uint64)), name
+        assert ra[1].tobytes() == rb[1].tobytes() and np.array_equal(ra[2], rb[2]), name
+        assert ra[3].rays_shadow == rb[3].rays_shadow, name
+
+
+# ---- 5. the other entry points ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("path", PATHS)
+def test_multi_rgb8_and_par_render_with_area_lights(hip, path, monkeypatch):
+    monkeypatch.setenv("RTC_KERNEL", path)
+    lib = bind(hip.lib)
+    world, cam = penumbra_world(jit=True), camera(100, 61)
+    gflat, gdesc = geometry_desc(world)
+    lx = ex_lights(world.lights)
+    scene = vp()
+    assert lib.rtc_scene_create_ex(C.byref(gdesc), lx, len(world.lights), 0, C.byref(scene)) == 0, lib.rtc_last_error()
+    rgb, hits, dig, st = render_scene(lib, scene, cam, 5)
+    n = cam.hsize * cam.vsize
+    assert st.rays_primary == n and st.rays_shadow == 25 * int((hits["prim"] >= 0).sum())   # one shadow ray per sample (matte: no bounces)
+    rc = ff.make_camera(cam)
+    rgb8, q = np.zeros(rgb.size, dtype=np.uint8), np.zeros(rgb.size, dtype=np.uint8)
+    assert lib.rtc_render_rgb8(scene, C.byref(rc), 5, rgb8.ctypes.data, None) == 0, lib.rtc_last_error()
+    assert lib.rtc_quantize(scene, np.ascontiguousarray(rgb).ctypes.data, rgb.size, q.ctypes.data) == 0, lib.rtc_last_error()
+    assert np.array_equal(rgb8, q)
+    lib.rtc_scene_destroy(scene)
+    m = vp()
+    devs = (C.c_int * 2)(0, 0)
+    assert lib.rtc_multi_create_ex(C.byref(gdesc), lx, len(world.lights), devs, 2, C.byref(m)) == 0, lib.rtc_last_error()
+    mrgb = np.full((n, 3), np.nan)
+    assert lib.rtc_render_multi(m, C.byref(rc), 5, mrgb.ctypes.data, None) == 0, lib.rtc_last_error()
+    lib.rtc_multi_destroy(m)
+    assert np.array_equal(mrgb, rgb)
+    img = Image.par_render(cam, world)
+    assert np.array_equal(np.asarray(img.pixels).reshape(-1, 3), rgb)
+
+
+# ---- 6. validation ------------------------------------------------------------------------------------------------------------------
+def test_area_light_validation(hip):
+    lib = bind(hip.lib)
+    world = penumbra_world()
+    flat = ff.flatten(World([world.lights[0]], world.elements))   # a descriptor with a point light of its own
+    full = flat.desc()
+    gflat, gdesc = geometry_desc(world)
+    P, V = Vector.point, Vector.vector
+
+    def create(desc, lights):
+        s = vp()
+        rc = lib.rtc_scene_create_ex(C.byref(desc), ex_lights(lights), len(lights), 0, C.byref(s))
+        if rc == 0:
+            lib.rtc_scene_destroy(s)
+        return rc
+
+    def area(us, vs):
+        return AreaLight(Color.white(), P(0, 5, 0), V(1, 0, 0), us, V(0, 0, 1), vs)
+    assert create(gdesc, [area(16, 16)]) == 0
+    assert create(gdesc, [area(0, 2)]) == 1 and create(gdesc, [area(2, 0)]) == 1                           # RTC_ERR_INVALID
+    assert create(full, [area(2, 2)]) == 1                                                                  # desc->lights and a list
+    assert create(gdesc, [area(17, 1)]) == 2 and create(gdesc, [area(1, 17)]) == 2                         # RTC_ERR_UNSUPPORTED
+    assert create(gdesc, [area(2, 2)] * 64) == 0 and create(gdesc, [area(2, 2)] * 65) == 2
+    inf = AreaLight(Color.white(), P(0, math.inf, 0), V(1, 0, 0), 2, V(0, 0, 1), 2)
+    assert create(gdesc, [inf]) == 0                                                                        # accepted like a point light's
