@@ -32,7 +32,8 @@ enum {
                               whose CSG intersection slab would exceed RTC_CSG_MAX_BYTES (16 GiB: a subtree with more
                               than 32 possible intersections gets that many rows per thread); a material whose
                               refractive_index is not in (1e-70, 1e70); more than 64 lights (an area light is one); an area
-                              light with more than 16 steps along a side; fuel above 16 */
+                              light with more than 16 steps along a side; a texture side above 16384 or more than 2^26
+                              texels in one scene; fuel above 16 */
   RTC_ERR_DEVICE = 3,      /* HIP failure / no device                                                   */
   RTC_ERR_NAN = 4          /* a NaN intersection t reached a sort the reference's comparator would run on: a list
                               of two or more entries of one World::intersect or CSG child list; the reference
@@ -124,6 +125,67 @@ typedef struct rtc_light_ex {
   double vvec[3];
 } rtc_light_ex;
 
+/* Texture mapping (the book's third bonus chapter, "Texture mapping"; not in the reference), for rtc_scene_create_ext /
+ * rtc_multi_create_ext.  A pattern node of tag RTC_PAT_UV maps its point to (u, v) and hands that to one rtc_uv_pattern record:
+ *   kind          = the map: RTC_UVMAP_PLANAR, _SPHERICAL, _CYLINDRICAL or _CUBE;
+ *   transform_inv = applied to the 4-vector point first, exactly as a Mixture applies it (the same four rows, w included);
+ *   left          = index of the node's first rtc_uv_pattern record.  A cube map uses six consecutive records, in the book's
+ *                   cube_map order: left, front, right, back, up, down.
+ *   Every other field is ignored.
+ * A UV node keeps no colour frame: like Checkers it selects a child or yields a colour, nests freely and does not count against
+ * RTC_MAX_PATTERN_DEPTH (the frames of its children do).  Children are evaluated at the UV node's transformed point, as Mixture
+ * children are.
+ * Every step below is one f64 operation on the transformed point (x, y, z); floor and round are C's (round: half away from zero),
+ * as_i32 = Rust's saturating `as i32` (NaN -> 0), wadd = wrapping i32 addition, PI = M_PI, m1(a) = a - floor(a),
+ * m2(a) = a - 2.0 * floor(a * 0.5).
+ *   PLANAR:      u = m1(x), v = m1(z).
+ *   SPHERICAL:   theta = atan2(x, z), r = sqrt(x*x + y*y + z*z), phi = acos(y / r), u = 1.0 - (theta / (2.0*PI) + 0.5),
+ *                v = 1.0 - phi / PI.
+ *   CYLINDRICAL: u as SPHERICAL, v = m1(y).
+ *   CUBE:        c = max(|x|, |y|, |z|) (a NaN operand is skipped, as Rust's f64::max does); the first test that holds picks the
+ *                face: c == x right, c == -x left, c == y up, c == -y down, c == z front, otherwise (NaN included) back.  Then
+ *                front (m2(x+1)/2, m2(y+1)/2), back (m2(1-x)/2, m2(y+1)/2), left (m2(z+1)/2, m2(y+1)/2),
+ *                right (m2(1-z)/2, m2(y+1)/2), up (m2(x+1)/2, m2(1-z)/2), down (m2(x+1)/2, m2(z+1)/2).
+ * The records (child[] entries are pattern-node indices; fields a kind does not use are ignored):
+ *   RTC_UV_CHECKERS:    wadd(as_i32(floor(u * width)), as_i32(floor(v * height))) % 2 == 0 selects child[0], else child[1].
+ *   RTC_UV_ALIGN_CHECK: children main, ul, ur, bl, br.  v > 0.8: u < 0.2 gives ul, u > 0.8 ur; else v < 0.2: u < 0.2 gives bl,
+ *                       u > 0.8 br; anything else (NaN included) gives main.
+ *   RTC_UV_IMAGE:       the texel of textures[texture] (w x h) at column xi = clamp(as_i32(round(u * (double)(w-1))), 0, w-1), row
+ *                       yi = clamp(as_i32(round((1.0 - v) * (double)(h-1))), 0, h-1); row 0 is the top row.  No filtering; every
+ *                       lookup stays in bounds (NaN and +-inf included).
+ * Textures are `height` rows of `width` f64 RGB triples, copied at scene creation; one texture may back any number of records and
+ * is uploaded once per device.
+ * Limits: RTC_ERR_INVALID for a UV node without records (always so in a plain rtc_scene_create descriptor), a cube map whose
+ * left + 6 exceeds the record count, an unknown map or record kind, a child or texture index out of range, a checkers width or
+ * height that is not finite and > 0, a texture of width or height 0 or with NULL rgb, a cycle through UV children;
+ * RTC_ERR_UNSUPPORTED for a texture side above RTC_TEXTURE_MAX_SIDE or more than RTC_TEXTURE_MAX_TEXELS texels in one scene. */
+enum { RTC_PAT_UV = 4 };
+enum { RTC_UVMAP_PLANAR = 0, RTC_UVMAP_SPHERICAL = 1, RTC_UVMAP_CYLINDRICAL = 2, RTC_UVMAP_CUBE = 3 };
+enum { RTC_UV_CHECKERS = 0, RTC_UV_ALIGN_CHECK = 1, RTC_UV_IMAGE = 2 };
+#define RTC_TEXTURE_MAX_SIDE 16384
+#define RTC_TEXTURE_MAX_TEXELS (1ull << 26)
+typedef struct rtc_uv_pattern {
+  int32_t kind;          /* RTC_UV_* */
+  int32_t texture;       /* RTC_UV_IMAGE: index into the ext's textures */
+  double width, height;  /* RTC_UV_CHECKERS: squares along u and v */
+  int32_t child[5];      /* CHECKERS: the two colours; ALIGN_CHECK: main, ul, ur, bl, br */
+  int32_t _pad;
+} rtc_uv_pattern;
+typedef struct rtc_texture {
+  uint32_t width, height;
+  const double* rgb;     /* height rows of width {r, g, b}, row 0 at the top */
+} rtc_texture;
+/* What rtc_scene_create_ext adds to a descriptor.  n_lights == 0: the lights are desc->lights (rtc_scene_create's rule); otherwise
+ * `lights` replace them under rtc_scene_create_ex's rule (desc->n_lights must be 0). */
+typedef struct rtc_scene_ext {
+  uint32_t n_lights;
+  const rtc_light_ex* lights;
+  uint32_t n_uv_patterns;
+  const rtc_uv_pattern* uv_patterns;
+  uint32_t n_textures;
+  const rtc_texture* textures;
+} rtc_scene_ext;
+
 /* The Element tree (src/shape.rs:31-34, :181-185) in DFS pre-order.  A group node carries the world-space
  * bounding box the reference computed for it (Element::composite + propagate_inverses; NaN/inf included,
  * SURVEY Q9) and `skip` = index of the first node after its subtree.  The device evaluates
@@ -200,8 +262,13 @@ int rtc_scene_create(const rtc_scene_desc* desc, int device, rtc_scene** out);
  * is exactly the rtc_scene_create scene (same kernels, same bits); one with an area light renders with kernel instantiations of its
  * own on both device paths.  Every render entry point takes either. */
 int rtc_scene_create_ex(const rtc_scene_desc* desc, const rtc_light_ex* lights, uint32_t n_lights, int device, rtc_scene** out);
+/* Same, with the extensions of rtc_scene_ext: lights (rtc_scene_create_ex's rule when ext->n_lights > 0), UV pattern records and
+ * textures for RTC_PAT_UV nodes.  An ext of NULL, or one with lights only, is exactly rtc_scene_create / rtc_scene_create_ex (same
+ * kernels, same bits); a scene with a UV node renders with kernel instantiations of its own on both device paths.  Every render
+ * entry point takes the result. */
+int rtc_scene_create_ext(const rtc_scene_desc* desc, const rtc_scene_ext* ext, int device, rtc_scene** out);
 void rtc_scene_destroy(rtc_scene*);
-/* Size in bytes of the scene's device buffers (accelerator included). */
+/* Size in bytes of the scene's device buffers (accelerator and texels included). */
 uint64_t rtc_scene_device_bytes(const rtc_scene*);
 
 /* Image::par_render for pixels i = first .. first+n-1 (row-major: x = i % hsize, y = i / hsize) or, when
@@ -255,6 +322,8 @@ typedef struct rtc_multi rtc_multi;
 int rtc_multi_create(const rtc_scene_desc* desc, const int* devices, int n_devices, rtc_multi** out);
 /* Same with the lights of rtc_scene_create_ex. */
 int rtc_multi_create_ex(const rtc_scene_desc* desc, const rtc_light_ex* lights, uint32_t n_lights, const int* devices, int n_devices, rtc_multi** out);
+/* Same with the extensions of rtc_scene_create_ext (every replica uploads its own copy of the texels). */
+int rtc_multi_create_ext(const rtc_scene_desc* desc, const rtc_scene_ext* ext, const int* devices, int n_devices, rtc_multi** out);
 void rtc_multi_destroy(rtc_multi*);
 int rtc_multi_device_count(const rtc_multi*);
 /* Rows per band of the partition (default 8; 1 = single rows interleaved).  Waits for queued frames. */

@@ -64,6 +64,23 @@ rtw_pattern* rtw_pattern_jitter(int jitter_kind, int noise_kind, double scale, u
 rtw_pattern* rtw_pattern_mixture(int mixture_kind, const double transform[16], const rtw_pattern* left, const rtw_pattern* right);
 void rtw_pattern_release(rtw_pattern*);
 
+/* Texture mapping (include/rtc.h RTC_PAT_UV; the book's bonus chapter, not in the reference).  Product library only: the oracle
+ * restates the reference, which has none, and rendering such a world needs rtc_scene_create_ext.
+ * rtw_texture_create copies h rows of w {r, g, b} (row 0 at the top); textures are immutable and ref-counted like patterns.
+ * rtw_pattern_uv: map_kind = RTC_UVMAP_*, transform as rtw_pattern_mixture's; n_faces = 1, or 6 for a cube map (left, front, right,
+ * back, up, down).  A face is one rtc_uv_pattern: kind RTC_UV_*, width / height (checkers), texture (image) and the children its
+ * kind reads (checkers: child[0], child[1]; align check: main, ul, ur, bl, br), all borrowed. */
+typedef struct rtw_texture rtw_texture;
+typedef struct rtw_uv_pattern {
+  int kind;
+  double width, height;
+  const rtw_texture* texture;
+  const rtw_pattern* child[5];
+} rtw_uv_pattern;
+rtw_texture* rtw_texture_create(uint32_t width, uint32_t height, const double* rgb);
+void rtw_texture_release(rtw_texture*);
+rtw_pattern* rtw_pattern_uv(int map_kind, const double transform[16], const rtw_uv_pattern* faces, size_t n_faces);
+
 /* Element::{sphere,plane,cube,cylinder,cone,triangle,smooth_triangle} (src/shape.rs:103-137).
  * params: cylinder/cone = {min, max, closed(0/1)}; triangle = p1,p2,p3 (9); smooth = p1,p2,p3,n1,n2,n3 (18). */
 rtw_element* rtw_shape(int geometry, const double transform[16], const rtw_material* material, int casts_shadow,

@@ -2,6 +2,7 @@
 
 Layout:
   scene.py    host mirror of the reference's scene API (Matrix, Material, Pattern, Element, World, Camera ...)
+  texture.py  texture mapping (the book's bonus chapter): Texture, UvPattern, the PPM reader
   scenes.py   the reference's scene programs + the BASELINE synthetic scenes, as data
   backend.py  ctypes binding of include/rtw.h
   image.py    Image::par_render / read / ppm on the HIP backend
@@ -12,6 +13,7 @@ The product path is the HIP library only: importing :func:`hip_backend` fails lo
 from .scene import *  # noqa: F401,F403
 from .scene import EPSILON, FUEL  # noqa: F401
 from .backend import Backend, RtwError, HIT_DTYPE  # noqa: F401
+from .texture import Texture, UvPattern, read_ppm  # noqa: F401
 
 import os as _os
 

@@ -14,6 +14,7 @@ from typing import Dict, Optional
 import numpy as np
 
 from .scene import (FUEL, GEOMETRY, GROUP_KINDS, JITTER_KINDS, MIXTURE_KINDS, AreaLight, Camera, Element, Material, Pattern, World)
+from .texture import UV_KINDS, UV_MAPS, Texture
 
 HIT_DTYPE = np.dtype([("t", "<f8"), ("prim", "<i4"), ("push_idx", "<i4")])
 
@@ -26,6 +27,10 @@ class _MaterialC(C.Structure):
     _fields_ = [("ambient", C.c_double), ("diffuse", C.c_double), ("specular", C.c_double), ("shininess", C.c_double),
                 ("reflective", C.c_double), ("transparency", C.c_double), ("refractive_index", C.c_double),
                 ("pattern", C.c_void_p)]
+
+
+class _UvFaceC(C.Structure):  # include/rtw.h rtw_uv_pattern
+    _fields_ = [("kind", C.c_int), ("width", C.c_double), ("height", C.c_double), ("texture", C.c_void_p), ("child", C.c_void_p * 5)]
 
 
 class CameraC(C.Structure):
@@ -102,6 +107,15 @@ class Backend:
         if self.has_area_lights:
             lib.rtw_world_add_area_light.restype = i
             lib.rtw_world_add_area_light.argtypes = [vp, dp, dp, dp, C.c_uint32, dp, C.c_uint32, i]
+        # texture-mapped patterns: the same (the oracle has none)
+        self.has_texture_map = hasattr(lib, "rtw_pattern_uv")
+        if self.has_texture_map:
+            lib.rtw_texture_create.restype = vp
+            lib.rtw_texture_create.argtypes = [C.c_uint32, C.c_uint32, dp]
+            lib.rtw_texture_release.restype = None
+            lib.rtw_texture_release.argtypes = [vp]
+            lib.rtw_pattern_uv.restype = vp
+            lib.rtw_pattern_uv.argtypes = [i, dp, C.POINTER(_UvFaceC), sz]
 
     # ---- errors
     def _err(self) -> str:
@@ -132,12 +146,31 @@ class Backend:
         elif p.tag == "mixture":
             l, r = self._pattern(p.left, cache, owned), self._pattern(p.right, cache, owned)
             h = lib.rtw_pattern_mixture(MIXTURE_KINDS[p.kind], _d16(p.transform), l, r)
+        elif p.tag == "uv":
+            if not self.has_texture_map:
+                raise RtwError("texture-mapped patterns need librtc_amd.so (backend %r has no rtw_pattern_uv)" % self.name)
+            faces = (_UvFaceC * len(p.faces))()
+            for k, f in enumerate(p.faces):
+                faces[k].kind, faces[k].width, faces[k].height = UV_KINDS[f.kind], f.width, f.height
+                faces[k].texture = self._texture(f.texture, cache, owned) if f.texture is not None else None
+                for c, child in enumerate(f.children):
+                    faces[k].child[c] = self._pattern(child, cache, owned)
+            h = lib.rtw_pattern_uv(UV_MAPS[p.kind], _d16(p.transform), faces, len(p.faces))
         else:
             raise RtwError("unknown pattern tag %r" % (p.tag,))
         self._check_ptr(h, "pattern")
         cache[key] = h
         owned.append(h)
         return h
+
+    def _texture(self, t: Texture, cache, owned) -> int:
+        key = ("texture", id(t))
+        if key not in cache:
+            rgb = np.ascontiguousarray(t.rgb, dtype=np.float64)
+            h = self._check_ptr(self.lib.rtw_texture_create(t.width, t.height, rgb.ctypes.data_as(C.POINTER(C.c_double))), "texture")
+            cache[key] = h
+            owned.append(("texture", h))
+        return cache[key]
 
     def _material(self, m: Material, cache, owned) -> _MaterialC:
         return _MaterialC(m.ambient, m.diffuse, m.specular, m.shininess, m.reflective, m.transparency, m.refractive_index,
@@ -187,7 +220,10 @@ class Backend:
             raise
         finally:
             for h in owned:
-                lib.rtw_pattern_release(h)
+                if isinstance(h, tuple):
+                    lib.rtw_texture_release(h[1])
+                else:
+                    lib.rtw_pattern_release(h)
         return NativeWorld(self, w, len(world.lights))
 
     # ---- the path

@@ -124,10 +124,24 @@ struct DPat {  // pattern node, 192 bytes
   int32_t tag, kind, noise_kind;
   uint32_t octaves;
   int32_t left, right;
-  int32_t pad[2];
+  int64_t uv;      // RTC_PAT_UV: byte offset from DScene.pats of the node's first DUv record
   double scale;
   double color[3];
   double m[16];
+};
+
+
+// UV pattern record (include/rtc.h rtc_uv_pattern) with its texture resolved at scene build, so that a lookup reads this record and
+// one texel triple.  Scenes with a UV node (DScene.has_uv) keep the records and every texture's texels in the tail of the pattern
+// table (scene_build.hpp build_arrays): DScene keeps its size, and so do the kernels that never read them.  64 bytes.
+struct DUv {
+  int32_t kind;      // RTC_UV_*
+  int32_t tw, th;    // RTC_UV_IMAGE: texture width, height
+  int32_t pad;
+  int32_t child[5];  // pattern-node indices
+  int32_t pad2;
+  int64_t off;       // RTC_UV_IMAGE: byte offset from DScene.pats of the texture's first texel
+  double width, height;
 };
 
 struct DScene {
@@ -190,7 +204,7 @@ struct DScene {
   int32_t bvh_stack;  // entries each lane's traversal stack needs for this scene's trees (LDS is sized from it at launch)
   int32_t n_bvh, n_items, n_mtri, n_quirk, n_qitem, n_qcell, n_groups, n_qgrids;
   int32_t has_area;   // 1: some light is an area light: `lights` holds RTC_ALIGHT doubles per light and the area kernels render the scene
-  int32_t pad_area;
+  int32_t has_uv;     // 1: some pattern node is an RTC_PAT_UV node: the UV kernel instantiations render the scene (DUv)
 };
 
 // Which pixels a launch covers.

@@ -127,13 +127,33 @@ struct Box {  // src/bounding_box.rs
 
 struct Pat;
 using PatRef = std::shared_ptr<const Pat>;
+// An image texture (include/rtc.h rtc_texture): h rows of w {r, g, b}, row 0 at the top.
+struct Tex {
+  uint32_t w = 0, h = 0;
+  std::vector<double> rgb;
+};
+using TexRef = std::shared_ptr<const Tex>;
+// One UV pattern record of a texture-mapped node (include/rtc.h rtc_uv_pattern): the children it reads (checkers: 2, align check: 5).
+struct UvFace {
+  int kind = RTC_UV_CHECKERS;
+  double width = 1.0, height = 1.0;
+  TexRef texture;
+  PatRef child[5];
+  int n_children() const { return kind == RTC_UV_CHECKERS ? 2 : (kind == RTC_UV_ALIGN_CHECK ? 5 : 0); }
+};
 struct Pat {  // src/material.rs:60-65
   int tag = RTC_PAT_PLAIN, kind = 0, noise_kind = 0;
   uint32_t octaves = 1;
   double scale = 1.0, color[3] = {1, 1, 1};
   M4 transform_inv = M4::identity();
   PatRef left, right;
-  int depth() const { return 1 + std::max(left ? left->depth() : 0, right ? right->depth() : 0); }
+  std::vector<UvFace> faces;  // RTC_PAT_UV (kind = the map): one record, six for a cube map
+  int depth() const {
+    int d = std::max(left ? left->depth() : 0, right ? right->depth() : 0);
+    for (const UvFace& f : faces)
+      for (int c = 0; c < f.n_children(); c++) d = std::max(d, f.child[c]->depth());
+    return 1 + d;
+  }
   // Frames the device's pattern walk keeps on a root-to-leaf path (rtc_device.hpp pattern_color): only a node that needs BOTH its
   // children's colours (Blend / RingGradient / Gradient) or post-processes its child's colour (colour jitter) keeps one; checkers,
   // rings, stripes and point jitters pass through.  The Box tree of the reference (src/material.rs:60-65) has no depth limit; the
@@ -141,7 +161,12 @@ struct Pat {  // src/material.rs:60-65
   bool keeps_frame() const {
     return (tag == RTC_PAT_JITTER && kind == RTC_JITTER_COLOR) || (tag == RTC_PAT_MIXTURE && (kind == RTC_MIX_BLEND || kind == RTC_MIX_RING_GRADIENT || kind == RTC_MIX_GRADIENT));
   }
-  int frame_depth() const { return (keeps_frame() ? 1 : 0) + std::max(left ? left->frame_depth() : 0, right ? right->frame_depth() : 0); }
+  int frame_depth() const {
+    int f = std::max(left ? left->frame_depth() : 0, right ? right->frame_depth() : 0);
+    for (const UvFace& x : faces)  // a UV node keeps no frame; its children's count
+      for (int c = 0; c < x.n_children(); c++) f = std::max(f, x.child[c]->frame_depth());
+    return (keeps_frame() ? 1 : 0) + f;
+  }
 };
 
 struct Mat {  // src/material.rs:19-43
@@ -440,6 +465,8 @@ struct Flat {
   std::vector<rtc_material> materials;
   std::vector<rtc_pattern_node> pats;
   std::vector<rtc_light> lights;
+  std::vector<rtc_uv_pattern> uv_pats;  // texture-mapped patterns: rtc_scene_create_ext's records and textures (rgb: the Tex's own)
+  std::vector<rtc_texture> textures;
   std::string error;
 
   rtc_scene_desc desc() const {
@@ -496,6 +523,14 @@ class Flattener {
  private:
   Flat& f_;
   std::map<const Pat*, int32_t> pat_ids_;
+  std::map<const Tex*, int32_t> tex_ids_;  // a texture is emitted once however many records use it
+  int32_t texture(const TexRef& t) {
+    auto it = tex_ids_.find(t.get());
+    if (it != tex_ids_.end()) return it->second;
+    rtc_texture r{t->w, t->h, t->rgb.data()};
+    f_.textures.push_back(r);
+    return tex_ids_[t.get()] = (int32_t)f_.textures.size() - 1;
+  }
   // materials are de-duplicated on (pattern node, 7 scalars): a whole OBJ group shares one
   std::map<std::vector<uint64_t>, int32_t> mat_ids_;
 
@@ -503,6 +538,19 @@ class Flattener {
     auto it = pat_ids_.find(p.get());
     if (it != pat_ids_.end()) return it->second;
     int32_t l = p->left ? pattern(p->left) : -1, r = p->right ? pattern(p->right) : -1;
+    if (p->tag == RTC_PAT_UV) {  // every child first: a cube map's six records must be consecutive
+      std::vector<rtc_uv_pattern> recs(p->faces.size());
+      for (size_t k = 0; k < p->faces.size(); k++) {
+        const UvFace& fc = p->faces[k];
+        rtc_uv_pattern& q = recs[k];
+        q = rtc_uv_pattern{};
+        q.kind = fc.kind; q.width = fc.width; q.height = fc.height;
+        q.texture = fc.texture ? texture(fc.texture) : -1;
+        for (int c = 0; c < 5; c++) q.child[c] = c < fc.n_children() ? pattern(fc.child[c]) : -1;
+      }
+      l = (int32_t)f_.uv_pats.size();
+      f_.uv_pats.insert(f_.uv_pats.end(), recs.begin(), recs.end());
+    }
     rtc_pattern_node n{};
     n.tag = p->tag; n.kind = p->kind; n.noise_kind = p->noise_kind; n.octaves = p->octaves;
     n.left = l; n.right = r; n.scale = p->scale;

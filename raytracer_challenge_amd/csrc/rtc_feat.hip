@@ -10,6 +10,9 @@
 //                                                                  fetches, LDS-resident tables, three waves per SIMD)
 //   6         3, area lights (AREA: DScene.has_area)               memory (serves every scene with an area light)
 //   7         1, area lights                                       kernel arguments (area-light scenes variants 0 and 1 would serve)
+//   8         3, UV patterns (UV: DScene.has_uv)                   memory (the one-kernel path of every scene with a UV pattern; the
+//                                                                  wavefront path keeps its traversal variant and runs wf_shade's UV build)
+//   9         3, UV patterns and area lights                       memory
 // Exports rtc_launch_trace_v<N> / rtc_launch_wf_ts_v<N> for the dispatchers in rtc_kernels.hip.
 #if defined(RTC_VARIANT) && RTC_VARIANT == 5 && !defined(RTC_WF_TS_WAVES_MAXFEAT)
 #define RTC_WF_TS_WAVES_MAXFEAT 2   // this variant's traversal kernel at three waves per SIMD like variants 0 and 1
@@ -20,7 +23,7 @@
 #endif
 
 #ifndef RTC_VARIANT
-#error "compile with -DRTC_VARIANT=0..7"
+#error "compile with -DRTC_VARIANT=0..9"
 #endif
 #ifndef RTC_CAT
 #define RTC_CAT2(a, b) a##b
@@ -29,10 +32,16 @@
 #undef RTC_V_FEAT
 #undef RTC_V_KOPS
 #undef RTC_V_AREA
-#if RTC_VARIANT >= 6
+#undef RTC_V_UV
+#if RTC_VARIANT == 6 || RTC_VARIANT == 7 || RTC_VARIANT == 9
 #define RTC_V_AREA 1
 #else
 #define RTC_V_AREA 0
+#endif
+#if RTC_VARIANT >= 8
+#define RTC_V_UV 1
+#else
+#define RTC_V_UV 0
 #endif
 #if RTC_VARIANT == 0
 #define RTC_V_FEAT 0
@@ -46,7 +55,7 @@
 #elif RTC_VARIANT == 3
 #define RTC_V_FEAT 2
 #define RTC_V_KOPS false
-#elif RTC_VARIANT == 4 || RTC_VARIANT == 6
+#elif RTC_VARIANT == 4 || RTC_VARIANT == 6 || RTC_VARIANT >= 8
 #define RTC_V_FEAT 3
 #define RTC_V_KOPS false
 #elif RTC_VARIANT == 7
@@ -65,7 +74,12 @@
 
 void RTC_CAT(rtc_launch_trace_v, RTC_VARIANT)(bool count, int waves, unsigned grid, hipStream_t stream, const DScene& S, const DCamera& cam, const DPixelMap& pm, int fuel, double* rgb,
                                               double* hit_t, int* hit_prim, int* hit_k, DStats* stats) {
-#if RTC_V_AREA
+#if RTC_V_UV
+  // UV-pattern scenes: one build per counting mode
+  (void)waves;
+  if (count) hipLaunchKernelGGL((rtc_trace_kernel_uv<true, RTC_V_FEAT, RTC_V_KOPS, (bool)RTC_V_AREA>), dim3(grid), dim3(RTC_BLOCK), rtc_stack_bytes(S), stream, S, cam, pm, fuel, rgb, hit_t, hit_prim, hit_k, stats);
+  else hipLaunchKernelGGL((rtc_trace_kernel_uv<false, RTC_V_FEAT, RTC_V_KOPS, (bool)RTC_V_AREA>), dim3(grid), dim3(RTC_BLOCK), rtc_stack_bytes(S), stream, S, cam, pm, fuel, rgb, hit_t, hit_prim, hit_k, stats);
+#elif RTC_V_AREA
   // area-light scenes: one build per counting mode (no 3-wave or lean build)
   (void)waves;
   if (count) hipLaunchKernelGGL((rtc_trace_kernel<true, RTC_V_FEAT, RTC_V_KOPS, 0, false, true>), dim3(grid), dim3(RTC_BLOCK), rtc_stack_bytes(S), stream, S, cam, pm, fuel, rgb, hit_t, hit_prim, hit_k, stats);
@@ -90,6 +104,7 @@ void RTC_CAT(rtc_launch_trace_v, RTC_VARIANT)(bool count, int waves, unsigned gr
 #endif
 }
 
+#if !RTC_V_UV
 void RTC_CAT(rtc_launch_wf_ts_v, RTC_VARIANT)(bool count, unsigned grid, hipStream_t stream, const DScene& S, const DCamera& cam, const DPixelMap& pm, const DWave& W, int tl, int sl,
                                               unsigned n0, int slot, int fuel_left, double* hit_t, int* hit_prim, int* hit_k, DStats* stats) {
 #if RTC_V_AREA
@@ -145,3 +160,4 @@ int RTC_CAT(rtc_wf_ts_blocks_per_cu_v, RTC_VARIANT)(unsigned lds_bytes) {
   return nb;
 }
 #endif
+#endif  // !RTC_V_UV

@@ -456,8 +456,9 @@ int rtc_device_count(void) {
 }  // extern "C"
 
 namespace {
-// rtc_scene_create (ex == false) and rtc_scene_create_ex (ex == true: the lights are `lx`, desc->lights must be empty)
-int scene_create(const rtc_scene_desc* desc, bool ex, const rtc_light_ex* lx, uint32_t n_lx, int device, rtc_scene** out) {
+// rtc_scene_create (ex == false) and rtc_scene_create_ex (ex == true: the lights are `lx`, desc->lights must be empty); `uv`: the UV
+// pattern records and textures of rtc_scene_create_ext
+int scene_create(const rtc_scene_desc* desc, bool ex, const rtc_light_ex* lx, uint32_t n_lx, int device, rtc_scene** out, const rtb::UvInput& uv = rtb::UvInput{}) {
   if (!desc || !out) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
   *out = nullptr;
   int ndev = 0;
@@ -473,8 +474,8 @@ int scene_create(const rtc_scene_desc* desc, bool ex, const rtc_light_ex* lx, ui
   const char* dbe = std::getenv("RTC_DEVICE_BVH");
   const bool device_bvh = !(dbe && dbe[0] == '0');
   const size_t device_min = (dbe && dbe[0] == '1') ? 4096 : 100000;
-  int rc = ex ? rtb::build_arrays_ex(*desc, lx, n_lx, &H, &err, device_bvh ? rtc_bvh_build_device : nullptr, device_min)
-              : rtb::build_arrays(*desc, &H, &err, device_bvh ? rtc_bvh_build_device : nullptr, device_min);
+  int rc = ex ? rtb::build_arrays_ex(*desc, lx, n_lx, &H, &err, device_bvh ? rtc_bvh_build_device : nullptr, device_min, uv)
+              : rtb::build_arrays(*desc, &H, &err, device_bvh ? rtc_bvh_build_device : nullptr, device_min, uv);
   if (rc != RTC_OK) return rtc_fail(rc, err);
   const bool timing = std::getenv("RTC_TIMING") != nullptr;
   const auto t_up0 = std::chrono::steady_clock::now();
@@ -532,6 +533,7 @@ int scene_create(const rtc_scene_desc* desc, bool ex, const rtc_light_ex* lx, ui
     d.n_bvh = hv.n_bvh; d.n_items = hv.n_items; d.n_mtri = hv.n_mtri; d.n_quirk = hv.n_quirk;
     d.n_qitem = hv.n_qitem; d.n_qcell = hv.n_qcell; d.n_groups = hv.n_groups; d.n_qgrids = hv.n_qgrids;
     d.has_area = hv.has_area;
+    d.has_uv = hv.has_uv;
   }
   s->n_prims_total = desc->n_prims;
   for (uint32_t i = 0; i < desc->n_prims; i++) {
@@ -588,6 +590,11 @@ extern "C" {
 int rtc_scene_create(const rtc_scene_desc* desc, int device, rtc_scene** out) { return scene_create(desc, false, nullptr, 0, device, out); }
 int rtc_scene_create_ex(const rtc_scene_desc* desc, const rtc_light_ex* lights, uint32_t n_lights, int device, rtc_scene** out) {
   return scene_create(desc, true, lights, n_lights, device, out);
+}
+int rtc_scene_create_ext(const rtc_scene_desc* desc, const rtc_scene_ext* ext, int device, rtc_scene** out) {
+  if (!ext) return scene_create(desc, false, nullptr, 0, device, out);
+  const rtb::UvInput uv{ext->uv_patterns, ext->n_uv_patterns, ext->textures, ext->n_textures};
+  return scene_create(desc, ext->n_lights > 0, ext->lights, ext->n_lights, device, out, uv);
 }
 
 void rtc_scene_destroy(rtc_scene* s) {
@@ -1023,13 +1030,14 @@ int render_multi(rtc_multi* m, const rtc_camera* cam, int32_t fuel, double* rgb_
 }  // namespace
 
 namespace {
-int multi_create(const rtc_scene_desc* desc, bool ex, const rtc_light_ex* lx, uint32_t n_lx, const int* devices, int n_devices, rtc_multi** out) {
+int multi_create(const rtc_scene_desc* desc, bool ex, const rtc_light_ex* lx, uint32_t n_lx, const int* devices, int n_devices, rtc_multi** out,
+                 const rtb::UvInput& uv = rtb::UvInput{}) {
   if (!desc || !devices || !out || n_devices <= 0) return rtc_fail(RTC_ERR_INVALID, "NULL argument / no devices");
   *out = nullptr;
   std::unique_ptr<rtc_multi> m(new rtc_multi());
   for (int k = 0; k < n_devices; k++) {
     rtc_scene* s = nullptr;
-    int rc = scene_create(desc, ex, lx, n_lx, devices[k], &s);
+    int rc = scene_create(desc, ex, lx, n_lx, devices[k], &s, uv);
     if (rc != RTC_OK) { rtc_multi_destroy(m.release()); return rc; }
     m->scenes.push_back(s);
     m->tiles.push_back(nullptr);
@@ -1066,6 +1074,11 @@ int multi_create(const rtc_scene_desc* desc, bool ex, const rtc_light_ex* lx, ui
 int rtc_multi_create(const rtc_scene_desc* desc, const int* devices, int n_devices, rtc_multi** out) { return multi_create(desc, false, nullptr, 0, devices, n_devices, out); }
 int rtc_multi_create_ex(const rtc_scene_desc* desc, const rtc_light_ex* lights, uint32_t n_lights, const int* devices, int n_devices, rtc_multi** out) {
   return multi_create(desc, true, lights, n_lights, devices, n_devices, out);
+}
+int rtc_multi_create_ext(const rtc_scene_desc* desc, const rtc_scene_ext* ext, const int* devices, int n_devices, rtc_multi** out) {
+  if (!ext) return multi_create(desc, false, nullptr, 0, devices, n_devices, out);
+  const rtb::UvInput uv{ext->uv_patterns, ext->n_uv_patterns, ext->textures, ext->n_textures};
+  return multi_create(desc, ext->n_lights > 0, ext->lights, ext->n_lights, devices, n_devices, out, uv);
 }
 
 void rtc_multi_destroy(rtc_multi* m) {

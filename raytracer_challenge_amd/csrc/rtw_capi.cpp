@@ -19,8 +19,11 @@ using namespace rth;
 // Weak: the CPU emulator of the kernels (tests/cpu_emu) links this file without the _ex entry point; a world with an area light then
 // fails to render with a message instead of the whole library failing to load.
 extern "C" int rtc_scene_create_ex(const rtc_scene_desc*, const rtc_light_ex*, uint32_t, int, rtc_scene**) __attribute__((weak));
+// (the same for texture-mapped patterns)
+extern "C" int rtc_scene_create_ext(const rtc_scene_desc*, const rtc_scene_ext*, int, rtc_scene**) __attribute__((weak));
 
 struct rtw_pattern { PatRef p; };
+struct rtw_texture { TexRef t; };
 struct rtw_element { std::unique_ptr<Elem> e; };
 struct rtw_world {
   WorldH w;
@@ -56,7 +59,14 @@ static int ensure_scene(rtw_world* w) {
     rtc_scene_desc d = f.desc();
     if (timing) std::fprintf(stderr, "[rtc-timing] %-28s %.3f s\n", "flatten (host mirror -> desc)", since(t0));
     const auto t1 = std::chrono::steady_clock::now();
-    if (!w->lights_ex.empty()) {  // area lights: the light list replaces the descriptor's point lights
+    if (!f.uv_pats.empty()) {  // texture-mapped patterns: records and textures (and an area light's list) through the ext
+      if (!rtc_scene_create_ext) return fail("texture-mapped patterns need rtc_scene_create_ext (librtc_amd.so)");
+      rtc_scene_ext x{};
+      if (!w->lights_ex.empty()) { d.n_lights = 0; d.lights = nullptr; x.n_lights = (uint32_t)w->lights_ex.size(); x.lights = w->lights_ex.data(); }
+      x.n_uv_patterns = (uint32_t)f.uv_pats.size(); x.uv_patterns = f.uv_pats.data();
+      x.n_textures = (uint32_t)f.textures.size(); x.textures = f.textures.data();
+      rc = rtc_scene_create_ext(&d, &x, w->device, &w->scene);
+    } else if (!w->lights_ex.empty()) {  // area lights: the light list replaces the descriptor's point lights
       if (!rtc_scene_create_ex) return fail("area lights need rtc_scene_create_ex (librtc_amd.so)");
       d.n_lights = 0; d.lights = nullptr;
       rc = rtc_scene_create_ex(&d, w->lights_ex.data(), (uint32_t)w->lights_ex.size(), w->device, &w->scene);
@@ -105,6 +115,47 @@ rtw_pattern* rtw_pattern_mixture(int mk, const double t[16], const rtw_pattern* 
   return new rtw_pattern{p};
 }
 void rtw_pattern_release(rtw_pattern* p) { delete p; }
+
+rtw_texture* rtw_texture_create(uint32_t width, uint32_t height, const double* rgb) {
+  if (width == 0 || height == 0) { fail("texture: width and height must be at least 1"); return nullptr; }
+  if (width > RTC_TEXTURE_MAX_SIDE || height > RTC_TEXTURE_MAX_SIDE) { fail("texture: a side above RTC_TEXTURE_MAX_SIDE (16384)"); return nullptr; }
+  if (!rgb) { fail("texture: rgb is NULL"); return nullptr; }
+  auto t = std::make_shared<Tex>();
+  t->w = width; t->h = height;
+  t->rgb.assign(rgb, rgb + (size_t)3 * width * height);
+  return new rtw_texture{t};
+}
+void rtw_texture_release(rtw_texture* t) { delete t; }
+rtw_pattern* rtw_pattern_uv(int map_kind, const double t[16], const rtw_uv_pattern* faces, size_t n_faces) {
+  if (map_kind < RTC_UVMAP_PLANAR || map_kind > RTC_UVMAP_CUBE) { fail("uv: map kind out of range (planar, spherical, cylindrical, cube)"); return nullptr; }
+  if (!t) { fail("uv: transform is NULL"); return nullptr; }
+  const size_t want = map_kind == RTC_UVMAP_CUBE ? 6 : 1;
+  if (!faces || n_faces != want) { fail(map_kind == RTC_UVMAP_CUBE ? "uv: a cube map takes 6 faces" : "uv: this map takes 1 face"); return nullptr; }
+  auto p = std::make_shared<Pat>();
+  p->tag = RTC_PAT_UV; p->kind = map_kind;
+  for (size_t k = 0; k < n_faces; k++) {
+    const rtw_uv_pattern& in = faces[k];
+    UvFace f;
+    f.kind = in.kind; f.width = in.width; f.height = in.height;
+    if (in.kind < RTC_UV_CHECKERS || in.kind > RTC_UV_IMAGE) { fail("uv: face kind out of range (checkers, align_check, image)"); return nullptr; }
+    if (in.kind == RTC_UV_CHECKERS && !(std::isfinite(in.width) && in.width > 0.0 && std::isfinite(in.height) && in.height > 0.0)) {
+      fail("uv: checkers width and height must be finite and > 0");
+      return nullptr;
+    }
+    if (in.kind == RTC_UV_IMAGE) {
+      if (!in.texture) { fail("uv: image face without a texture"); return nullptr; }
+      f.texture = in.texture->t;
+    }
+    for (int c = 0; c < f.n_children(); c++) {
+      if (!in.child[c]) { fail("uv: child is NULL"); return nullptr; }
+      f.child[c] = in.child[c]->p;
+    }
+    p->faces.push_back(f);
+  }
+  if (!M4::from(t).invert(&p->transform_inv)) { fail("uv: singular transform"); return nullptr; }
+  if (p->frame_depth() > RTC_MAX_PATTERN_DEPTH) { fail("pattern keeps more than RTC_MAX_PATTERN_DEPTH colour frames on one path (blends / gradients / colour jitters nested deeper than 8)"); return nullptr; }
+  return new rtw_pattern{p};
+}
 
 rtw_element* rtw_shape(int geometry, const double t[16], const rtw_material* material, int casts_shadow, const double* p, size_t np) {
   Geo g;
@@ -254,11 +305,16 @@ int rtw_make_camera(const rtw_camera* cam, rtc_camera* out) {
 static int refuse_area(const rtw_world* w) {
   return w->lights_ex.empty() ? 0 : fail("flatten: the world has area lights; its lights are an rtc_light_ex list for rtc_scene_create_ex, not desc->lights");
 }
+// ... and a world with a texture-mapped pattern, whose records and textures only rtc_scene_create_ext takes.
+static int refuse_uv(const Flat& f) {
+  return f.uv_pats.empty() ? 0 : fail("flatten: the world has texture-mapped patterns; their records and textures go to rtc_scene_create_ext, not into a descriptor");
+}
 int rtw_world_flatten_counts(rtw_world* w, uint32_t counts[8]) {
   if (refuse_area(w)) return 1;
   Flat f;
   Flattener fl(f);
   if (!fl.run(w->w)) return fail("flatten: " + f.error);
+  if (refuse_uv(f)) return 1;
   rtc_scene_desc d = f.desc();
   counts[0] = d.n_nodes; counts[1] = d.n_prims; counts[2] = d.n_xforms; counts[3] = d.n_limits;
   counts[4] = d.n_tris; counts[5] = d.n_materials; counts[6] = d.n_pattern_nodes; counts[7] = d.n_lights;
@@ -272,6 +328,7 @@ int rtw_world_flatten_desc(rtw_world* w, rtc_scene_desc* out) {
   w->flat.reset(new Flat());
   Flattener fl(*w->flat);
   if (!fl.run(w->w)) return fail("flatten: " + w->flat->error);
+  if (refuse_uv(*w->flat)) return 1;
   *out = w->flat->desc();
   return 0;
 }

@@ -563,7 +563,18 @@ struct ProgramBuilder {
   }
 };
 
-inline int validate(const rtc_scene_desc& D, std::string* err) {
+// Texture mapping (include/rtc.h RTC_PAT_UV): the UV pattern records and textures of rtc_scene_create_ext (none for the other entry
+// points, so a UV node there has no records and is RTC_ERR_INVALID).
+struct UvInput {
+  const rtc_uv_pattern* pats = nullptr;
+  uint32_t n_pats = 0;
+  const rtc_texture* tex = nullptr;
+  uint32_t n_tex = 0;
+};
+// children of a UV record that its kind reads (checkers: 2, align check: 5, image: none)
+inline int uv_children(const rtc_uv_pattern& q) { return q.kind == RTC_UV_CHECKERS ? 2 : (q.kind == RTC_UV_ALIGN_CHECK ? 5 : 0); }
+
+inline int validate(const rtc_scene_desc& D, std::string* err, const UvInput& uv = UvInput{}) {
   auto bad = [&](const char* m) { *err = m; return RTC_ERR_INVALID; };
   if (D.n_lights > 0 && !D.lights) return bad("lights is NULL");
   for (uint32_t i = 0; i < D.n_prims; i++) {
@@ -595,6 +606,20 @@ inline int validate(const rtc_scene_desc& D, std::string* err) {
       return RTC_ERR_UNSUPPORTED;
     }
   }
+  if ((uv.n_pats > 0 && !uv.pats) || (uv.n_tex > 0 && !uv.tex)) return bad("uv_patterns / textures is NULL");
+  for (uint32_t k = 0; k < uv.n_pats; k++) {
+    const rtc_uv_pattern& q = uv.pats[k];
+    if (q.kind < RTC_UV_CHECKERS || q.kind > RTC_UV_IMAGE) return bad("UV pattern kind out of range");
+    for (int c = 0; c < uv_children(q); c++)
+      if (q.child[c] < 0 || (uint32_t)q.child[c] >= D.n_pattern_nodes) return bad("UV pattern child out of range");
+    if (q.kind == RTC_UV_CHECKERS && !(std::isfinite(q.width) && q.width > 0.0 && std::isfinite(q.height) && q.height > 0.0))
+      return bad("UV checkers width and height must be finite and > 0");
+    if (q.kind == RTC_UV_IMAGE && (q.texture < 0 || (uint32_t)q.texture >= uv.n_tex)) return bad("UV pattern texture index out of range");
+  }
+  for (uint32_t t = 0; t < uv.n_tex; t++) {
+    if (uv.tex[t].width == 0 || uv.tex[t].height == 0) return bad("texture of width or height 0");
+    if (!uv.tex[t].rgb) return bad("texture rgb is NULL");
+  }
   // pattern nodes: children need not precede parents; check indices, that the graph is a forest without cycles (tree depth can be
   // anything: the reference's Box tree is unbounded, src/material.rs:60-65) and the number of colour frames the device's walk
   // keeps on one path (rtc_device.hpp pattern_color: Blend / RingGradient / Gradient mixtures and colour jitters): <= RTC_MAX_PATTERN_DEPTH
@@ -603,9 +628,20 @@ inline int validate(const rtc_scene_desc& D, std::string* err) {
     bool changed = false;
     for (uint32_t i = 0; i < D.n_pattern_nodes; i++) {
       const rtc_pattern_node& p = D.pattern_nodes[i];
-      if (p.tag < RTC_PAT_DEBUG || p.tag > RTC_PAT_MIXTURE) return bad("pattern tag out of range");
+      if (p.tag < RTC_PAT_DEBUG || p.tag > RTC_PAT_UV) return bad("pattern tag out of range");
       int d = 1, f = 0;
-      if (p.tag >= RTC_PAT_JITTER) {
+      if (p.tag == RTC_PAT_UV) {  // its records' children, at the node's transformed point; the node keeps no frame
+        if (p.kind < RTC_UVMAP_PLANAR || p.kind > RTC_UVMAP_CUBE) return bad("UV map kind out of range");
+        const int64_t nrec = p.kind == RTC_UVMAP_CUBE ? 6 : 1;
+        if (p.left < 0 || (int64_t)p.left + nrec > (int64_t)uv.n_pats)
+          return bad("UV node without its rtc_uv_pattern records (left + 1, or + 6 for a cube map, exceeds n_uv_patterns)");
+        for (int64_t k = p.left; k < p.left + nrec; k++)
+          for (int c = 0; c < uv_children(uv.pats[k]); c++) {
+            d = std::max(d, 1 + depth[uv.pats[k].child[c]]);
+            f = std::max(f, frames[uv.pats[k].child[c]]);
+          }
+      }
+      if (p.tag == RTC_PAT_JITTER || p.tag == RTC_PAT_MIXTURE) {
         if (p.left < 0 || (uint32_t)p.left >= D.n_pattern_nodes) return bad("pattern child out of range");
         d = std::max(d, 1 + depth[p.left]);
         f = std::max(f, frames[p.left]);
@@ -628,6 +664,15 @@ inline int validate(const rtc_scene_desc& D, std::string* err) {
     }
     if (!changed) break;
   }
+  uint64_t texels = 0;
+  for (uint32_t t = 0; t < uv.n_tex; t++) {
+    if (uv.tex[t].width > RTC_TEXTURE_MAX_SIDE || uv.tex[t].height > RTC_TEXTURE_MAX_SIDE) {
+      *err = "texture " + std::to_string(t) + ": a side above RTC_TEXTURE_MAX_SIDE (16384)";
+      return RTC_ERR_UNSUPPORTED;
+    }
+    texels += (uint64_t)uv.tex[t].width * uv.tex[t].height;
+  }
+  if (texels > RTC_TEXTURE_MAX_TEXELS) { *err = "more than RTC_TEXTURE_MAX_TEXELS (2^26) texels in one scene"; return RTC_ERR_UNSUPPORTED; }
   return RTC_OK;
 }
 
@@ -650,11 +695,12 @@ struct HostArrays {
   std::vector<int32_t> bvh_prims;  // host only: primitives the analytic BVH reaches
   std::vector<double> xf_inv, xf_matinv, limits, tri_geo, tri_nrm, mat;
   std::vector<int32_t> mat_pattern;
-  std::vector<DPat> pats;
+  std::vector<DPat> pats;      // has_uv: the DUv records and the texels follow the nodes (device_scene.h DUv)
   std::vector<double> lights;
   mutable int backface_cached = -1;  // view(): the magnitude scan behind DScene.backface_skip, done once
   int32_t n_lights = 0, all_cast_shadow = 1, bvh_depth = 0, bvh_stack = 8, csg_max_hits = 0, built_on_device = 0;
   int32_t has_area = 0;    // lights holds RTC_ALIGHT doubles per light (build_arrays_ex)
+  int32_t has_uv = 0;      // some pattern node is an RTC_PAT_UV node
   int32_t area_bounded = 1;  // every area light's sample positions lie below 1e30 in magnitude (the back-face scan's condition)
   double quirk_reach2 = 0.0, abvh_frame[4] = {0, 0, 0, 0};  // see DScene
 
@@ -765,6 +811,7 @@ struct HostArrays {
       d.backface_skip = on ? backface_cached : 0;
     }
     d.has_area = has_area;
+    d.has_uv = has_uv;
     d.has_recs = 0;
     for (size_t i = 0; i < ops.size(); i++) {
       const DOp& o = ops[i];
@@ -776,8 +823,9 @@ struct HostArrays {
 };
 
 // desc -> arrays.  Returns an RTC_* status; message in *err.
-inline int build_arrays(const rtc_scene_desc& D, HostArrays* H, std::string* err, bvh::DeviceBuildFn device_build = nullptr, size_t device_build_min = 4096) {
-  int rc = validate(D, err);
+inline int build_arrays(const rtc_scene_desc& D, HostArrays* H, std::string* err, bvh::DeviceBuildFn device_build = nullptr, size_t device_build_min = 4096,
+                        const UvInput& uv = UvInput{}) {
+  int rc = validate(D, err, uv);
   if (rc != RTC_OK) return rc;
   if (D.n_lights > 64) { *err = "more than 64 lights (the wavefront path keeps one shadow bit per light)"; return RTC_ERR_UNSUPPORTED; }
   const bool timing = std::getenv("RTC_TIMING") != nullptr;
@@ -848,6 +896,29 @@ inline int build_arrays(const rtc_scene_desc& D, HostArrays* H, std::string* err
     std::memcpy(&H->lights[(size_t)i * 6 + 3], D.lights[i].origin, 3 * sizeof(double));
   }
   H->n_lights = (int32_t)D.n_lights;
+  for (const DPat& p : H->pats) if (p.tag == RTC_PAT_UV) H->has_uv = 1;
+  if (H->has_uv) {
+    // the tail of the pattern table: the records (textures resolved), then every texture's texels once; offsets in bytes from the
+    // table's start (DPat.uv, DUv.off), so the scene uploads and replicates it as one array
+    const size_t rec0 = H->pats.size() * sizeof(DPat), tex0 = rec0 + (size_t)uv.n_pats * sizeof(DUv);
+    std::vector<size_t> toff(uv.n_tex);
+    size_t end = tex0;
+    for (uint32_t t = 0; t < uv.n_tex; t++) { toff[t] = end; end += (size_t)3 * uv.tex[t].width * uv.tex[t].height * sizeof(double); }
+    for (DPat& p : H->pats) if (p.tag == RTC_PAT_UV) p.uv = (int64_t)(rec0 + (size_t)p.left * sizeof(DUv));
+    H->pats.resize((end + sizeof(DPat) - 1) / sizeof(DPat));  // (value-initialised: zeros)
+    char* base = (char*)H->pats.data();
+    for (uint32_t k = 0; k < uv.n_pats; k++) {
+      const rtc_uv_pattern& q = uv.pats[k];
+      DUv o;
+      std::memset(&o, 0, sizeof(o));
+      o.kind = q.kind;
+      std::memcpy(o.child, q.child, sizeof(o.child));
+      o.width = q.width; o.height = q.height;
+      if (q.kind == RTC_UV_IMAGE) { o.tw = (int32_t)uv.tex[q.texture].width; o.th = (int32_t)uv.tex[q.texture].height; o.off = (int64_t)toff[(size_t)q.texture]; }
+      std::memcpy(base + rec0 + (size_t)k * sizeof(DUv), &o, sizeof(o));
+    }
+    for (uint32_t t = 0; t < uv.n_tex; t++) std::memcpy(base + toff[t], uv.tex[t].rgb, (size_t)3 * uv.tex[t].width * uv.tex[t].height * sizeof(double));
+  }
   if (pb.ops.empty()) {  // empty world: one group whose rejected branch ends the program
     pb.ops.push_back({OP_GROUP, 0, 1, 0, -1, {0, 0, 0}});
     pb.group_box.insert(pb.group_box.end(), {1, 1, 1, 0, 0, 0});
@@ -885,7 +956,9 @@ inline int build_arrays(const rtc_scene_desc& D, HostArrays* H, std::string* err
     for (int i = 0; i < dv.n_kplanes; i++) H->prims[(size_t)dv.kplanes[i].prim].pad[0] = i + 1;
     // the 128-byte intersection records, one per primitive -- only if some op of the program reads them (DScene.has_recs): a mesh
     // and a few planes in the kernel arguments do not, and 10^6 triangles would carry 128 MB of them to the device for nothing
-    if (dv.has_recs) {
+    // (scenes with a UV pattern always get them: the one-kernel path renders them with a build that reads the program from memory,
+    // rtc_feat.hip variants 8 and 9, whatever the program's own variant)
+    if (dv.has_recs || H->has_uv) {
       // ... and only up to the last primitive an op can name: the program's own OP_PRIMs (CSG sub-programs included) and the analytic
       // BVH's primitives.  Mesh triangles are reached through their BVH's packed triangle array, never through a record; an OBJ
       // group at the end of the world -- where the bins put it -- leaves the array a few entries long.
@@ -918,7 +991,7 @@ inline int build_arrays(const rtc_scene_desc& D, HostArrays* H, std::string* err
 // light, which its record names; area-light samples move with the shading point and walk the BVH.  `lights` then holds the
 // RTC_ALIGHT-double records the area kernels read, every light in list order (device_scene.h).
 inline int build_arrays_ex(const rtc_scene_desc& D, const rtc_light_ex* L, uint32_t n, HostArrays* H, std::string* err, bvh::DeviceBuildFn device_build = nullptr,
-                           size_t device_build_min = 4096) {
+                           size_t device_build_min = 4096, const UvInput& uv = UvInput{}) {
   if (D.n_lights != 0) { *err = "rtc_scene_create_ex: desc->n_lights must be 0 (the light list replaces desc->lights)"; return RTC_ERR_INVALID; }
   if (n > 0 && !L) { *err = "rtc_scene_create_ex: lights is NULL"; return RTC_ERR_INVALID; }
   bool area = false;
@@ -946,7 +1019,7 @@ inline int build_arrays_ex(const rtc_scene_desc& D, const rtc_light_ex* L, uint3
   rtc_scene_desc D2 = D;
   D2.n_lights = (uint32_t)pts.size();
   D2.lights = pts.empty() ? nullptr : pts.data();
-  const int rc = build_arrays(D2, H, err, device_build, device_build_min);
+  const int rc = build_arrays(D2, H, err, device_build, device_build_min, uv);
   if (rc != RTC_OK || !area) return rc;
   H->has_area = 1;
   H->n_lights = (int32_t)n;

@@ -159,13 +159,14 @@ MIXTURE_KINDS = {"blend": 0, "checkers": 1, "ring_gradient": 2, "ring": 3, "grad
 
 @dataclass(frozen=True)
 class Pattern:  # src/material.rs:60-65, constructors :110-162
-    tag: str  # "debug" | "plain" | "jitter" | "mixture"
+    tag: str  # "debug" | "plain" | "jitter" | "mixture" | "uv"
     color: Optional[Color] = None
-    kind: Optional[str] = None
+    kind: Optional[str] = None  # uv: the map ("planar", "spherical", "cylindrical", "cube")
     noise: Optional[Noise] = None
     transform: Optional[Matrix] = None
     left: Optional["Pattern"] = None  # jitter: the wrapped pattern
     right: Optional["Pattern"] = None
+    faces: Tuple = ()  # uv: its UvPattern (texture.py), six for a cube map (left, front, right, back, up, down)
 
     @staticmethod
     def debug(): return Pattern("debug")
@@ -189,6 +190,25 @@ class Pattern:  # src/material.rs:60-65, constructors :110-162
     def gradient(t, l, r): return Pattern._mix("gradient", t, l, r)
     @staticmethod
     def stripes(t, l, r): return Pattern._mix("stripes", t, l, r)
+
+    # texture mapping (include/rtc.h RTC_PAT_UV; the book's bonus chapter, product library only)
+    @staticmethod
+    def texture_map(transform: Matrix, mapping: str, uv) -> "Pattern":
+        from .texture import UvPattern
+        if mapping not in ("planar", "spherical", "cylindrical"):
+            raise ValueError("Pattern.texture_map: mapping must be 'planar', 'spherical' or 'cylindrical' (cube_map for cubes), got %r" % (mapping,))
+        if not isinstance(uv, UvPattern):
+            raise TypeError("Pattern.texture_map: a UvPattern expected, got %s" % type(uv).__name__)
+        return Pattern("uv", kind=mapping, transform=transform, faces=(uv,))
+
+    @staticmethod
+    def cube_map(transform: Matrix, left, front, right, back, up, down) -> "Pattern":
+        from .texture import UvPattern
+        faces = (left, front, right, back, up, down)
+        for f in faces:
+            if not isinstance(f, UvPattern):
+                raise TypeError("Pattern.cube_map: six UvPatterns expected, got %s" % type(f).__name__)
+        return Pattern("uv", kind="cube", transform=transform, faces=faces)
 
 
 @dataclass(frozen=True)

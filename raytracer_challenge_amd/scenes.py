@@ -382,3 +382,42 @@ def synthetic_mesh(obj_path: str, nx: int = 708, nz: int = 708, seed: int = 1234
     world = World([PointLight(Color.new(0.7, 0.7, 0.7), Vector.point(-100.0, 100.0, -100.0)), PointLight(Color.new(0.5, 0.5, 0.5), Vector.point(60.0, 80.0, -40.0))],
                   [floor, mesh, ball, glass])
     return _cam(3840, 2160, 1.2, (0.0, 22.0, -32.0), (0.0, 2.0, 8.0), (0.0, 1.0, 0.0), hsize, vsize), world
+
+
+def procedural_texture(width: int = 64, height: int = 32, seed: int = 2024):
+    """A seeded image texture (nothing is downloaded): smooth colour bands plus noise, as a :class:`Texture`."""
+    import numpy as np
+    from .texture import Texture
+    rng = np.random.RandomState(seed)
+    y, x = np.mgrid[0:height, 0:width].astype(np.float64)
+    r = 0.5 + 0.5 * np.sin(2.0 * PI * x / width)
+    g = 0.5 + 0.5 * np.cos(PI * y / height)
+    b = rng.uniform(0.0, 1.0, size=(height, width))
+    return Texture(np.stack([r, g, b], axis=2))
+
+
+def texture_showcase(hsize=None, vsize=None) -> Tuple[Camera, World]:
+    """Texture mapping (the book's bonus chapter): a planar-checkered floor, spherical UV checkers (16 x 8) on a sphere,
+    cylindrical checkers on a cylinder, an align-check cube map, a sphere with a seeded image texture and a glass sphere in front."""
+    from .texture import UvPattern
+    c = Color.new
+    plain = Pattern.plain
+    floor = Element.plane(ShapeArgs(material=Material(
+        pattern=Pattern.texture_map(Matrix.id(), "planar", UvPattern.checkers(2.0, 2.0, plain(c(0.9, 0.9, 0.9)), plain(c(0.3, 0.3, 0.35)))),
+        specular=0.0, reflective=0.1)))
+    globe = Element.sphere(ShapeArgs(transform=Matrix.translation(-2.5, 1.0, 1.5), material=Material(
+        pattern=Pattern.texture_map(Matrix.rotation_y(0.4), "spherical", UvPattern.checkers(16.0, 8.0, plain(c(0.1, 0.4, 0.9)), plain(c(0.95, 0.95, 0.2)))),
+        diffuse=0.7, specular=0.3)))
+    can = Element.cylinder(ShapeArgs(transform=Matrix.translation(2.5, 0.0, 2.0) * Matrix.scaling(0.8, 1.0, 0.8), material=Material(
+        pattern=Pattern.texture_map(Matrix.scaling(1.0, 0.5, 1.0), "cylindrical", UvPattern.checkers(12.0, 1.0, plain(c(0.8, 0.2, 0.2)), plain(c(0.2, 0.8, 0.3)))),
+        diffuse=0.8)), 0.0, 2.0, True)
+    faces = [UvPattern.align_check(plain(c(*m)), plain(c(1, 0, 0)), plain(c(1, 1, 0)), plain(c(0, 1, 0)), plain(c(0, 1, 1)))
+             for m in ((1, 1, 0), (0, 1, 1), (1, 0, 0), (0, 0, 1), (1, 0.5, 0), (0, 1, 0))]
+    box = Element.cube(ShapeArgs(transform=Matrix.translation(0.0, 1.0, 4.0) * Matrix.rotation_y(0.7) * Matrix.rotation_x(0.5), material=Material(
+        pattern=Pattern.cube_map(Matrix.id(), *faces), diffuse=0.8, specular=0.2)))
+    earth = Element.sphere(ShapeArgs(transform=Matrix.translation(0.3, 0.8, -0.5) * Matrix.scaling(0.8, 0.8, 0.8), material=Material(
+        pattern=Pattern.texture_map(Matrix.id(), "spherical", UvPattern.image(procedural_texture())), diffuse=0.9, specular=0.1)))
+    glass = Element.sphere(ShapeArgs(transform=Matrix.translation(-0.8, 0.6, -2.5) * Matrix.scaling(0.6, 0.6, 0.6), material=Material(
+        pattern=plain(Color.black()), diffuse=0.1, shininess=300.0, reflective=0.9, transparency=0.9, refractive_index=1.5)))
+    world = World([PointLight(Color.white(), Vector.point(-8.0, 10.0, -10.0))], [floor, globe, can, box, earth, glass])
+    return _cam(1920, 1080, PI / 3.0, (0.0, 2.5, -7.5), (0.0, 1.0, 1.0), (0.0, 1.0, 0.0), hsize, vsize), world

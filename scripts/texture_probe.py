@@ -1,0 +1,120 @@
+#!/usr/bin/env python3
+"""Cost of texture mapping (include/rtc.h RTC_PAT_UV) on config 2's scene, 1920x1080, fuel 5, on each device path, in three versions:
+  plain     the scene as it is (Plain colours: the kernels without a pattern walk where the scene allows them);
+  checkers  every surface's colour c as a 3D Checkers(c, c / 2) (the pattern-walking kernel instantiations);
+  textured  planes planar-mapped UV checkers, spheres spherically mapped onto one 1024x512 image, cubes cube-mapped (align-check
+            faces), cylinders cylindrically mapped UV checkers (the UV kernel instantiations).
+textured - checkers is the cost of the UV lookups; checkers - plain that of the pattern-walking kernels every patterned scene runs.
+ms per frame: device time between stream markers around K asynchronous whole-frame launches.
+
+usage: texture_probe.py [K]                 (GPU)
+       texture_probe.py --resource-usage    (no GPU: `make resource-usage VARIANTS="8 9"`, the UV instantiations)"""
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+from dataclasses import replace
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+CSRC = os.path.join(ROOT, "raytracer_challenge_amd", "csrc")
+
+
+def resource_usage():
+    out = subprocess.run(["make", "-s", "-C", CSRC, "resource-usage", "VARIANTS=8 9"], check=True, stdout=subprocess.PIPE, text=True).stdout
+    for line in out.splitlines():   # the UV builds: variants 8 and 9 and wf_shade_uv (the other kernels of rtc_kernels.hip are not)
+        if "_uv" in line:
+            print("  " + "  ".join(f for f in line.split("\t") if "LDS" not in f))
+
+
+def versions():
+    import numpy as np
+    from raytracer_challenge_amd import Texture, UvPattern, scenes
+    from raytracer_challenge_amd.scene import Color, Matrix, Pattern, World
+    cam, world = scenes.synthetic_analytic(n_primitives=512, seed=12345, cones=False, grouped=False, hsize=1920, vsize=1080)
+    rng = np.random.RandomState(5)
+    image = Texture(rng.uniform(0.0, 1.0, size=(512, 1024, 3)))
+
+    def repattern(how):
+        out = []
+        for e in world.elements:
+            c = e.args.material.pattern.color
+            a, b = Pattern.plain(c), Pattern.plain(Color(c.r * 0.5, c.g * 0.5, c.b * 0.5))
+            p = how(e.geometry, a, b)
+            out.append(replace(e, args=replace(e.args, material=replace(e.args.material, pattern=p))))
+        return World(world.lights, out)
+
+    def checkers(geom, a, b):
+        return Pattern.checkers(Matrix.scaling(0.5, 0.5, 0.5), a, b)
+
+    def textured(geom, a, b):
+        if geom == "plane":
+            return Pattern.texture_map(Matrix.scaling(2.0, 2.0, 2.0), "planar", UvPattern.checkers(2.0, 2.0, a, b))
+        if geom == "sphere":
+            return Pattern.texture_map(Matrix.id(), "spherical", UvPattern.image(image))
+        if geom == "cylinder":
+            return Pattern.texture_map(Matrix.id(), "cylindrical", UvPattern.checkers(8.0, 2.0, a, b))
+        return Pattern.cube_map(Matrix.id(), *[UvPattern.align_check(a, b, b, b, b)] * 6)
+    return cam, [("plain", world), ("checkers", repattern(checkers)), ("textured", repattern(textured))]
+
+
+def main(k):
+    import numpy as np
+    import torch
+    import raytracer_challenge_amd as rt
+    from raytracer_challenge_amd.device import RtcStatsC
+
+    cam, worlds = versions()
+    be = rt.hip_backend()
+    lib = be.lib
+    vp = C.c_void_p
+    lib.rtw_world_scene.restype, lib.rtw_world_scene.argtypes = vp, [vp, C.c_int]
+    lib.rtw_make_camera.restype, lib.rtw_make_camera.argtypes = C.c_int, [vp, vp]
+    lib.rtc_render.restype, lib.rtc_render.argtypes = C.c_int, [vp, vp, C.c_int32, vp, C.c_uint64, C.c_uint64, vp, vp, C.POINTER(RtcStatsC)]
+    lib.rtc_render_rows_device.restype = C.c_int
+    lib.rtc_render_rows_device.argtypes = [vp, vp, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.POINTER(RtcStatsC), C.c_int, C.c_int]
+    for f in ("rtc_scene_record", "rtc_scene_wait"):
+        getattr(lib, f).restype, getattr(lib, f).argtypes = C.c_int, [vp, C.c_int]
+    lib.rtc_scene_elapsed_ms.restype, lib.rtc_scene_elapsed_ms.argtypes = C.c_int, [vp, C.c_int, C.c_int, C.POINTER(C.c_double)]
+    lib.rtc_scene_device_bytes.restype, lib.rtc_scene_device_bytes.argtypes = C.c_uint64, [vp]
+    lib.rtc_last_error.restype = C.c_char_p
+    n = cam.hsize * cam.vsize
+    rc_cam = (C.c_double * 21)()
+    assert lib.rtw_make_camera(C.byref(be.camera_c(cam)), rc_cam) == 0
+    out = torch.empty(n * 3, dtype=torch.float64, device="cuda:0")
+    rgb = np.empty((n, 3))
+    results = {}
+    for label, w in worlds:
+        for path in ("1", "4"):
+            os.environ["RTC_KERNEL"] = path
+            nw = be.build_world(w)
+            scene = lib.rtw_world_scene(nw.handle, 0)
+            assert scene, be._err()
+            st = RtcStatsC()
+            assert lib.rtc_render(scene, rc_cam, 5, None, 0, n, rgb.ctypes.data, None, C.byref(st)) == 0, lib.rtc_last_error()
+            for _ in range(2):   # warm-up: code loading, queues
+                assert lib.rtc_render_rows_device(scene, rc_cam, 5, 0, 1, cam.vsize, C.c_void_p(out.data_ptr()), None, 0, 1) == 0, lib.rtc_last_error()
+            assert lib.rtc_scene_record(scene, 0) == 0
+            for _ in range(k):
+                assert lib.rtc_render_rows_device(scene, rc_cam, 5, 0, 1, cam.vsize, C.c_void_p(out.data_ptr()), None, 0, 0) == 0, lib.rtc_last_error()
+            assert lib.rtc_scene_record(scene, 1) == 0 and lib.rtc_scene_wait(scene, 1) == 0
+            ms = C.c_double()
+            assert lib.rtc_scene_elapsed_ms(scene, 0, 1, C.byref(ms)) == 0
+            per = ms.value / k
+            rays = st.rays_primary + st.rays_reflect + st.rays_refract
+            results["%s_path%s" % (label, path)] = {"ms_per_frame": per, "shaded_rays": rays, "device_bytes": lib.rtc_scene_device_bytes(scene)}
+            print("%-9s path %s: %8.2f ms/frame  %6.1f M camera + secondary rays  %8.1f MB on the device" % (
+                label, path, per, rays / 1e6, lib.rtc_scene_device_bytes(scene) / 1e6), flush=True)
+            nw.close()
+    for path in ("1", "4"):
+        p, c, t = (results["%s_path%s" % (v, path)]["ms_per_frame"] for v in ("plain", "checkers", "textured"))
+        print("path %s: checkers - plain %+.2f ms (%+.1f %%), textured - checkers %+.2f ms (%+.1f %%)" % (path, c - p, 100 * (c - p) / p, t - c, 100 * (t - c) / c))
+    print(json.dumps({"k": k, "results": results}))
+
+
+if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--resource-usage":
+        resource_usage()
+    else:
+        main(int(sys.argv[1]) if len(sys.argv) > 1 else 10)

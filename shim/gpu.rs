@@ -92,6 +92,38 @@ pub struct RtcLightEx {
     pub vvec: [f64; 3],
 }
 
+// include/rtc.h texture mapping (not in the reference): RTC_PAT_UV nodes, their records and textures, for rtc_scene_create_ext /
+// rtc_multi_create_ext
+#[allow(dead_code)]
+pub const RTC_PAT_UV: i32 = 4;
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtcUvPattern {
+    pub kind: i32,    // RTC_UV_CHECKERS / _ALIGN_CHECK / _IMAGE
+    pub texture: i32, // image: index into the ext's textures
+    pub width: f64,
+    pub height: f64,
+    pub child: [i32; 5], // pattern-node indices
+    pub _pad: i32,
+}
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtcTexture {
+    pub width: u32,
+    pub height: u32,
+    pub rgb: *const f64, // height rows of width {r, g, b}, row 0 at the top
+}
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtcSceneExt {
+    pub n_lights: u32,
+    pub lights: *const RtcLightEx,
+    pub n_uv_patterns: u32,
+    pub uv_patterns: *const RtcUvPattern,
+    pub n_textures: u32,
+    pub textures: *const RtcTexture,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct RtcNode {
@@ -182,6 +214,10 @@ extern "C" {
     #[allow(dead_code)]
     fn rtc_multi_create_ex(desc: *const RtcSceneDesc, lights: *const RtcLightEx, n_lights: u32, devices: *const c_int, n_devices: c_int,
                            out: *mut *mut RtcMulti) -> c_int;
+    #[allow(dead_code)]
+    fn rtc_scene_create_ext(desc: *const RtcSceneDesc, ext: *const RtcSceneExt, device: c_int, out: *mut *mut RtcScene) -> c_int;
+    #[allow(dead_code)]
+    fn rtc_multi_create_ext(desc: *const RtcSceneDesc, ext: *const RtcSceneExt, devices: *const c_int, n_devices: c_int, out: *mut *mut RtcMulti) -> c_int;
     fn rtc_multi_destroy(multi: *mut RtcMulti);
     fn rtc_render_multi(multi: *mut RtcMulti, camera: *const RtcCamera, fuel: i32, rgb: *mut f64, stats: *mut RtcStats) -> c_int;
     #[allow(dead_code)] // Color::clamp'ed pixels (what Image::ppm writes): 3 bytes per pixel cross xGMI instead of 24
