@@ -1,69 +1,30 @@
-// rtc_kernels.hip — hand-written HIP for gfx950 (MI355X): the kernels of the hot path that do not depend on the scene's feature
-// level (wf_shade, wf_gather, the quantiser) and the host-callable launchers.  The ray kernels (rtc_trace_kernel, wf_ts) are
-// templates in rtc_device.hpp, instantiated per feature level by rtc_feat.hip (one translation unit per level, built in parallel).
+// rtc_kernels.hip — hand-written HIP for gfx950 (MI355X): the kernels of the hot path that do not depend on the scene's kernel
+// variant (wf_shade, wf_gather, the quantiser) and the host-callable launchers.  The ray kernels (rtc_trace_kernel, wf_ts) are
+// templates in rtc_device.hpp, instantiated per row of RTC_VARIANTS by rtc_feat.hip (one translation unit per row, built in parallel);
+// the launchers here pick a scene's row (rtc_variant) and call through its RtcVariantOps.
 #include <cstdio>
 #include <cstdlib>
+#include <utility>
 
 #include "rtc_device.hpp"
 
-#define RTC_VARIANT_DECL(N)                                                                                                                                   \
-  void rtc_launch_trace_v##N(bool count, int waves, unsigned grid, hipStream_t stream, const DScene& S, const DCamera& cam, const DPixelMap& pm, int fuel, double* rgb, \
-                             double* hit_t, int* hit_prim, int* hit_k, DStats* stats);                                                                       \
-  void rtc_launch_wf_ts_v##N(bool count, unsigned grid, hipStream_t stream, const DScene& S, const DCamera& cam, const DPixelMap& pm, const DWave& W, int tl, \
-                             int sl, unsigned n0, int slot, int fuel_left, double* hit_t, int* hit_prim, int* hit_k, DStats* stats);                         \
-  int rtc_wf_ts_blocks_per_cu_v##N(unsigned lds_bytes);                                                                                                        \
-  bool rtc_launch_wf_ts_lds_v##N(bool count, unsigned grid, unsigned lds_bytes, hipStream_t stream, const DScene& S, const DCamera& cam, const DPixelMap& pm,   \
-                                 const DWave& W, int tl, int sl, unsigned n0, int slot, int fuel_left, double* hit_t, int* hit_prim, int* hit_k, DStats* stats);
-RTC_VARIANT_DECL(0) RTC_VARIANT_DECL(1) RTC_VARIANT_DECL(2) RTC_VARIANT_DECL(3) RTC_VARIANT_DECL(4) RTC_VARIANT_DECL(5)
-#ifndef RTC_EMU
-RTC_VARIANT_DECL(6) RTC_VARIANT_DECL(7)  // area-light scenes (the CPU emulator has no entry point that creates one)
-#define RTC_AREA_CASES(call)   \
-  case 6: call(6); break;      \
-  case 7: call(7); break;
-// one-kernel path of scenes with a UV pattern (8; 9 with an area light): the wavefront path keeps the traversal variant and runs the
-// UV build of wf_shade
-void rtc_launch_trace_v8(bool count, int waves, unsigned grid, hipStream_t stream, const DScene& S, const DCamera& cam, const DPixelMap& pm, int fuel, double* rgb,
-                         double* hit_t, int* hit_prim, int* hit_k, DStats* stats);
-void rtc_launch_trace_v9(bool count, int waves, unsigned grid, hipStream_t stream, const DScene& S, const DCamera& cam, const DPixelMap& pm, int fuel, double* rgb,
-                         double* hit_t, int* hit_prim, int* hit_k, DStats* stats);
-#define RTC_UV_CASES(call)     \
-  case 8: call(8); break;      \
-  case 9: call(9); break;
-#else
-#define RTC_AREA_CASES(call)
-#define RTC_UV_CASES(call)
-#endif
-#undef RTC_VARIANT_DECL
 #ifdef RTC_EMU
-// the CPU emulator (tests/cpu_emu) compiles everything as one translation unit
-#define RTC_VARIANT 0
-#include "rtc_feat.hip"
-#undef RTC_VARIANT
-#define RTC_VARIANT 1
-#include "rtc_feat.hip"
-#undef RTC_VARIANT
-#define RTC_VARIANT 2
-#include "rtc_feat.hip"
-#undef RTC_VARIANT
-#define RTC_VARIANT 3
-#include "rtc_feat.hip"
-#undef RTC_VARIANT
-#define RTC_VARIANT 4
-#include "rtc_feat.hip"
-#undef RTC_VARIANT
-#define RTC_VARIANT 5
-#include "rtc_feat.hip"
-#undef RTC_VARIANT
+#include "rtc_feat.hip"  // the CPU emulator (tests/cpu_emu) compiles everything as one translation unit
+constexpr int RTC_VARIANTS_BUILT = 6;  // ... with variants 0..5 only: it has no entry point that creates an area-light or UV scene
+#else
+constexpr int RTC_VARIANTS_BUILT = RTC_N_VARIANTS;
 #endif
-
-// kernel variant a scene needs (rtc_feat.hip): its feature level (rtc_device.hpp, visit_prim) and where its program lives
-static int rtc_variant(const DScene& S) {
+// the launchers of variant v (rtc_feat.hip), one record per row of RTC_VARIANTS (all null for a row that is not built)
+template <int... V>
+static const RtcVariantOps& rtc_ops(int v, std::integer_sequence<int, V...>) {
+  static const RtcVariantOps ops[RTC_N_VARIANTS] = {rtc_variant_ops<V>()...};
+  return ops[v];
+}
+static const RtcVariantOps& rtc_ops(int v) { return rtc_ops(v, std::make_integer_sequence<int, RTC_VARIANTS_BUILT>{}); }
+// kernel variant that renders a scene on a device path (rtc_pick_variant)
+static int rtc_variant(const DScene& S, bool wavefront) {
   const int feat = S.has_csg ? 3 : (S.has_groups == 2 ? 2 : (S.has_groups ? 1 : 0));
-  // scenes with an area light: the AREA builds of the kernel-argument variants 0 / 1, or of the most general one (4) for the rest
-  if (S.has_area) return (feat <= 1 && S.n_kops > 0) ? 7 : 6;
-  if (feat <= 1 && S.n_kops > 0) return feat;
-  if (feat == 2 && S.n_kops > 0) return 5;
-  return feat <= 1 ? 2 : feat + 1;
+  return rtc_pick_variant(feat, S.n_kops > 0, S.has_area != 0, S.has_uv != 0, wavefront);
 }
 
 #ifndef RTC_WF_SHADE_WAVES
@@ -71,15 +32,143 @@ static int rtc_variant(const DScene& S) {
 #endif
 // PAT = false: every pattern of the scene is a Plain colour (DScene.all_plain): no pattern-tree walk and none of its 672 B of scratch per lane.
 // UV: scenes with a texture-mapped pattern (DScene.has_uv): the pattern walk with the RTC_PAT_UV branch (pattern_color_uv).
-template <bool COUNT, bool PAT = true>
+template <bool COUNT, bool PAT = true, bool UV = false>
 __global__ void __launch_bounds__(RTC_WF_SHADE_BLOCK, RTC_WF_SHADE_WAVES) wf_shade(DScene S, DCamera cam, DPixelMap pm, DWave W, int level, unsigned n0, int fuel0, DStats* __restrict__ stats) {
-  constexpr bool UV = false;
-#include "wf_shade_body.inc"
-}
-template <bool COUNT>
-__global__ void __launch_bounds__(RTC_WF_SHADE_BLOCK, RTC_WF_SHADE_WAVES) wf_shade_uv(DScene S, DCamera cam, DPixelMap pm, DWave W, int level, unsigned n0, int fuel0, DStats* __restrict__ stats) {
-  constexpr bool PAT = true, UV = true;
-#include "wf_shade_body.inc"
+  // per wave and class: its count, then its base index in the queue (double-buffered by iteration parity: no barrier needed before
+  // the next iteration writes).  Classes keep like with like inside a block's span of the queues, so that most 64-item chunks of the
+  // next traversal launch hold one kind of ray: shade records on planes / on other primitives; reflected rays off planes (mirror
+  // images of their coherent parents) / off other primitives / refracted rays.
+  __shared__ unsigned s_rec2[2][2][16], s_child2[2][3][16];
+  unsigned parity = 0;
+  const WorkMap wm = make_workmap(pm, cam);
+  const unsigned count = wf_count(W, level, n0);
+  const size_t cap = W.cap;
+  const double L = (double)S.n_lights;
+  const int fuel = fuel0 - level;
+  unsigned n_reflect = 0, n_refract = 0;
+  int32_t* ch = W.child + (size_t)level * 2 * cap;
+  double* nq = W.rq[(level + 1) & 1];
+  const int lane = RTC_LANE_ID;
+  const int wave = (int)(threadIdx.x / (RTC_WF_SHADE_BLOCK >= 64 ? 64 : 1));
+  const int n_waves = RTC_WF_SHADE_BLOCK >= 64 ? RTC_WF_SHADE_BLOCK / 64 : 1;
+  for (unsigned base = blockIdx.x * RTC_WF_SHADE_BLOCK; base < count; base += gridDim.x * RTC_WF_SHADE_BLOCK) {  // block-uniform bound: barriers inside
+    const unsigned i = base + threadIdx.x;
+    int prim = -1;
+    if (i < count) prim = W.h_prim[i];
+    const bool hit = prim >= 0;
+    State st;
+    double cr = 0.0, cg = 0.0, cbl = 0.0, weight = 1.0, n1 = 1.0, n2 = 1.0;
+    int mat = 0, geom = 0;
+    double reflective = 0.0, transparency = 0.0;
+    if (hit) {
+      Ray ray;
+      if (level == 0) {
+        uint64_t q = 0;
+        (void)work_to_slot(wm, i, q);
+        ray = slot_ray(pm, cam, q);
+      } else {
+        ray = wf_load_ray(W, level, i, weight);
+      }
+      const DPrim P = S.prims[prim];
+      mat = P.mat;
+      geom = P.geom;
+      const double* M = S.mat + 8 * P.mat;
+      reflective = M[4]; transparency = M[5];
+      double hu, hv;
+      hit_uv(S, P, ray, hu, hv);
+      prepare_state(S, P, ray, W.h_t[i], hu, hv, st);
+      if (transparency != 0.0 && fuel > 0) { n1 = W.h_n12[i]; n2 = W.h_n12[cap + i]; }  // stored under the same condition
+      // Pattern::color_at(material_inv * over_point) — identical for every light (src/shape.rs:437)
+      const double* mi = S.xf_matinv + 16 * P.xform;
+      double x = mi[0] * st.px + mi[1] * st.py + mi[2] * st.pz + mi[3] * 1.0;
+      double y = mi[4] * st.px + mi[5] * st.py + mi[6] * st.pz + mi[7] * 1.0;
+      double z = mi[8] * st.px + mi[9] * st.py + mi[10] * st.pz + mi[11] * 1.0;
+      double w = mi[12] * st.px + mi[13] * st.py + mi[14] * st.pz + mi[15] * 1.0;
+      const DPat& root = S.pats[S.mat_pattern[P.mat]];
+      if (!PAT || root.tag == 1) { cr = root.color[0]; cg = root.color[1]; cbl = root.color[2]; }
+      else if constexpr (UV) pattern_color_uv(S, S.mat_pattern[P.mat], x, y, z, w, cr, cg, cbl);
+      else pattern_color(S, S.mat_pattern[P.mat], x, y, z, w, cr, cg, cbl);
+    }
+    const bool blend = hit && reflective > 0.0 && transparency > 0.0;
+    double R = 0.0;
+    if (blend) R = blend_reflectance(st, n1, n2, fuel, cr, cg, cbl);  // (a NaN reflectance: the record's colour becomes NaN)
+    // reflected_color / refracted_color (src/world.rs:84-132), once per light in the reference -> factor L
+    bool do_refl = false, do_refr = false;
+    double wr = 0.0, wt = 0.0, tdx = 0.0, tdy = 0.0, tdz = 0.0;
+    if (hit && fuel > 0) {
+      do_refl = reflective != 0.0;
+      do_refr = transparency != 0.0;
+      wr = weight * L * reflective; wt = weight * L * transparency;
+      if (blend) {
+        wr *= R;
+        wt *= (1.0 - R);
+      }
+      if (do_refr) {
+        double n_ratio = n1 / n2;
+        double cos_i = st.ex * st.nx + st.ey * st.ny + st.ez * st.nz;
+        double sin2_t = (n_ratio * n_ratio) * (1.0 - cos_i * cos_i);
+        if (sin2_t > 1.0) do_refr = false;
+        else {
+          double cos_t = sqrt(1.0 - sin2_t);
+          double kk = n_ratio * cos_i - cos_t;
+          tdx = st.nx * kk - st.ex * n_ratio; tdy = st.ny * kk - st.ey * n_ratio; tdz = st.nz * kk - st.ez * n_ratio;
+        }
+      }
+    }
+    // queue space: shade records and child rays (a wave's reflected rays first, then its refracted ones); one pair of
+    // atomics per block and iteration
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    const bool on_plane = hit && geom == 1;
+    const unsigned long long m_rec0 = __ballot(hit && on_plane ? 1 : 0), m_rec1 = __ballot(hit && !on_plane ? 1 : 0);
+    const unsigned long long m_c0 = __ballot(do_refl && on_plane ? 1 : 0), m_c1 = __ballot(do_refl && !on_plane ? 1 : 0), m_c2 = __ballot(do_refr ? 1 : 0);
+    unsigned (*s_rec)[16] = s_rec2[parity];
+    unsigned (*s_child)[16] = s_child2[parity];
+    parity ^= 1u;
+    if (lane == 0) {
+      s_rec[0][wave] = (unsigned)__popcll(m_rec0); s_rec[1][wave] = (unsigned)__popcll(m_rec1);
+      s_child[0][wave] = (unsigned)__popcll(m_c0); s_child[1][wave] = (unsigned)__popcll(m_c1); s_child[2][wave] = (unsigned)__popcll(m_c2);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      unsigned tr = 0, tc = 0;
+      for (int w = 0; w < n_waves; w++) { tr += s_rec[0][w] + s_rec[1][w]; tc += s_child[0][w] + s_child[1][w] + s_child[2][w]; }
+      unsigned br = tr ? atomicAdd(&W.counts[RTC_WF_SHADE_COUNT + level], tr) : 0u;
+      unsigned bc = tc ? atomicAdd(&W.counts[level + 1], tc) : 0u;
+      if ((unsigned long long)br + tr > W.cap || (unsigned long long)bc + tc > W.cap) { W.counts[RTC_WF_OVERFLOW] = 1u; stats->wf_overflow = 1ull; }
+      for (int k = 0; k < 2; k++)
+        for (int w = 0; w < n_waves; w++) { unsigned r = s_rec[k][w]; s_rec[k][w] = br; br += r; }
+      for (int k = 0; k < 3; k++)
+        for (int w = 0; w < n_waves; w++) { unsigned c = s_child[k][w]; s_child[k][w] = bc; bc += c; }
+    }
+    __syncthreads();
+    const unsigned s = on_plane ? s_rec[0][wave] + (unsigned)__popcll(m_rec0 & lt) : s_rec[1][wave] + (unsigned)__popcll(m_rec1 & lt);
+    const unsigned jr = on_plane ? s_child[0][wave] + (unsigned)__popcll(m_c0 & lt) : s_child[1][wave] + (unsigned)__popcll(m_c1 & lt);
+    const unsigned jt = s_child[2][wave] + (unsigned)__popcll(m_c2 & lt);
+    if (hit && s < W.cap) {
+      double* r = W.sr;
+      r[s] = st.px; r[cap + s] = st.py; r[2 * cap + s] = st.pz;
+      r[3 * cap + s] = st.nx; r[4 * cap + s] = st.ny; r[5 * cap + s] = st.nz;
+      r[6 * cap + s] = cr; r[7 * cap + s] = cg; r[8 * cap + s] = cbl;
+      W.sr_mat[s] = mat;
+      W.sr_node[s] = (int32_t)i;
+    }
+    if (do_refl && jr < W.cap) {
+      nq[jr] = st.px; nq[cap + jr] = st.py; nq[2 * cap + jr] = st.pz; nq[3 * cap + jr] = st.rx; nq[4 * cap + jr] = st.ry; nq[5 * cap + jr] = st.rz;
+      nq[6 * cap + jr] = wr;
+      ch[i] = (int32_t)jr;
+      n_reflect++;
+    }
+    if (do_refr && jt < W.cap) {
+      nq[jt] = st.ux; nq[cap + jt] = st.uy; nq[2 * cap + jt] = st.uz; nq[3 * cap + jt] = tdx; nq[4 * cap + jt] = tdy; nq[5 * cap + jt] = tdz;
+      nq[6 * cap + jt] = wt;
+      ch[cap + i] = (int32_t)jt;
+      n_refract++;
+    }
+  }
+  if (COUNT) {
+    atomicAdd(&stats->rays_reflect, (unsigned long long)n_reflect);
+    atomicAdd(&stats->rays_refract, (unsigned long long)n_refract);
+  }
 }
 
 // Pixel = the contributions of its ray tree added in the order the one-kernel path adds them (a ray, then its reflected
@@ -116,54 +205,20 @@ __global__ void __launch_bounds__(256) wf_gather(DCamera cam, DPixelMap pm, DWav
 }
 
 
-static void launch_wf_ts(int v, bool count, unsigned grid, hipStream_t stream, const DScene& S, const DCamera& cam, const DPixelMap& pm, const DWave& W, int tl, int sl,
-                         unsigned n0, int slot, int fuel_left, double* hit_t, int* hit_prim, int* hit_k, DStats* stats) {
-  switch (v) {
-    case 0: rtc_launch_wf_ts_v0(count, grid, stream, S, cam, pm, W, tl, sl, n0, slot, fuel_left, hit_t, hit_prim, hit_k, stats); break;
-    case 1: rtc_launch_wf_ts_v1(count, grid, stream, S, cam, pm, W, tl, sl, n0, slot, fuel_left, hit_t, hit_prim, hit_k, stats); break;
-    case 2: rtc_launch_wf_ts_v2(count, grid, stream, S, cam, pm, W, tl, sl, n0, slot, fuel_left, hit_t, hit_prim, hit_k, stats); break;
-    case 3: rtc_launch_wf_ts_v3(count, grid, stream, S, cam, pm, W, tl, sl, n0, slot, fuel_left, hit_t, hit_prim, hit_k, stats); break;
-    case 5: rtc_launch_wf_ts_v5(count, grid, stream, S, cam, pm, W, tl, sl, n0, slot, fuel_left, hit_t, hit_prim, hit_k, stats); break;
-#define RTC_CALL(N) rtc_launch_wf_ts_v##N(count, grid, stream, S, cam, pm, W, tl, sl, n0, slot, fuel_left, hit_t, hit_prim, hit_k, stats)
-    RTC_AREA_CASES(RTC_CALL)
-#undef RTC_CALL
-    default: rtc_launch_wf_ts_v4(count, grid, stream, S, cam, pm, W, tl, sl, n0, slot, fuel_left, hit_t, hit_prim, hit_k, stats); break;
-  }
-}
-
 #ifndef RTC_EMU
 // LDS-resident scene (rtc_device.hpp, LdsScene): bytes of dynamic LDS a block of the LDSC traversal kernel needs, or 0 when the
 // scene does not qualify (program not in the kernel arguments, tables + stacks beyond a CU's 160 KB) or RTC_WF_LDS=0.
 unsigned rtc_wavefront_lds_bytes(const DScene& S) {
   static const bool off = [] { const char* e = std::getenv("RTC_WF_LDS"); return e && e[0] == '0'; }();
-  if (off || (rtc_variant(S) > 1 && rtc_variant(S) != 5)) return 0;
+  if (off || !rtc_v_lds(RTC_VARIANTS[rtc_variant(S, true)])) return 0;
   const unsigned long long need = rtc_lds_table_bytes(S) + (unsigned long long)RTC_LDS_BLOCK * (unsigned)S.bvh_stack * sizeof(int);
   return need <= 158ull * 1024 ? (unsigned)need : 0u;
-}
-static bool launch_wf_ts_lds(int v, bool count, unsigned grid, unsigned lds, hipStream_t stream, const DScene& S, const DCamera& cam, const DPixelMap& pm, const DWave& W, int tl,
-                             int sl, unsigned n0, int slot, int fuel_left, double* hit_t, int* hit_prim, int* hit_k, DStats* stats) {
-  if (v == 0) return rtc_launch_wf_ts_lds_v0(count, grid, lds, stream, S, cam, pm, W, tl, sl, n0, slot, fuel_left, hit_t, hit_prim, hit_k, stats);
-  if (v == 5) return rtc_launch_wf_ts_lds_v5(count, grid, lds, stream, S, cam, pm, W, tl, sl, n0, slot, fuel_left, hit_t, hit_prim, hit_k, stats);
-  return rtc_launch_wf_ts_lds_v1(count, grid, lds, stream, S, cam, pm, W, tl, sl, n0, slot, fuel_left, hit_t, hit_prim, hit_k, stats);
 }
 
 // Grid of the wavefront traversal kernel: as many one-wave blocks as the chip holds at once (the kernel hands out chunks
 // itself), from the occupancy the runtime reports for this scene's variant and LDS stack size.
 unsigned rtc_wavefront_grid(const DScene& S, int n_cu) {
-  const unsigned lds = rtc_stack_bytes(S);
-  int per_cu = 8;
-  switch (rtc_variant(S)) {
-    case 0: per_cu = rtc_wf_ts_blocks_per_cu_v0(lds); break;
-    case 1: per_cu = rtc_wf_ts_blocks_per_cu_v1(lds); break;
-    case 2: per_cu = rtc_wf_ts_blocks_per_cu_v2(lds); break;
-    case 3: per_cu = rtc_wf_ts_blocks_per_cu_v3(lds); break;
-    case 5: per_cu = rtc_wf_ts_blocks_per_cu_v5(lds); break;
-#define RTC_CALL(N) per_cu = rtc_wf_ts_blocks_per_cu_v##N(lds)
-    RTC_AREA_CASES(RTC_CALL)
-#undef RTC_CALL
-    default: per_cu = rtc_wf_ts_blocks_per_cu_v4(lds); break;
-  }
-  return (unsigned)std::max(1, n_cu * per_cu);
+  return (unsigned)std::max(1, n_cu * rtc_ops(rtc_variant(S, true)).wf_ts_blocks_per_cu(rtc_stack_bytes(S)));
 }
 #endif
 
@@ -179,7 +234,8 @@ uint64_t rtc_wavefront_work(const DCamera& cam, const DPixelMap& pm) {
 void rtc_launch_wavefront(const DScene& S, const DCamera& cam, const DPixelMap& pm, int fuel, const DWave& W, double* rgb, double* hit_t, int* hit_prim, int* hit_k,
                           DStats* stats, bool count, hipStream_t stream, unsigned blocks, unsigned shade_blocks) {
   if (pm.n == 0) return;
-  const int v = rtc_variant(S);
+  const RtcVariantOps& ops = rtc_ops(rtc_variant(S, true));
+  const RtcFrame F = {S, cam, pm, hit_t, hit_prim, hit_k, stats, stream, count};
   const unsigned n0 = (unsigned)rtc_wavefront_work(cam, pm);
 #ifndef RTC_EMU
   const unsigned lds = rtc_wavefront_lds_bytes(S);
@@ -191,14 +247,14 @@ void rtc_launch_wavefront(const DScene& S, const DCamera& cam, const DPixelMap& 
     const int tl = level <= fuel ? level : -1, sl = level - 1;
 #ifndef RTC_EMU
     // (a device that refuses the LDS size — the opt-in is per device — runs the kernel that reads the tables from memory)
-    if (!lds || !launch_wf_ts_lds(v, count, lds_blocks, lds, stream, S, cam, pm, W, tl, sl, n0, level, fuel - level, hit_t, hit_prim, hit_k, stats))
+    if (!lds || !ops.launch_wf_ts_lds(F, RtcLevel{W, tl, sl, n0, level, fuel - level, lds_blocks, lds}))
 #endif
-    launch_wf_ts(v, count, blocks, stream, S, cam, pm, W, tl, sl, n0, level, fuel - level, hit_t, hit_prim, hit_k, stats);
+    ops.launch_wf_ts(F, RtcLevel{W, tl, sl, n0, level, fuel - level, blocks, 0u});
     if (level <= fuel) {
 #ifndef RTC_EMU
       if (S.has_uv) {
-        if (count) hipLaunchKernelGGL((wf_shade_uv<true>), sgrid, sblock, 0, stream, S, cam, pm, W, level, n0, fuel, stats);
-        else hipLaunchKernelGGL((wf_shade_uv<false>), sgrid, sblock, 0, stream, S, cam, pm, W, level, n0, fuel, stats);
+        if (count) hipLaunchKernelGGL((wf_shade<true, true, true>), sgrid, sblock, 0, stream, S, cam, pm, W, level, n0, fuel, stats);
+        else hipLaunchKernelGGL((wf_shade<false, true, true>), sgrid, sblock, 0, stream, S, cam, pm, W, level, n0, fuel, stats);
         continue;
       }
 #endif
@@ -211,6 +267,8 @@ void rtc_launch_wavefront(const DScene& S, const DCamera& cam, const DPixelMap& 
 }
 
 // ---- host-callable launcher (C++ linkage, used by rtc_scene.cpp) ------------------------------------------
+// grid of the element-wise kernels below (grid-stride loops over n elements)
+static dim3 rtc_elementwise_grid(unsigned long long n) { return dim3((unsigned)std::min<unsigned long long>((n + 255) / 256, 8192)); }
 // Color::clamp (src/color.rs:42-46) over a flat array of channel values.
 __global__ void __launch_bounds__(256) rtc_quantize_kernel(const double* __restrict__ rgb, unsigned char* __restrict__ out, unsigned long long n) {
   unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -233,22 +291,21 @@ __global__ void __launch_bounds__(256) rtc_pack_hits_kernel(const double* __rest
 }
 void rtc_launch_pack_hits(const double* t, const int* prim, const int* k, DHit* out, unsigned long long n, hipStream_t stream) {
   if (n == 0) return;
-  unsigned long long blocks = (n + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(rtc_pack_hits_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, t, prim, k, out, n);
+  hipLaunchKernelGGL(rtc_pack_hits_kernel, rtc_elementwise_grid(n), dim3(256), 0, stream, t, prim, k, out, n);
 }
 void rtc_launch_quantize(const double* rgb, unsigned char* out, unsigned long long n, hipStream_t stream) {
   if (n == 0) return;
-  unsigned long long blocks = (n + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(rtc_quantize_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, rgb, out, n);
+  hipLaunchKernelGGL(rtc_quantize_kernel, rtc_elementwise_grid(n), dim3(256), 0, stream, rgb, out, n);
 }
 
 
 // Multi-GPU gather, last step: image row k + n j  <-  row j of replica k's dense tile in the slab.
 // (bands of `band` rows: image row y is row ((y / band) / n) * band + y % band of replica (y / band) % n's tile)
-__global__ void __launch_bounds__(256) rtc_deinterleave_kernel(const double* __restrict__ slab, double* __restrict__ image, unsigned rowlen, unsigned vsize, unsigned n,
-                                                               unsigned max_rows, unsigned band) {
+// T = double, or unsigned char for quantised tiles (rtc_render_multi_rgb8: every replica quantises its own rows, so 3 bytes per pixel
+// cross xGMI, not 24).
+template <typename T>
+__global__ void __launch_bounds__(256) rtc_deinterleave_kernel(const T* __restrict__ slab, T* __restrict__ image, unsigned rowlen, unsigned vsize, unsigned n, unsigned max_rows,
+                                                               unsigned band) {
   const unsigned long long total = (unsigned long long)vsize * rowlen;
   for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (unsigned long long)gridDim.x * blockDim.x) {
     const unsigned y = (unsigned)(i / rowlen), x = (unsigned)(i % rowlen);
@@ -256,29 +313,17 @@ __global__ void __launch_bounds__(256) rtc_deinterleave_kernel(const double* __r
     image[i] = slab[((unsigned long long)(b % n) * max_rows + (b / n) * band + y % band) * rowlen + x];
   }
 }
-// The same for quantised tiles (rtc_render_multi_rgb8: every replica quantises its own rows, so 3 bytes per pixel cross xGMI, not 24).
-__global__ void __launch_bounds__(256) rtc_deinterleave8_kernel(const unsigned char* __restrict__ slab, unsigned char* __restrict__ image, unsigned rowlen, unsigned vsize,
-                                                                unsigned n, unsigned max_rows, unsigned band) {
+template <typename T>
+static void launch_deinterleave(const T* slab, T* image, unsigned rowlen, unsigned vsize, unsigned n, unsigned max_rows, unsigned band, hipStream_t stream) {
   const unsigned long long total = (unsigned long long)vsize * rowlen;
-  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (unsigned long long)gridDim.x * blockDim.x) {
-    const unsigned y = (unsigned)(i / rowlen), x = (unsigned)(i % rowlen);
-    const unsigned b = y / band;
-    image[i] = slab[((unsigned long long)(b % n) * max_rows + (b / n) * band + y % band) * rowlen + x];
-  }
+  if (total == 0) return;
+  hipLaunchKernelGGL(rtc_deinterleave_kernel<T>, rtc_elementwise_grid(total), dim3(256), 0, stream, slab, image, rowlen, vsize, n, max_rows, band ? band : 1u);
 }
 void rtc_launch_deinterleave8(const unsigned char* slab, unsigned char* image, unsigned rowlen, unsigned vsize, unsigned n, unsigned max_rows, unsigned band, hipStream_t stream) {
-  const unsigned long long total = (unsigned long long)vsize * rowlen;
-  if (total == 0) return;
-  unsigned long long blocks = (total + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(rtc_deinterleave8_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, slab, image, rowlen, vsize, n, max_rows, band ? band : 1u);
+  launch_deinterleave(slab, image, rowlen, vsize, n, max_rows, band, stream);
 }
 void rtc_launch_deinterleave(const double* slab, double* image, unsigned rowlen, unsigned vsize, unsigned n, unsigned max_rows, unsigned band, hipStream_t stream) {
-  const unsigned long long total = (unsigned long long)vsize * rowlen;
-  if (total == 0) return;
-  unsigned long long blocks = (total + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(rtc_deinterleave_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, slab, image, rowlen, vsize, n, max_rows, band ? band : 1u);
+  launch_deinterleave(slab, image, rowlen, vsize, n, max_rows, band, stream);
 }
 
 // One-kernel path: one lane per work id (tile padding included).  big_scene: the accelerator does not fit the L2s.
@@ -286,17 +331,6 @@ void rtc_launch_trace(const DScene& S, const DCamera& cam, const DPixelMap& pm, 
                       DStats* stats, bool count, hipStream_t stream, bool big_scene) {
   if (pm.n == 0) return;
   const unsigned grid = (unsigned)((rtc_wavefront_work(cam, pm) + RTC_BLOCK - 1) / RTC_BLOCK);
-  const int waves = big_scene ? 3 : 0;
-  switch (S.has_uv ? (S.has_area ? 9 : 8) : rtc_variant(S)) {
-    case 0: rtc_launch_trace_v0(count, waves, grid, stream, S, cam, pm, fuel, rgb, hit_t, hit_prim, hit_k, stats); break;
-    case 1: rtc_launch_trace_v1(count, waves, grid, stream, S, cam, pm, fuel, rgb, hit_t, hit_prim, hit_k, stats); break;
-    case 2: rtc_launch_trace_v2(count, waves, grid, stream, S, cam, pm, fuel, rgb, hit_t, hit_prim, hit_k, stats); break;
-    case 3: rtc_launch_trace_v3(count, waves, grid, stream, S, cam, pm, fuel, rgb, hit_t, hit_prim, hit_k, stats); break;
-    case 5: rtc_launch_trace_v5(count, waves, grid, stream, S, cam, pm, fuel, rgb, hit_t, hit_prim, hit_k, stats); break;
-#define RTC_CALL(N) rtc_launch_trace_v##N(count, waves, grid, stream, S, cam, pm, fuel, rgb, hit_t, hit_prim, hit_k, stats)
-    RTC_AREA_CASES(RTC_CALL)
-    RTC_UV_CASES(RTC_CALL)
-#undef RTC_CALL
-    default: rtc_launch_trace_v4(count, waves, grid, stream, S, cam, pm, fuel, rgb, hit_t, hit_prim, hit_k, stats); break;
-  }
+  const RtcFrame F = {S, cam, pm, hit_t, hit_prim, hit_k, stats, stream, count};
+  rtc_ops(rtc_variant(S, false)).launch_trace(F, big_scene, grid, fuel, rgb);
 }

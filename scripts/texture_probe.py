@@ -12,6 +12,7 @@ usage: texture_probe.py [K]                 (GPU)
 import ctypes as C
 import json
 import os
+import re
 import subprocess
 import sys
 from dataclasses import replace
@@ -23,8 +24,11 @@ CSRC = os.path.join(ROOT, "raytracer_challenge_amd", "csrc")
 
 def resource_usage():
     out = subprocess.run(["make", "-s", "-C", CSRC, "resource-usage", "VARIANTS=8 9"], check=True, stdout=subprocess.PIPE, text=True).stdout
-    for line in out.splitlines():   # the UV builds: variants 8 and 9 and wf_shade_uv (the other kernels of rtc_kernels.hip are not)
-        if "_uv" in line:
+    # the UV builds: pattern_color_uv and the instantiations of rtc_trace_kernel (variants 8 and 9) and wf_shade whose last template
+    # argument, UV, is true (the other kernels of rtc_kernels.hip are not)
+    uv = re.compile(r"_uv|rtc_trace_kernelI(L[bi]\d+E){6}Lb1EE|wf_shadeI(Lb\dE){2}Lb1EE")
+    for line in out.splitlines():
+        if uv.search(line):
             print("  " + "  ".join(f for f in line.split("\t") if "LDS" not in f))
 
 
