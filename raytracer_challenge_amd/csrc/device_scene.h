@@ -166,7 +166,9 @@ struct DScene {
   const double* limits;      // x {min, max}
   const double* tri_geo;     // x {p1, e1, e2}
   const double* tri_nrm;     // x {n1, n2, n3}
-  const double* mat;         // n_materials x 8 {ambient, diffuse, specular, shininess, reflective, transparency, refractive_index, -}
+  const double* mat;         // n_materials x 8 {ambient, diffuse, specular, shininess, reflective, transparency, refractive_index, index of the
+                             // material's shading row}, then n_materials shading rows of 8 {ambient, diffuse, specular, shininess, root colour
+                             // rgb (a Plain root pattern; else 0), 0}: what the wavefront path's shadow role reads of a material, in one row
   const int32_t* mat_pattern;
   const DPat* pats;
   const double* lights;      // n_lights x {intensity rgb, origin xyz}; scenes with an area light (has_area): n_lights x RTC_ALIGHT doubles
@@ -300,6 +302,7 @@ static inline RTC_HD double rtc_area_jitter(unsigned long long h, unsigned j) {
 #ifndef RTC_WF_CHUNK
 #define RTC_WF_CHUNK 64u       // work items per chunk: one wave pass (larger chunks leave waves idle at the small, deep levels: 256 -> +25 %)
 #endif
+#define RTC_SR_PLAIN 0x40000000  // DWave.sr_mat: the record's colour is its material's constant (DScene.mat, shading rows)
 #define RTC_WF_MISS (-2)        // child row 0 of a ray that hit nothing: no contribution was written for it, it has no children
 struct DWave {
   double* rq[2];        // ray queues (level parity): 7 rows ox oy oz dx dy dz weight
@@ -308,7 +311,8 @@ struct DWave {
   double* h_n12;        //   2 rows: n1, n2 — written and read only for hits on transparent surfaces that can still spawn rays
   double* sr;           // shade records (compact): 9 rows over-point(3) normal(3) colour(3); the eye vector and the path weight
                         //   are read back from the ray queue (eye = -direction), which still holds the level while its shadow pass runs
-  int32_t* sr_mat;      //   material index
+  int32_t* sr_mat;      //   row of DScene.mat with the Phong terms: the material index and colour rows 6..8 written, or RTC_SR_PLAIN | the
+                        //   material's shading row, which holds the colour too (a Plain root pattern: rows 6..8 are NOT written)
   int32_t* sr_node;     //   ray index within the level
   double* contrib;      // (levels) x 3 rows: colour contribution of each ray that hit something (written by the shadow pass)
   int32_t* child;       // (levels) x 2 rows: index of the reflected / refracted child ray in the next level (-1 none); row 0 = RTC_WF_MISS: no hit

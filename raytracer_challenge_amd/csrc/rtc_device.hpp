@@ -1929,7 +1929,13 @@ __device__ __forceinline__ void wf_shadow_rec(const DScene& S, const DCamera& ca
   DIAG_LOOP(20);
   DIAG_SPAN_BEGIN();
   const double nx = r[3 * cap + s], ny = r[4 * cap + s], nz = r[5 * cap + s];
-  const double cr = r[6 * cap + s], cg = r[7 * cap + s], cbl = r[8 * cap + s];
+  // the Phong terms and -- for a material whose root pattern is Plain -- the colour: one row of the material table; any other record
+  // carries its colour in rows 6..8 (wf_shade)
+  const int mrow = W.sr_mat[s];
+  const double* M = S.mat + 8 * (mrow & (RTC_SR_PLAIN - 1));
+  double cr, cg, cbl;
+  if (mrow & RTC_SR_PLAIN) { cr = M[4]; cg = M[5]; cbl = M[6]; }
+  else { cr = r[6 * cap + s]; cg = r[7 * cap + s]; cbl = r[8 * cap + s]; }
   // the eye vector (= -direction, src/intersection.rs:56) and the path weight of the ray come from where the ray itself came
   // from: the level's queue (still intact: the next shading kernel is the first to overwrite it) or, at level 0, the camera
   const int node = W.sr_node[s];
@@ -1943,7 +1949,6 @@ __device__ __forceinline__ void wf_shadow_rec(const DScene& S, const DCamera& ca
     const double* rq = W.rq[level & 1];
     ex = -rq[3 * cap + node]; ey = -rq[4 * cap + node]; ez = -rq[5 * cap + node]; weight = rq[6 * cap + node];
   }
-  const double* M = S.mat + 8 * W.sr_mat[s];
   const double ambient = M[0], diffuse = M[1], specular = M[2], shininess = M[3];
   double sr = 0.0, sg = 0.0, sb = 0.0;
   for (int l = 0; l < S.n_lights * ((RTC_PROBE & 8) ? 2 : 1); l++) {
@@ -1997,10 +2002,14 @@ __device__ __forceinline__ void wf_shadow_rec_area(const DScene& S, const DCamer
     const double* rq = W.rq[level & 1];
     ex = -rq[3 * cap + node]; ey = -rq[4 * cap + node]; ez = -rq[5 * cap + node]; weight = rq[6 * cap + node];
   }
-  const double* M = S.mat + 8 * W.sr_mat[s];
+  const int mrow = W.sr_mat[s];  // (as in wf_shadow_rec)
+  const double* M = S.mat + 8 * (mrow & (RTC_SR_PLAIN - 1));
+  double cr, cg, cbl;
+  if (mrow & RTC_SR_PLAIN) { cr = M[4]; cg = M[5]; cbl = M[6]; }
+  else { cr = r[6 * cap + s]; cg = r[7 * cap + s]; cbl = r[8 * cap + s]; }
   double sr = 0.0, sg = 0.0, sb = 0.0;
-  shade_lights_area<FEAT, KOPS, LDSC, false>(S, r[s], r[cap + s], r[2 * cap + s], r[3 * cap + s], r[4 * cap + s], r[5 * cap + s], ex, ey, ez, r[6 * cap + s],
-                                             r[7 * cap + s], r[8 * cap + s], M[0], M[1], M[2], M[3], C, stack, stride, n_shadow, L, sr, sg, sb);
+  shade_lights_area<FEAT, KOPS, LDSC, false>(S, r[s], r[cap + s], r[2 * cap + s], r[3 * cap + s], r[4 * cap + s], r[5 * cap + s], ex, ey, ez, cr, cg, cbl, M[0], M[1], M[2],
+                                             M[3], C, stack, stride, n_shadow, L, sr, sg, sb);
   cb[node] = weight * sr; cb[cap + node] = weight * sg; cb[2 * cap + node] = weight * sb;
 }
 

@@ -30,15 +30,54 @@ static int rtc_variant(const DScene& S, bool wavefront) {
 #ifndef RTC_WF_SHADE_WAVES
 #define RTC_WF_SHADE_WAVES 4  // <= 128 VGPRs: two 512-thread blocks per CU, so one block's wait for its queue atomics is covered by the other
 #endif
+namespace {
+// What a PIPE build of wf_shade reads of a ray one iteration ahead: the ray's hit, and of levels > 0 the ray itself.
+struct WfShadeIn {
+  int prim;  // -1: a miss, tile padding, or past the level's end
+  Ray ray;
+  double weight, t;
+};
+__device__ __forceinline__ int wf_shade_fetch_prim(const DWave& W, unsigned long long i, unsigned count) { return i < count ? W.h_prim[i] : -1; }
+// Every lane loads, without a branch: values that arrive under a branch are merged with the other path's by register copies, for which
+// the compiler waits right there -- in front of the barrier the loads are meant to cross.  A lane without a hit reads the element of
+// its wave's first lane instead of its own (or element 0 past the level's end): one address for all of them, in a line the wave's hits
+// fetch anyway, so a miss's ray still costs no bandwidth (71 % of level 3 on the headline scene are misses).
+template <bool LV0>
+__device__ __forceinline__ WfShadeIn wf_shade_prefetch(const DWave& W, int level, unsigned long long i, int lane, unsigned count, int prim) {
+  const unsigned long long first = i - (unsigned)lane;
+  const unsigned j = prim >= 0 ? (unsigned)i : (first < count ? (unsigned)first : 0u);
+  WfShadeIn in = {prim, {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, 1.0, 0.0};
+  if (!LV0) in.ray = wf_load_ray(W, level, j, in.weight);  // (level 0: the camera's ray, computed where it is used)
+  in.t = W.h_t[j];
+  return in;
+}
+#ifndef RTC_EMU
+// lane l's value + the values of lanes l - 1 ... down to the start of its row of 16 lanes (DPP row shifts, zeros shifted in)
+__device__ __forceinline__ unsigned wf_row_scan16(unsigned v) {
+  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);  // row_shr:1
+  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);  // row_shr:2
+  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);  // row_shr:4
+  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);  // row_shr:8
+  return v;
+}
+#endif
+}  // namespace
 // PAT = false: every pattern of the scene is a Plain colour (DScene.all_plain): no pattern-tree walk and none of its 672 B of scratch per lane.
 // UV: scenes with a texture-mapped pattern (DScene.has_uv): the pattern walk with the RTC_PAT_UV branch (pattern_color_uv).
-template <bool COUNT, bool PAT = true, bool UV = false>
+// PIPE: the loop is software-pipelined: h_prim of the NEXT iteration is requested before this one's evaluation, the ray and h_t of its
+// hits before this one's barrier, so they travel while the block reserves queue space and stores; and wave 0 scans the 40 class
+// counters with one lane each, where thread 0 of the other builds walks them.  25 more VGPRs (97 -> 122): the PAT builds, at 127
+// with 672 B of scratch (UV: 896 B), keep the plain loop -- the wave scan alone cost them 16 B more scratch per lane.
+// LV0 (PIPE builds): the launch is level 0's, a compile-time fact there so that no branch surrounds the prefetch.
+template <bool COUNT, bool PAT = true, bool UV = false, bool PIPE = false, bool LV0 = false>
 __global__ void __launch_bounds__(RTC_WF_SHADE_BLOCK, RTC_WF_SHADE_WAVES) wf_shade(DScene S, DCamera cam, DPixelMap pm, DWave W, int level, unsigned n0, int fuel0, DStats* __restrict__ stats) {
-  // per wave and class: its count, then its base index in the queue (double-buffered by iteration parity: no barrier needed before
+  // per class and wave: its count, then its base index in the queue (double-buffered by iteration parity: no barrier needed before
   // the next iteration writes).  Classes keep like with like inside a block's span of the queues, so that most 64-item chunks of the
-  // next traversal launch hold one kind of ray: shade records on planes / on other primitives; reflected rays off planes (mirror
-  // images of their coherent parents) / off other primitives / refracted rays.
-  __shared__ unsigned s_rec2[2][2][16], s_child2[2][3][16];
+  // next traversal launch hold one kind of ray: shade records on planes / on other primitives [0..15]; reflected rays off planes
+  // (mirror images of their coherent parents) / off other primitives / refracted rays [16..39].  Entry = 8 * class + wave.
+  constexpr int n_waves = RTC_WF_SHADE_BLOCK >= 64 ? RTC_WF_SHADE_BLOCK / 64 : 1;
+  static_assert(n_waves <= 8, "wf_shade: eight counters per class");
+  __shared__ unsigned s_cnt2[2][40];
   unsigned parity = 0;
   const WorkMap wm = make_workmap(pm, cam);
   const unsigned count = wf_count(W, level, n0);
@@ -50,48 +89,70 @@ __global__ void __launch_bounds__(RTC_WF_SHADE_BLOCK, RTC_WF_SHADE_WAVES) wf_sha
   double* nq = W.rq[(level + 1) & 1];
   const int lane = RTC_LANE_ID;
   const int wave = (int)(threadIdx.x / (RTC_WF_SHADE_BLOCK >= 64 ? 64 : 1));
-  const int n_waves = RTC_WF_SHADE_BLOCK >= 64 ? RTC_WF_SHADE_BLOCK / 64 : 1;
-  for (unsigned base = blockIdx.x * RTC_WF_SHADE_BLOCK; base < count; base += gridDim.x * RTC_WF_SHADE_BLOCK) {  // block-uniform bound: barriers inside
-    const unsigned i = base + threadIdx.x;
-    int prim = -1;
-    if (i < count) prim = W.h_prim[i];
+  const unsigned long long step = (unsigned long long)gridDim.x * RTC_WF_SHADE_BLOCK;
+  WfShadeIn nx = {-1, {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, 1.0, 0.0};
+  int nx_prim = -1;
+  const bool level0 = PIPE ? LV0 : level == 0;
+  if (PIPE) {
+    const unsigned long long i0 = (unsigned long long)blockIdx.x * RTC_WF_SHADE_BLOCK + threadIdx.x;
+    nx = wf_shade_prefetch<LV0>(W, level, i0, lane, count, wf_shade_fetch_prim(W, i0, count));
+  }
+  for (unsigned long long base = (unsigned long long)blockIdx.x * RTC_WF_SHADE_BLOCK; base < count; base += step) {  // block-uniform bound: barriers inside
+    const unsigned i = (unsigned)base + threadIdx.x;
+    const WfShadeIn in = nx;
+    const int prim = PIPE ? in.prim : wf_shade_fetch_prim(W, i, count);
+    if (PIPE) nx_prim = wf_shade_fetch_prim(W, base + step + threadIdx.x, count);
     const bool hit = prim >= 0;
     State st;
     double cr = 0.0, cg = 0.0, cbl = 0.0, weight = 1.0, n1 = 1.0, n2 = 1.0;
-    int mat = 0, geom = 0;
+    int mat = 0, shading_row = 0, geom = 0;
     double reflective = 0.0, transparency = 0.0;
+    // mat >= 0: the record carries its colour (rows 6..8): the root pattern is not Plain, or blend_reflectance() made the colour the
+    // NaN it computed (whose bits no table knows).  mat < 0, material ~mat: the colour is the material's constant and the shadow role
+    // reads it with the Phong terms from the material's shading row (DScene.mat): sr_mat = RTC_SR_PLAIN | that row, rows 6..8 stay
+    // unwritten.  (One register for both facts: the PAT builds have none to spare.)
     if (hit) {
       Ray ray;
-      if (level == 0) {
+      if (level0) {
         uint64_t q = 0;
         (void)work_to_slot(wm, i, q);
         ray = slot_ray(pm, cam, q);
+      } else if (PIPE) {
+        ray = in.ray;
+        weight = in.weight;
       } else {
         ray = wf_load_ray(W, level, i, weight);
       }
       const DPrim P = S.prims[prim];
-      mat = P.mat;
       geom = P.geom;
       const double* M = S.mat + 8 * P.mat;
       reflective = M[4]; transparency = M[5];
+      mat = ~P.mat;
+      if (PIPE) shading_row = (int)M[7];  // (the other builds read it where they store it: they have no register to spare)
       double hu, hv;
       hit_uv(S, P, ray, hu, hv);
-      prepare_state(S, P, ray, W.h_t[i], hu, hv, st);
+      prepare_state(S, P, ray, PIPE ? in.t : W.h_t[i], hu, hv, st);
       if (transparency != 0.0 && fuel > 0) { n1 = W.h_n12[i]; n2 = W.h_n12[cap + i]; }  // stored under the same condition
-      // Pattern::color_at(material_inv * over_point) — identical for every light (src/shape.rs:437)
-      const double* mi = S.xf_matinv + 16 * P.xform;
-      double x = mi[0] * st.px + mi[1] * st.py + mi[2] * st.pz + mi[3] * 1.0;
-      double y = mi[4] * st.px + mi[5] * st.py + mi[6] * st.pz + mi[7] * 1.0;
-      double z = mi[8] * st.px + mi[9] * st.py + mi[10] * st.pz + mi[11] * 1.0;
-      double w = mi[12] * st.px + mi[13] * st.py + mi[14] * st.pz + mi[15] * 1.0;
-      const DPat& root = S.pats[S.mat_pattern[P.mat]];
-      if (!PAT || root.tag == 1) { cr = root.color[0]; cg = root.color[1]; cbl = root.color[2]; }
-      else if constexpr (UV) pattern_color_uv(S, S.mat_pattern[P.mat], x, y, z, w, cr, cg, cbl);
-      else pattern_color(S, S.mat_pattern[P.mat], x, y, z, w, cr, cg, cbl);
+      if constexpr (PAT) {
+        // Pattern::color_at(material_inv * over_point) — identical for every light (src/shape.rs:437)
+        const double* mi = S.xf_matinv + 16 * P.xform;
+        double x = mi[0] * st.px + mi[1] * st.py + mi[2] * st.pz + mi[3] * 1.0;
+        double y = mi[4] * st.px + mi[5] * st.py + mi[6] * st.pz + mi[7] * 1.0;
+        double z = mi[8] * st.px + mi[9] * st.py + mi[10] * st.pz + mi[11] * 1.0;
+        double w = mi[12] * st.px + mi[13] * st.py + mi[14] * st.pz + mi[15] * 1.0;
+        if (S.pats[S.mat_pattern[P.mat]].tag != 1) {
+          if constexpr (UV) pattern_color_uv(S, S.mat_pattern[P.mat], x, y, z, w, cr, cg, cbl);
+          else pattern_color(S, S.mat_pattern[P.mat], x, y, z, w, cr, cg, cbl);
+          mat = P.mat;
+        }
+      }
     }
     const bool blend = hit && reflective > 0.0 && transparency > 0.0;
     double R = 0.0;
-    if (blend) R = blend_reflectance(st, n1, n2, fuel, cr, cg, cbl);  // (a NaN reflectance: the record's colour becomes NaN)
+    if (blend) {
+      R = blend_reflectance(st, n1, n2, fuel, cr, cg, cbl);  // (a NaN reflectance: the record's colour becomes that NaN)
+      if (R != R && mat < 0) mat = ~mat;
+    }
     // reflected_color / refracted_color (src/world.rs:84-132), once per light in the reference -> factor L
     bool do_refl = false, do_refr = false;
     double wr = 0.0, wt = 0.0, tdx = 0.0, tdy = 0.0, tdz = 0.0;
@@ -116,40 +177,64 @@ __global__ void __launch_bounds__(RTC_WF_SHADE_BLOCK, RTC_WF_SHADE_WAVES) wf_sha
       }
     }
     // queue space: shade records and child rays (a wave's reflected rays first, then its refracted ones); one pair of
-    // atomics per block and iteration
+    // atomics per block and iteration, after the evaluation
     const unsigned long long lt = (1ull << lane) - 1ull;
     const bool on_plane = hit && geom == 1;
     const unsigned long long m_rec0 = __ballot(hit && on_plane ? 1 : 0), m_rec1 = __ballot(hit && !on_plane ? 1 : 0);
     const unsigned long long m_c0 = __ballot(do_refl && on_plane ? 1 : 0), m_c1 = __ballot(do_refl && !on_plane ? 1 : 0), m_c2 = __ballot(do_refr ? 1 : 0);
-    unsigned (*s_rec)[16] = s_rec2[parity];
-    unsigned (*s_child)[16] = s_child2[parity];
+    unsigned* s_cnt = s_cnt2[parity];
     parity ^= 1u;
     if (lane == 0) {
-      s_rec[0][wave] = (unsigned)__popcll(m_rec0); s_rec[1][wave] = (unsigned)__popcll(m_rec1);
-      s_child[0][wave] = (unsigned)__popcll(m_c0); s_child[1][wave] = (unsigned)__popcll(m_c1); s_child[2][wave] = (unsigned)__popcll(m_c2);
+      s_cnt[wave] = (unsigned)__popcll(m_rec0); s_cnt[8 + wave] = (unsigned)__popcll(m_rec1);
+      s_cnt[16 + wave] = (unsigned)__popcll(m_c0); s_cnt[24 + wave] = (unsigned)__popcll(m_c1); s_cnt[32 + wave] = (unsigned)__popcll(m_c2);
     }
+    if (PIPE) nx = wf_shade_prefetch<LV0>(W, level, base + step + threadIdx.x, lane, count, nx_prim);  // in flight across the reservation and the stores
     __syncthreads();
+#ifndef RTC_EMU
+    if (PIPE && n_waves == 8 && wave == 0) {
+      // one lane per counter: lanes 0..15 the record classes (one DPP row), 16..39 the child classes (a row and a half); both totals
+      // in one atomic instruction (lanes 0 and 1), so the block waits for one round trip
+      const unsigned c = lane < 40 ? s_cnt[lane] : 0u;
+      const unsigned in_row = wf_row_scan16(c);
+      const unsigned tr = (unsigned)__builtin_amdgcn_readlane((int)in_row, 15), t1 = (unsigned)__builtin_amdgcn_readlane((int)in_row, 31);
+      const unsigned tc = t1 + (unsigned)__builtin_amdgcn_readlane((int)in_row, 39);
+      const unsigned total = lane == 0 ? tr : tc;
+      unsigned old = 0u;
+      if (lane < 2 && total) {
+        old = atomicAdd(&W.counts[lane == 0 ? RTC_WF_SHADE_COUNT + level : level + 1], total);
+        if ((unsigned long long)old + total > W.cap) { W.counts[RTC_WF_OVERFLOW] = 1u; stats->wf_overflow = 1ull; }
+      }
+      const unsigned br = (unsigned)__builtin_amdgcn_readlane((int)old, 0), bc = (unsigned)__builtin_amdgcn_readlane((int)old, 1);
+      if (lane < 40) s_cnt[lane] = (lane < 16 ? br : bc + (lane >= 32 ? t1 : 0u)) + in_row - c;
+    }
+    if (!PIPE || n_waves != 8)
+#endif
     if (threadIdx.x == 0) {
       unsigned tr = 0, tc = 0;
-      for (int w = 0; w < n_waves; w++) { tr += s_rec[0][w] + s_rec[1][w]; tc += s_child[0][w] + s_child[1][w] + s_child[2][w]; }
+      for (int w = 0; w < n_waves; w++) { tr += s_cnt[w] + s_cnt[8 + w]; tc += s_cnt[16 + w] + s_cnt[24 + w] + s_cnt[32 + w]; }
       unsigned br = tr ? atomicAdd(&W.counts[RTC_WF_SHADE_COUNT + level], tr) : 0u;
       unsigned bc = tc ? atomicAdd(&W.counts[level + 1], tc) : 0u;
       if ((unsigned long long)br + tr > W.cap || (unsigned long long)bc + tc > W.cap) { W.counts[RTC_WF_OVERFLOW] = 1u; stats->wf_overflow = 1ull; }
       for (int k = 0; k < 2; k++)
-        for (int w = 0; w < n_waves; w++) { unsigned r = s_rec[k][w]; s_rec[k][w] = br; br += r; }
-      for (int k = 0; k < 3; k++)
-        for (int w = 0; w < n_waves; w++) { unsigned c = s_child[k][w]; s_child[k][w] = bc; bc += c; }
+        for (int w = 0; w < n_waves; w++) { unsigned r = s_cnt[8 * k + w]; s_cnt[8 * k + w] = br; br += r; }
+      for (int k = 2; k < 5; k++)
+        for (int w = 0; w < n_waves; w++) { unsigned c = s_cnt[8 * k + w]; s_cnt[8 * k + w] = bc; bc += c; }
     }
     __syncthreads();
-    const unsigned s = on_plane ? s_rec[0][wave] + (unsigned)__popcll(m_rec0 & lt) : s_rec[1][wave] + (unsigned)__popcll(m_rec1 & lt);
-    const unsigned jr = on_plane ? s_child[0][wave] + (unsigned)__popcll(m_c0 & lt) : s_child[1][wave] + (unsigned)__popcll(m_c1 & lt);
-    const unsigned jt = s_child[2][wave] + (unsigned)__popcll(m_c2 & lt);
+    const unsigned s = on_plane ? s_cnt[wave] + (unsigned)__popcll(m_rec0 & lt) : s_cnt[8 + wave] + (unsigned)__popcll(m_rec1 & lt);
+    const unsigned jr = on_plane ? s_cnt[16 + wave] + (unsigned)__popcll(m_c0 & lt) : s_cnt[24 + wave] + (unsigned)__popcll(m_c1 & lt);
+    const unsigned jt = s_cnt[32 + wave] + (unsigned)__popcll(m_c2 & lt);
     if (hit && s < W.cap) {
       double* r = W.sr;
       r[s] = st.px; r[cap + s] = st.py; r[2 * cap + s] = st.pz;
       r[3 * cap + s] = st.nx; r[4 * cap + s] = st.ny; r[5 * cap + s] = st.nz;
-      r[6 * cap + s] = cr; r[7 * cap + s] = cg; r[8 * cap + s] = cbl;
-      W.sr_mat[s] = mat;
+      if (mat >= 0) {
+        r[6 * cap + s] = cr; r[7 * cap + s] = cg; r[8 * cap + s] = cbl;
+        W.sr_mat[s] = mat;
+      } else {
+        if (!PIPE) shading_row = (int)S.mat[8 * ~mat + 7];
+        W.sr_mat[s] = RTC_SR_PLAIN | shading_row;
+      }
       W.sr_node[s] = (int32_t)i;
     }
     if (do_refl && jr < W.cap) {
@@ -259,7 +344,8 @@ void rtc_launch_wavefront(const DScene& S, const DCamera& cam, const DPixelMap& 
       }
 #endif
       if (count) hipLaunchKernelGGL((wf_shade<true>), sgrid, sblock, 0, stream, S, cam, pm, W, level, n0, fuel, stats);
-      else if (S.all_plain) hipLaunchKernelGGL((wf_shade<false, false>), sgrid, sblock, 0, stream, S, cam, pm, W, level, n0, fuel, stats);
+      else if (S.all_plain && level == 0) hipLaunchKernelGGL((wf_shade<false, false, false, true, true>), sgrid, sblock, 0, stream, S, cam, pm, W, level, n0, fuel, stats);
+      else if (S.all_plain) hipLaunchKernelGGL((wf_shade<false, false, false, true, false>), sgrid, sblock, 0, stream, S, cam, pm, W, level, n0, fuel, stats);
       else hipLaunchKernelGGL((wf_shade<false>), sgrid, sblock, 0, stream, S, cam, pm, W, level, n0, fuel, stats);
     }
   }

@@ -784,7 +784,7 @@ struct HostArrays {
     d.all_plain = 1;
     for (int32_t root : mat_pattern) if (root < 0 || (size_t)root >= pats.size() || pats[(size_t)root].tag != 1) d.all_plain = 0;
     d.no_glass_mirror = 1;
-    for (size_t m = 0; m + 7 < mat.size(); m += 8) if (mat[m + 4] != 0.0 && mat[m + 5] != 0.0) d.no_glass_mirror = 0;
+    for (size_t m = 0; m < mat_pattern.size(); m++) if (mat[8 * m + 4] != 0.0 && mat[8 * m + 5] != 0.0) d.no_glass_mirror = 0;  // (the shading rows follow)
     {
       // light_is_behind() relies on a finite ray never producing a NaN t (the reference would panic on one in a list of two or more,
       // whether or not the shadow test's answer matters): true while no intermediate of the intersection formulas can overflow
@@ -873,13 +873,18 @@ inline int build_arrays(const rtc_scene_desc& D, HostArrays* H, std::string* err
   H->limits.assign(D.limits, D.limits + (size_t)D.n_limits * 2);
   H->tri_geo.assign(D.tri_p1e1e2, D.tri_p1e1e2 + (size_t)D.n_tris * 9);
   H->tri_nrm.assign(D.tri_normals, D.tri_normals + (size_t)D.n_tris * 9);
-  H->mat.assign((size_t)D.n_materials * 8, 0.0);
+  H->mat.assign((size_t)D.n_materials * 16, 0.0);  // the material rows, then the shading rows (device_scene.h DScene.mat)
   H->mat_pattern.resize(D.n_materials);
   for (uint32_t i = 0; i < D.n_materials; i++) {
     const rtc_material& m = D.materials[i];
     double* q = &H->mat[(size_t)i * 8];
     q[0] = m.ambient; q[1] = m.diffuse; q[2] = m.specular; q[3] = m.shininess; q[4] = m.reflective; q[5] = m.transparency; q[6] = m.refractive_index;
     H->mat_pattern[i] = m.pattern;
+    q[7] = (double)((size_t)D.n_materials + i);
+    double* t = &H->mat[((size_t)D.n_materials + i) * 8];
+    t[0] = m.ambient; t[1] = m.diffuse; t[2] = m.specular; t[3] = m.shininess;
+    // the colour a record of this material carries when its root pattern is Plain: the bits wf_shade used to copy from the node
+    if (m.pattern >= 0 && (uint32_t)m.pattern < D.n_pattern_nodes && D.pattern_nodes[m.pattern].tag == 1) std::memcpy(t + 4, D.pattern_nodes[m.pattern].color, 3 * sizeof(double));
   }
   H->pats.resize(D.n_pattern_nodes);
   for (uint32_t i = 0; i < D.n_pattern_nodes; i++) {
