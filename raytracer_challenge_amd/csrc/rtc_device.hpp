@@ -1378,8 +1378,9 @@ __device__ __forceinline__ double blend_reflectance(const State& st, double n1, 
 // 0 * inf is ignored by f64::max / min unless all three axes have one; infinite limits give infinite, not NaN, cap t's), which
 // DScene.backface_skip vouches for together with the bound on |v| here.  The decision uses v . n with a margin of 1e-6 |v| -- far
 // outside the rounding of the reference's own `(v / |v|) . n` (~1e-15), so every ray skipped here has a computed light . normal
-// below zero; NaN operands fail the comparisons (then the ray is traced).  v = light - over_point, n = the unit normal.
-__device__ __forceinline__ bool light_is_behind(const DScene& S, double vx, double vy, double vz, double nx, double ny, double nz) {
+// below zero; NaN operands fail the comparisons (then the ray is traced).  v = light - over_point (shadow_ray()'s v), n = the unit normal.
+__device__ __forceinline__ bool light_is_behind(const DScene& S, double px, double py, double pz, double lx, double ly, double lz, double nx, double ny, double nz) {
+  const double vx = lx - px, vy = ly - py, vz = lz - pz;
   const double vn = vx * nx + vy * ny + vz * nz, vv = vx * vx + vy * vy + vz * vz;
   return S.backface_skip && vn < 0.0 && vn * vn > 1e-12 * vv && vv < 1e60;
 }
@@ -1478,6 +1479,161 @@ __device__ __forceinline__ Ray slot_ray(const DPixelMap& pm, const DCamera& cam,
   return camera_ray(cam, i);
 }
 
+// ---- World::shade_hit's pieces (src/world.rs:50-132): ONE copy of each, called by the one-kernel path, by the wavefront kernels and
+// by shade_lights_area, so that a formula or its operation order cannot differ between the device paths -------------
+
+// The shadow ray of World::is_shadowed (src/world.rs:139-143): v = light - point, distance = |v|, direction = v / distance -- which is
+// also Shape::lighting's light vector, (light - point).normalize() (src/shape.rs:440).
+struct ShadowRay {
+  Ray ray;
+  double distance;
+};
+__device__ __forceinline__ ShadowRay shadow_ray(double px, double py, double pz, double lx, double ly, double lz) {
+  const double vx = lx - px, vy = ly - py, vz = lz - pz;
+  ShadowRay s;
+  s.distance = sqrt(vx * vx + vy * vy + vz * vz);
+  s.ray.ox = px; s.ray.oy = py; s.ray.oz = pz;
+  s.ray.dx = vx / s.distance; s.ray.dy = vy / s.distance; s.ray.dz = vz / s.distance;
+  return s;
+}
+
+// World::is_shadowed (src/world.rs:134-149), the two halves around the traversal of the shadow ray: an any-hit pass where every shape
+// casts a shadow (DScene.all_cast_shadow), else the closest hit decides with its shape's casts_shadow flag.  light: the light grid the
+// ray may use, or -1; unordered: the any-hit pass skips the nearest-first ordering (wavefront and area code; a measured choice, like
+// their compile-time pass mode).  The traverse() call itself stays with the caller: as part of one shared function -- traverse() inlined
+// into it, it into the kernel -- thirteen kernels changed their scratch size by 16-48 B (profiles/shade_helpers_isa_diff.txt).
+__device__ __forceinline__ Trav shadow_pass(const DScene& S, double distance, int light, bool unordered) {
+  Trav Sh;
+  reset_closest(Sh, S.all_cast_shadow ? MODE_SHADOW_ANY : MODE_SHADOW_CLOSEST);
+  if (S.all_cast_shadow) { Sh.thi = distance; Sh.unordered = unordered ? 1 : 0; }
+  Sh.light = light; Sh.c1_t = distance;
+  return Sh;
+}
+__device__ __forceinline__ bool shadow_result(const DScene& S, const Trav& Sh, double distance, Counters& C) {
+  nan_commit(Sh, C);
+  if (S.all_cast_shadow) return Sh.shadowed != 0;
+  return (Sh.best_prim != 0x7fffffff) && (S.prims[Sh.best_prim].flags & 1u) && (Sh.best_t < distance);
+}
+
+// Shape::lighting (src/shape.rs:429-462) for one light, added to (sr, sg, sb).  LG: the light's intensity; (ldx, ldy, ldz): the light
+// vector = the shadow ray's direction; n, e: normal and eye; c: the pattern colour at the point.
+__device__ __forceinline__ void phong_add(const double* LG, double ldx, double ldy, double ldz, bool shadowed, double nx, double ny, double nz, double ex, double ey,
+                                          double ez, double cr, double cg, double cb, double ambient, double diffuse, double specular, double shininess, double& sr,
+                                          double& sg, double& sb) {
+  const double er = cr * LG[0], eg = cg * LG[1], eb = cb * LG[2];  // effective_color
+  const double lr = er * ambient, lg = eg * ambient, lb = eb * ambient;
+  const double ldn = ldx * nx + ldy * ny + ldz * nz;
+  double dr = 0.0, dg = 0.0, db = 0.0, pr = 0.0, pg = 0.0, pb = 0.0;
+  if (!shadowed && ldn >= 0.0) {
+    dr = er * diffuse * ldn; dg = eg * diffuse * ldn; db = eb * diffuse * ldn;
+    // reflect = (-light).reflect(normal)
+    const double mlx = -ldx, mly = -ldy, mlz = -ldz;
+    const double d2 = 2.0 * (mlx * nx + mly * ny + mlz * nz);
+    const double rfx = mlx - nx * d2, rfy = mly - ny * d2, rfz = mlz - nz * d2;
+    const double rde = rfx * ex + rfy * ey + rfz * ez;
+    if (rde > 0.0) {
+      const double f = specular_factor(rde, shininess, specular);
+      pr = LG[0] * specular * f; pg = LG[1] * specular * f; pb = LG[2] * specular * f;
+    }
+  }
+  sr += (lr + dr) + pr; sg += (lg + dg) + pg; sb += (lb + db) + pb;
+}
+
+// The same sum for a light that light_is_behind() took out: ambient term only, in the expression of the general case (diffuse and
+// specular stay the 0.0 they start as, src/shape.rs:446-447).
+__device__ __forceinline__ void ambient_add(const double* LG, double cr, double cg, double cb, double ambient, double& sr, double& sg, double& sb) {
+  const double lr = (cr * LG[0]) * ambient, lg = (cg * LG[1]) * ambient, lb = (cb * LG[2]) * ambient;
+  sr += (lr + 0.0) + 0.0; sg += (lg + 0.0) + 0.0; sb += (lb + 0.0) + 0.0;
+}
+
+// n1 / n2 of Intersection::prepare_state (src/intersection.rs:70-103), the two halves around the container pass (the caller's
+// traverse<..., MODE_CONTAINERS> over the same ray, for the reason given at shadow_pass): its state from the finished closest pass T,
+// which keeps the hit key (thi = best_t, best_prim, best_klast); then the refractive indices of the two shapes it found, 1.0 for none.
+struct N12 {
+  double n1, n2;
+};
+__device__ __forceinline__ Trav container_trav(const Trav& T) {
+  Trav K = T;
+  K.mode = MODE_CONTAINERS;
+  K.tlo = -DINF; K.thi = T.best_t;
+  K.c1_prim = -1; K.c2_prim = -1; K.c1_t = 0.0; K.c2_t = 0.0;
+  return K;
+}
+__device__ __forceinline__ N12 container_n12(const DScene& S, const Trav& K) {
+  N12 n = {1.0, 1.0};
+  if (K.c1_prim >= 0) n.n1 = S.mat[8 * S.prims[K.c1_prim].mat + 6];
+  if (K.c2_prim >= 0) n.n2 = S.mat[8 * S.prims[K.c2_prim].mat + 6];
+  return n;
+}
+
+// Pattern::color_at(material_inv * over_point) (src/shape.rs:437) -- identical for every light -- for a material whose root pattern
+// is not Plain (a Plain root's colour: DPat.color on the one-kernel path, the material's shading row on the wavefront path).
+template <bool UV>
+__device__ __forceinline__ void pattern_at(const DScene& S, const DPrim& P, const State& st, double& r, double& g, double& b) {
+  const double* mi = S.xf_matinv + 16 * P.xform;
+  const double x = mi[0] * st.px + mi[1] * st.py + mi[2] * st.pz + mi[3] * 1.0;
+  const double y = mi[4] * st.px + mi[5] * st.py + mi[6] * st.pz + mi[7] * 1.0;
+  const double z = mi[8] * st.px + mi[9] * st.py + mi[10] * st.pz + mi[11] * 1.0;
+  const double w = mi[12] * st.px + mi[13] * st.py + mi[14] * st.pz + mi[15] * 1.0;
+  if constexpr (UV) pattern_color_uv(S, S.mat_pattern[P.mat], x, y, z, w, r, g, b);
+  else pattern_color(S, S.mat_pattern[P.mat], x, y, z, w, r, g, b);
+}
+
+// reflected_color / refracted_color (src/world.rs:84-132) of a hit with fuel left: which child rays it spawns, their path weights
+// (once per light in the reference -> factor L; a reflective and transparent surface blends them with the reflectance R) and the
+// refracted direction (Snell; total internal reflection spawns none).  The reflected direction is State's.
+struct ChildRays {
+  bool refl, refr;
+  double wr, wt, tdx, tdy, tdz;
+};
+__device__ __forceinline__ ChildRays child_rays(const State& st, double n1, double n2, double weight, double L, double reflective, double transparency, bool blend, double R) {
+  ChildRays c = {reflective != 0.0, transparency != 0.0, weight * L * reflective, weight * L * transparency, 0.0, 0.0, 0.0};
+  if (blend) {
+    c.wr *= R;
+    c.wt *= (1.0 - R);
+  }
+  if (c.refr) {
+    const double n_ratio = n1 / n2;
+    const double cos_i = st.ex * st.nx + st.ey * st.ny + st.ez * st.nz;
+    const double sin2_t = (n_ratio * n_ratio) * (1.0 - cos_i * cos_i);
+    if (sin2_t > 1.0) c.refr = false;
+    else {
+      const double cos_t = sqrt(1.0 - sin2_t);
+      const double kk = n_ratio * cos_i - cos_t;
+      c.tdx = st.nx * kk - st.ex * n_ratio; c.tdy = st.ny * kk - st.ey * n_ratio; c.tdz = st.nz * kk - st.ez * n_ratio;
+    }
+  }
+  return c;
+}
+
+// The primary-hit record of output slot q (include/rtc.h rtc_hit) and the hit-hash base of a ray (device_scene.h rtc_hit_hash), from
+// its finished closest pass; a miss is (t 0, primitive -1, push 0).
+__device__ __forceinline__ bool trav_hit(const Trav& T) { return T.best_prim != 0x7fffffff; }
+__device__ __forceinline__ void store_primary_hit(const Trav& T, uint64_t q, double* __restrict__ hit_t, int* __restrict__ hit_prim, int* __restrict__ hit_k) {
+  const bool did_hit = trav_hit(T);
+  hit_t[q] = did_hit ? T.best_t : 0.0;
+  hit_prim[q] = did_hit ? T.best_prim : -1;
+  hit_k[q] = did_hit ? T.best_k : 0;
+}
+__device__ __forceinline__ unsigned long long trav_hash_base(const Trav& T) {
+  const bool did_hit = trav_hit(T);
+  unsigned long long tb = 0ull;
+  if (did_hit) __builtin_memcpy(&tb, &T.best_t, 8);
+  return rtc_hit_hash_base(tb, did_hit ? T.best_prim : -1, did_hit ? T.best_k : 0);
+}
+
+// A ray kernel's traversal counters into the launch's statistics (counting variants).
+__device__ __forceinline__ void publish_counters(DStats* __restrict__ stats, const Counters& C) {
+  atomicAdd(&stats->accel_nodes, (unsigned long long)C.accel_nodes);
+  atomicAdd(&stats->group_tests, (unsigned long long)C.group_tests);
+  atomicAdd(&stats->tri_tests, (unsigned long long)C.tri_tests);
+  atomicAdd(&stats->analytic_tests, (unsigned long long)C.analytic_tests);
+  atomicAdd(&stats->knodes, (unsigned long long)C.knodes);
+  atomicAdd(&stats->kplanes, (unsigned long long)C.kplanes);
+  atomicAdd(&stats->light_cells, (unsigned long long)C.light_cells);
+  atomicAdd(&stats->kgroups, (unsigned long long)C.kgroups);
+}
+
 }  // namespace
 
 // Area lights (include/rtc.h rtc_light_ex; DScene.has_area: RTC_ALIGHT doubles per light): World::shade_hit's per-light terms
@@ -1510,45 +1666,20 @@ __device__ __forceinline__ void shade_lights_area(const DScene& S, double px, do
         ly = (LG[4] + LG[7] * fu) + LG[10] * fv;
         lz = (LG[5] + LG[8] * fu) + LG[11] * fv;
       }
-      const double vx = lx - px, vy = ly - py, vz = lz - pz;
       n_shadow++;
-      if (BEHIND && light_is_behind(S, vx, vy, vz, nx, ny, nz)) {  // ambient term only, in the expression of the general case
-        const double lr = (cr * LG[0]) * ambient, lg = (cg * LG[1]) * ambient, lb = (cb * LG[2]) * ambient;
-        sr += (lr + 0.0) + 0.0; sg += (lg + 0.0) + 0.0; sb += (lb + 0.0) + 0.0;
+      if (BEHIND && light_is_behind(S, px, py, pz, lx, ly, lz, nx, ny, nz)) {
+        ambient_add(LG, cr, cg, cb, ambient, sr, sg, sb);
         continue;
       }
-      const double distance = sqrt(vx * vx + vy * vy + vz * vz);
-      Ray sray;
-      sray.ox = px; sray.oy = py; sray.oz = pz;
-      sray.dx = vx / distance; sray.dy = vy / distance; sray.dz = vz / distance;
-      Trav Sh;
+      const ShadowRay s = shadow_ray(px, py, pz, lx, ly, lz);
+      Trav Sh;  // mirrors shadow_pass(S, s.distance, light, true): calling it here adds 32 B of scratch to three area kernels of variant 6
       reset_closest(Sh, S.all_cast_shadow ? MODE_SHADOW_ANY : MODE_SHADOW_CLOSEST);
-      if (S.all_cast_shadow) { Sh.thi = distance; Sh.unordered = 1; }
-      Sh.light = area ? -1 : (int)LG[15]; Sh.c1_t = distance;
-      if (S.all_cast_shadow) traverse<FEAT, KOPS, MODE_SHADOW_ANY, LDSC>(S, sray, Sh, C, stack, stride, Ls);
-      else traverse<FEAT, KOPS, MODE_SHADOW_CLOSEST, LDSC>(S, sray, Sh, C, stack, stride, Ls);
-      nan_commit(Sh, C);
-      bool shadowed;
-      if (S.all_cast_shadow) shadowed = Sh.shadowed != 0;
-      else shadowed = (Sh.best_prim != 0x7fffffff) && (S.prims[Sh.best_prim].flags & 1u) && (Sh.best_t < distance);
-      const double er = cr * LG[0], eg = cg * LG[1], eb = cb * LG[2];  // effective_color
-      const double lr = er * ambient, lg = eg * ambient, lb = eb * ambient;
-      // light vector: (p_k - point).normalize() -- the shadow ray's direction
-      const double ldn = sray.dx * nx + sray.dy * ny + sray.dz * nz;
-      double dr = 0.0, dg = 0.0, db = 0.0, pr = 0.0, pg = 0.0, pb = 0.0;
-      if (!shadowed && ldn >= 0.0) {
-        dr = er * diffuse * ldn; dg = eg * diffuse * ldn; db = eb * diffuse * ldn;
-        // reflect = (-light).reflect(normal)
-        const double mlx = -sray.dx, mly = -sray.dy, mlz = -sray.dz;
-        const double d2 = 2.0 * (mlx * nx + mly * ny + mlz * nz);
-        const double rfx = mlx - nx * d2, rfy = mly - ny * d2, rfz = mlz - nz * d2;
-        const double rde = rfx * ex + rfy * ey + rfz * ez;
-        if (rde > 0.0) {
-          const double f = specular_factor(rde, shininess, specular);
-          pr = LG[0] * specular * f; pg = LG[1] * specular * f; pb = LG[2] * specular * f;
-        }
-      }
-      sr += (lr + dr) + pr; sg += (lg + dg) + pg; sb += (lb + db) + pb;
+      if (S.all_cast_shadow) { Sh.thi = s.distance; Sh.unordered = 1; }
+      Sh.light = area ? -1 : (int)LG[15]; Sh.c1_t = s.distance;
+      if (S.all_cast_shadow) traverse<FEAT, KOPS, MODE_SHADOW_ANY, LDSC>(S, s.ray, Sh, C, stack, stride, Ls);
+      else traverse<FEAT, KOPS, MODE_SHADOW_CLOSEST, LDSC>(S, s.ray, Sh, C, stack, stride, Ls);
+      const bool shadowed = shadow_result(S, Sh, s.distance, C);
+      phong_add(LG, s.ray.dx, s.ray.dy, s.ray.dz, shadowed, nx, ny, nz, ex, ey, ez, cr, cg, cb, ambient, diffuse, specular, shininess, sr, sg, sb);
     }
   }
 }
@@ -1608,21 +1739,12 @@ __global__ void __launch_bounds__(RTC_BLOCK, WAVES ? WAVES : ((FEAT >= 2 && RTC_
       traverse<FEAT, KOPS, MODE_CLOSEST>(S, ray, T, C, stack, stride);
       nan_commit(T, C);
       DIAG_REGION(0);
-      bool did_hit = T.best_prim != 0x7fffffff;
-      if (COUNT && pm.digest) {
-        unsigned long long tb = 0ull;
-        if (did_hit) __builtin_memcpy(&tb, &T.best_t, 8);
-        dg += rtc_hit_hash(rtc_hit_hash_base(tb, did_hit ? T.best_prim : -1, did_hit ? T.best_k : 0), fuel0 - fuel, kind);
-      }
+      if (COUNT && pm.digest) dg += rtc_hit_hash(trav_hash_base(T), fuel0 - fuel, kind);
       if (first) {
         first = false;
-        if (hit_t) {
-          hit_t[q] = did_hit ? T.best_t : 0.0;
-          hit_prim[q] = did_hit ? T.best_prim : -1;
-          hit_k[q] = did_hit ? T.best_k : 0;
-        }
+        if (hit_t) store_primary_hit(T, q, hit_t, hit_prim, hit_k);
       }
-      if (did_hit) {
+      if (trav_hit(T)) {
         const DPrim P = S.prims[T.best_prim];
         const double* M = S.mat + 8 * P.mat;
         const double ambient = M[0], diffuse = M[1], specular = M[2], shininess = M[3], reflective = M[4], transparency = M[5];
@@ -1635,29 +1757,17 @@ __global__ void __launch_bounds__(RTC_BLOCK, WAVES ? WAVES : ((FEAT >= 2 && RTC_
         double n1 = 1.0, n2 = 1.0;
         if (transparency != 0.0 && fuel > 0) {
           n_container++;
-          Trav K = T;  // keeps the hit key (thi = best_t, best_prim, best_klast)
-          K.mode = MODE_CONTAINERS;
-          K.tlo = -DINF; K.thi = T.best_t;
-          K.c1_prim = -1; K.c2_prim = -1; K.c1_t = 0.0; K.c2_t = 0.0;
+          Trav K = container_trav(T);
           traverse<FEAT, KOPS, MODE_CONTAINERS>(S, ray, K, C, stack, stride);
-          if (K.c1_prim >= 0) n1 = S.mat[8 * S.prims[K.c1_prim].mat + 6];
-          if (K.c2_prim >= 0) n2 = S.mat[8 * S.prims[K.c2_prim].mat + 6];
+          const N12 n = container_n12(S, K);
+          n1 = n.n1; n2 = n.n2;
           DIAG_REGION(1);
         }
 
-        // Pattern::color_at(material_inv * over_point) — identical for every light (src/shape.rs:437)
         double cr, cg, cb;
-        {
-          const double* mi = S.xf_matinv + 16 * P.xform;
-          double x = mi[0] * st.px + mi[1] * st.py + mi[2] * st.pz + mi[3] * 1.0;
-          double y = mi[4] * st.px + mi[5] * st.py + mi[6] * st.pz + mi[7] * 1.0;
-          double z = mi[8] * st.px + mi[9] * st.py + mi[10] * st.pz + mi[11] * 1.0;
-          double w = mi[12] * st.px + mi[13] * st.py + mi[14] * st.pz + mi[15] * 1.0;
-          const DPat& root = S.pats[S.mat_pattern[P.mat]];
-          if (LEAN || root.tag == 1) { cr = root.color[0]; cg = root.color[1]; cb = root.color[2]; }
-          else if constexpr (UV) pattern_color_uv(S, S.mat_pattern[P.mat], x, y, z, w, cr, cg, cb);
-          else pattern_color(S, S.mat_pattern[P.mat], x, y, z, w, cr, cg, cb);
-        }
+        const DPat& root = S.pats[S.mat_pattern[P.mat]];
+        if (LEAN || root.tag == 1) { cr = root.color[0]; cg = root.color[1]; cb = root.color[2]; }
+        else pattern_at<UV>(S, P, st, cr, cg, cb);
 
         const bool blend = !LEAN && reflective > 0.0 && transparency > 0.0;  // (LEAN: DScene.no_glass_mirror)
         double R = 0.0;
@@ -1673,86 +1783,39 @@ __global__ void __launch_bounds__(RTC_BLOCK, WAVES ? WAVES : ((FEAT >= 2 && RTC_
         for (int l = 0; l < S.n_lights; l++) {
           DIAG_LOOP(5);
           const double* LG = S.lights + 6 * l;
-          double vx = LG[3] - st.px, vy = LG[4] - st.py, vz = LG[5] - st.pz;
           n_shadow++;
-          if (light_is_behind(S, vx, vy, vz, st.nx, st.ny, st.nz)) {  // ambient term only, in the expression of the general case
-            const double lr = (cr * LG[0]) * ambient, lg = (cg * LG[1]) * ambient, lb = (cb * LG[2]) * ambient;
-            sr += (lr + 0.0) + 0.0; sg += (lg + 0.0) + 0.0; sb += (lb + 0.0) + 0.0;
+          if (light_is_behind(S, st.px, st.py, st.pz, LG[3], LG[4], LG[5], st.nx, st.ny, st.nz)) {
+            ambient_add(LG, cr, cg, cb, ambient, sr, sg, sb);
             continue;
           }
-          double distance = sqrt(vx * vx + vy * vy + vz * vz);
-          Ray sray;
-          sray.ox = st.px; sray.oy = st.py; sray.oz = st.pz;
-          sray.dx = vx / distance; sray.dy = vy / distance; sray.dz = vz / distance;
-          Trav Sh;
-          reset_closest(Sh, S.all_cast_shadow ? MODE_SHADOW_ANY : MODE_SHADOW_CLOSEST);
-          if (S.all_cast_shadow) Sh.thi = distance;
-          Sh.light = l; Sh.c1_t = distance;
+          const ShadowRay s = shadow_ray(st.px, st.py, st.pz, LG[3], LG[4], LG[5]);
           DIAG_T0();
-          traverse<FEAT, KOPS>(S, sray, Sh, C, stack, stride);
-          nan_commit(Sh, C);
+          Trav Sh = shadow_pass(S, s.distance, l, false);
+          traverse<FEAT, KOPS>(S, s.ray, Sh, C, stack, stride);
+          const bool shadowed = shadow_result(S, Sh, s.distance, C);
           DIAG_REGION(3);
-          bool shadowed;
-          if (S.all_cast_shadow) shadowed = Sh.shadowed != 0;
-          else shadowed = (Sh.best_prim != 0x7fffffff) && (S.prims[Sh.best_prim].flags & 1u) && (Sh.best_t < distance);
-
-          double er = cr * LG[0], eg = cg * LG[1], eb = cb * LG[2];  // effective_color
-          double lr = er * ambient, lg = eg * ambient, lb = eb * ambient;
-          // light vector: (light.origin - point).normalize() — same numbers as the shadow ray direction
-          double ldn = sray.dx * st.nx + sray.dy * st.ny + sray.dz * st.nz;
-          double dr = 0.0, dg = 0.0, db = 0.0, pr = 0.0, pg = 0.0, pb = 0.0;
-          if (!shadowed && ldn >= 0.0) {
-            dr = er * diffuse * ldn; dg = eg * diffuse * ldn; db = eb * diffuse * ldn;
-            // reflect = (-light).reflect(normal)
-            double mlx = -sray.dx, mly = -sray.dy, mlz = -sray.dz;
-            double d2 = 2.0 * (mlx * st.nx + mly * st.ny + mlz * st.nz);
-            double rfx = mlx - st.nx * d2, rfy = mly - st.ny * d2, rfz = mlz - st.nz * d2;
-            double rde = rfx * st.ex + rfy * st.ey + rfz * st.ez;
-            if (rde > 0.0) {
-              double f = specular_factor(rde, shininess, specular);
-              pr = LG[0] * specular * f; pg = LG[1] * specular * f; pb = LG[2] * specular * f;
-            }
-          }
-          sr += (lr + dr) + pr; sg += (lg + dg) + pg; sb += (lb + db) + pb;
+          phong_add(LG, s.ray.dx, s.ray.dy, s.ray.dz, shadowed, st.nx, st.ny, st.nz, st.ex, st.ey, st.ez, cr, cg, cb, ambient, diffuse, specular, shininess, sr, sg, sb);
         }
         acc_r += weight * sr; acc_g += weight * sg; acc_b += weight * sb;
         DIAG_T0();
 
         // reflected_color / refracted_color (src/world.rs:84-132), once per light in the reference -> factor L
         if (fuel > 0) {
-          bool do_refl = reflective != 0.0;
-          bool do_refr = transparency != 0.0;
-          double wr = weight * L * reflective, wt = weight * L * transparency;
-          if (blend) {
-            wr *= R;
-            wt *= (1.0 - R);
-          }
-          double tdx = 0.0, tdy = 0.0, tdz = 0.0;
-          if (do_refr) {
-            double n_ratio = n1 / n2;
-            double cos_i = st.ex * st.nx + st.ey * st.ny + st.ez * st.nz;
-            double sin2_t = (n_ratio * n_ratio) * (1.0 - cos_i * cos_i);
-            if (sin2_t > 1.0) do_refr = false;
-            else {
-              double cos_t = sqrt(1.0 - sin2_t);
-              double kk = n_ratio * cos_i - cos_t;
-              tdx = st.nx * kk - st.ex * n_ratio; tdy = st.ny * kk - st.ey * n_ratio; tdz = st.nz * kk - st.ez * n_ratio;
-            }
-          }
+          const ChildRays spawn = child_rays(st, n1, n2, weight, L, reflective, transparency, blend, R);
           // depth-first: the reflection ray (if any) is traced next; only a refraction ray that has to wait is stacked
-          if (!LEAN && do_refr && do_refl) {
+          if (!LEAN && spawn.refr && spawn.refl) {
             Pending& p = pend[np++];
-            p.ox = st.ux; p.oy = st.uy; p.oz = st.uz; p.dx = tdx; p.dy = tdy; p.dz = tdz;
-            p.weight = wt; p.fuel = fuel - 1; p.kind = 2;
+            p.ox = st.ux; p.oy = st.uy; p.oz = st.uz; p.dx = spawn.tdx; p.dy = spawn.tdy; p.dz = spawn.tdz;
+            p.weight = spawn.wt; p.fuel = fuel - 1; p.kind = 2;
           }
-          if (do_refl) {
+          if (spawn.refl) {
             ray.ox = st.px; ray.oy = st.py; ray.oz = st.pz; ray.dx = st.rx; ray.dy = st.ry; ray.dz = st.rz;
-            weight = wr; fuel = fuel - 1; kind = 1;
+            weight = spawn.wr; fuel = fuel - 1; kind = 1;
             continue;
           }
-          if (do_refr) {
-            ray.ox = st.ux; ray.oy = st.uy; ray.oz = st.uz; ray.dx = tdx; ray.dy = tdy; ray.dz = tdz;
-            weight = wt; fuel = fuel - 1; kind = 2;
+          if (spawn.refr) {
+            ray.ox = st.ux; ray.oy = st.uy; ray.oz = st.uz; ray.dx = spawn.tdx; ray.dy = spawn.tdy; ray.dz = spawn.tdz;
+            weight = spawn.wt; fuel = fuel - 1; kind = 2;
             continue;
           }
         }
@@ -1785,14 +1848,7 @@ __global__ void __launch_bounds__(RTC_BLOCK, WAVES ? WAVES : ((FEAT >= 2 && RTC_
     atomicAdd(&stats->rays_reflect, (unsigned long long)n_reflect);
     atomicAdd(&stats->rays_refract, (unsigned long long)n_refract);
     atomicAdd(&stats->rays_container, (unsigned long long)n_container);
-    atomicAdd(&stats->accel_nodes, (unsigned long long)C.accel_nodes);
-    atomicAdd(&stats->group_tests, (unsigned long long)C.group_tests);
-    atomicAdd(&stats->tri_tests, (unsigned long long)C.tri_tests);
-    atomicAdd(&stats->analytic_tests, (unsigned long long)C.analytic_tests);
-    atomicAdd(&stats->knodes, (unsigned long long)C.knodes);
-    atomicAdd(&stats->kplanes, (unsigned long long)C.kplanes);
-    atomicAdd(&stats->light_cells, (unsigned long long)C.light_cells);
-    atomicAdd(&stats->kgroups, (unsigned long long)C.kgroups);
+    publish_counters(stats, C);
   }
 }
 
@@ -1818,6 +1874,34 @@ __device__ __forceinline__ Ray wf_load_ray(const DWave& W, int level, unsigned i
   r.ox = q[i]; r.oy = q[cap + i]; r.oz = q[2 * cap + i]; r.dx = q[3 * cap + i]; r.dy = q[4 * cap + i]; r.dz = q[5 * cap + i];
   weight = q[6 * cap + i];
   return r;
+}
+
+// A shade record's eye vector (= -direction, src/intersection.rs:56) and path weight: they come from where the record's ray `node`
+// came from -- the level's queue (still intact: the next shading kernel is the first to overwrite it) or, at level 0, the camera.
+struct RecView {
+  double ex, ey, ez, weight;
+};
+__device__ __forceinline__ RecView shade_rec_view(const DCamera& cam, const DPixelMap& pm, const DWave& W, const WorkMap& wm, int level, int node) {
+  if (level == 0) {
+    uint64_t q = 0;
+    (void)work_to_slot(wm, (unsigned)node, q);
+    const Ray pr = slot_ray(pm, cam, q);
+    return {-pr.dx, -pr.dy, -pr.dz, 1.0};
+  }
+  const double* rq = W.rq[level & 1];
+  const size_t cap = W.cap;
+  return {-rq[3 * cap + node], -rq[4 * cap + node], -rq[5 * cap + node], rq[6 * cap + node]};
+}
+// A shade record's row of the material table (the Phong terms M[0..3]) and its colour: for a material whose root pattern is Plain
+// (RTC_SR_PLAIN) the same row holds it, any other record carries its colour in rows 6..8 (wf_shade).
+__device__ __forceinline__ const double* shade_rec_material(const DScene& S, const DWave& W, unsigned s, double& cr, double& cg, double& cb) {
+  const double* r = W.sr;
+  const size_t cap = W.cap;
+  const int mrow = W.sr_mat[s];
+  const double* M = S.mat + 8 * (mrow & (RTC_SR_PLAIN - 1));
+  if (mrow & RTC_SR_PLAIN) { cr = M[4]; cg = M[5]; cb = M[6]; }
+  else { cr = r[6 * cap + s]; cg = r[7 * cap + s]; cb = r[8 * cap + s]; }
+  return M;
 }
 
 }  // namespace
@@ -1848,18 +1932,10 @@ __device__ __forceinline__ void wf_trace_ray(const DScene& S, const DCamera& cam
     nan_commit(T, C);
     DIAG_SPAN_END(0);
   }
-  const bool did_hit = T.best_prim != 0x7fffffff;
-  if (level == 0 && hit_t) {
-    hit_t[q] = did_hit ? T.best_t : 0.0;
-    hit_prim[q] = did_hit ? T.best_prim : -1;
-    hit_k[q] = did_hit ? T.best_k : 0;
-  }
+  const bool did_hit = trav_hit(T);
+  if (level == 0 && hit_t) store_primary_hit(T, q, hit_t, hit_prim, hit_k);
   W.h_prim[i] = did_hit ? T.best_prim : -1;
-  if (digest) {
-    unsigned long long tb = 0ull;
-    if (did_hit) __builtin_memcpy(&tb, &T.best_t, 8);
-    W.dig[(size_t)level * cap + i] = rtc_hit_hash_base(tb, did_hit ? T.best_prim : -1, did_hit ? T.best_k : 0);
-  }
+  if (digest) W.dig[(size_t)level * cap + i] = trav_hash_base(T);
   // child links: none yet; a miss is marked as such (the gather then knows that no contribution was written for this ray)
   ch[i] = did_hit ? -1 : RTC_WF_MISS; ch[cap + i] = -1;
   if (!did_hit) return;
@@ -1867,12 +1943,8 @@ __device__ __forceinline__ void wf_trace_ray(const DScene& S, const DCamera& cam
   // n1 / n2 are only consumed — and only stored — when the surface is transparent and the hit can still spawn rays
   // (src/world.rs:70-78, :110); wf_shade reads them under the same condition
   if (fuel_left > 0 && S.mat[8 * S.prims[T.best_prim].mat + 5] != 0.0) {
-    double n1 = 1.0, n2 = 1.0;
     n_container++;
-    Trav K = T;  // keeps the hit key (thi = best_t, best_prim, best_klast)
-    K.mode = MODE_CONTAINERS;
-    K.tlo = -DINF; K.thi = T.best_t;
-    K.c1_prim = -1; K.c2_prim = -1; K.c1_t = 0.0; K.c2_t = 0.0;
+    Trav K = container_trav(T);
     DIAG_LOOP(19);
     {
       DIAG_SPAN_BEGIN();
@@ -1884,9 +1956,8 @@ __device__ __forceinline__ void wf_trace_ray(const DScene& S, const DCamera& cam
       }
       DIAG_SPAN_END(1);
     }
-    if (K.c1_prim >= 0) n1 = S.mat[8 * S.prims[K.c1_prim].mat + 6];
-    if (K.c2_prim >= 0) n2 = S.mat[8 * S.prims[K.c2_prim].mat + 6];
-    W.h_n12[i] = n1; W.h_n12[cap + i] = n2;
+    const N12 n = container_n12(S, K);
+    W.h_n12[i] = n.n1; W.h_n12[cap + i] = n.n2;
   }
 }
 
@@ -1905,81 +1976,38 @@ __device__ __forceinline__ void wf_shadow_rec(const DScene& S, const DCamera& ca
   unsigned long long shadow_mask = 0ull;  // <= 64 lights (checked at scene creation)
   for (int l = 0; l < S.n_lights; l++) {
     const double* LG = S.lights + 6 * l;
-    double vx = LG[3] - px, vy = LG[4] - py, vz = LG[5] - pz;
-    double distance = sqrt(vx * vx + vy * vy + vz * vz);
-    Ray sray;
-    sray.ox = px; sray.oy = py; sray.oz = pz;
-    sray.dx = vx / distance; sray.dy = vy / distance; sray.dz = vz / distance;
+    const ShadowRay sh = shadow_ray(px, py, pz, LG[3], LG[4], LG[5]);
     n_shadow++;
-    Trav Sh;
-    reset_closest(Sh, S.all_cast_shadow ? MODE_SHADOW_ANY : MODE_SHADOW_CLOSEST);
-    if (S.all_cast_shadow) { Sh.thi = distance; Sh.unordered = 1; }
-    Sh.light = l; Sh.c1_t = distance;
     DIAG_LOOP(18);
     DIAG_SPAN_BEGIN();
-    if (S.all_cast_shadow) traverse<FEAT, KOPS, MODE_SHADOW_ANY, LDSC>(S, sray, Sh, C, stack, stride, L);  // mode: a compile-time constant in each
-    else traverse<FEAT, KOPS, MODE_SHADOW_CLOSEST, LDSC>(S, sray, Sh, C, stack, stride, L);
-    nan_commit(Sh, C);
-    DIAG_SPAN_END(3);
+    Trav Sh = shadow_pass(S, sh.distance, l, true);
+    if (S.all_cast_shadow) traverse<FEAT, KOPS, MODE_SHADOW_ANY, LDSC>(S, sh.ray, Sh, C, stack, stride, L);
+    else traverse<FEAT, KOPS, MODE_SHADOW_CLOSEST, LDSC>(S, sh.ray, Sh, C, stack, stride, L);
+    nan_commit(Sh, C);  // mirrors shadow_result(S, Sh, sh.distance, C): calling it here moves the LDSC builds of variant 5 by 16 B of scratch
     bool shadowed;
     if (S.all_cast_shadow) shadowed = Sh.shadowed != 0;
-    else shadowed = (Sh.best_prim != 0x7fffffff) && (S.prims[Sh.best_prim].flags & 1u) && (Sh.best_t < distance);
+    else shadowed = (Sh.best_prim != 0x7fffffff) && (S.prims[Sh.best_prim].flags & 1u) && (Sh.best_t < sh.distance);
+    DIAG_SPAN_END(3);
     if (shadowed) shadow_mask |= 1ull << l;
   }
   DIAG_LOOP(20);
   DIAG_SPAN_BEGIN();
   const double nx = r[3 * cap + s], ny = r[4 * cap + s], nz = r[5 * cap + s];
-  // the Phong terms and -- for a material whose root pattern is Plain -- the colour: one row of the material table; any other record
-  // carries its colour in rows 6..8 (wf_shade)
-  const int mrow = W.sr_mat[s];
-  const double* M = S.mat + 8 * (mrow & (RTC_SR_PLAIN - 1));
   double cr, cg, cbl;
-  if (mrow & RTC_SR_PLAIN) { cr = M[4]; cg = M[5]; cbl = M[6]; }
-  else { cr = r[6 * cap + s]; cg = r[7 * cap + s]; cbl = r[8 * cap + s]; }
-  // the eye vector (= -direction, src/intersection.rs:56) and the path weight of the ray come from where the ray itself came
-  // from: the level's queue (still intact: the next shading kernel is the first to overwrite it) or, at level 0, the camera
+  const double* M = shade_rec_material(S, W, s, cr, cg, cbl);
   const int node = W.sr_node[s];
-  double ex, ey, ez, weight;
-  if (level == 0) {
-    uint64_t q = 0;
-    (void)work_to_slot(wm, (unsigned)node, q);
-    const Ray pr = slot_ray(pm, cam, q);
-    ex = -pr.dx; ey = -pr.dy; ez = -pr.dz; weight = 1.0;
-  } else {
-    const double* rq = W.rq[level & 1];
-    ex = -rq[3 * cap + node]; ey = -rq[4 * cap + node]; ez = -rq[5 * cap + node]; weight = rq[6 * cap + node];
-  }
-  const double ambient = M[0], diffuse = M[1], specular = M[2], shininess = M[3];
+  const RecView v = shade_rec_view(cam, pm, W, wm, level, node);
   double sr = 0.0, sg = 0.0, sb = 0.0;
   for (int l = 0; l < S.n_lights * ((RTC_PROBE & 8) ? 2 : 1); l++) {
     if ((RTC_PROBE & 8) && l == S.n_lights) { sr = sg = sb = 0.0; }
     const int li = (RTC_PROBE & 8) ? l % S.n_lights : l;
     const double* LG = S.lights + 6 * li;
-    double vx = LG[3] - px, vy = LG[4] - py, vz = LG[5] - pz;
-    if (RTC_PROBE & 8) RTC_LAUNDER(vx);
-    double distance = sqrt(vx * vx + vy * vy + vz * vz);
-    const double ldx = vx / distance, ldy = vy / distance, ldz = vz / distance;  // the shadow ray's direction again
-    const bool shadowed = (shadow_mask >> li) & 1ull;
-    double er = cr * LG[0], eg = cg * LG[1], eb = cbl * LG[2];  // effective_color
-    double lr = er * ambient, lg = eg * ambient, lb = eb * ambient;
-    // light vector: (light.origin - point).normalize() — same numbers as the shadow ray direction
-    double ldn = ldx * nx + ldy * ny + ldz * nz;
-    double dr = 0.0, dg = 0.0, db = 0.0, pr = 0.0, pg = 0.0, pb = 0.0;
-    if (!shadowed && ldn >= 0.0) {
-      dr = er * diffuse * ldn; dg = eg * diffuse * ldn; db = eb * diffuse * ldn;
-      // reflect = (-light).reflect(normal)
-      double mlx = -ldx, mly = -ldy, mlz = -ldz;
-      double d2 = 2.0 * (mlx * nx + mly * ny + mlz * nz);
-      double rfx = mlx - nx * d2, rfy = mly - ny * d2, rfz = mlz - nz * d2;
-      double rde = rfx * ex + rfy * ey + rfz * ez;
-      if (rde > 0.0) {
-        double f = specular_factor(rde, shininess, specular);
-        pr = LG[0] * specular * f; pg = LG[1] * specular * f; pb = LG[2] * specular * f;
-      }
-    }
-    sr += (lr + dr) + pr; sg += (lg + dg) + pg; sb += (lb + db) + pb;
+    double qx = px;
+    if (RTC_PROBE & 8) RTC_LAUNDER(qx);
+    const ShadowRay sh = shadow_ray(qx, py, pz, LG[3], LG[4], LG[5]);  // the shadow ray's direction again
+    phong_add(LG, sh.ray.dx, sh.ray.dy, sh.ray.dz, (shadow_mask >> li) & 1ull, nx, ny, nz, v.ex, v.ey, v.ez, cr, cg, cbl, M[0], M[1], M[2], M[3], sr, sg, sb);
   }
-  cb[node] = weight * sr; cb[cap + node] = weight * sg; cb[2 * cap + node] = weight * sb;
+  cb[node] = v.weight * sr; cb[cap + node] = v.weight * sg; cb[2 * cap + node] = v.weight * sb;
   DIAG_SPAN_END(5);
 }
 
@@ -1992,25 +2020,13 @@ __device__ __forceinline__ void wf_shadow_rec_area(const DScene& S, const DCamer
   double* cb = W.contrib + (size_t)level * 3 * cap;
   const double* r = W.sr;
   const int node = W.sr_node[s];
-  double ex, ey, ez, weight;
-  if (level == 0) {
-    uint64_t q = 0;
-    (void)work_to_slot(wm, (unsigned)node, q);
-    const Ray pr = slot_ray(pm, cam, q);
-    ex = -pr.dx; ey = -pr.dy; ez = -pr.dz; weight = 1.0;
-  } else {
-    const double* rq = W.rq[level & 1];
-    ex = -rq[3 * cap + node]; ey = -rq[4 * cap + node]; ez = -rq[5 * cap + node]; weight = rq[6 * cap + node];
-  }
-  const int mrow = W.sr_mat[s];  // (as in wf_shadow_rec)
-  const double* M = S.mat + 8 * (mrow & (RTC_SR_PLAIN - 1));
+  const RecView v = shade_rec_view(cam, pm, W, wm, level, node);
   double cr, cg, cbl;
-  if (mrow & RTC_SR_PLAIN) { cr = M[4]; cg = M[5]; cbl = M[6]; }
-  else { cr = r[6 * cap + s]; cg = r[7 * cap + s]; cbl = r[8 * cap + s]; }
+  const double* M = shade_rec_material(S, W, s, cr, cg, cbl);
   double sr = 0.0, sg = 0.0, sb = 0.0;
-  shade_lights_area<FEAT, KOPS, LDSC, false>(S, r[s], r[cap + s], r[2 * cap + s], r[3 * cap + s], r[4 * cap + s], r[5 * cap + s], ex, ey, ez, cr, cg, cbl, M[0], M[1], M[2],
-                                             M[3], C, stack, stride, n_shadow, L, sr, sg, sb);
-  cb[node] = weight * sr; cb[cap + node] = weight * sg; cb[2 * cap + node] = weight * sb;
+  shade_lights_area<FEAT, KOPS, LDSC, false>(S, r[s], r[cap + s], r[2 * cap + s], r[3 * cap + s], r[4 * cap + s], r[5 * cap + s], v.ex, v.ey, v.ez, cr, cg, cbl, M[0], M[1],
+                                             M[2], M[3], C, stack, stride, n_shadow, L, sr, sg, sb);
+  cb[node] = v.weight * sr; cb[cap + node] = v.weight * sg; cb[2 * cap + node] = v.weight * sb;
 }
 
 // Traversal kernel of the wavefront path: the closest-hit pass of level `tl` and the shadow + lighting pass of level `sl`
@@ -2096,14 +2112,7 @@ __global__ void __launch_bounds__(LDSC ? RTC_LDS_BLOCK : RTC_BLOCK, (KOPS || FEA
     if (tl == 0) atomicAdd(&stats->rays_primary, (unsigned long long)n_rays);
     atomicAdd(&stats->rays_container, (unsigned long long)n_container);
     atomicAdd(&stats->rays_shadow, (unsigned long long)n_shadow);
-    atomicAdd(&stats->accel_nodes, (unsigned long long)C.accel_nodes);
-    atomicAdd(&stats->group_tests, (unsigned long long)C.group_tests);
-    atomicAdd(&stats->tri_tests, (unsigned long long)C.tri_tests);
-    atomicAdd(&stats->analytic_tests, (unsigned long long)C.analytic_tests);
-    atomicAdd(&stats->knodes, (unsigned long long)C.knodes);
-    atomicAdd(&stats->kplanes, (unsigned long long)C.kplanes);
-    atomicAdd(&stats->light_cells, (unsigned long long)C.light_cells);
-    atomicAdd(&stats->kgroups, (unsigned long long)C.kgroups);
+    publish_counters(stats, C);
   }
 }
 

@@ -134,15 +134,8 @@ __global__ void __launch_bounds__(RTC_WF_SHADE_BLOCK, RTC_WF_SHADE_WAVES) wf_sha
       prepare_state(S, P, ray, PIPE ? in.t : W.h_t[i], hu, hv, st);
       if (transparency != 0.0 && fuel > 0) { n1 = W.h_n12[i]; n2 = W.h_n12[cap + i]; }  // stored under the same condition
       if constexpr (PAT) {
-        // Pattern::color_at(material_inv * over_point) — identical for every light (src/shape.rs:437)
-        const double* mi = S.xf_matinv + 16 * P.xform;
-        double x = mi[0] * st.px + mi[1] * st.py + mi[2] * st.pz + mi[3] * 1.0;
-        double y = mi[4] * st.px + mi[5] * st.py + mi[6] * st.pz + mi[7] * 1.0;
-        double z = mi[8] * st.px + mi[9] * st.py + mi[10] * st.pz + mi[11] * 1.0;
-        double w = mi[12] * st.px + mi[13] * st.py + mi[14] * st.pz + mi[15] * 1.0;
         if (S.pats[S.mat_pattern[P.mat]].tag != 1) {
-          if constexpr (UV) pattern_color_uv(S, S.mat_pattern[P.mat], x, y, z, w, cr, cg, cbl);
-          else pattern_color(S, S.mat_pattern[P.mat], x, y, z, w, cr, cg, cbl);
+          pattern_at<UV>(S, P, st, cr, cg, cbl);
           mat = P.mat;
         }
       }
@@ -154,34 +147,14 @@ __global__ void __launch_bounds__(RTC_WF_SHADE_BLOCK, RTC_WF_SHADE_WAVES) wf_sha
       if (R != R && mat < 0) mat = ~mat;
     }
     // reflected_color / refracted_color (src/world.rs:84-132), once per light in the reference -> factor L
-    bool do_refl = false, do_refr = false;
-    double wr = 0.0, wt = 0.0, tdx = 0.0, tdy = 0.0, tdz = 0.0;
-    if (hit && fuel > 0) {
-      do_refl = reflective != 0.0;
-      do_refr = transparency != 0.0;
-      wr = weight * L * reflective; wt = weight * L * transparency;
-      if (blend) {
-        wr *= R;
-        wt *= (1.0 - R);
-      }
-      if (do_refr) {
-        double n_ratio = n1 / n2;
-        double cos_i = st.ex * st.nx + st.ey * st.ny + st.ez * st.nz;
-        double sin2_t = (n_ratio * n_ratio) * (1.0 - cos_i * cos_i);
-        if (sin2_t > 1.0) do_refr = false;
-        else {
-          double cos_t = sqrt(1.0 - sin2_t);
-          double kk = n_ratio * cos_i - cos_t;
-          tdx = st.nx * kk - st.ex * n_ratio; tdy = st.ny * kk - st.ey * n_ratio; tdz = st.nz * kk - st.ez * n_ratio;
-        }
-      }
-    }
+    ChildRays spawn = {false, false, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (hit && fuel > 0) spawn = child_rays(st, n1, n2, weight, L, reflective, transparency, blend, R);
     // queue space: shade records and child rays (a wave's reflected rays first, then its refracted ones); one pair of
     // atomics per block and iteration, after the evaluation
     const unsigned long long lt = (1ull << lane) - 1ull;
     const bool on_plane = hit && geom == 1;
     const unsigned long long m_rec0 = __ballot(hit && on_plane ? 1 : 0), m_rec1 = __ballot(hit && !on_plane ? 1 : 0);
-    const unsigned long long m_c0 = __ballot(do_refl && on_plane ? 1 : 0), m_c1 = __ballot(do_refl && !on_plane ? 1 : 0), m_c2 = __ballot(do_refr ? 1 : 0);
+    const unsigned long long m_c0 = __ballot(spawn.refl && on_plane ? 1 : 0), m_c1 = __ballot(spawn.refl && !on_plane ? 1 : 0), m_c2 = __ballot(spawn.refr ? 1 : 0);
     unsigned* s_cnt = s_cnt2[parity];
     parity ^= 1u;
     if (lane == 0) {
@@ -237,15 +210,15 @@ __global__ void __launch_bounds__(RTC_WF_SHADE_BLOCK, RTC_WF_SHADE_WAVES) wf_sha
       }
       W.sr_node[s] = (int32_t)i;
     }
-    if (do_refl && jr < W.cap) {
+    if (spawn.refl && jr < W.cap) {
       nq[jr] = st.px; nq[cap + jr] = st.py; nq[2 * cap + jr] = st.pz; nq[3 * cap + jr] = st.rx; nq[4 * cap + jr] = st.ry; nq[5 * cap + jr] = st.rz;
-      nq[6 * cap + jr] = wr;
+      nq[6 * cap + jr] = spawn.wr;
       ch[i] = (int32_t)jr;
       n_reflect++;
     }
-    if (do_refr && jt < W.cap) {
-      nq[jt] = st.ux; nq[cap + jt] = st.uy; nq[2 * cap + jt] = st.uz; nq[3 * cap + jt] = tdx; nq[4 * cap + jt] = tdy; nq[5 * cap + jt] = tdz;
-      nq[6 * cap + jt] = wt;
+    if (spawn.refr && jt < W.cap) {
+      nq[jt] = st.ux; nq[cap + jt] = st.uy; nq[2 * cap + jt] = st.uz; nq[3 * cap + jt] = spawn.tdx; nq[4 * cap + jt] = spawn.tdy; nq[5 * cap + jt] = spawn.tdz;
+      nq[6 * cap + jt] = spawn.wt;
       ch[cap + i] = (int32_t)jt;
       n_refract++;
     }

@@ -158,13 +158,14 @@ def around(world, n=2, size=1.0):
                   for l in world.lights], world.elements)
 
 
-@pytest.mark.parametrize("name", ["csg_scene", "synthetic_cones_grouped", "teapot_low"])
+@pytest.mark.parametrize("name", ["csg_scene", "synthetic_cones_grouped", "teapot_low", "all_primitives"])
 @pytest.mark.parametrize("path", PATHS)
 def test_area_lights_on_csg_grouped_and_mesh_scenes(hip, orc, path, name, monkeypatch):
     """The two oracle identities on scenes the area kernels of variant 6 serve (feature level 3, program in memory: CSG, per-primitive
     group gates) and on a mesh: degenerate lights against the point-light world at fuel 5, and 2x2 lights against their sample points
     at fuel 0.  (These scenes reflect and refract: the expanded world has N point lights per area light and would add the secondary
-    colour N times -- the once-per-light rule -- so the sample-point identity holds for the surface colour alone, i.e. without bounces.)"""
+    colour N times -- the once-per-light rule -- so the sample-point identity holds for the surface colour alone, i.e. without bounces.)
+    all_primitives has a shape that casts no shadow: the one small case whose shadow rays take the closest-hit rule in shade_lights_area."""
     monkeypatch.setenv("RTC_KERNEL", path)
     cam, world = cases.SMALL_CASES[name]()
     ref = orc.render_with_digest(orc.build_world(world), cam, 5)
