@@ -33,7 +33,7 @@ enum {
                               than 32 possible intersections gets that many rows per thread); a material whose
                               refractive_index is not in (1e-70, 1e70); more than 64 lights (an area light is one); an area
                               light with more than 16 steps along a side; a texture side above 16384 or more than 2^26
-                              texels in one scene; fuel above 16 */
+                              texels in one scene; fuel above 16; a sampled camera with more than 16 samples along a side */
   RTC_ERR_DEVICE = 3,      /* HIP failure / no device                                                   */
   RTC_ERR_NAN = 4          /* a NaN intersection t reached a sort the reference's comparator would run on: a list
                               of two or more entries of one World::intersect or CSG child list; the reference
@@ -185,6 +185,35 @@ typedef struct rtc_scene_ext {
   uint32_t n_textures;
   const rtc_texture* textures;
 } rtc_scene_ext;
+
+/* The sampled camera (not in the reference, whose Camera::ray_at_pixel sends one ray through each pixel centre from a pinhole): n x n
+ * samples per pixel (anti-aliasing, box filter) and an optional thin lens (depth of field), for the rtc_render_sampled* entry points
+ * and rtc_camera_rays.  Pixel i has x = i % hsize, y = i / hsize; sample k of its N = n * n has sx = k % n, sy = k / n.  Every step is
+ * one f64 operation; m = SplitMix64's finaliser (rtc_splitmix64, csrc/device_scene.h), rtc_area_jitter as for rtc_light_ex.
+ *   h = m(m(m(seed) ^ i) ^ k), draw(j) = rtc_area_jitter(h, j) = (m(h ^ j) >> 11) * 2^-53.  Nothing of the launch, chunk, device or
+ *     device path enters: any partition of the image gives the same bits.
+ *   Sub-pixel position: without RTC_SAMPLE_JITTER jx = jy = 0.5; with it jx = draw(0), jy = draw(1) (stratified: one sample per cell).
+ *     fx = ((double)sx + jx) / (double)n, fy likewise; xoffset = ((double)x + fx) * pixel_size, yoffset likewise;
+ *     world_x = half_width - xoffset, world_y = half_height - yoffset.
+ *   lens_radius R == 0 (pinhole): the rest is Camera::ray_at_pixel's (src/camera.rs:46-54) on world_x, world_y.  side = 1 without
+ *     jitter is therefore exactly rtc_render's ray (0.5 / 1.0 = 0.5).
+ *   R > 0 (thin lens): a = 2.0 * draw(2) - 1.0, b = 2.0 * draw(3) - 1.0 (hashed whether or not RTC_SAMPLE_JITTER is set); concentric
+ *     map: a == 0 && b == 0 gives lx = ly = 0; else if fabs(a) > fabs(b): r = a, phi = (M_PI / 4.0) * (b / a); else r = b,
+ *     phi = M_PI / 2.0 - (M_PI / 4.0) * (a / b); lx = (R * r) * cos(phi), ly = (R * r) * sin(phi).  Origin = rows 0-2 of transform_inv
+ *     applied to (lx, ly, 0, 1), target = the same rows applied to (world_x * F, world_y * F, -F, 1), F = focal_distance, each row as
+ *     m[0]*px + m[1]*py + m[2]*pz + m[3]*1.0 left to right; direction = (target - origin) normalised as ray_at_pixel normalises.
+ *   Pixel colour: (((c_0 + c_1) + c_2) + ... + c_{N-1}) / (double)N per channel, c_k = World::color_at(ray_k, fuel).
+ * Limits: RTC_ERR_INVALID for side == 0, unknown flag bits, R negative or not finite, R > 0 with F not finite or <= 0, NULL
+ * arguments; RTC_ERR_UNSUPPORTED for side > RTC_SAMPLES_MAX_SIDE. */
+enum { RTC_SAMPLE_JITTER = 1u };
+#define RTC_SAMPLES_MAX_SIDE 16
+typedef struct rtc_sampling {
+  uint32_t side;          /* n: n x n samples per pixel, N = n*n */
+  uint32_t flags;         /* RTC_SAMPLE_JITTER */
+  uint64_t seed;
+  double lens_radius;     /* R; 0 = pinhole */
+  double focal_distance;  /* F, camera-space depth that is in focus; read only when R > 0 */
+} rtc_sampling;
 
 /* The Element tree (src/shape.rs:31-34, :181-185) in DFS pre-order.  A group node carries the world-space
  * bounding box the reference computed for it (Element::composite + propagate_inverses; NaN/inf included,
@@ -340,6 +369,25 @@ int rtc_multi_sync(rtc_multi*);
 /* World::color_at(ray, fuel) for n rays {ox,oy,oz,dx,dy,dz} (host arrays). */
 int rtc_trace_rays(rtc_scene*, const double* rays, uint64_t n, int32_t fuel, double* rgb, rtc_hit* hits, rtc_stats* stats);
 
+/* ---- the sampled camera (rtc_sampling above) ------------------------------------------------------------------------------------
+ * rtc_render / rtc_render_rgb8 / rtc_render_bands_device / rtc_render_multi with n x n samples per pixel and an optional thin lens.
+ * A device kernel generates the sample rays of a chunk of pixels (at most RTC_SAMPLED_MAX_RAYS rays, an environment variable read at
+ * each call, default 2^22; never fewer than one row or one pixel), the scene's ray kernels trace them as explicit rays -- every scene
+ * kind, both device paths --, a second kernel averages them into the pixel; chunk after chunk on the scene's stream.  Only pixels
+ * leave the device.  Whole-row launches choose their device path as rtc_scene_path_info describes (the launch shape includes the
+ * sampling; the guess counts a chunk's rays); pixel lists stay on the one-kernel path.  rtc_stats: pixels = the pixel count,
+ * rays_primary = pixels * N, counters summed over the chunks, kernel_ms = generator + traces + resolve.  No hit records or digests:
+ * a pixel has N primary hits.  side = 1 without jitter or lens gives rtc_render's pixels bit for bit. */
+int rtc_render_sampled(rtc_scene*, const rtc_camera*, const rtc_sampling*, int32_t fuel, const uint64_t* pixel_indices, uint64_t first, uint64_t n,
+                       double* rgb, rtc_stats* stats);
+int rtc_render_sampled_rgb8(rtc_scene*, const rtc_camera*, const rtc_sampling*, int32_t fuel, uint8_t* rgb8, rtc_stats* stats);
+int rtc_render_sampled_bands_device(rtc_scene*, const rtc_camera*, const rtc_sampling*, int32_t fuel, uint32_t band_rows, uint32_t band_first,
+                                    uint32_t band_step, uint32_t n_rows, double* rgb_dev, rtc_stats* stats, int count_stats, int sync);
+int rtc_render_multi_sampled(rtc_multi*, const rtc_camera*, const rtc_sampling*, int32_t fuel, double* rgb, rtc_stats* stats);
+/* The sample rays themselves: n*N rows {o, d}, pixel-major, k inner (host array).  scene != NULL: generated by the device kernel and
+ * copied back; scene == NULL: evaluated on the host by the same function, no device needed (like rtc_ppm). */
+int rtc_camera_rays(rtc_scene*, const rtc_camera*, const rtc_sampling*, const uint64_t* pixel_indices, uint64_t first, uint64_t n, double* rays);
+
 /* ---- the step after the path: Color::clamp and Image::ppm ---------------------------------
  * Color::clamp (src/color.rs:42-46): u8 = round(min(max(c, 0), 1) * 255), round half away from zero, NaN -> 255 (Rust's
  * f64::min returns the non-NaN operand).  n_values = 3 * pixels.  Device pointers, on the scene's stream. */
@@ -390,7 +438,9 @@ uint32_t rtc_scene_wavefront_lds_bytes(const rtc_scene*);
  * pays for code loading and scratch), every later launch of that shape takes the faster.  Until a shape is measured — a caller
  * that renders one frame per scene, asynchronous launches — a guess from the scene decides: wavefront iff it has >= 32 bounded
  * analytic primitives, >= 10 % of its primitives reflect or refract, fuel >= 2 and the launch has >= 256 K pixels (the one-kernel
- * path needs no ray queues).  Reports the state for
+ * path needs no ray queues).  Whole-row launches of the sampled camera (rtc_render_sampled*) are launch shapes too -- camera, sampling,
+ * rows and fuel; the guess counts the rays of a chunk, the measurement sums the chunks' device times --; their pixel lists stay on
+ * the one-kernel path.  Reports the state for
  * the most recent launch shape: *choice = 0 while undecided, else 1 or 4; the measured device times in ms (< 0 = not yet
  * measured).  Any pointer may be NULL. */
 void rtc_scene_path_info(const rtc_scene*, int32_t* choice, double* one_kernel_ms, double* wavefront_ms);

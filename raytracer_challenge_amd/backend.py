@@ -13,7 +13,7 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from .scene import (FUEL, GEOMETRY, GROUP_KINDS, JITTER_KINDS, MIXTURE_KINDS, AreaLight, Camera, Element, Material, Pattern, World)
+from .scene import (FUEL, GEOMETRY, GROUP_KINDS, JITTER_KINDS, MIXTURE_KINDS, AreaLight, Camera, Element, Material, Pattern, Sampling, World)
 from .texture import UV_KINDS, UV_MAPS, Texture
 
 HIT_DTYPE = np.dtype([("t", "<f8"), ("prim", "<i4"), ("push_idx", "<i4")])
@@ -35,6 +35,14 @@ class _UvFaceC(C.Structure):  # include/rtw.h rtw_uv_pattern
 
 class CameraC(C.Structure):
     _fields_ = [("hsize", C.c_uint64), ("vsize", C.c_uint64), ("field_of_view", C.c_double), ("transform", C.c_double * 16)]
+
+
+class SamplingC(C.Structure):  # include/rtc.h rtc_sampling
+    _fields_ = [("side", C.c_uint32), ("flags", C.c_uint32), ("seed", C.c_uint64), ("lens_radius", C.c_double), ("focal_distance", C.c_double)]
+
+    @staticmethod
+    def of(s: Sampling) -> "SamplingC":
+        return SamplingC(int(s.side), 1 if s.jitter else 0, int(s.seed), float(s.lens_radius), float(s.focal_distance))
 
 
 RTW_SYMBOLS = [
@@ -273,6 +281,68 @@ class Backend:
         if lib.rtc_render_hit_digest(scene, C.byref(rc_cam), int(fuel), idx_p, 0, n, out.ctypes.data) != 0:
             raise RtwError("rtc_render_hit_digest: %s" % (lib.rtc_last_error() or b"").decode())
         return out
+
+    def _sampled_lib(self):
+        """The rtc_* entry points of the sampled camera, bound; RtwError for a library that has none (the CPU emulator, the oracle)."""
+        lib = self.lib
+        if not (hasattr(lib, "rtc_render_sampled") and hasattr(lib, "rtc_camera_rays")):
+            raise RtwError("sampled cameras need librtc_amd.so (backend %r has no rtc_render_sampled)" % self.name)
+        vp = C.c_void_p
+        lib.rtw_world_scene.restype, lib.rtw_world_scene.argtypes = vp, [vp, C.c_int]
+        lib.rtw_make_camera.restype, lib.rtw_make_camera.argtypes = C.c_int, [vp, vp]
+        lib.rtc_render_sampled.restype = C.c_int
+        lib.rtc_render_sampled.argtypes = [vp, vp, C.POINTER(SamplingC), C.c_int32, vp, C.c_uint64, C.c_uint64, vp, vp]
+        lib.rtc_camera_rays.restype = C.c_int
+        lib.rtc_camera_rays.argtypes = [vp, vp, C.POINTER(SamplingC), vp, C.c_uint64, C.c_uint64, vp]
+        lib.rtc_last_error.restype = C.c_char_p
+        return lib
+
+    def _rtc_camera(self, lib, camera: Camera):
+        cc = self.camera_c(camera)
+        rc_cam = (C.c_double * 21)()   # rtc_camera: 2 x u64 + 3 + 16 doubles
+        if lib.rtw_make_camera(C.byref(cc), C.byref(rc_cam)) != 0:
+            raise RtwError("camera: %s" % self._err())
+        return rc_cam
+
+    def render_sampled(self, nw: NativeWorld, camera: Camera, sampling: Sampling, fuel: int = FUEL, pixel_indices: Optional[np.ndarray] = None,
+                       device: int = 0) -> np.ndarray:
+        """include/rtc.h rtc_render_sampled: every pixel (row-major) or the listed pixel indices as the mean of `sampling`'s rays.
+        Returns rgb[n,3]."""
+        lib = self._sampled_lib()
+        scene = lib.rtw_world_scene(nw.handle, int(device))
+        if not scene:
+            raise RtwError("scene upload failed: %s" % self._err())
+        rc_cam, sp = self._rtc_camera(lib, camera), SamplingC.of(sampling)
+        if pixel_indices is None:
+            n, idx_p = camera.hsize * camera.vsize, None
+        else:
+            pixel_indices = np.ascontiguousarray(pixel_indices, dtype=np.uint64)
+            n, idx_p = pixel_indices.size, pixel_indices.ctypes.data
+        rgb = np.empty((n, 3), dtype=np.float64)
+        if lib.rtc_render_sampled(scene, C.byref(rc_cam), C.byref(sp), int(fuel), idx_p, 0, n, rgb.ctypes.data, None) != 0:
+            raise RtwError("rtc_render_sampled: %s" % (lib.rtc_last_error() or b"").decode())
+        return rgb
+
+    def camera_rays(self, camera: Camera, sampling: Sampling, pixel_indices: Optional[np.ndarray] = None, nw: Optional[NativeWorld] = None,
+                    device: int = 0) -> np.ndarray:
+        """include/rtc.h rtc_camera_rays: the sample rays {o, d} of every pixel or of the listed ones, [n, side*side, 6].  With a world
+        they come from the device's generator kernel, without one from the same function evaluated on the host (no GPU needed)."""
+        lib = self._sampled_lib()
+        scene = None
+        if nw is not None:
+            scene = lib.rtw_world_scene(nw.handle, int(device))
+            if not scene:
+                raise RtwError("scene upload failed: %s" % self._err())
+        rc_cam, sp = self._rtc_camera(lib, camera), SamplingC.of(sampling)
+        if pixel_indices is None:
+            n, idx_p = camera.hsize * camera.vsize, None
+        else:
+            pixel_indices = np.ascontiguousarray(pixel_indices, dtype=np.uint64)
+            n, idx_p = pixel_indices.size, pixel_indices.ctypes.data
+        rays = np.empty((n, sampling.samples, 6), dtype=np.float64)
+        if lib.rtc_camera_rays(scene, C.byref(rc_cam), C.byref(sp), idx_p, 0, n, rays.ctypes.data) != 0:
+            raise RtwError("rtc_camera_rays: %s" % (lib.rtc_last_error() or b"").decode())
+        return rays
 
     def color_at(self, nw: NativeWorld, rays: np.ndarray, fuel: int = FUEL):
         """World::color_at for rays given as rows {ox,oy,oz,dx,dy,dz}.  Returns (rgb[n,3], hits[n])."""

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/rtc.h"
+#include "camera_sampling.h"
 #include "device_scene.h"
 #include "scene_build.hpp"
 
@@ -34,6 +35,9 @@ void rtc_launch_wavefront(const DScene& S, const DCamera& cam, const DPixelMap& 
 uint64_t rtc_wavefront_work(const DCamera& cam, const DPixelMap& pm);
 unsigned rtc_wavefront_grid(const DScene& S, int n_cu);
 unsigned rtc_wavefront_lds_bytes(const DScene& S);
+void rtc_launch_gen_rays(const DCamera& cam, const DPixelMap& pm, const rtc_sampling& sp, unsigned long long slot_first, unsigned long long n_slots, double* rays,
+                         hipStream_t stream);
+void rtc_launch_resolve_samples(const double* ray_rgb, unsigned n_samples, unsigned long long n_slots, double* dst, hipStream_t stream);
 int32_t rtc_bvh_build_device(const std::vector<bvh::Item>& items, std::vector<DBvhNode>& n2, std::vector<uint32_t>& order, uint32_t base, int leaf_max, double* frame);
 
 static thread_local std::string g_rtc_err;
@@ -71,6 +75,11 @@ struct rtc_scene {
   uint64_t* d_idx = nullptr;
   double* d_rays = nullptr;
   uint64_t cap_px = 0, cap_idx = 0, cap_rays = 0;
+  // sampled camera (run_sampled): the sample rays of one chunk of pixels and their colours, reused chunk after chunk on the stream
+  double* d_srays = nullptr;
+  double* d_srgb = nullptr;
+  uint64_t cap_srays = 0, cap_srgb = 0;
+  hipEvent_t evs0 = nullptr, evs1 = nullptr;  // around a chunk's generator, traces and resolve
   int kernel_version = 0;  // 0: measured choice between the one-kernel (1) and the wavefront (4) path, per launch signature
   uint64_t tune_sig = 0;
   double tune_ms[2] = {-1.0, -1.0};
@@ -411,10 +420,150 @@ int make_pixel_map(rtc_scene* s, const rtc_camera* cam, const uint64_t* pixel_in
   return RTC_OK;
 }
 
+// ---- the sampled camera (include/rtc.h rtc_sampling; kernels in rtc_camera.hip) ---------------------------------------------------
+int check_sampling(const rtc_sampling* sp) {
+  if (!sp) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  if (sp->side == 0) return rtc_fail(RTC_ERR_INVALID, "sampling: side must be >= 1");
+  if (sp->flags & ~(uint32_t)RTC_SAMPLE_JITTER) return rtc_fail(RTC_ERR_INVALID, "sampling: unknown flag bits");
+  if (!std::isfinite(sp->lens_radius) || sp->lens_radius < 0.0) return rtc_fail(RTC_ERR_INVALID, "sampling: lens_radius must be finite and >= 0");
+  if (sp->lens_radius > 0.0 && (!std::isfinite(sp->focal_distance) || sp->focal_distance <= 0.0))
+    return rtc_fail(RTC_ERR_INVALID, "sampling: focal_distance must be finite and > 0 when lens_radius > 0");
+  if (sp->side > RTC_SAMPLES_MAX_SIDE) return rtc_fail(RTC_ERR_UNSUPPORTED, "sampling: side exceeds RTC_SAMPLES_MAX_SIDE (16)");
+  return RTC_OK;
+}
+
+// Rays per chunk of a sampled launch.  RTC_SAMPLED_MAX_RAYS (read at each call; tests force many chunks with it); default 2^22: a
+// 201 MB ray buffer, and wavefront queues of the size a 4 MP frame's are (profiles/sampled_camera_probe.txt).
+uint64_t sampled_max_rays() {
+  const char* e = std::getenv("RTC_SAMPLED_MAX_RAYS");
+  const uint64_t v = e ? std::strtoull(e, nullptr, 10) : 0;
+  return v ? v : (1ull << 22);
+}
+
+int ensure_sampled(rtc_scene* s, uint64_t n_rays, bool colours) {
+  if (n_rays > s->cap_srays) {
+    HIP_OK(hipStreamSynchronize(s->stream));
+    (void)hipFree(s->d_srays);
+    s->d_srays = nullptr; s->cap_srays = 0;
+    HIP_OK(hipMalloc((void**)&s->d_srays, n_rays * 6 * sizeof(double)));
+    s->cap_srays = n_rays;
+  }
+  if (colours && n_rays > s->cap_srgb) {
+    HIP_OK(hipStreamSynchronize(s->stream));
+    (void)hipFree(s->d_srgb);
+    s->d_srgb = nullptr; s->cap_srgb = 0;
+    HIP_OK(hipMalloc((void**)&s->d_srgb, n_rays * 3 * sizeof(double)));
+    s->cap_srgb = n_rays;
+  }
+  return RTC_OK;
+}
+
+// launch_signature of a sampled launch: the pixel set's, and the sampling
+uint64_t sampled_signature(const DCamera& cam, const DPixelMap& pm, const rtc_sampling& sp, int fuel) {
+  uint64_t h = launch_signature(cam, pm, fuel) ^ 0x73616d706c656473ull;
+  auto mix = [&](const void* p, size_t n) { for (size_t i = 0; i < n; i++) { h ^= ((const unsigned char*)p)[i]; h *= 1099511628211ull; } };
+  mix(&sp.side, sizeof(sp.side)); mix(&sp.flags, sizeof(sp.flags)); mix(&sp.seed, sizeof(sp.seed));
+  mix(&sp.lens_radius, sizeof(sp.lens_radius)); mix(&sp.focal_distance, sizeof(sp.focal_distance));
+  return h ? h : 1;
+}
+
+// run() for a sampled camera: the pixel set `pm` (mode 1 or 2) is cut into chunks of whole rows (mode 2) or slices of the list (mode 1)
+// of at most RTC_SAMPLED_MAX_RAYS rays, never fewer than one row / pixel; per chunk rtc_gen_rays fills the scene's ray buffer, run()
+// traces it as explicit rays into the per-ray colours, rtc_resolve_samples writes the pixels' means to their slots of d_rgb.  All on
+// the scene's stream, so the two buffers are reused chunk after chunk.  A synchronous launch reads every chunk's state back (a chunk
+// whose wavefront queues overflowed is rendered again by run() before its rays are overwritten; the resolve only writes).
+// Path: whole-row launches go through pick_path ONCE per call -- the shape is the whole launch's (camera, sampling, rows, fuel), the
+// guess counts the rays of a chunk, the measurement is the sum of the chunks' trace times -- and every chunk takes that path; lists
+// are left to run(), which keeps them on the one-kernel path.  `after`: behind the last chunk's resolve (see run()).
+int run_sampled(rtc_scene* s, const DCamera& cam, const DPixelMap& pm, const rtc_sampling& sp, int fuel, double* d_rgb, rtc_stats* stats, bool count, bool sync,
+                const AfterLaunch* after = nullptr) {
+  if (fuel < 0) fuel = 0;
+  HIP_OK(hipSetDevice(s->device));
+  const uint64_t N = (uint64_t)sp.side * sp.side;
+  const bool rows = pm.mode == 2;
+  const uint64_t unit = rows ? cam.hsize : 1;  // pixels a chunk grows by
+  const uint64_t chunk_px = std::min<uint64_t>(pm.n / unit, std::max<uint64_t>(1, sampled_max_rays() / (unit * N))) * unit;
+  if (chunk_px * N > 0x7fffff00ull) return rtc_fail(RTC_ERR_UNSUPPORTED, "one row of this sampled launch exceeds 2^31 rays");
+  int rc = ensure_sampled(s, chunk_px * N, true);
+  if (rc != RTC_OK) return rc;
+  const bool will_sync = sync || stats != nullptr;
+  const bool tuned = rows && s->kernel_version == 0;
+  int force = 0;
+  if (tuned) {
+    force = pick_path(s, sampled_signature(cam, pm, sp, s->d.n_lights == 0 ? 0 : fuel), chunk_px * N, fuel, will_sync, false);
+    if (force == 4 && s->wave_alloc_failed) force = 1;
+  }
+  const int first_path = force;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  double trace_ms = 0.0;
+  DCamera ray_cam{};
+  ray_cam.hsize = 1; ray_cam.vsize = 1;
+  for (uint64_t p0 = 0; p0 < pm.n; p0 += chunk_px) {
+    const uint64_t np = std::min(chunk_px, pm.n - p0);
+    const bool last = p0 + np == pm.n;
+    if (stats) HIP_OK(hipEventRecord(s->evs0, s->stream));
+    rtc_launch_gen_rays(cam, pm, sp, p0, np, s->d_srays, s->stream);
+    HIP_OK(hipGetLastError());
+    DPixelMap rm{};
+    rm.n = np * N; rm.mode = 3; rm.rays = s->d_srays;
+    const AfterLaunch resolve = [&]() -> int {
+      rtc_launch_resolve_samples(s->d_srgb, (unsigned)N, np, d_rgb + 3 * p0, s->stream);
+      hipError_t e = hipGetLastError();
+      if (e == hipSuccess && stats) e = hipEventRecord(s->evs1, s->stream);
+      if (e != hipSuccess) return rtc_fail(RTC_ERR_DEVICE, std::string("rtc_resolve_samples: ") + hipGetErrorString(e));
+      return (last && after) ? (*after)() : RTC_OK;
+    };
+    rtc_stats st;
+    rc = run(s, ray_cam, rm, fuel, s->d_srgb, false, stats ? &st : nullptr, count, sync, force, &resolve);
+    if (rc == RTC_ERR_UNSUPPORTED && force == 4) {  // the queues were refused: this shape stays on the one-kernel path (same bits)
+      s->tune_ms[1] = 1e30; s->tune_n[1] = 2; s->tune_choice = 1;
+      force = 1;
+      rc = run(s, ray_cam, rm, fuel, s->d_srgb, false, stats ? &st : nullptr, count, sync, force, &resolve);
+    }
+    if (rc != RTC_OK) return rc;
+    if (force == 4 && will_sync && !s->last_wavefront) {  // run() rendered the chunk again on the one-kernel path after an overflow
+      s->tune_ms[1] = 1e30; s->tune_n[1] = 2; s->tune_choice = 1;
+      force = 1;
+    }
+    if (will_sync) {
+      float ms = 0.f;
+      HIP_OK(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+      trace_ms += ms;
+    }
+    if (stats) {
+      float ms = 0.f;
+      HIP_OK(hipEventElapsedTime(&ms, s->evs0, s->evs1));
+      if (std::getenv("RTC_SAMPLED_TIMING")) {  // debug aid (scripts/sampled_camera_probe.py): the chunk's three parts by the events around them
+        float g = 0.f, t = 0.f, r = 0.f;
+        HIP_OK(hipEventElapsedTime(&g, s->evs0, s->ev0));
+        HIP_OK(hipEventElapsedTime(&t, s->ev0, s->ev1));
+        HIP_OK(hipEventElapsedTime(&r, s->ev1, s->evs1));
+        std::fprintf(stderr, "[rtc-sampled] chunk of %llu rays: generator %.3f ms, traces %.3f ms, resolve %.3f ms\n", (unsigned long long)rm.n, g, t, r);
+      }
+      stats->rays_primary += st.rays_primary; stats->rays_shadow += st.rays_shadow; stats->rays_reflect += st.rays_reflect; stats->rays_refract += st.rays_refract;
+      stats->rays_container += st.rays_container; stats->accel_nodes += st.accel_nodes; stats->group_tests += st.group_tests; stats->tri_tests += st.tri_tests;
+      stats->analytic_tests += st.analytic_tests; stats->nan_ts += st.nan_ts; stats->n_launches += st.n_launches + 2u;
+      stats->accel_nodes_kernarg += st.accel_nodes_kernarg; stats->analytic_tests_kernarg += st.analytic_tests_kernarg;
+      stats->light_grid_cells += st.light_grid_cells; stats->group_tests_uniform += st.group_tests_uniform;
+      stats->kernel_ms += ms;
+    }
+  }
+  if (tuned && will_sync && !count && !s->tune_choice && force == first_path) {  // one sample of pick_path's measurement, as run() takes it
+    const int k = force == 4 ? 1 : 0;
+    s->tune_ms[k] = s->tune_n[k] ? std::min(s->tune_ms[k], trace_ms) : trace_ms;
+    s->tune_n[k]++;
+    if (s->tune_n[0] >= 2 && s->tune_n[1] >= 2) s->tune_choice = s->tune_ms[1] < s->tune_ms[0] ? 4 : 1;
+  }
+  if (stats) stats->pixels = pm.n;
+  return RTC_OK;
+}
+
 // One launch whose results go to the caller's host buffers: rgb (n x 3 doubles) or rgb8 (n x 3 bytes, Color::clamp on the device),
 // and optionally the primary-hit records.  The destination's pages are touched by host threads while the device renders, the
 // copies are queued behind the kernels (see pretouch_pages above).
-int render_to_host(rtc_scene* s, const DCamera& dc, const DPixelMap& pm, int fuel, double* rgb, uint8_t* rgb8, rtc_hit* hits, rtc_stats* stats) {
+// `sp`: the launch goes through run_sampled (no hit records).
+int render_to_host(rtc_scene* s, const DCamera& dc, const DPixelMap& pm, int fuel, double* rgb, uint8_t* rgb8, rtc_hit* hits, rtc_stats* stats,
+                   const rtc_sampling* sp = nullptr) {
   static_assert(sizeof(DHit) == sizeof(rtc_hit) && offsetof(DHit, prim) == offsetof(rtc_hit, prim) && offsetof(DHit, k) == offsetof(rtc_hit, push_idx), "hit layout");
   const uint64_t n = pm.n;
   std::vector<std::thread> pool;
@@ -436,7 +585,8 @@ int render_to_host(rtc_scene* s, const DCamera& dc, const DPixelMap& pm, int fue
     if (e != hipSuccess) return rtc_fail(RTC_ERR_DEVICE, std::string("copy to the host: ") + hipGetErrorString(e));
     return RTC_OK;
   };
-  const int rc = run(s, dc, pm, fuel, s->d_rgb, hits != nullptr, stats, stats != nullptr, true, 0, &after);
+  const int rc = sp ? run_sampled(s, dc, pm, *sp, fuel, s->d_rgb, stats, stats != nullptr, true, &after)
+                    : run(s, dc, pm, fuel, s->d_rgb, hits != nullptr, stats, stats != nullptr, true, 0, &after);
   join_all(&pool);  // (an error before the hook ran its join)
   return rc;
 }
@@ -487,6 +637,8 @@ int scene_create(const rtc_scene_desc* desc, bool ex, const rtc_light_ex* lx, ui
   HIP_OK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
   HIP_OK(hipEventCreate(&s->ev0));
   HIP_OK(hipEventCreate(&s->ev1));
+  HIP_OK(hipEventCreate(&s->evs0));
+  HIP_OK(hipEventCreate(&s->evs1));
   for (auto& m : s->marker) HIP_OK(hipEventCreate(&m));
 
   DScene& d = s->d;
@@ -609,6 +761,9 @@ void rtc_scene_destroy(rtc_scene* s) {
   (void)hipFree(s->csg_slab);
   if (s->d_idx) (void)hipFree(s->d_idx);
   if (s->d_rays) (void)hipFree(s->d_rays);
+  (void)hipFree(s->d_srays); (void)hipFree(s->d_srgb);
+  if (s->evs0) (void)hipEventDestroy(s->evs0);
+  if (s->evs1) (void)hipEventDestroy(s->evs1);
   for (auto& m : s->marker) if (m) (void)hipEventDestroy(m);
   if (s->ev0) (void)hipEventDestroy(s->ev0);
   if (s->ev1) (void)hipEventDestroy(s->ev1);
@@ -747,6 +902,102 @@ int rtc_trace_rays(rtc_scene* s, const double* rays, uint64_t n, int32_t fuel, d
   return render_to_host(s, dc, pm, fuel, rgb, nullptr, hits, stats);
 }
 
+// ---- the sampled camera's entry points (include/rtc.h) ---------------------------------------------------------------------------
+int rtc_render_sampled(rtc_scene* s, const rtc_camera* cam, const rtc_sampling* sp, int32_t fuel, const uint64_t* pixel_indices, uint64_t first, uint64_t n,
+                       double* rgb, rtc_stats* stats) {
+  if (!s || !cam || !sp || (!rgb && n)) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  int rc = check_sampling(sp);
+  if (rc != RTC_OK) return rc;
+  if (cam->hsize == 0 || cam->vsize == 0) return rtc_fail(RTC_ERR_INVALID, "empty camera");
+  const uint64_t total = cam->hsize * cam->vsize;
+  if (!pixel_indices && first + n > total) return rtc_fail(RTC_ERR_INVALID, "pixel range exceeds the image");
+  if (n == 0) { if (stats) std::memset(stats, 0, sizeof(*stats)); return RTC_OK; }
+  HIP_OK(hipSetDevice(s->device));
+  rc = ensure_px(s, n, false);
+  if (rc != RTC_OK) return rc;
+  DPixelMap pm{};
+  std::vector<uint64_t> range_idx;
+  rc = make_pixel_map(s, cam, pixel_indices, first, n, &pm, &range_idx);
+  if (rc != RTC_OK) return rc;
+  DCamera dc;
+  to_dcam(*cam, &dc);
+  return render_to_host(s, dc, pm, fuel, rgb, nullptr, nullptr, stats, sp);
+}
+
+int rtc_render_sampled_rgb8(rtc_scene* s, const rtc_camera* cam, const rtc_sampling* sp, int32_t fuel, uint8_t* rgb8, rtc_stats* stats) {
+  if (!s || !cam || !sp || !rgb8) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  int rc = check_sampling(sp);
+  if (rc != RTC_OK) return rc;
+  if (cam->hsize == 0 || cam->vsize == 0) return rtc_fail(RTC_ERR_INVALID, "empty camera");
+  HIP_OK(hipSetDevice(s->device));
+  const uint64_t n = cam->hsize * cam->vsize;
+  rc = ensure_px(s, n, false);
+  if (rc != RTC_OK) return rc;
+  if (3 * n > s->cap_rgb8) {
+    (void)hipFree(s->d_rgb8);
+    s->d_rgb8 = nullptr; s->cap_rgb8 = 0;
+    HIP_OK(hipMalloc((void**)&s->d_rgb8, 3 * n));
+    s->cap_rgb8 = 3 * n;
+  }
+  DPixelMap pm{};
+  pm.n = n; pm.mode = 2; pm.row_first = 0; pm.row_step = 1;
+  DCamera dc;
+  to_dcam(*cam, &dc);
+  return render_to_host(s, dc, pm, fuel, nullptr, rgb8, nullptr, stats, sp);
+}
+
+int rtc_render_sampled_bands_device(rtc_scene* s, const rtc_camera* cam, const rtc_sampling* sp, int32_t fuel, uint32_t band_rows, uint32_t band_first,
+                                    uint32_t band_step, uint32_t n_rows, double* rgb_dev, rtc_stats* stats, int count_stats, int sync) {
+  if (!s || !cam || !sp || (!rgb_dev && n_rows)) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  int rc = check_sampling(sp);
+  if (rc != RTC_OK) return rc;
+  if (band_step == 0 || band_rows == 0) return rtc_fail(RTC_ERR_INVALID, "band_rows and band_step must be >= 1");
+  if (cam->hsize == 0 || cam->vsize == 0) return rtc_fail(RTC_ERR_INVALID, "empty camera");
+  if (n_rows) {
+    const uint64_t j = n_rows - 1, last_row = ((uint64_t)band_first + (j / band_rows) * band_step) * band_rows + j % band_rows;
+    if (last_row >= cam->vsize) return rtc_fail(RTC_ERR_INVALID, "rows exceed the image");
+  }
+  DPixelMap pm{};
+  pm.n = (uint64_t)n_rows * cam->hsize;
+  pm.mode = 2; pm.row_first = band_first; pm.row_step = band_step; pm.band = band_rows;
+  if (pm.n == 0) { if (stats) std::memset(stats, 0, sizeof(*stats)); return RTC_OK; }
+  DCamera dc;
+  to_dcam(*cam, &dc);
+  return run_sampled(s, dc, pm, *sp, fuel, rgb_dev, stats, count_stats != 0, sync != 0);
+}
+
+int rtc_camera_rays(rtc_scene* s, const rtc_camera* cam, const rtc_sampling* sp, const uint64_t* pixel_indices, uint64_t first, uint64_t n, double* rays) {
+  if (!cam || !sp || (!rays && n)) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  int rc = check_sampling(sp);
+  if (rc != RTC_OK) return rc;
+  if (cam->hsize == 0 || cam->vsize == 0) return rtc_fail(RTC_ERR_INVALID, "empty camera");
+  const uint64_t total = cam->hsize * cam->vsize;
+  if (!pixel_indices && (first > total || n > total - first)) return rtc_fail(RTC_ERR_INVALID, "pixel range exceeds the image");
+  if (n == 0) return RTC_OK;
+  const uint64_t N = (uint64_t)sp->side * sp->side;
+  DCamera dc;
+  to_dcam(*cam, &dc);
+  if (!s) {  // the same function on the host
+    for (uint64_t j = 0; j < n; j++) {
+      const uint64_t i = pixel_indices ? pixel_indices[j] : first + j;
+      if (i >= total) return rtc_fail(RTC_ERR_INVALID, "pixel index exceeds the image");
+      for (uint64_t k = 0; k < N; k++) rtc_sample_ray(dc, *sp, i, (uint32_t)k, rays + 6 * (j * N + k));
+    }
+    return RTC_OK;
+  }
+  HIP_OK(hipSetDevice(s->device));
+  DPixelMap pm{};
+  std::vector<uint64_t> range_idx;
+  rc = make_pixel_map(s, cam, pixel_indices, first, n, &pm, &range_idx);
+  if (rc != RTC_OK) return rc;
+  rc = ensure_sampled(s, n * N, false);
+  if (rc != RTC_OK) return rc;
+  rtc_launch_gen_rays(dc, pm, *sp, 0, n, s->d_srays, s->stream);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(rays, s->d_srays, n * N * 6 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  HIP_OK(hipStreamSynchronize(s->stream));
+  return RTC_OK;
+}
 
 int rtc_quantize_device(rtc_scene* s, const double* rgb_dev, uint64_t n_values, uint8_t* out_dev, int sync) {
   if (!s || (n_values && (!rgb_dev || !out_dev))) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
@@ -881,7 +1132,10 @@ struct rtc_multi {
 namespace {
 int multi_fail(rtc_multi* m, int rc) { (void)m; return rc; }
 
-int render_multi(rtc_multi* m, const rtc_camera* cam, int32_t fuel, double* rgb_dev_out, double* rgb_host, rtc_stats* stats, bool sync, uint8_t* rgb8_host = nullptr) {
+// `sp`: every replica renders its tile through run_sampled (with stats: synchronously, one replica after the other -- a sampled
+// launch's counters are summed over its chunks by the host).
+int render_multi(rtc_multi* m, const rtc_camera* cam, int32_t fuel, double* rgb_dev_out, double* rgb_host, rtc_stats* stats, bool sync, uint8_t* rgb8_host = nullptr,
+                 const rtc_sampling* sp = nullptr) {
   const bool q8 = rgb8_host != nullptr;
   if (!m || !cam) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
   if (cam->hsize == 0 || cam->vsize == 0) return rtc_fail(RTC_ERR_INVALID, "empty camera");
@@ -946,6 +1200,7 @@ int render_multi(rtc_multi* m, const rtc_camera* cam, int32_t fuel, double* rgb_
   }
   double* image = rgb_dev_out ? rgb_dev_out : m->image;
   if (stats) std::memset(stats, 0, sizeof(*stats));
+  std::vector<rtc_stats> sampled_stats(sp && stats ? n : 0);
   // every replica traces its interleaved rows on its own device and stream; nothing is exchanged while tracing
   for (uint32_t k = 0; k < n; k++) {
     rtc_scene* s = m->scenes[k];
@@ -958,7 +1213,8 @@ int render_multi(rtc_multi* m, const rtc_camera* cam, int32_t fuel, double* rgb_
       HIP_OK(hipStreamWaitEvent(s->stream, m->copied[k], 0));
     }
     // asynchronous on the replica's own stream (the counting variant when stats are wanted: they are read back after the gather)
-    int rc = run(s, dc, pm, fuel, m->tiles[k], false, nullptr, stats != nullptr, false);
+    int rc = sp ? run_sampled(s, dc, pm, *sp, fuel, m->tiles[k], stats ? &sampled_stats[k] : nullptr, stats != nullptr, false)
+                : run(s, dc, pm, fuel, m->tiles[k], false, nullptr, stats != nullptr, false);
     if (rc != RTC_OK) return rc;
     HIP_OK(hipSetDevice(s->device));
     if (q8) {  // Color::clamp on the replica's own device, behind its trace kernels
@@ -1009,13 +1265,14 @@ int render_multi(rtc_multi* m, const rtc_camera* cam, int32_t fuel, double* rgb_
     if (h.wf_overflow) {  // an unsynchronised wavefront launch overflowed its queues: once more, synchronously (falls back by itself)
       DPixelMap pm{};
       pm.n = rows * H; pm.mode = 2; pm.row_first = k; pm.row_step = n; pm.band = B;
-      rc = run(s, dc, pm, fuel, m->tiles[k], false, nullptr, false, true);
+      rc = sp ? run_sampled(s, dc, pm, *sp, fuel, m->tiles[k], nullptr, false, true) : run(s, dc, pm, fuel, m->tiles[k], false, nullptr, false, true);
       if (rc != RTC_OK) return rc;
-      return render_multi(m, cam, fuel, rgb_dev_out, rgb_host, stats, true, rgb8_host);
+      return render_multi(m, cam, fuel, rgb_dev_out, rgb_host, stats, true, rgb8_host, sp);
     }
     if (stats && rows) {
       rtc_stats st;
-      rc = fill_stats(s, h, rows * H, &st);
+      if (sp) st = sampled_stats[k];
+      else rc = fill_stats(s, h, rows * H, &st);
       if (rc != RTC_OK) return rc;
       stats->pixels += st.pixels; stats->rays_primary += st.rays_primary; stats->rays_shadow += st.rays_shadow; stats->rays_reflect += st.rays_reflect;
       stats->rays_refract += st.rays_refract; stats->rays_container += st.rays_container; stats->accel_nodes += st.accel_nodes; stats->group_tests += st.group_tests;
@@ -1118,6 +1375,13 @@ int rtc_multi_set_band_rows(rtc_multi* m, uint32_t band_rows) {
 int rtc_render_multi(rtc_multi* m, const rtc_camera* cam, int32_t fuel, double* rgb, rtc_stats* stats) {
   if (!rgb) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
   return render_multi(m, cam, fuel, nullptr, rgb, stats, true);
+}
+
+int rtc_render_multi_sampled(rtc_multi* m, const rtc_camera* cam, const rtc_sampling* sp, int32_t fuel, double* rgb, rtc_stats* stats) {
+  if (!rgb || !sp) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  const int rc = check_sampling(sp);
+  if (rc != RTC_OK) return rc;
+  return render_multi(m, cam, fuel, nullptr, rgb, stats, true, nullptr, sp);
 }
 
 int rtc_render_multi_rgb8(rtc_multi* m, const rtc_camera* cam, int32_t fuel, uint8_t* rgb8, rtc_stats* stats) {

@@ -7,8 +7,8 @@ from __future__ import annotations
 
 import ctypes as C
 
-from .backend import Backend, CameraC, NativeWorld, RtwError
-from .scene import Camera
+from .backend import Backend, CameraC, NativeWorld, RtwError, SamplingC
+from .scene import Camera, Sampling
 
 
 class RtcCameraC(C.Structure):
@@ -121,8 +121,22 @@ class DeviceRenderer:
         if lib.rtw_make_camera(C.byref(cc), C.byref(self.cam)) != 0:
             raise RtwError("camera: %s" % backend._err())
 
+    def _bands(self, sampling, fuel, band_rows, row_first, row_step, n_rows, out_tensor, stats, count, sync) -> int:
+        """rtc_render_bands_device, or with a Sampling rtc_render_sampled_bands_device."""
+        lib = self.backend.lib
+        tail = (int(fuel), int(band_rows), int(row_first), int(row_step), int(n_rows), C.c_void_p(out_tensor.data_ptr()), stats, 1 if count else 0, 1 if sync else 0)
+        if sampling is None:
+            return lib.rtc_render_bands_device(self.scene, C.byref(self.cam), *tail)
+        if not hasattr(lib, "rtc_render_sampled_bands_device"):
+            raise RtwError("sampled cameras need librtc_amd.so (backend %r has no rtc_render_sampled_bands_device)" % self.backend.name)
+        lib.rtc_render_sampled_bands_device.restype = C.c_int
+        lib.rtc_render_sampled_bands_device.argtypes = [C.c_void_p, C.POINTER(RtcCameraC), C.POINTER(SamplingC), C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                        C.c_uint32, C.c_void_p, C.POINTER(RtcStatsC), C.c_int, C.c_int]
+        sp = SamplingC.of(sampling)
+        return lib.rtc_render_sampled_bands_device(self.scene, C.byref(self.cam), C.byref(sp), *tail)
+
     def render_rows(self, fuel: int, row_first: int, row_step: int, n_rows: int, out_tensor, count: bool = False, sync: bool = True,
-                    want_stats: bool = True, band_rows: int = 1) -> dict:
+                    want_stats: bool = True, band_rows: int = 1, sampling: Sampling = None) -> dict:
         """The first n_rows rows of the dense tile of part `row_first` of `row_step` -> out_tensor (float64, n_rows*hsize*3, on this
         scene's GPU).  band_rows = 1: image rows row_first, row_first+row_step, ...; band_rows = B: bands of B rows dealt out the
         same way (include/rtc.h rtc_render_bands_device; parallel.BAND_ROWS = 8 is the multi-GPU partition)."""
@@ -130,8 +144,7 @@ class DeviceRenderer:
         if out_tensor.numel() < need or out_tensor.element_size() != 8 or not (out_tensor.is_cuda or self._cpu_standin):
             raise RtwError("output tensor must be a float64 device tensor with >= %d elements" % need)
         st = RtcStatsC()
-        rc = self.backend.lib.rtc_render_bands_device(self.scene, C.byref(self.cam), int(fuel), int(band_rows), int(row_first), int(row_step), int(n_rows),
-                                                      C.c_void_p(out_tensor.data_ptr()), C.byref(st) if want_stats else None, 1 if count else 0, 1 if sync else 0)
+        rc = self._bands(sampling, fuel, band_rows, row_first, row_step, n_rows, out_tensor, C.byref(st) if want_stats else None, count, sync)
         if rc != 0:
             raise RtwError("rtc_render_bands_device: %s" % (self.backend.lib.rtc_last_error() or b"").decode())
         return st.as_dict() if want_stats else {}
@@ -140,13 +153,12 @@ class DeviceRenderer:
         if rc != 0:
             raise RtwError("%s: %s" % (what, (self.backend.lib.rtc_last_error() or b"").decode()))
 
-    def render_rows_async(self, fuel: int, row_first: int, row_step: int, n_rows: int, out_tensor, band_rows: int = 1):
+    def render_rows_async(self, fuel: int, row_first: int, row_step: int, n_rows: int, out_tensor, band_rows: int = 1, sampling: Sampling = None):
         """Queue a render on the scene's stream and return immediately (errors are reported by check())."""
         need = n_rows * self.camera.hsize * 3
         if out_tensor.numel() < need or out_tensor.element_size() != 8 or not (out_tensor.is_cuda or self._cpu_standin):
             raise RtwError("output tensor must be a float64 device tensor with >= %d elements" % need)
-        self._rc(self.backend.lib.rtc_render_bands_device(self.scene, C.byref(self.cam), int(fuel), int(band_rows), int(row_first), int(row_step), int(n_rows),
-                                                         C.c_void_p(out_tensor.data_ptr()), None, 0, 0), "rtc_render_bands_device")
+        self._rc(self._bands(sampling, fuel, band_rows, row_first, row_step, n_rows, out_tensor, None, False, False), "rtc_render_bands_device")
 
     def record(self, slot: int):
         self._rc(self.backend.lib.rtc_scene_record(self.scene, slot), "rtc_scene_record")

@@ -10,7 +10,7 @@ import ctypes as C
 
 import numpy as np
 
-from .scene import FUEL, Camera, Color, World
+from .scene import FUEL, Camera, Color, Sampling, World
 
 
 class Image:
@@ -20,10 +20,14 @@ class Image:
         self._native = _native  # (backend, NativeWorld) that rendered it, for the device quantiser
 
     @staticmethod
-    def par_render(camera: Camera, world: World, fuel: int = FUEL, backend=None) -> "Image":
+    def par_render(camera: Camera, world: World, fuel: int = FUEL, backend=None, sampling: Sampling = None) -> "Image":
+        """sampling: a :class:`Sampling` renders every pixel as the mean of its sample rays (anti-aliasing, depth of field); None is
+        the reference's one ray per pixel."""
         from . import hip_backend
         be = backend or hip_backend()
         nw = be.build_world(world)
+        if sampling is not None:
+            return Image(camera.hsize, camera.vsize, be.render_sampled(nw, camera, sampling, fuel), (be, nw))
         rgb, _ = be.render(nw, camera, fuel, want_hits=False)
         return Image(camera.hsize, camera.vsize, rgb, (be, nw))
 

@@ -319,6 +319,39 @@ class World:  # src/world.rs:12-15; lights: PointLight and AreaLight in any orde
         return World([PointLight(Color.white(), Vector.point(-10.0, 10.0, -10.0))], [s1, s2])
 
 
+SAMPLES_MAX_SIDE = 16  # include/rtc.h RTC_SAMPLES_MAX_SIDE
+
+
+@dataclass(frozen=True)
+class Sampling:
+    """The sampled camera (include/rtc.h rtc_sampling; not in the reference): ``side x side`` samples per pixel, at the cell centres
+    or, with ``jitter``, at hashed positions inside the cells (``seed``), averaged with a box filter; ``lens_radius > 0`` adds a thin
+    lens focused at camera-space depth ``focal_distance``.  ``Sampling()`` is the reference's one ray through the pixel centre.
+    Rendered by the HIP library only."""
+    side: int = 1
+    jitter: bool = False
+    seed: int = 0
+    lens_radius: float = 0.0
+    focal_distance: float = 1.0
+
+    def __post_init__(self):
+        import math
+        if int(self.side) != self.side or self.side < 1:
+            raise ValueError("Sampling.side must be an integer >= 1")
+        if self.side > SAMPLES_MAX_SIDE:
+            raise ValueError("Sampling.side exceeds %d" % SAMPLES_MAX_SIDE)
+        if not 0 <= int(self.seed) < 1 << 64:
+            raise ValueError("Sampling.seed must fit 64 bits")
+        if not math.isfinite(self.lens_radius) or self.lens_radius < 0.0:
+            raise ValueError("Sampling.lens_radius must be finite and >= 0")
+        if self.lens_radius > 0.0 and (not math.isfinite(self.focal_distance) or self.focal_distance <= 0.0):
+            raise ValueError("Sampling.focal_distance must be finite and > 0 when lens_radius > 0")
+
+    @property
+    def samples(self) -> int:
+        return self.side * self.side
+
+
 @dataclass(frozen=True)
 class Camera:  # src/camera.rs:5-13; derived fields are computed natively from `transform`
     hsize: int

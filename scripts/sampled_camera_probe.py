@@ -1,0 +1,199 @@
+#!/usr/bin/env python3
+"""Cost of the sampled camera (include/rtc.h rtc_sampling) on config 2's scene at fuel 5: the 1920x1080 frame sampled 2x2 and 4x4,
+grid and jittered, on each pinned device path and with the library choosing, beside the plain 3840x2160 and 7680x4320 frames of the
+same build -- the only way to the same image without the feature.  Device time between stream markers around K asynchronous
+whole-frame launches, warmed; ROUNDS rounds that alternate over all configurations in one process, so every figure has a run-to-run
+spread (min / median / max over the rounds).
+
+Alongside: the generator's and the resolve's own times (RTC_SAMPLED_TIMING=1: the events around a chunk's three parts), the chunk
+bounds 2^20, 2^22 and 2^24 rays (RTC_SAMPLED_MAX_RAYS), and host pixels: rtc_render_sampled 2x2 against rtc_render at 4K plus a numpy
+box filter (wall clock).
+
+The bar (printed at the end): the 2x2 frame may cost more than the plain 4K frame of the same run by at most the 4K frame's measured
+spread plus the time its extra traffic needs at the HBM peak (8.0 TB/s): 48 B written and read per ray, 24 B per ray colour.
+
+usage: sampled_camera_probe.py [K [ROUNDS]]     (GPU)
+       sampled_camera_probe.py --resource-usage  (no GPU: the compiler's figures for rtc_gen_rays and rtc_resolve_samples)"""
+import ctypes as C
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+CSRC = os.path.join(ROOT, "raytracer_challenge_amd", "csrc")
+HBM_PEAK = 8.0e12   # bytes / s
+
+
+def resource_usage():
+    out = subprocess.run(["make", "-s", "-C", CSRC, "resource-usage", "VARIANTS="], check=True, stdout=subprocess.PIPE, text=True).stdout
+    for line in out.splitlines():
+        if "rtc_gen_rays" in line or "rtc_resolve_samples" in line:
+            print("  " + "  ".join(line.split("\t")))
+
+
+def main(k, rounds):
+    import numpy as np
+    import torch
+    import raytracer_challenge_amd as rt
+    from raytracer_challenge_amd import scenes
+    from raytracer_challenge_amd.backend import SamplingC
+    from raytracer_challenge_amd.device import RtcStatsC
+    from raytracer_challenge_amd.scene import Camera, Sampling
+
+    cam, world = scenes.synthetic_analytic(n_primitives=512, seed=12345, cones=False, grouped=False, hsize=1920, vsize=1080)
+    be = rt.hip_backend()
+    lib = be.lib
+    vp = C.c_void_p
+    lib.rtw_world_scene.restype, lib.rtw_world_scene.argtypes = vp, [vp, C.c_int]
+    lib.rtw_make_camera.restype, lib.rtw_make_camera.argtypes = C.c_int, [vp, vp]
+    lib.rtc_render.restype, lib.rtc_render.argtypes = C.c_int, [vp, vp, C.c_int32, vp, C.c_uint64, C.c_uint64, vp, vp, vp]
+    lib.rtc_render_sampled.restype, lib.rtc_render_sampled.argtypes = C.c_int, [vp, vp, vp, C.c_int32, vp, C.c_uint64, C.c_uint64, vp, vp]
+    lib.rtc_render_rows_device.restype = C.c_int
+    lib.rtc_render_rows_device.argtypes = [vp, vp, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.POINTER(RtcStatsC), C.c_int, C.c_int]
+    lib.rtc_render_sampled_bands_device.restype = C.c_int
+    lib.rtc_render_sampled_bands_device.argtypes = [vp, vp, vp, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.POINTER(RtcStatsC), C.c_int, C.c_int]
+    for f in ("rtc_scene_record", "rtc_scene_wait"):
+        getattr(lib, f).restype, getattr(lib, f).argtypes = C.c_int, [vp, C.c_int]
+    lib.rtc_scene_check.restype, lib.rtc_scene_check.argtypes = C.c_int, [vp]
+    lib.rtc_scene_elapsed_ms.restype, lib.rtc_scene_elapsed_ms.argtypes = C.c_int, [vp, C.c_int, C.c_int, C.POINTER(C.c_double)]
+    lib.rtc_scene_path_info.restype, lib.rtc_scene_path_info.argtypes = None, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.rtc_last_error.restype = C.c_char_p
+
+    def rtc_camera(c):
+        out = (C.c_double * 21)()
+        assert lib.rtw_make_camera(C.byref(be.camera_c(c)), out) == 0
+        return out
+    cams = {s: Camera.new(1920 * s, 1080 * s, cam.field_of_view, cam.transform_matrix) for s in (1, 2, 4)}
+    rcs = {s: rtc_camera(c) for s, c in cams.items()}
+    out = torch.empty(7680 * 4320 * 3, dtype=torch.float64, device="cuda:0")
+    torch.cuda.synchronize()
+    outp = C.c_void_p(out.data_ptr())
+
+    # one scene per path setting (RTC_KERNEL is read when a scene is created)
+    scene_of, worlds = {}, []
+    for path in ("1", "4", "auto"):
+        if path == "auto":
+            os.environ.pop("RTC_KERNEL", None)
+        else:
+            os.environ["RTC_KERNEL"] = path
+        nw = be.build_world(world)
+        worlds.append(nw)
+        scene_of[path] = lib.rtw_world_scene(nw.handle, 0)
+        assert scene_of[path], be._err()
+    os.environ.pop("RTC_KERNEL", None)
+
+    def launch(scene, cfg, sync):
+        kind, a, jit = cfg
+        if kind == "plain":
+            return lib.rtc_render_rows_device(scene, rcs[a], 5, 0, 1, 1080 * a, outp, None, 0, sync)
+        sp = SamplingC.of(Sampling(side=a, jitter=jit, seed=1))
+        return lib.rtc_render_sampled_bands_device(scene, rcs[1], C.byref(sp), 5, 1, 0, 1, 1080, outp, None, 0, sync)
+
+    def timed(scene, cfg, n):
+        if scene == scene_of["auto"]:   # the library remembers ONE measured launch shape: measure this one again (four synchronous launches)
+            for _ in range(4):
+                assert launch(scene, cfg, 1) == 0, lib.rtc_last_error()
+        assert lib.rtc_scene_record(scene, 0) == 0
+        for _ in range(n):
+            assert launch(scene, cfg, 0) == 0, lib.rtc_last_error()
+        assert lib.rtc_scene_record(scene, 1) == 0 and lib.rtc_scene_wait(scene, 1) == 0
+        ms = C.c_double()
+        assert lib.rtc_scene_elapsed_ms(scene, 0, 1, C.byref(ms)) == 0
+        assert lib.rtc_scene_check(scene) == 0, lib.rtc_last_error()
+        return ms.value / n
+
+    configs = [("plain", 2, False), ("plain", 4, False), ("sampled", 2, False), ("sampled", 2, True), ("sampled", 4, False), ("sampled", 4, True)]
+
+    def label(cfg):
+        kind, a, jit = cfg
+        return "plain %dx%d" % (1920 * a, 1080 * a) if kind == "plain" else "1080p %dx%d %s" % (a, a, "jittered" if jit else "grid")
+    results, choice = {}, {}
+    # warm-up: code loading, queues, buffers; with the library choosing, the four synchronous launches of its measurement
+    for path, scene in scene_of.items():
+        for cfg in configs:
+            for _ in range(4 if path == "auto" else 2):
+                assert launch(scene, cfg, 1) == 0, lib.rtc_last_error()
+            if path == "auto":
+                ch, m1, m4 = C.c_int32(), C.c_double(), C.c_double()
+                lib.rtc_scene_path_info(scene, C.byref(ch), C.byref(m1), C.byref(m4))
+                choice[label(cfg)] = {"path": ch.value, "one_kernel_ms": m1.value, "wavefront_ms": m4.value}
+                print("%-24s library's choice: path %d (traces: one kernel %.2f ms, wavefront %.2f ms)" % (label(cfg), ch.value, m1.value, m4.value), flush=True)
+    for r in range(rounds):
+        for cfg in configs:
+            for path, scene in scene_of.items():
+                results.setdefault((label(cfg), path), []).append(timed(scene, cfg, k))
+    print("ms per frame, min / median / max over %d rounds of %d frames:" % (rounds, k))
+    table = {}
+    for (lb, path), v in results.items():
+        table["%s | path %s" % (lb, path)] = {"min": min(v), "median": statistics.median(v), "max": max(v)}
+        print("  %-24s path %-4s  %8.3f / %8.3f / %8.3f" % (lb, path, min(v), statistics.median(v), max(v)), flush=True)
+
+    # the generator's and the resolve's own times: one synchronous frame with stats per sampling, the chunks' parts on stderr
+    parts = {}
+    os.environ["RTC_SAMPLED_TIMING"] = "1"
+    for cfg in configs[2:]:
+        st = RtcStatsC()
+        sp = SamplingC.of(Sampling(side=cfg[1], jitter=cfg[2], seed=1))
+        sys.stderr.write("[probe] %s, path auto:\n" % label(cfg))
+        sys.stderr.flush()
+        assert lib.rtc_render_sampled_bands_device(scene_of["auto"], rcs[1], C.byref(sp), 5, 1, 0, 1, 1080, outp, C.byref(st), 0, 1) == 0, lib.rtc_last_error()
+        parts[label(cfg)] = {"kernel_ms": st.kernel_ms, "n_launches": st.n_launches}
+    os.environ.pop("RTC_SAMPLED_TIMING")
+
+    # chunk bounds
+    chunks = {}
+    for bound in (1 << 20, 1 << 22, 1 << 24):
+        os.environ["RTC_SAMPLED_MAX_RAYS"] = str(bound)
+        for cfg in (configs[2], configs[4]):
+            for path in ("1", "4"):
+                launch(scene_of[path], cfg, 1)
+                v = [timed(scene_of[path], cfg, k) for _ in range(3)]
+                chunks["%s | path %s | 2^%d rays" % (label(cfg), path, bound.bit_length() - 1)] = statistics.median(v)
+                print("  chunk bound 2^%d: %-24s path %s  %8.3f ms" % (bound.bit_length() - 1, label(cfg), path, statistics.median(v)), flush=True)
+    os.environ.pop("RTC_SAMPLED_MAX_RAYS")
+
+    # host pixels: the sampled frame against the 4K frame plus a numpy box filter (wall clock, best of 3)
+    n1, n2 = 1920 * 1080, 3840 * 2160
+    rgb1, rgb2 = np.empty((n1, 3)), np.empty((n2, 3))
+    sp = SamplingC.of(Sampling(side=2))
+    host = {}
+    for path in ("1", "4", "auto"):
+        scene = scene_of[path]
+        a, b = [], []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            assert lib.rtc_render_sampled(scene, rcs[1], C.byref(sp), 5, None, 0, n1, rgb1.ctypes.data, None) == 0, lib.rtc_last_error()
+            t1 = time.perf_counter()
+            assert lib.rtc_render(scene, rcs[2], 5, None, 0, n2, rgb2.ctypes.data, None, None) == 0, lib.rtc_last_error()
+            f = rgb2.reshape(1080, 2, 1920, 2, 3)
+            box = (((f[:, 0, :, 0] + f[:, 0, :, 1]) + f[:, 1, :, 0]) + f[:, 1, :, 1]) / 4.0
+            t2 = time.perf_counter()
+            a.append((t1 - t0) * 1e3)
+            b.append((t2 - t1) * 1e3)
+        same = bool(np.array_equal(box.reshape(-1, 3), rgb1))
+        host[path] = {"rtc_render_sampled_ms": min(a), "rtc_render_4k_plus_numpy_ms": min(b), "bit_identical": same}
+        print("host pixels, path %-4s: rtc_render_sampled 2x2 %.1f ms; rtc_render at 4K + numpy box filter %.1f ms; bit-identical: %s" % (path, min(a), min(b), same), flush=True)
+
+    # the bar
+    rays = n1 * 4
+    traffic_ms = rays * (48 * 2 + 24 * 2) / HBM_PEAK * 1e3
+    bar = {}
+    for path in ("1", "4", "auto"):
+        p4k, s22 = table["plain 3840x2160 | path %s" % path], table["1080p 2x2 grid | path %s" % path]
+        spread = p4k["max"] - p4k["min"]
+        over = s22["median"] - p4k["median"]
+        bar[path] = {"over_ms": over, "allowed_ms": spread + traffic_ms, "spread_4k_ms": spread, "traffic_ms": traffic_ms, "within": over <= spread + traffic_ms}
+        print("bar, path %-4s: 2x2 grid %.3f ms - plain 4K %.3f ms = %+.3f ms; allowed %.3f ms (4K spread %.3f + traffic at HBM peak %.3f): %s"
+              % (path, s22["median"], p4k["median"], over, spread + traffic_ms, spread, traffic_ms, "within" if bar[path]["within"] else "OVER"))
+    print(json.dumps({"k": k, "rounds": rounds, "ms": table, "choice": choice, "parts": parts, "chunks": chunks, "host": host, "bar": bar}))
+
+
+if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--resource-usage":
+        resource_usage()
+    else:
+        main(int(sys.argv[1]) if len(sys.argv) > 1 else 5, int(sys.argv[2]) if len(sys.argv) > 2 else 5)

@@ -124,6 +124,21 @@ pub struct RtcSceneExt {
     pub textures: *const RtcTexture,
 }
 
+// include/rtc.h rtc_sampling: n x n samples per pixel and an optional thin lens (not in the reference) for rtc_render_sampled*
+#[allow(dead_code)]
+pub const RTC_SAMPLE_JITTER: u32 = 1;
+#[allow(dead_code)]
+pub const RTC_SAMPLES_MAX_SIDE: u32 = 16;
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtcSampling {
+    pub side: u32,  // n: n x n samples per pixel
+    pub flags: u32, // RTC_SAMPLE_JITTER
+    pub seed: u64,
+    pub lens_radius: f64,    // 0 = pinhole
+    pub focal_distance: f64, // camera-space depth in focus; read only when lens_radius > 0
+}
+
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct RtcNode {
@@ -224,6 +239,20 @@ extern "C" {
     fn rtc_render_multi_rgb8(multi: *mut RtcMulti, camera: *const RtcCamera, fuel: i32, rgb8: *mut u8, stats: *mut RtcStats) -> c_int;
     #[allow(dead_code)] // the same on one device: quantised on the GPU, 3 bytes per pixel cross PCIe
     fn rtc_render_rgb8(scene: *mut RtcScene, camera: *const RtcCamera, fuel: i32, rgb8: *mut u8, stats: *mut RtcStats) -> c_int;
+    // the sampled camera: rtc_render / rtc_render_rgb8 / rtc_render_bands_device / rtc_render_multi with an RtcSampling; the rays alone
+    #[allow(dead_code)]
+    fn rtc_render_sampled(scene: *mut RtcScene, camera: *const RtcCamera, sampling: *const RtcSampling, fuel: i32, pixel_indices: *const u64, first: u64,
+                          n: u64, rgb: *mut f64, stats: *mut RtcStats) -> c_int;
+    #[allow(dead_code)]
+    fn rtc_render_sampled_rgb8(scene: *mut RtcScene, camera: *const RtcCamera, sampling: *const RtcSampling, fuel: i32, rgb8: *mut u8, stats: *mut RtcStats) -> c_int;
+    #[allow(dead_code)]
+    fn rtc_render_sampled_bands_device(scene: *mut RtcScene, camera: *const RtcCamera, sampling: *const RtcSampling, fuel: i32, band_rows: u32, band_first: u32,
+                                       band_step: u32, n_rows: u32, rgb_dev: *mut f64, stats: *mut RtcStats, count_stats: c_int, sync: c_int) -> c_int;
+    #[allow(dead_code)]
+    fn rtc_render_multi_sampled(multi: *mut RtcMulti, camera: *const RtcCamera, sampling: *const RtcSampling, fuel: i32, rgb: *mut f64, stats: *mut RtcStats) -> c_int;
+    #[allow(dead_code)] // scene = null: evaluated on the host, no device needed
+    fn rtc_camera_rays(scene: *mut RtcScene, camera: *const RtcCamera, sampling: *const RtcSampling, pixel_indices: *const u64, first: u64, n: u64,
+                       rays: *mut f64) -> c_int;
 }
 
 #[derive(Debug)]
