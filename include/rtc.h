@@ -215,6 +215,31 @@ typedef struct rtc_sampling {
   double focal_distance;  /* F, camera-space depth that is in focus; read only when R > 0 */
 } rtc_sampling;
 
+/* Adaptive sampling (not in the reference): render the frame once with `base`, find the pixels that differ from a neighbour, render
+ * those again with `fine`; for rtc_render_adaptive* and, the contrast rule alone, rtc_contrast_pixels.  Pixel i has x = i % hsize,
+ * y = i / hsize; every step is one f64 operation or comparison (csrc/adaptive_contrast.h, one function for device and host).
+ *   Base frame: B[i] = rtc_render_sampled's pixel i with `base`, for every pixel of the frame.
+ *   Contrast: q(c) = c < 0 ? 0 : (c > 1 ? 1 : c) per channel value -- what a viewer sees after Color::clamp; NaN passes through.  The
+ *     neighbours of p = (x, y) are (x-1, y), (x+1, y), (x, y-1), (x, y+1) and, with neighbours == 8, the four diagonals; only those inside
+ *     the image count.  For a neighbour r: d = fabs(q(B[p][0]) - q(B[r][0])), then for c = 1, 2: e = fabs(q(B[p][c]) - q(B[r][c])),
+ *     d = (e > d) ? e : d -- so a NaN in the first channel stays (d is NaN), a NaN in a later channel is skipped.
+ *   p is REFINED iff some neighbour has !(d <= threshold).  d is symmetric in p and r: both sides of an edge refine.  A NaN d refines at
+ *     any threshold; threshold = +inf refines nothing else; a negative threshold refines every pixel that has a neighbour (every pixel
+ *     of a frame larger than 1x1); a 1x1 frame refines nothing.
+ *   Result: a refined pixel is exactly rtc_render_sampled's pixel with `fine` (the base sample is not blended in), any other pixel is
+ *     B[i]: every pixel of the result is, bit for bit, a pixel of one of two rtc_render_sampled frames.
+ * Limits: `base` and `fine` as rtc_sampling's; RTC_ERR_INVALID for a NaN threshold, neighbours other than 4 or 8, NULL arguments;
+ * RTC_ERR_UNSUPPORTED for a frame of 2^39 pixels or more.
+ * Not covered: bands, rtc_render_multi and several devices (a band's edge rows need neighbours another device owns); a measured device
+ * path for the refined list; filters other than the box mean; refining the refined pixels again. */
+typedef struct rtc_adaptive {
+  rtc_sampling base;      /* first pass: every pixel */
+  rtc_sampling fine;      /* second pass: the refined pixels */
+  double threshold;
+  uint32_t neighbours;    /* 4 or 8 */
+  uint32_t _pad;
+} rtc_adaptive;
+
 /* The Element tree (src/shape.rs:31-34, :181-185) in DFS pre-order.  A group node carries the world-space
  * bounding box the reference computed for it (Element::composite + propagate_inverses; NaN/inf included,
  * SURVEY Q9) and `skip` = index of the first node after its subtree.  The device evaluates
@@ -387,6 +412,26 @@ int rtc_render_multi_sampled(rtc_multi*, const rtc_camera*, const rtc_sampling*,
 /* The sample rays themselves: n*N rows {o, d}, pixel-major, k inner (host array).  scene != NULL: generated by the device kernel and
  * copied back; scene == NULL: evaluated on the host by the same function, no device needed (like rtc_ppm). */
 int rtc_camera_rays(rtc_scene*, const rtc_camera*, const rtc_sampling*, const uint64_t* pixel_indices, uint64_t first, uint64_t n, double* rays);
+
+/* ---- adaptive sampling (rtc_adaptive above) ---------------------------------------------------------------------------------------
+ * The whole frame (the rule needs neighbours), on one device.  On the scene's stream: the base pass into the frame buffer (`base` of
+ * side 1 without jitter or lens goes the way rtc_render goes: row launch, measured path choice; the bits are the same), three small
+ * kernels that flag the refined pixels and compact their indices into an ascending device list (ballot masks, a scan of per-block counts,
+ * a scatter: no atomic orders it), then rtc_render_sampled's chunks over that list with `fine`, whose resolve writes each mean to
+ * its pixel of the frame.  The host must know the list's length to size the chunks: ONE 8-byte read-back between the passes is the
+ * synchronisation this feature adds (the base pass itself ends as a synchronous rtc_render does).  A list of 0 pixels skips the second pass.
+ * Device path of the second pass: RTC_KERNEL pins as ever; otherwise the scene's first guess (rtc_scene_path_info) over the rays of
+ * a chunk -- the list's length changes with every frame, so nothing is measured.
+ * rgb: hsize*vsize*3 doubles (host).  mask (optional): hsize*vsize bytes (host), 1 = refined.  n_refined (optional): the list's length.
+ * rtc_stats: pixels = the frame's, rays_primary = pixels * Nb + n_refined * Nf, counters summed over both passes, kernel_ms = both
+ * passes and the kernels between them. */
+int rtc_render_adaptive(rtc_scene*, const rtc_camera*, const rtc_adaptive*, int32_t fuel, double* rgb, uint8_t* mask, uint64_t* n_refined, rtc_stats* stats);
+/* Same, quantised on the device (Color::clamp): rgb8 = hsize*vsize*3 bytes (host). */
+int rtc_render_adaptive_rgb8(rtc_scene*, const rtc_camera*, const rtc_adaptive*, int32_t fuel, uint8_t* rgb8, uint8_t* mask, uint64_t* n_refined, rtc_stats* stats);
+/* The contrast rule alone on a host frame (rgb: hsize*vsize*3 doubles): indices[0 .. *n - 1] = the refined pixels' image indices in
+ * ascending order (indices: room for hsize*vsize values, host).  scene != NULL: the frame is uploaded, the device kernels flag and
+ * compact, the list is copied back; scene == NULL: evaluated on the host by the same function, no device needed (like rtc_camera_rays). */
+int rtc_contrast_pixels(rtc_scene*, uint64_t hsize, uint64_t vsize, const double* rgb, double threshold, uint32_t neighbours, uint64_t* indices, uint64_t* n);
 
 /* ---- the step after the path: Color::clamp and Image::ppm ---------------------------------
  * Color::clamp (src/color.rs:42-46): u8 = round(min(max(c, 0), 1) * 255), round half away from zero, NaN -> 255 (Rust's

@@ -13,7 +13,7 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from .scene import (FUEL, GEOMETRY, GROUP_KINDS, JITTER_KINDS, MIXTURE_KINDS, AreaLight, Camera, Element, Material, Pattern, Sampling, World)
+from .scene import (FUEL, GEOMETRY, GROUP_KINDS, JITTER_KINDS, MIXTURE_KINDS, Adaptive, AreaLight, Camera, Element, Material, Pattern, Sampling, World)
 from .texture import UV_KINDS, UV_MAPS, Texture
 
 HIT_DTYPE = np.dtype([("t", "<f8"), ("prim", "<i4"), ("push_idx", "<i4")])
@@ -43,6 +43,14 @@ class SamplingC(C.Structure):  # include/rtc.h rtc_sampling
     @staticmethod
     def of(s: Sampling) -> "SamplingC":
         return SamplingC(int(s.side), 1 if s.jitter else 0, int(s.seed), float(s.lens_radius), float(s.focal_distance))
+
+
+class AdaptiveC(C.Structure):  # include/rtc.h rtc_adaptive
+    _fields_ = [("base", SamplingC), ("fine", SamplingC), ("threshold", C.c_double), ("neighbours", C.c_uint32), ("_pad", C.c_uint32)]
+
+    @staticmethod
+    def of(a: Adaptive) -> "AdaptiveC":
+        return AdaptiveC(SamplingC.of(a.base), SamplingC.of(a.fine), float(a.threshold), int(a.neighbours), 0)
 
 
 RTW_SYMBOLS = [
@@ -343,6 +351,56 @@ class Backend:
         if lib.rtc_camera_rays(scene, C.byref(rc_cam), C.byref(sp), idx_p, 0, n, rays.ctypes.data) != 0:
             raise RtwError("rtc_camera_rays: %s" % (lib.rtc_last_error() or b"").decode())
         return rays
+
+    def _adaptive_lib(self):
+        """The rtc_* entry points of adaptive sampling, bound; RtwError for a library that has none (the CPU emulator, the oracle)."""
+        lib = self.lib
+        if not (hasattr(lib, "rtc_render_adaptive") and hasattr(lib, "rtc_contrast_pixels")):
+            raise RtwError("adaptive sampling needs librtc_amd.so (backend %r has no rtc_render_adaptive)" % self.name)
+        vp = C.c_void_p
+        lib.rtw_world_scene.restype, lib.rtw_world_scene.argtypes = vp, [vp, C.c_int]
+        lib.rtw_make_camera.restype, lib.rtw_make_camera.argtypes = C.c_int, [vp, vp]
+        lib.rtc_render_adaptive.restype = C.c_int
+        lib.rtc_render_adaptive.argtypes = [vp, vp, C.POINTER(AdaptiveC), C.c_int32, vp, vp, C.POINTER(C.c_uint64), vp]
+        lib.rtc_contrast_pixels.restype = C.c_int
+        lib.rtc_contrast_pixels.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.c_double, C.c_uint32, vp, C.POINTER(C.c_uint64)]
+        lib.rtc_last_error.restype = C.c_char_p
+        return lib
+
+    def render_adaptive(self, nw: NativeWorld, camera: Camera, adaptive: Adaptive, fuel: int = FUEL, want_mask: bool = False, device: int = 0):
+        """include/rtc.h rtc_render_adaptive: the whole frame, base pass plus the refined pixels' fine pass.  Returns rgb[n,3] or, with
+        want_mask, (rgb[n,3], mask[n] of bool: the refined pixels)."""
+        lib = self._adaptive_lib()
+        scene = lib.rtw_world_scene(nw.handle, int(device))
+        if not scene:
+            raise RtwError("scene upload failed: %s" % self._err())
+        rc_cam, ad = self._rtc_camera(lib, camera), AdaptiveC.of(adaptive)
+        n = camera.hsize * camera.vsize
+        rgb = np.empty((n, 3), dtype=np.float64)
+        mask = np.zeros(n, dtype=np.uint8) if want_mask else None
+        if lib.rtc_render_adaptive(scene, C.byref(rc_cam), C.byref(ad), int(fuel), rgb.ctypes.data, mask.ctypes.data if want_mask else None, None, None) != 0:
+            raise RtwError("rtc_render_adaptive: %s" % (lib.rtc_last_error() or b"").decode())
+        return (rgb, mask.astype(bool)) if want_mask else rgb
+
+    def contrast_pixels(self, frame: np.ndarray, hsize: int, vsize: int, threshold: float, neighbours: int = 4, nw: Optional[NativeWorld] = None,
+                        device: int = 0) -> np.ndarray:
+        """include/rtc.h rtc_contrast_pixels: the image indices (ascending, uint64) of the pixels of `frame` (hsize*vsize rows of r, g, b)
+        that adaptive sampling would refine.  With a world the device kernels flag and compact them, without one the same function
+        is evaluated on the host (no GPU needed)."""
+        lib = self._adaptive_lib()
+        scene = None
+        if nw is not None:
+            scene = lib.rtw_world_scene(nw.handle, int(device))
+            if not scene:
+                raise RtwError("scene upload failed: %s" % self._err())
+        frame = np.ascontiguousarray(frame, dtype=np.float64)
+        if frame.size != int(hsize) * int(vsize) * 3:
+            raise ValueError("frame must hold hsize * vsize * 3 values")
+        out = np.empty(max(1, int(hsize) * int(vsize)), dtype=np.uint64)
+        n = C.c_uint64(0)
+        if lib.rtc_contrast_pixels(scene, int(hsize), int(vsize), frame.ctypes.data, float(threshold), int(neighbours), out.ctypes.data, C.byref(n)) != 0:
+            raise RtwError("rtc_contrast_pixels: %s" % (lib.rtc_last_error() or b"").decode())
+        return out[:n.value].copy()
 
     def color_at(self, nw: NativeWorld, rays: np.ndarray, fuel: int = FUEL):
         """World::color_at for rays given as rows {ox,oy,oz,dx,dy,dz}.  Returns (rgb[n,3], hits[n])."""

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/rtc.h"
+#include "adaptive_contrast.h"
 #include "camera_sampling.h"
 #include "device_scene.h"
 #include "scene_build.hpp"
@@ -38,6 +39,12 @@ unsigned rtc_wavefront_lds_bytes(const DScene& S);
 void rtc_launch_gen_rays(const DCamera& cam, const DPixelMap& pm, const rtc_sampling& sp, unsigned long long slot_first, unsigned long long n_slots, double* rays,
                          hipStream_t stream);
 void rtc_launch_resolve_samples(const double* ray_rgb, unsigned n_samples, unsigned long long n_slots, double* dst, hipStream_t stream);
+unsigned long long rtc_contrast_blocks(unsigned long long n);
+unsigned long long rtc_contrast_work_words(unsigned long long n);
+unsigned rtc_launch_contrast_compact(const double* frame, unsigned long long hsize, unsigned long long vsize, double threshold, unsigned neighbours,
+                                     unsigned long long* work, unsigned long long* list, unsigned long long* count, hipStream_t stream);
+void rtc_launch_resolve_samples_scatter(const double* ray_rgb, unsigned n_samples, unsigned long long n_slots, const unsigned long long* indices, double* frame,
+                                        hipStream_t stream);
 int32_t rtc_bvh_build_device(const std::vector<bvh::Item>& items, std::vector<DBvhNode>& n2, std::vector<uint32_t>& order, uint32_t base, int leaf_max, double* frame);
 
 static thread_local std::string g_rtc_err;
@@ -80,6 +87,12 @@ struct rtc_scene {
   double* d_srgb = nullptr;
   uint64_t cap_srays = 0, cap_srgb = 0;
   hipEvent_t evs0 = nullptr, evs1 = nullptr;  // around a chunk's generator, traces and resolve
+  // adaptive sampling (run_adaptive, rtc_contrast_pixels): the refined pixels' list (one slot per pixel of the largest frame so far),
+  // the wave masks and scan levels of the compaction, the list's length
+  unsigned long long* d_alist = nullptr;
+  unsigned long long* d_awork = nullptr;
+  unsigned long long* d_acount = nullptr;
+  uint64_t cap_alist = 0;
   int kernel_version = 0;  // 0: measured choice between the one-kernel (1) and the wavefront (4) path, per launch signature
   uint64_t tune_sig = 0;
   double tune_ms[2] = {-1.0, -1.0};
@@ -475,8 +488,11 @@ uint64_t sampled_signature(const DCamera& cam, const DPixelMap& pm, const rtc_sa
 // Path: whole-row launches go through pick_path ONCE per call -- the shape is the whole launch's (camera, sampling, rows, fuel), the
 // guess counts the rays of a chunk, the measurement is the sum of the chunks' trace times -- and every chunk takes that path; lists
 // are left to run(), which keeps them on the one-kernel path.  `after`: behind the last chunk's resolve (see run()).
+// `scatter` (run_adaptive's refine pass; pm is a device-resident list): d_rgb is the whole FRAME and a slot's mean goes to its pixel
+// of it (rtc_resolve_samples_scatter); such a list may be millions of rays, 64 consecutive of which belong to four neighbouring
+// pixels, so its chunks take the scene's first guess over a chunk's rays (nothing is measured: the list changes with every frame).
 int run_sampled(rtc_scene* s, const DCamera& cam, const DPixelMap& pm, const rtc_sampling& sp, int fuel, double* d_rgb, rtc_stats* stats, bool count, bool sync,
-                const AfterLaunch* after = nullptr) {
+                const AfterLaunch* after = nullptr, bool scatter = false) {
   if (fuel < 0) fuel = 0;
   HIP_OK(hipSetDevice(s->device));
   const uint64_t N = (uint64_t)sp.side * sp.side;
@@ -492,6 +508,8 @@ int run_sampled(rtc_scene* s, const DCamera& cam, const DPixelMap& pm, const rtc
   if (tuned) {
     force = pick_path(s, sampled_signature(cam, pm, sp, s->d.n_lights == 0 ? 0 : fuel), chunk_px * N, fuel, will_sync, false);
     if (force == 4 && s->wave_alloc_failed) force = 1;
+  } else if (scatter && s->kernel_version == 0) {
+    force = s->wave_alloc_failed ? 1 : first_guess(s, chunk_px * N, fuel);
   }
   const int first_path = force;
   if (stats) std::memset(stats, 0, sizeof(*stats));
@@ -507,7 +525,8 @@ int run_sampled(rtc_scene* s, const DCamera& cam, const DPixelMap& pm, const rtc
     DPixelMap rm{};
     rm.n = np * N; rm.mode = 3; rm.rays = s->d_srays;
     const AfterLaunch resolve = [&]() -> int {
-      rtc_launch_resolve_samples(s->d_srgb, (unsigned)N, np, d_rgb + 3 * p0, s->stream);
+      if (scatter) rtc_launch_resolve_samples_scatter(s->d_srgb, (unsigned)N, np, (const unsigned long long*)pm.indices + p0, d_rgb, s->stream);
+      else rtc_launch_resolve_samples(s->d_srgb, (unsigned)N, np, d_rgb + 3 * p0, s->stream);
       hipError_t e = hipGetLastError();
       if (e == hipSuccess && stats) e = hipEventRecord(s->evs1, s->stream);
       if (e != hipSuccess) return rtc_fail(RTC_ERR_DEVICE, std::string("rtc_resolve_samples: ") + hipGetErrorString(e));
@@ -516,13 +535,13 @@ int run_sampled(rtc_scene* s, const DCamera& cam, const DPixelMap& pm, const rtc
     rtc_stats st;
     rc = run(s, ray_cam, rm, fuel, s->d_srgb, false, stats ? &st : nullptr, count, sync, force, &resolve);
     if (rc == RTC_ERR_UNSUPPORTED && force == 4) {  // the queues were refused: this shape stays on the one-kernel path (same bits)
-      s->tune_ms[1] = 1e30; s->tune_n[1] = 2; s->tune_choice = 1;
+      if (tuned) { s->tune_ms[1] = 1e30; s->tune_n[1] = 2; s->tune_choice = 1; }
       force = 1;
       rc = run(s, ray_cam, rm, fuel, s->d_srgb, false, stats ? &st : nullptr, count, sync, force, &resolve);
     }
     if (rc != RTC_OK) return rc;
     if (force == 4 && will_sync && !s->last_wavefront) {  // run() rendered the chunk again on the one-kernel path after an overflow
-      s->tune_ms[1] = 1e30; s->tune_n[1] = 2; s->tune_choice = 1;
+      if (tuned) { s->tune_ms[1] = 1e30; s->tune_n[1] = 2; s->tune_choice = 1; }
       force = 1;
     }
     if (will_sync) {
@@ -558,12 +577,121 @@ int run_sampled(rtc_scene* s, const DCamera& cam, const DPixelMap& pm, const rtc
   return RTC_OK;
 }
 
+// ---- adaptive sampling (include/rtc.h rtc_adaptive; kernels in rtc_adaptive.hip, the rule in adaptive_contrast.h) -------------------
+int check_adaptive(const rtc_adaptive* ad) {
+  if (!ad) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  int rc = check_sampling(&ad->base);
+  if (rc == RTC_OK) rc = check_sampling(&ad->fine);
+  if (rc != RTC_OK) return rc;
+  if (std::isnan(ad->threshold)) return rtc_fail(RTC_ERR_INVALID, "adaptive: threshold is NaN");
+  if (ad->neighbours != 4 && ad->neighbours != 8) return rtc_fail(RTC_ERR_INVALID, "adaptive: neighbours must be 4 or 8");
+  return RTC_OK;
+}
+int check_contrast_frame(uint64_t hsize, uint64_t vsize) {
+  if (hsize == 0 || vsize == 0) return rtc_fail(RTC_ERR_INVALID, "empty frame");
+  if (hsize >= (1ull << 39) || vsize >= (1ull << 39) || hsize * vsize >= (1ull << 39)) return rtc_fail(RTC_ERR_UNSUPPORTED, "adaptive: frames of 2^39 pixels or more");
+  return RTC_OK;
+}
+
+// The compaction's buffers for a frame of n pixels, grown like d_srays.
+int ensure_adaptive(rtc_scene* s, uint64_t n) {
+  if (!s->d_acount) HIP_OK(hipMalloc((void**)&s->d_acount, sizeof(unsigned long long)));
+  if (n > s->cap_alist) {
+    HIP_OK(hipStreamSynchronize(s->stream));
+    (void)hipFree(s->d_alist); (void)hipFree(s->d_awork);
+    s->d_alist = nullptr; s->d_awork = nullptr; s->cap_alist = 0;
+    HIP_OK(hipMalloc((void**)&s->d_alist, n * sizeof(unsigned long long)));
+    HIP_OK(hipMalloc((void**)&s->d_awork, rtc_contrast_work_words(n) * sizeof(unsigned long long)));  // (monotonic in n)
+    s->cap_alist = n;
+  }
+  return RTC_OK;
+}
+
+// Detect and compact over the frame in d_frame (hsize x vsize), on the stream; then the ONE read-back the host needs: the list's length.
+int contrast_compact(rtc_scene* s, const double* d_frame, uint64_t hsize, uint64_t vsize, double threshold, uint32_t neighbours, uint64_t* n_refined,
+                     unsigned* n_kernels, bool timed) {
+  int rc = ensure_adaptive(s, hsize * vsize);
+  if (rc != RTC_OK) return rc;
+  if (timed) HIP_OK(hipEventRecord(s->evs0, s->stream));
+  *n_kernels = rtc_launch_contrast_compact(d_frame, hsize, vsize, threshold, neighbours, s->d_awork, s->d_alist, s->d_acount, s->stream);
+  HIP_OK(hipGetLastError());
+  if (timed) HIP_OK(hipEventRecord(s->evs1, s->stream));
+  unsigned long long c = 0;
+  HIP_OK(hipMemcpyAsync(&c, s->d_acount, sizeof(c), hipMemcpyDeviceToHost, s->stream));
+  HIP_OK(hipStreamSynchronize(s->stream));
+  if (c > hsize * vsize) return rtc_fail(RTC_ERR_DEVICE, "adaptive: the compaction counted more pixels than the frame has");
+  *n_refined = c;
+  return RTC_OK;
+}
+
+void add_stats(rtc_stats* a, const rtc_stats& b) {
+  a->rays_primary += b.rays_primary; a->rays_shadow += b.rays_shadow; a->rays_reflect += b.rays_reflect; a->rays_refract += b.rays_refract;
+  a->rays_container += b.rays_container; a->accel_nodes += b.accel_nodes; a->group_tests += b.group_tests; a->tri_tests += b.tri_tests;
+  a->analytic_tests += b.analytic_tests; a->nan_ts += b.nan_ts; a->n_launches += b.n_launches;
+  a->accel_nodes_kernarg += b.accel_nodes_kernarg; a->analytic_tests_kernarg += b.analytic_tests_kernarg;
+  a->light_grid_cells += b.light_grid_cells; a->group_tests_uniform += b.group_tests_uniform;
+  a->kernel_ms += b.kernel_ms;
+}
+
+// The whole frame of `cam` into s->d_rgb (ensure_px'ed by the caller) under the rule `ad`: base pass, detect and compact, count
+// read-back, refine pass over the device-resident list with the scatter resolve.  `mask` / `n_refined`: optional host outputs.
+// `after`: queued behind the last kernel that writes the frame (see run()).
+int run_adaptive(rtc_scene* s, const DCamera& cam, const rtc_adaptive& ad, int fuel, rtc_stats* stats, uint8_t* mask, uint64_t* n_refined, const AfterLaunch* after) {
+  const uint64_t n = cam.hsize * cam.vsize;
+  const bool count = stats != nullptr;
+  DPixelMap rows{};
+  rows.n = n; rows.mode = 2; rows.row_first = 0; rows.row_step = 1;
+  rtc_stats st_base, st_fine;
+  std::memset(&st_fine, 0, sizeof(st_fine));
+  // 1. base: one centre sample per pixel IS rtc_render's frame (include/rtc.h rtc_sampling), so it takes rtc_render's launch
+  const bool plain = ad.base.side == 1 && !(ad.base.flags & RTC_SAMPLE_JITTER) && !(ad.base.lens_radius > 0.0);
+  int rc = plain ? run(s, cam, rows, fuel, s->d_rgb, false, stats ? &st_base : nullptr, count, true)
+                 : run_sampled(s, cam, rows, ad.base, fuel, s->d_rgb, stats ? &st_base : nullptr, count, true);
+  if (rc != RTC_OK) return rc;
+  // 2. + 3. the refined pixels' list and its length
+  uint64_t refined = 0;
+  unsigned n_kernels = 0;
+  rc = contrast_compact(s, s->d_rgb, cam.hsize, cam.vsize, ad.threshold, ad.neighbours, &refined, &n_kernels, stats != nullptr);
+  if (rc != RTC_OK) return rc;
+  float detect_ms = 0.f;
+  if (stats) HIP_OK(hipEventElapsedTime(&detect_ms, s->evs0, s->evs1));
+  if (stats && std::getenv("RTC_SAMPLED_TIMING"))  // debug aid (scripts/adaptive_probe.py)
+    std::fprintf(stderr, "[rtc-adaptive] detect + compact %.3f ms (%u kernels): %llu of %llu pixels refined\n", detect_ms, n_kernels, (unsigned long long)refined, (unsigned long long)n);
+  if (n_refined) *n_refined = refined;
+  if (mask) {  // from the list: the stream is idle, the pass below only reads it
+    std::vector<unsigned long long> list(refined);
+    if (refined) HIP_OK(hipMemcpy(list.data(), s->d_alist, refined * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    std::memset(mask, 0, n);
+    for (unsigned long long i : list) if (i < n) mask[i] = 1;
+  }
+  // 4. refine: run_sampled's chunks over the list, each mean written to its pixel of the frame
+  if (refined) {
+    DPixelMap lm{};
+    lm.n = refined; lm.mode = 1; lm.indices = (const uint64_t*)s->d_alist;
+    rc = run_sampled(s, cam, lm, ad.fine, fuel, s->d_rgb, stats ? &st_fine : nullptr, count, true, after, true);
+    if (rc != RTC_OK) return rc;
+  } else if (after) {
+    rc = (*after)();
+    if (rc != RTC_OK) return rc;
+    HIP_OK(hipStreamSynchronize(s->stream));
+  }
+  if (stats) {
+    *stats = st_base;
+    add_stats(stats, st_fine);
+    stats->pixels = n;
+    stats->n_launches += n_kernels;
+    stats->kernel_ms += detect_ms;
+  }
+  return RTC_OK;
+}
+
 // One launch whose results go to the caller's host buffers: rgb (n x 3 doubles) or rgb8 (n x 3 bytes, Color::clamp on the device),
 // and optionally the primary-hit records.  The destination's pages are touched by host threads while the device renders, the
 // copies are queued behind the kernels (see pretouch_pages above).
-// `sp`: the launch goes through run_sampled (no hit records).
+// `sp`: the launch goes through run_sampled (no hit records).  `ad`: the whole frame through run_adaptive (pm covers it).
+struct AdaptiveOut { const rtc_adaptive* rule; uint8_t* mask; uint64_t* n_refined; };
 int render_to_host(rtc_scene* s, const DCamera& dc, const DPixelMap& pm, int fuel, double* rgb, uint8_t* rgb8, rtc_hit* hits, rtc_stats* stats,
-                   const rtc_sampling* sp = nullptr) {
+                   const rtc_sampling* sp = nullptr, const AdaptiveOut* ad = nullptr) {
   static_assert(sizeof(DHit) == sizeof(rtc_hit) && offsetof(DHit, prim) == offsetof(rtc_hit, prim) && offsetof(DHit, k) == offsetof(rtc_hit, push_idx), "hit layout");
   const uint64_t n = pm.n;
   std::vector<std::thread> pool;
@@ -585,7 +713,8 @@ int render_to_host(rtc_scene* s, const DCamera& dc, const DPixelMap& pm, int fue
     if (e != hipSuccess) return rtc_fail(RTC_ERR_DEVICE, std::string("copy to the host: ") + hipGetErrorString(e));
     return RTC_OK;
   };
-  const int rc = sp ? run_sampled(s, dc, pm, *sp, fuel, s->d_rgb, stats, stats != nullptr, true, &after)
+  const int rc = ad ? run_adaptive(s, dc, *ad->rule, fuel, stats, ad->mask, ad->n_refined, &after)
+                 : sp ? run_sampled(s, dc, pm, *sp, fuel, s->d_rgb, stats, stats != nullptr, true, &after)
                     : run(s, dc, pm, fuel, s->d_rgb, hits != nullptr, stats, stats != nullptr, true, 0, &after);
   join_all(&pool);  // (an error before the hook ran its join)
   return rc;
@@ -762,6 +891,7 @@ void rtc_scene_destroy(rtc_scene* s) {
   if (s->d_idx) (void)hipFree(s->d_idx);
   if (s->d_rays) (void)hipFree(s->d_rays);
   (void)hipFree(s->d_srays); (void)hipFree(s->d_srgb);
+  (void)hipFree(s->d_alist); (void)hipFree(s->d_awork); (void)hipFree(s->d_acount);
   if (s->evs0) (void)hipEventDestroy(s->evs0);
   if (s->evs1) (void)hipEventDestroy(s->evs1);
   for (auto& m : s->marker) if (m) (void)hipEventDestroy(m);
@@ -996,6 +1126,69 @@ int rtc_camera_rays(rtc_scene* s, const rtc_camera* cam, const rtc_sampling* sp,
   HIP_OK(hipGetLastError());
   HIP_OK(hipMemcpyAsync(rays, s->d_srays, n * N * 6 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
   HIP_OK(hipStreamSynchronize(s->stream));
+  return RTC_OK;
+}
+
+// ---- adaptive sampling's entry points (include/rtc.h) -------------------------------------------------------------------------------
+static int render_adaptive(rtc_scene* s, const rtc_camera* cam, const rtc_adaptive* ad, int32_t fuel, double* rgb, uint8_t* rgb8, uint8_t* mask, uint64_t* n_refined,
+                           rtc_stats* stats) {
+  int rc = check_adaptive(ad);  // (the rule first: it is checked without a device)
+  if (rc != RTC_OK) return rc;
+  if (!s || !cam || (!rgb && !rgb8)) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  if (cam->hsize == 0 || cam->vsize == 0) return rtc_fail(RTC_ERR_INVALID, "empty camera");
+  rc = check_contrast_frame(cam->hsize, cam->vsize);
+  if (rc != RTC_OK) return rc;
+  HIP_OK(hipSetDevice(s->device));
+  const uint64_t n = cam->hsize * cam->vsize;
+  rc = ensure_px(s, n, false);
+  if (rc != RTC_OK) return rc;
+  if (rgb8 && 3 * n > s->cap_rgb8) {
+    (void)hipFree(s->d_rgb8);
+    s->d_rgb8 = nullptr; s->cap_rgb8 = 0;
+    HIP_OK(hipMalloc((void**)&s->d_rgb8, 3 * n));
+    s->cap_rgb8 = 3 * n;
+  }
+  DPixelMap pm{};
+  pm.n = n; pm.mode = 2; pm.row_first = 0; pm.row_step = 1;
+  DCamera dc;
+  to_dcam(*cam, &dc);
+  const AdaptiveOut out{ad, mask, n_refined};
+  return render_to_host(s, dc, pm, fuel, rgb, rgb8, nullptr, stats, nullptr, &out);
+}
+
+int rtc_render_adaptive(rtc_scene* s, const rtc_camera* cam, const rtc_adaptive* ad, int32_t fuel, double* rgb, uint8_t* mask, uint64_t* n_refined, rtc_stats* stats) {
+  return render_adaptive(s, cam, ad, fuel, rgb, nullptr, mask, n_refined, stats);
+}
+
+int rtc_render_adaptive_rgb8(rtc_scene* s, const rtc_camera* cam, const rtc_adaptive* ad, int32_t fuel, uint8_t* rgb8, uint8_t* mask, uint64_t* n_refined,
+                             rtc_stats* stats) {
+  return render_adaptive(s, cam, ad, fuel, nullptr, rgb8, mask, n_refined, stats);
+}
+
+int rtc_contrast_pixels(rtc_scene* s, uint64_t hsize, uint64_t vsize, const double* rgb, double threshold, uint32_t neighbours, uint64_t* indices, uint64_t* n) {
+  if (!rgb || !indices || !n) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  if (std::isnan(threshold)) return rtc_fail(RTC_ERR_INVALID, "adaptive: threshold is NaN");
+  if (neighbours != 4 && neighbours != 8) return rtc_fail(RTC_ERR_INVALID, "adaptive: neighbours must be 4 or 8");
+  int rc = check_contrast_frame(hsize, vsize);
+  if (rc != RTC_OK) return rc;
+  const uint64_t total = hsize * vsize;
+  if (!s) {  // the same function on the host
+    uint64_t k = 0;
+    for (uint64_t i = 0; i < total; i++)
+      if (rtc_contrast_refined(rgb, hsize, vsize, i, threshold, neighbours)) indices[k++] = i;
+    *n = k;
+    return RTC_OK;
+  }
+  HIP_OK(hipSetDevice(s->device));
+  rc = ensure_px(s, total, false);
+  if (rc != RTC_OK) return rc;
+  HIP_OK(hipMemcpyAsync(s->d_rgb, rgb, total * 3 * sizeof(double), hipMemcpyHostToDevice, s->stream));
+  uint64_t refined = 0;
+  unsigned n_kernels = 0;
+  rc = contrast_compact(s, s->d_rgb, hsize, vsize, threshold, neighbours, &refined, &n_kernels, false);
+  if (rc != RTC_OK) return rc;
+  if (refined) HIP_OK(hipMemcpy(indices, s->d_alist, refined * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  *n = refined;
   return RTC_OK;
 }
 

@@ -10,7 +10,7 @@ import ctypes as C
 
 import numpy as np
 
-from .scene import FUEL, Camera, Color, Sampling, World
+from .scene import FUEL, Adaptive, Camera, Color, Sampling, World
 
 
 class Image:
@@ -20,12 +20,17 @@ class Image:
         self._native = _native  # (backend, NativeWorld) that rendered it, for the device quantiser
 
     @staticmethod
-    def par_render(camera: Camera, world: World, fuel: int = FUEL, backend=None, sampling: Sampling = None) -> "Image":
+    def par_render(camera: Camera, world: World, fuel: int = FUEL, backend=None, sampling: Sampling = None, adaptive: Adaptive = None) -> "Image":
         """sampling: a :class:`Sampling` renders every pixel as the mean of its sample rays (anti-aliasing, depth of field); None is
-        the reference's one ray per pixel."""
+        the reference's one ray per pixel.  adaptive: an :class:`Adaptive` renders the frame with its base sampling and only the pixels
+        that differ from a neighbour with its fine one; it carries both samplings, so giving `sampling` as well is a ValueError."""
+        if adaptive is not None and sampling is not None:
+            raise ValueError("par_render: give `adaptive` or `sampling`, not both (an Adaptive carries its two samplings)")
         from . import hip_backend
         be = backend or hip_backend()
         nw = be.build_world(world)
+        if adaptive is not None:
+            return Image(camera.hsize, camera.vsize, be.render_adaptive(nw, camera, adaptive, fuel), (be, nw))
         if sampling is not None:
             return Image(camera.hsize, camera.vsize, be.render_sampled(nw, camera, sampling, fuel), (be, nw))
         rgb, _ = be.render(nw, camera, fuel, want_hits=False)

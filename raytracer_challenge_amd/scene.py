@@ -353,6 +353,31 @@ class Sampling:
 
 
 @dataclass(frozen=True)
+class Adaptive:
+    """Adaptive sampling (include/rtc.h rtc_adaptive; not in the reference): the frame is rendered with ``base``; a pixel whose clamped
+    colour differs from one of its ``neighbours`` (4 or 8) by more than ``threshold`` in some channel is rendered again with ``fine``
+    and takes that colour, every other pixel keeps the base colour.  A negative threshold refines every pixel, ``math.inf`` only those
+    with a NaN contrast.  Rendered by the HIP library only."""
+    base: Sampling
+    fine: Sampling
+    threshold: float
+    neighbours: int = 4
+
+    def __post_init__(self):
+        import math
+        if not isinstance(self.base, Sampling) or not isinstance(self.fine, Sampling):
+            raise ValueError("Adaptive.base and Adaptive.fine must be Sampling values")
+        try:
+            bad = math.isnan(self.threshold)
+        except TypeError:
+            bad = True
+        if bad:
+            raise ValueError("Adaptive.threshold must be a number, not NaN")
+        if self.neighbours not in (4, 8) or int(self.neighbours) != self.neighbours:
+            raise ValueError("Adaptive.neighbours must be 4 or 8")
+
+
+@dataclass(frozen=True)
 class Camera:  # src/camera.rs:5-13; derived fields are computed natively from `transform`
     hsize: int
     vsize: int

@@ -3,8 +3,8 @@
 
     scripts/kernel_isa_diff.py OLD_TREE NEW_TREE [--rename 'REGEX=>REPLACEMENT']... [--jobs N] [--keep DIR [--reuse]]
 
-For each tree: rtc_feat.hip for every variant id of its csrc/Makefile and rtc_kernels.hip are compiled to device-only
-assembly with that Makefile's FLAGS.  The assembly is split per function; comments, directives and label definitions
+For each tree: rtc_feat.hip for every variant id of its csrc/Makefile, rtc_kernels.hip and, where the tree has them,
+rtc_camera.hip and rtc_adaptive.hip are compiled to device-only assembly with that Makefile's FLAGS.  The assembly is split per function; comments, directives and label definitions
 are dropped, local label references (.LBB<fn>_<n> ...) lose their function number, the function's own symbol becomes
 <self>; what remains is counted and hashed.  Printed per function of NEW_TREE: unit, demangled name, instruction
 count, hash, next_free_vgpr, next_free_sgpr, private segment size (device functions that are not kernels: the
@@ -38,7 +38,11 @@ def units(tree):
     mk = open(os.path.join(tree, CSRC, "Makefile")).read()
     flags = make_var(mk, "FLAGS")
     out = [("feat%s" % v, "rtc_feat.hip", flags + ["-DRTC_VARIANT=%s" % v]) for v in make_var(mk, "VARIANT_IDS", "VARIANTS")]
-    return out + [("kernels", "rtc_kernels.hip", flags)]
+    out.append(("kernels", "rtc_kernels.hip", flags))
+    for unit, src in (("camera", "rtc_camera.hip"), ("adaptive", "rtc_adaptive.hip")):   # the small kernels beside the ray kernels, where a tree has them
+        if os.path.exists(os.path.join(tree, CSRC, src)):
+            out.append((unit, src, flags))
+    return out
 
 
 def compile_unit(tree, unit, src, flags, outdir, reuse):

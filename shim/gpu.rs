@@ -139,6 +139,18 @@ pub struct RtcSampling {
     pub focal_distance: f64, // camera-space depth in focus; read only when lens_radius > 0
 }
 
+// include/rtc.h rtc_adaptive: the frame with `base`, then only the pixels that differ from a neighbour again with `fine` (not in the
+// reference) for rtc_render_adaptive*
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtcAdaptive {
+    pub base: RtcSampling, // first pass: every pixel
+    pub fine: RtcSampling, // second pass: the refined pixels
+    pub threshold: f64,
+    pub neighbours: u32, // 4 or 8
+    pub _pad: u32,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct RtcNode {
@@ -253,6 +265,16 @@ extern "C" {
     #[allow(dead_code)] // scene = null: evaluated on the host, no device needed
     fn rtc_camera_rays(scene: *mut RtcScene, camera: *const RtcCamera, sampling: *const RtcSampling, pixel_indices: *const u64, first: u64, n: u64,
                        rays: *mut f64) -> c_int;
+    // adaptive sampling: the whole frame on one device; mask (one byte per pixel) and n_refined may be null
+    #[allow(dead_code)]
+    fn rtc_render_adaptive(scene: *mut RtcScene, camera: *const RtcCamera, adaptive: *const RtcAdaptive, fuel: i32, rgb: *mut f64, mask: *mut u8,
+                           n_refined: *mut u64, stats: *mut RtcStats) -> c_int;
+    #[allow(dead_code)]
+    fn rtc_render_adaptive_rgb8(scene: *mut RtcScene, camera: *const RtcCamera, adaptive: *const RtcAdaptive, fuel: i32, rgb8: *mut u8, mask: *mut u8,
+                                n_refined: *mut u64, stats: *mut RtcStats) -> c_int;
+    #[allow(dead_code)] // the contrast rule alone on a host frame; scene = null: evaluated on the host, no device needed
+    fn rtc_contrast_pixels(scene: *mut RtcScene, hsize: u64, vsize: u64, rgb: *const f64, threshold: f64, neighbours: u32, indices: *mut u64,
+                           n: *mut u64) -> c_int;
 }
 
 #[derive(Debug)]
