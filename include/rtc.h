@@ -240,6 +240,40 @@ typedef struct rtc_adaptive {
   uint32_t _pad;
 } rtc_adaptive;
 
+/* Pixel reconstruction filters (not in the reference) for the sampled camera: a pixel is the weighted mean of the samples of every
+ * pixel within `radius` of its centre, for the rtc_render_filtered* entry points and, the filter step alone, rtc_filter_frame.  `radius`
+ * is in pixels, measured from the pixel centre per axis; the filter is separable.  Every step is one f64 operation, in the order written
+ * here (csrc/filter_weights.h, one function for device and host); only exp of the Gaussian comes from different libraries on the two sides.
+ *   Sample position: sample k of image pixel q = (qx, qy) sits at the sub-pixel position (fx, fy) of rtc_sampling above (same hash, same
+ *     jx / jy; 0.5 without RTC_SAMPLE_JITTER).  The lens draws do not enter.
+ *   Window: W = (uint32_t)ceil(radius - 0.5).  The window of output pixel p = (x, y) is the pixels q with |qx - x| <= W and |qy - y| <= W;
+ *     only those inside the image count.
+ *   Weight of sample (q, k) for p: dx = (double)((int64_t)qx - (int64_t)x) + (fx - 0.5), dy likewise; w = f(dx) * f(dy).  In f,
+ *     a = fabs(d) and r = radius; f = 0.0 unless a < r, else
+ *       BOX       1.0
+ *       TENT      1.0 - a / r
+ *       GAUSSIAN  exp(-alpha * a * a) - exp(-alpha * r * r), each product left to right
+ *       MITCHELL  (B = C = 1/3; alpha is ignored) t = (a + a) / r;
+ *                 t < 1.0:  ((((7.0 * t - 12.0) * t) * t) + 16.0 / 3.0) / 6.0
+ *                 else:     ((((-7.0 / 3.0) * t + 12.0) * t - 20.0) * t + 32.0 / 3.0) / 6.0
+ *   Pixel value: num[c] = 0.0, den = 0.0; loop qy ascending (outer), qx ascending, k ascending (inner); a sample with w == 0.0 is skipped
+ *     (a NaN or infinite colour outside the support cannot reach the pixel); otherwise num[c] = num[c] + w * colour_k(q)[c] and
+ *     den = den + w.  The pixel is num[c] / den; a zero den gives what IEEE gives.
+ *   Identity: BOX with radius 0.5 has W = 0 and every weight 1.0, den is N exactly, and the pixel is rtc_render_sampled's bit for bit --
+ *     unless a jitter draw is exactly 0 (probability 2^-53 per draw): that sample sits on the pixel's edge, a == r, and is skipped.
+ * Limits: RTC_ERR_INVALID for NULL arguments, an unknown kind, radius not finite or < 0.5, GAUSSIAN with alpha not finite or <= 0, a row
+ * range outside the image or empty; RTC_ERR_UNSUPPORTED for radius > RTC_FILTER_MAX_RADIUS.  rtc_sampling's own limits apply as ever.
+ * Not covered: pixel lists; bands, rtc_render_multi and several devices; filtering rtc_render_adaptive's refine pass; filters given as
+ * tables; a radial (non-separable) support. */
+enum { RTC_FILTER_BOX = 0, RTC_FILTER_TENT = 1, RTC_FILTER_GAUSSIAN = 2, RTC_FILTER_MITCHELL = 3 };
+#define RTC_FILTER_MAX_RADIUS 3.0
+typedef struct rtc_filter {
+  int32_t kind;           /* RTC_FILTER_* */
+  uint32_t _pad;
+  double radius;          /* r, in pixels from the pixel centre, per axis */
+  double alpha;           /* GAUSSIAN's falloff; read by no other kind */
+} rtc_filter;
+
 /* The Element tree (src/shape.rs:31-34, :181-185) in DFS pre-order.  A group node carries the world-space
  * bounding box the reference computed for it (Element::composite + propagate_inverses; NaN/inf included,
  * SURVEY Q9) and `skip` = index of the first node after its subtree.  The device evaluates
@@ -432,6 +466,26 @@ int rtc_render_adaptive_rgb8(rtc_scene*, const rtc_camera*, const rtc_adaptive*,
  * ascending order (indices: room for hsize*vsize values, host).  scene != NULL: the frame is uploaded, the device kernels flag and
  * compact, the list is copied back; scene == NULL: evaluated on the host by the same function, no device needed (like rtc_camera_rays). */
 int rtc_contrast_pixels(rtc_scene*, uint64_t hsize, uint64_t vsize, const double* rgb, double threshold, uint32_t neighbours, uint64_t* indices, uint64_t* n);
+
+/* ---- pixel reconstruction filters (rtc_filter above) ------------------------------------------------------------------------------
+ * rtc_render_sampled's whole-row launches with a filter wider than the pixel, on one device.  Renders the rows [row_first, row_first +
+ * n_rows) of the image (rgb: n_rows*hsize*3 doubles, host), filtered over the whole image's neighbours: the output rows are cut into
+ * chunks of whole rows; a chunk of rows [a, b) traces the rows [max(0, a - W), min(vsize, b + W)) -- generator, the scene's ray kernels
+ * over explicit rays, then a gather kernel (csrc/rtc_filter.hip) that writes the chunk's own rows and nothing else.  The W halo rows of a
+ * chunk are traced again by its neighbour: the price of two reusable buffers; the samples do not depend on the chunk, so any split of the
+ * frame into row ranges, and any RTC_SAMPLED_MAX_RAYS (which bounds the TRACED rays of a chunk, halo included; never less than one output
+ * row and its halo), gives the whole frame's bits.  Device path as for rtc_render_sampled's row launches (the launch shape includes the
+ * filter and the row range; the guess counts a chunk's traced rays).  rtc_stats: pixels = the output pixels, rays_primary = the rays
+ * actually traced (halo rows counted each time), counters summed, kernel_ms = generator + traces + filter kernel. */
+int rtc_render_filtered(rtc_scene*, const rtc_camera*, const rtc_sampling*, const rtc_filter*, int32_t fuel, uint32_t row_first, uint32_t n_rows,
+                        double* rgb, rtc_stats* stats);
+/* The whole frame, quantised on the device (Color::clamp): rgb8 = hsize*vsize*3 bytes (host). */
+int rtc_render_filtered_rgb8(rtc_scene*, const rtc_camera*, const rtc_sampling*, const rtc_filter*, int32_t fuel, uint8_t* rgb8, rtc_stats* stats);
+/* The filter step alone on the caller's sample colours: sample_rgb = hsize*vsize*N*3 doubles, pixel-major, k inner (rtc_trace_rays'
+ * colours of rtc_camera_rays' rays); rgb = hsize*vsize*3 doubles (both host).  scene != NULL: the colours are uploaded, the device
+ * kernel filters, the frame is copied back; scene == NULL: evaluated on the host by the same function, no device needed (like
+ * rtc_contrast_pixels).  Of `sampling` only side, flags and seed are read (its lens is validated). */
+int rtc_filter_frame(rtc_scene*, uint64_t hsize, uint64_t vsize, const rtc_sampling*, const rtc_filter*, const double* sample_rgb, double* rgb);
 
 /* ---- the step after the path: Color::clamp and Image::ppm ---------------------------------
  * Color::clamp (src/color.rs:42-46): u8 = round(min(max(c, 0), 1) * 255), round half away from zero, NaN -> 255 (Rust's

@@ -13,7 +13,7 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from .scene import (FUEL, GEOMETRY, GROUP_KINDS, JITTER_KINDS, MIXTURE_KINDS, Adaptive, AreaLight, Camera, Element, Material, Pattern, Sampling, World)
+from .scene import (FUEL, GEOMETRY, GROUP_KINDS, JITTER_KINDS, MIXTURE_KINDS, Adaptive, AreaLight, Camera, Element, FILTER_KINDS, Filter, Material, Pattern, Sampling, World)
 from .texture import UV_KINDS, UV_MAPS, Texture
 
 HIT_DTYPE = np.dtype([("t", "<f8"), ("prim", "<i4"), ("push_idx", "<i4")])
@@ -51,6 +51,14 @@ class AdaptiveC(C.Structure):  # include/rtc.h rtc_adaptive
     @staticmethod
     def of(a: Adaptive) -> "AdaptiveC":
         return AdaptiveC(SamplingC.of(a.base), SamplingC.of(a.fine), float(a.threshold), int(a.neighbours), 0)
+
+
+class FilterC(C.Structure):  # include/rtc.h rtc_filter
+    _fields_ = [("kind", C.c_int32), ("_pad", C.c_uint32), ("radius", C.c_double), ("alpha", C.c_double)]
+
+    @staticmethod
+    def of(f: Filter) -> "FilterC":
+        return FilterC(FILTER_KINDS.index(f.kind), 0, float(f.radius), float(f.alpha))
 
 
 RTW_SYMBOLS = [
@@ -401,6 +409,57 @@ class Backend:
         if lib.rtc_contrast_pixels(scene, int(hsize), int(vsize), frame.ctypes.data, float(threshold), int(neighbours), out.ctypes.data, C.byref(n)) != 0:
             raise RtwError("rtc_contrast_pixels: %s" % (lib.rtc_last_error() or b"").decode())
         return out[:n.value].copy()
+
+    def _filter_lib(self):
+        """The rtc_* entry points of the reconstruction filters, bound; RtwError for a library that has none (the CPU emulator, the oracle)."""
+        lib = self.lib
+        if not (hasattr(lib, "rtc_render_filtered") and hasattr(lib, "rtc_filter_frame")):
+            raise RtwError("reconstruction filters need librtc_amd.so (backend %r has no rtc_render_filtered)" % self.name)
+        vp = C.c_void_p
+        lib.rtw_world_scene.restype, lib.rtw_world_scene.argtypes = vp, [vp, C.c_int]
+        lib.rtw_make_camera.restype, lib.rtw_make_camera.argtypes = C.c_int, [vp, vp]
+        lib.rtc_render_filtered.restype = C.c_int
+        lib.rtc_render_filtered.argtypes = [vp, vp, C.POINTER(SamplingC), C.POINTER(FilterC), C.c_int32, C.c_uint32, C.c_uint32, vp, vp]
+        lib.rtc_filter_frame.restype = C.c_int
+        lib.rtc_filter_frame.argtypes = [vp, C.c_uint64, C.c_uint64, C.POINTER(SamplingC), C.POINTER(FilterC), vp, vp]
+        lib.rtc_last_error.restype = C.c_char_p
+        return lib
+
+    def render_filtered(self, nw: NativeWorld, camera: Camera, sampling: Sampling, filter: Filter, fuel: int = FUEL, row_first: int = 0,
+                        n_rows: Optional[int] = None, device: int = 0) -> np.ndarray:
+        """include/rtc.h rtc_render_filtered: the rows row_first .. row_first + n_rows - 1 (default: to the last row) of the frame, every
+        pixel the `filter`-weighted mean of `sampling`'s samples around it -- neighbours outside the row range included.  Returns rgb[n,3]."""
+        lib = self._filter_lib()
+        scene = lib.rtw_world_scene(nw.handle, int(device))
+        if not scene:
+            raise RtwError("scene upload failed: %s" % self._err())
+        rc_cam, sp, fl = self._rtc_camera(lib, camera), SamplingC.of(sampling), FilterC.of(filter)
+        if n_rows is None:
+            n_rows = camera.vsize - int(row_first)
+        rgb = np.empty((max(0, int(n_rows)) * camera.hsize, 3), dtype=np.float64)
+        if lib.rtc_render_filtered(scene, C.byref(rc_cam), C.byref(sp), C.byref(fl), int(fuel), int(row_first), int(n_rows), rgb.ctypes.data, None) != 0:
+            raise RtwError("rtc_render_filtered: %s" % (lib.rtc_last_error() or b"").decode())
+        return rgb
+
+    def filter_frame(self, samples: np.ndarray, hsize: int, vsize: int, sampling: Sampling, filter: Filter, nw: Optional[NativeWorld] = None,
+                     device: int = 0) -> np.ndarray:
+        """include/rtc.h rtc_filter_frame: the filter step alone over `samples` (hsize*vsize*side*side rows of r, g, b: pixel-major, k
+        inner).  With a world the device kernel filters them, without one the same function is evaluated on the host (no GPU needed).
+        Returns rgb[hsize*vsize,3]."""
+        lib = self._filter_lib()
+        scene = None
+        if nw is not None:
+            scene = lib.rtw_world_scene(nw.handle, int(device))
+            if not scene:
+                raise RtwError("scene upload failed: %s" % self._err())
+        samples = np.ascontiguousarray(samples, dtype=np.float64)
+        if samples.size != int(hsize) * int(vsize) * sampling.samples * 3:
+            raise ValueError("samples must hold hsize * vsize * side * side * 3 values")
+        sp, fl = SamplingC.of(sampling), FilterC.of(filter)
+        rgb = np.empty((int(hsize) * int(vsize), 3), dtype=np.float64)
+        if lib.rtc_filter_frame(scene, int(hsize), int(vsize), C.byref(sp), C.byref(fl), samples.ctypes.data, rgb.ctypes.data) != 0:
+            raise RtwError("rtc_filter_frame: %s" % (lib.rtc_last_error() or b"").decode())
+        return rgb
 
     def color_at(self, nw: NativeWorld, rays: np.ndarray, fuel: int = FUEL):
         """World::color_at for rays given as rows {ox,oy,oz,dx,dy,dz}.  Returns (rgb[n,3], hits[n])."""

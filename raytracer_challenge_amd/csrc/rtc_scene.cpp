@@ -23,6 +23,7 @@
 #include "adaptive_contrast.h"
 #include "camera_sampling.h"
 #include "device_scene.h"
+#include "filter_weights.h"
 #include "scene_build.hpp"
 
 void rtc_launch_trace(const DScene& S, const DCamera& cam, const DPixelMap& pm, int fuel, double* rgb, double* hit_t, int* hit_prim, int* hit_k,
@@ -45,6 +46,8 @@ unsigned rtc_launch_contrast_compact(const double* frame, unsigned long long hsi
                                      unsigned long long* work, unsigned long long* list, unsigned long long* count, hipStream_t stream);
 void rtc_launch_resolve_samples_scatter(const double* ray_rgb, unsigned n_samples, unsigned long long n_slots, const unsigned long long* indices, double* frame,
                                         hipStream_t stream);
+unsigned rtc_launch_resolve_filtered(const rtc_filter& f, const rtc_sampling& sp, unsigned long long hsize, unsigned long long row0, unsigned long long row1,
+                                     unsigned long long out0, unsigned long long out1, const double* samples, double* dst, hipStream_t stream, unsigned* tile);
 int32_t rtc_bvh_build_device(const std::vector<bvh::Item>& items, std::vector<DBvhNode>& n2, std::vector<uint32_t>& order, uint32_t base, int leaf_max, double* frame);
 
 static thread_local std::string g_rtc_err;
@@ -685,13 +688,125 @@ int run_adaptive(rtc_scene* s, const DCamera& cam, const rtc_adaptive& ad, int f
   return RTC_OK;
 }
 
+// ---- reconstruction filters (include/rtc.h rtc_filter; kernel in rtc_filter.hip, the rule in filter_weights.h) ------------------------
+int check_filter(const rtc_filter* f) {
+  if (!f) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  if (f->kind < RTC_FILTER_BOX || f->kind > RTC_FILTER_MITCHELL) return rtc_fail(RTC_ERR_INVALID, "filter: unknown kind");
+  if (!std::isfinite(f->radius) || f->radius < 0.5) return rtc_fail(RTC_ERR_INVALID, "filter: radius must be finite and >= 0.5");
+  if (f->kind == RTC_FILTER_GAUSSIAN && (!std::isfinite(f->alpha) || f->alpha <= 0.0)) return rtc_fail(RTC_ERR_INVALID, "filter: a Gaussian's alpha must be finite and > 0");
+  if (f->radius > RTC_FILTER_MAX_RADIUS) return rtc_fail(RTC_ERR_UNSUPPORTED, "filter: radius exceeds RTC_FILTER_MAX_RADIUS (3)");
+  return RTC_OK;
+}
+
+// sampled_signature of a filtered launch (pm = its output rows): and the filter
+uint64_t filtered_signature(const DCamera& cam, const DPixelMap& pm, const rtc_sampling& sp, const rtc_filter& f, int fuel) {
+  uint64_t h = sampled_signature(cam, pm, sp, fuel) ^ 0x66696c7465726564ull;
+  auto mix = [&](const void* p, size_t n) { for (size_t i = 0; i < n; i++) { h ^= ((const unsigned char*)p)[i]; h *= 1099511628211ull; } };
+  mix(&f.kind, sizeof(f.kind)); mix(&f.radius, sizeof(f.radius)); mix(&f.alpha, sizeof(f.alpha));
+  return h ? h : 1;
+}
+
+// run_sampled for whole rows with a reconstruction filter: pm (mode 2, row_step 1, no bands) names the OUTPUT rows [a, b); they are cut
+// into chunks of whole rows, a chunk [a', b') traces the image rows [max(0, a' - W), min(vsize, b' + W)) -- rtc_gen_rays, run() over
+// explicit rays -- and rtc_resolve_filtered, the hook behind run()'s kernels, writes the chunk's own rows of d_rgb and nothing else, so a
+// chunk that run() renders again resolves to the same bits.  RTC_SAMPLED_MAX_RAYS bounds a chunk's TRACED rays, halo included, never
+// below one output row and its halo.  The halo rows are traced again by the neighbouring chunk: the two buffers stay reusable.
+// Path: pick_path once per call as run_sampled does; the shape also holds the filter (and pm the row range), the guess counts a chunk's
+// traced rays.  `after`: behind the last chunk's filter kernel (see run()).
+int run_filtered(rtc_scene* s, const DCamera& cam, const DPixelMap& pm, const rtc_sampling& sp, const rtc_filter& f, int fuel, double* d_rgb, rtc_stats* stats,
+                 bool count, bool sync, const AfterLaunch* after = nullptr) {
+  if (fuel < 0) fuel = 0;
+  HIP_OK(hipSetDevice(s->device));
+  const uint64_t N = (uint64_t)sp.side * sp.side, W = rtc_filter_window(f.radius);
+  const uint64_t a = pm.row_first, b = a + pm.n / cam.hsize;
+  const uint64_t row_rays = cam.hsize * N, fit = sampled_max_rays() / row_rays;
+  const uint64_t chunk_rows = std::min<uint64_t>(b - a, fit > 2 * W + 1 ? fit - 2 * W : 1);
+  const uint64_t traced_rows = std::min<uint64_t>(chunk_rows + 2 * W, cam.vsize);
+  if (traced_rows * row_rays > 0x7fffff00ull) return rtc_fail(RTC_ERR_UNSUPPORTED, "one row of this filtered launch and its halo exceed 2^31 rays");
+  int rc = ensure_sampled(s, traced_rows * row_rays, true);
+  if (rc != RTC_OK) return rc;
+  const bool will_sync = sync || stats != nullptr;
+  const bool tuned = s->kernel_version == 0;
+  int force = 0;
+  if (tuned) {
+    force = pick_path(s, filtered_signature(cam, pm, sp, f, s->d.n_lights == 0 ? 0 : fuel), traced_rows * row_rays, fuel, will_sync, false);
+    if (force == 4 && s->wave_alloc_failed) force = 1;
+  }
+  const int first_path = force;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  double trace_ms = 0.0;
+  DCamera ray_cam{};
+  ray_cam.hsize = 1; ray_cam.vsize = 1;
+  for (uint64_t c0 = a; c0 < b; c0 += chunk_rows) {
+    const uint64_t c1 = std::min(c0 + chunk_rows, b);
+    const uint64_t t0 = c0 > W ? c0 - W : 0, t1 = std::min<uint64_t>(c1 + W, cam.vsize);
+    const bool last = c1 == b;
+    if (stats) HIP_OK(hipEventRecord(s->evs0, s->stream));
+    DPixelMap tm{};
+    tm.n = (t1 - t0) * cam.hsize; tm.mode = 2; tm.row_first = (uint32_t)t0; tm.row_step = 1;
+    rtc_launch_gen_rays(cam, tm, sp, 0, tm.n, s->d_srays, s->stream);
+    HIP_OK(hipGetLastError());
+    DPixelMap rm{};
+    rm.n = tm.n * N; rm.mode = 3; rm.rays = s->d_srays;
+    unsigned lds = 0, tile = 0;
+    const AfterLaunch resolve = [&]() -> int {
+      lds = rtc_launch_resolve_filtered(f, sp, cam.hsize, t0, t1, c0, c1, s->d_srgb, d_rgb + 3 * (c0 - a) * cam.hsize, s->stream, &tile);
+      hipError_t e = hipGetLastError();
+      if (e == hipSuccess && stats) e = hipEventRecord(s->evs1, s->stream);
+      if (e != hipSuccess) return rtc_fail(RTC_ERR_DEVICE, std::string("rtc_resolve_filtered: ") + hipGetErrorString(e));
+      return (last && after) ? (*after)() : RTC_OK;
+    };
+    rtc_stats st;
+    rc = run(s, ray_cam, rm, fuel, s->d_srgb, false, stats ? &st : nullptr, count, sync, force, &resolve);
+    if (rc == RTC_ERR_UNSUPPORTED && force == 4) {  // the queues were refused: this shape stays on the one-kernel path (same bits)
+      if (tuned) { s->tune_ms[1] = 1e30; s->tune_n[1] = 2; s->tune_choice = 1; }
+      force = 1;
+      rc = run(s, ray_cam, rm, fuel, s->d_srgb, false, stats ? &st : nullptr, count, sync, force, &resolve);
+    }
+    if (rc != RTC_OK) return rc;
+    if (force == 4 && will_sync && !s->last_wavefront) {  // run() rendered the chunk again on the one-kernel path after an overflow
+      if (tuned) { s->tune_ms[1] = 1e30; s->tune_n[1] = 2; s->tune_choice = 1; }
+      force = 1;
+    }
+    if (will_sync) {
+      float ms = 0.f;
+      HIP_OK(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+      trace_ms += ms;
+    }
+    if (stats) {
+      float ms = 0.f;
+      HIP_OK(hipEventElapsedTime(&ms, s->evs0, s->evs1));
+      if (std::getenv("RTC_SAMPLED_TIMING")) {  // debug aid (scripts/filter_probe.py): the chunk's three parts by the events around them
+        float g = 0.f, t = 0.f, r = 0.f;
+        HIP_OK(hipEventElapsedTime(&g, s->evs0, s->ev0));
+        HIP_OK(hipEventElapsedTime(&t, s->ev0, s->ev1));
+        HIP_OK(hipEventElapsedTime(&r, s->ev1, s->evs1));
+        std::fprintf(stderr, "[rtc-filtered] chunk of %llu rays for %llu rows: generator %.3f ms, traces %.3f ms, filter %.3f ms (%s, tile %ux%u, %u B of LDS)\n",
+                     (unsigned long long)rm.n, (unsigned long long)(c1 - c0), g, t, r, lds ? "LDS" : "memory", tile >> 16, tile & 0xffffu, lds);
+      }
+      st.n_launches += 2u;
+      st.kernel_ms = ms;
+      add_stats(stats, st);
+    }
+  }
+  if (tuned && will_sync && !count && !s->tune_choice && force == first_path) {  // one sample of pick_path's measurement, as run() takes it
+    const int k = force == 4 ? 1 : 0;
+    s->tune_ms[k] = s->tune_n[k] ? std::min(s->tune_ms[k], trace_ms) : trace_ms;
+    s->tune_n[k]++;
+    if (s->tune_n[0] >= 2 && s->tune_n[1] >= 2) s->tune_choice = s->tune_ms[1] < s->tune_ms[0] ? 4 : 1;
+  }
+  if (stats) stats->pixels = pm.n;
+  return RTC_OK;
+}
+
 // One launch whose results go to the caller's host buffers: rgb (n x 3 doubles) or rgb8 (n x 3 bytes, Color::clamp on the device),
 // and optionally the primary-hit records.  The destination's pages are touched by host threads while the device renders, the
 // copies are queued behind the kernels (see pretouch_pages above).
 // `sp`: the launch goes through run_sampled (no hit records).  `ad`: the whole frame through run_adaptive (pm covers it).
+// `sp` and `fl`: whole rows through run_filtered.
 struct AdaptiveOut { const rtc_adaptive* rule; uint8_t* mask; uint64_t* n_refined; };
 int render_to_host(rtc_scene* s, const DCamera& dc, const DPixelMap& pm, int fuel, double* rgb, uint8_t* rgb8, rtc_hit* hits, rtc_stats* stats,
-                   const rtc_sampling* sp = nullptr, const AdaptiveOut* ad = nullptr) {
+                   const rtc_sampling* sp = nullptr, const AdaptiveOut* ad = nullptr, const rtc_filter* fl = nullptr) {
   static_assert(sizeof(DHit) == sizeof(rtc_hit) && offsetof(DHit, prim) == offsetof(rtc_hit, prim) && offsetof(DHit, k) == offsetof(rtc_hit, push_idx), "hit layout");
   const uint64_t n = pm.n;
   std::vector<std::thread> pool;
@@ -714,6 +829,7 @@ int render_to_host(rtc_scene* s, const DCamera& dc, const DPixelMap& pm, int fue
     return RTC_OK;
   };
   const int rc = ad ? run_adaptive(s, dc, *ad->rule, fuel, stats, ad->mask, ad->n_refined, &after)
+                 : fl ? run_filtered(s, dc, pm, *sp, *fl, fuel, s->d_rgb, stats, stats != nullptr, true, &after)
                  : sp ? run_sampled(s, dc, pm, *sp, fuel, s->d_rgb, stats, stats != nullptr, true, &after)
                     : run(s, dc, pm, fuel, s->d_rgb, hits != nullptr, stats, stats != nullptr, true, 0, &after);
   join_all(&pool);  // (an error before the hook ran its join)
@@ -1189,6 +1305,75 @@ int rtc_contrast_pixels(rtc_scene* s, uint64_t hsize, uint64_t vsize, const doub
   if (rc != RTC_OK) return rc;
   if (refined) HIP_OK(hipMemcpy(indices, s->d_alist, refined * sizeof(uint64_t), hipMemcpyDeviceToHost));
   *n = refined;
+  return RTC_OK;
+}
+
+// ---- the reconstruction filters' entry points (include/rtc.h) ------------------------------------------------------------------------
+static int render_filtered(rtc_scene* s, const rtc_camera* cam, const rtc_sampling* sp, const rtc_filter* f, int32_t fuel, uint64_t row_first, uint64_t n_rows,
+                           double* rgb, uint8_t* rgb8, rtc_stats* stats) {
+  if (!s || !cam || !sp || !f || (!rgb && !rgb8)) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  int rc = check_sampling(sp);
+  if (rc == RTC_OK) rc = check_filter(f);
+  if (rc != RTC_OK) return rc;
+  if (cam->hsize == 0 || cam->vsize == 0) return rtc_fail(RTC_ERR_INVALID, "empty camera");
+  if (n_rows == 0 || row_first >= cam->vsize || n_rows > cam->vsize - row_first) return rtc_fail(RTC_ERR_INVALID, "filtered: the row range is empty or leaves the image");
+  if (cam->vsize > 0xffffffffull) return rtc_fail(RTC_ERR_UNSUPPORTED, "filtered: frames of 2^32 rows or more");
+  HIP_OK(hipSetDevice(s->device));
+  const uint64_t n = n_rows * cam->hsize;
+  rc = ensure_px(s, n, false);
+  if (rc != RTC_OK) return rc;
+  if (rgb8 && 3 * n > s->cap_rgb8) {
+    (void)hipFree(s->d_rgb8);
+    s->d_rgb8 = nullptr; s->cap_rgb8 = 0;
+    HIP_OK(hipMalloc((void**)&s->d_rgb8, 3 * n));
+    s->cap_rgb8 = 3 * n;
+  }
+  DPixelMap pm{};
+  pm.n = n; pm.mode = 2; pm.row_first = (uint32_t)row_first; pm.row_step = 1;
+  DCamera dc;
+  to_dcam(*cam, &dc);
+  return render_to_host(s, dc, pm, fuel, rgb, rgb8, nullptr, stats, sp, nullptr, f);
+}
+
+int rtc_render_filtered(rtc_scene* s, const rtc_camera* cam, const rtc_sampling* sp, const rtc_filter* f, int32_t fuel, uint32_t row_first, uint32_t n_rows, double* rgb,
+                        rtc_stats* stats) {
+  return render_filtered(s, cam, sp, f, fuel, row_first, n_rows, rgb, nullptr, stats);
+}
+
+int rtc_render_filtered_rgb8(rtc_scene* s, const rtc_camera* cam, const rtc_sampling* sp, const rtc_filter* f, int32_t fuel, uint8_t* rgb8, rtc_stats* stats) {
+  return render_filtered(s, cam, sp, f, fuel, 0, cam ? cam->vsize : 0, nullptr, rgb8, stats);
+}
+
+int rtc_filter_frame(rtc_scene* s, uint64_t hsize, uint64_t vsize, const rtc_sampling* sp, const rtc_filter* f, const double* sample_rgb, double* rgb) {
+  if (!sp || !f || !sample_rgb || !rgb) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  int rc = check_sampling(sp);
+  if (rc == RTC_OK) rc = check_filter(f);
+  if (rc != RTC_OK) return rc;
+  if (hsize == 0 || vsize == 0) return rtc_fail(RTC_ERR_INVALID, "empty frame");
+  const uint64_t N = (uint64_t)sp->side * sp->side;
+  if (hsize > 0x7fffff00ull || vsize > 0x7fffff00ull || hsize * vsize > 0x7fffff00ull / N) return rtc_fail(RTC_ERR_UNSUPPORTED, "filter: frames of 2^31 samples or more");
+  const uint64_t total = hsize * vsize;
+  if (!s) {  // the same function on the host
+    const uint32_t W = rtc_filter_window(f->radius);
+    const rtc_filter_mem_src src{sample_rgb, hsize, 0, (uint32_t)N, *sp};
+    for (uint64_t i = 0; i < total; i++) {
+      const uint64_t x = i % hsize, y = i / hsize;
+      uint64_t qx0, qx1, qy0, qy1;
+      rtc_filter_span(x, W, 0, hsize, &qx0, &qx1);
+      rtc_filter_span(y, W, 0, vsize, &qy0, &qy1);
+      rtc_filter_pixel(*f, (uint32_t)N, x, y, qx0, qx1, qy0, qy1, src, rgb + 3 * i);
+    }
+    return RTC_OK;
+  }
+  HIP_OK(hipSetDevice(s->device));
+  rc = ensure_px(s, total, false);
+  if (rc == RTC_OK) rc = ensure_sampled(s, total * N, true);
+  if (rc != RTC_OK) return rc;
+  HIP_OK(hipMemcpyAsync(s->d_srgb, sample_rgb, total * N * 3 * sizeof(double), hipMemcpyHostToDevice, s->stream));
+  (void)rtc_launch_resolve_filtered(*f, *sp, hsize, 0, vsize, 0, vsize, s->d_srgb, s->d_rgb, s->stream, nullptr);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(rgb, s->d_rgb, total * 3 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  HIP_OK(hipStreamSynchronize(s->stream));
   return RTC_OK;
 }
 

@@ -10,7 +10,7 @@ import ctypes as C
 
 import numpy as np
 
-from .scene import FUEL, Adaptive, Camera, Color, Sampling, World
+from .scene import FUEL, Adaptive, Camera, Color, Filter, Sampling, World
 
 
 class Image:
@@ -20,17 +20,24 @@ class Image:
         self._native = _native  # (backend, NativeWorld) that rendered it, for the device quantiser
 
     @staticmethod
-    def par_render(camera: Camera, world: World, fuel: int = FUEL, backend=None, sampling: Sampling = None, adaptive: Adaptive = None) -> "Image":
+    def par_render(camera: Camera, world: World, fuel: int = FUEL, backend=None, sampling: Sampling = None, adaptive: Adaptive = None,
+                   filter: Filter = None) -> "Image":
         """sampling: a :class:`Sampling` renders every pixel as the mean of its sample rays (anti-aliasing, depth of field); None is
         the reference's one ray per pixel.  adaptive: an :class:`Adaptive` renders the frame with its base sampling and only the pixels
-        that differ from a neighbour with its fine one; it carries both samplings, so giving `sampling` as well is a ValueError."""
+        that differ from a neighbour with its fine one; it carries both samplings, so giving `sampling` as well is a ValueError.
+        filter: a :class:`Filter` reconstructs every pixel from the samples within its radius instead of the pixel's own (without
+        `sampling` that is one centre sample per pixel); the adaptive refine pass is not filtered, so `adaptive` with it is a ValueError."""
         if adaptive is not None and sampling is not None:
             raise ValueError("par_render: give `adaptive` or `sampling`, not both (an Adaptive carries its two samplings)")
+        if adaptive is not None and filter is not None:
+            raise ValueError("par_render: `filter` does not apply to `adaptive` (the refine pass is a box mean)")
         from . import hip_backend
         be = backend or hip_backend()
         nw = be.build_world(world)
         if adaptive is not None:
             return Image(camera.hsize, camera.vsize, be.render_adaptive(nw, camera, adaptive, fuel), (be, nw))
+        if filter is not None:
+            return Image(camera.hsize, camera.vsize, be.render_filtered(nw, camera, sampling if sampling is not None else Sampling(side=1), filter, fuel), (be, nw))
         if sampling is not None:
             return Image(camera.hsize, camera.vsize, be.render_sampled(nw, camera, sampling, fuel), (be, nw))
         rgb, _ = be.render(nw, camera, fuel, want_hits=False)

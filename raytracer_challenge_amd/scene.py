@@ -377,6 +377,56 @@ class Adaptive:
             raise ValueError("Adaptive.neighbours must be 4 or 8")
 
 
+FILTER_KINDS = ("box", "tent", "gaussian", "mitchell")   # include/rtc.h RTC_FILTER_*
+FILTER_MAX_RADIUS = 3.0
+
+
+@dataclass(frozen=True)
+class Filter:
+    """A pixel reconstruction filter (include/rtc.h rtc_filter; not in the reference): a pixel is the weighted mean of the samples
+    within ``radius`` pixels of its centre per axis (separable), weights from ``kind``; ``alpha`` is the Gaussian's falloff.
+    ``Filter.box(0.5)`` is the sampled camera's own box mean.  Rendered by the HIP library only."""
+    kind: str
+    radius: float
+    alpha: float = 0.0
+
+    def __post_init__(self):
+        import math
+        if self.kind not in FILTER_KINDS:
+            raise ValueError("Filter.kind must be one of %s" % (FILTER_KINDS,))
+        try:
+            ok = math.isfinite(self.radius) and self.radius >= 0.5
+        except TypeError:
+            ok = False
+        if not ok:
+            raise ValueError("Filter.radius must be finite and >= 0.5")
+        if self.radius > FILTER_MAX_RADIUS:
+            raise ValueError("Filter.radius exceeds %g" % FILTER_MAX_RADIUS)
+        if self.kind == "gaussian":
+            try:
+                ok = math.isfinite(self.alpha) and self.alpha > 0.0
+            except TypeError:
+                ok = False
+            if not ok:
+                raise ValueError("Filter.alpha must be finite and > 0 for a Gaussian")
+
+    @classmethod
+    def box(cls, radius: float = 0.5) -> "Filter":
+        return cls("box", radius)
+
+    @classmethod
+    def tent(cls, radius: float = 1.5) -> "Filter":
+        return cls("tent", radius)
+
+    @classmethod
+    def gaussian(cls, radius: float = 1.5, alpha: float = 2.0) -> "Filter":
+        return cls("gaussian", radius, alpha)
+
+    @classmethod
+    def mitchell(cls, radius: float = 2.0) -> "Filter":
+        return cls("mitchell", radius)
+
+
 @dataclass(frozen=True)
 class Camera:  # src/camera.rs:5-13; derived fields are computed natively from `transform`
     hsize: int

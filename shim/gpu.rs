@@ -151,6 +151,26 @@ pub struct RtcAdaptive {
     pub _pad: u32,
 }
 
+// include/rtc.h rtc_filter: a pixel reconstruction filter wider than the pixel (not in the reference) for rtc_render_filtered*
+#[allow(dead_code)]
+pub const RTC_FILTER_BOX: i32 = 0;
+#[allow(dead_code)]
+pub const RTC_FILTER_TENT: i32 = 1;
+#[allow(dead_code)]
+pub const RTC_FILTER_GAUSSIAN: i32 = 2;
+#[allow(dead_code)]
+pub const RTC_FILTER_MITCHELL: i32 = 3;
+#[allow(dead_code)]
+pub const RTC_FILTER_MAX_RADIUS: f64 = 3.0;
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtcFilter {
+    pub kind: i32, // RTC_FILTER_*
+    pub _pad: u32,
+    pub radius: f64, // pixels from the pixel centre, per axis
+    pub alpha: f64,  // the Gaussian's falloff; read by no other kind
+}
+
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct RtcNode {
@@ -275,6 +295,16 @@ extern "C" {
     #[allow(dead_code)] // the contrast rule alone on a host frame; scene = null: evaluated on the host, no device needed
     fn rtc_contrast_pixels(scene: *mut RtcScene, hsize: u64, vsize: u64, rgb: *const f64, threshold: f64, neighbours: u32, indices: *mut u64,
                            n: *mut u64) -> c_int;
+    // reconstruction filters: rows [row_first, row_first + n_rows) filtered over the whole image's neighbours; the whole frame quantised
+    #[allow(dead_code)]
+    fn rtc_render_filtered(scene: *mut RtcScene, camera: *const RtcCamera, sampling: *const RtcSampling, filter: *const RtcFilter, fuel: i32, row_first: u32,
+                           n_rows: u32, rgb: *mut f64, stats: *mut RtcStats) -> c_int;
+    #[allow(dead_code)]
+    fn rtc_render_filtered_rgb8(scene: *mut RtcScene, camera: *const RtcCamera, sampling: *const RtcSampling, filter: *const RtcFilter, fuel: i32, rgb8: *mut u8,
+                                stats: *mut RtcStats) -> c_int;
+    #[allow(dead_code)] // the filter step alone on host sample colours; scene = null: evaluated on the host, no device needed
+    fn rtc_filter_frame(scene: *mut RtcScene, hsize: u64, vsize: u64, sampling: *const RtcSampling, filter: *const RtcFilter, sample_rgb: *const f64,
+                        rgb: *mut f64) -> c_int;
 }
 
 #[derive(Debug)]
