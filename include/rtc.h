@@ -186,6 +186,38 @@ typedef struct rtc_scene_ext {
   const rtc_texture* textures;
 } rtc_scene_ext;
 
+/* Spot lights (not in the reference; the light kind the book's readers build next): a cone with a smooth edge on one light of the
+ * scene's list, point or area, for rtc_scene_create_ext2 / rtc_multi_create_ext2.  `light` indexes the scene's light list, `axis` is
+ * the direction the light points in (any length), cos_inner / cos_outer are the cosines of the two half-angles: inside the inner cone
+ * the light is full, outside the outer one it is dark.  Cosines, not angles: no cos of any maths library enters the rule.  Every step is
+ * one f64 operation, in the order written here (csrc/spot_factor.h, one function for device and host).
+ *   At scene creation: m = sqrt((ax*ax + ay*ay) + az*az), a = axis / m componentwise (Vector::normalize's order).
+ *   For a sample at p_k (rtc_light_ex; a point light: its origin) and a shading point o = the over_point, the shadow rays' origin:
+ *     d  = the shadow ray's direction (World::is_shadowed, src/world.rs:139-143): v = p_k - o, dist = sqrt(vx*vx + vy*vy + vz*vz),
+ *          d = v / dist componentwise;
+ *     c  = ((-dx)*ax + (-dy)*ay) + (-dz)*az;
+ *     f  = 1.0 if c >= cos_inner; else 0.0 if c <= cos_outer; else t = (c - cos_outer) / (cos_inner - cos_outer),
+ *          f = (t * t) * (3.0 - 2.0 * t).  The tests run in that order: cos_inner == cos_outer is a hard edge and never divides by
+ *          zero.  A NaN c fails both tests: t and f are NaN and poison the sample.
+ *     f == 0.0: the sample adds nothing, no shadow ray is traced and rtc_stats.rays_shadow does not count it.
+ *     Otherwise the sample is exactly the reference's point-light term for a light at p_k of intensity I[ch] * f, one multiplication per
+ *     channel; I is the light's intensity, of an area light already divided by N.  x * 1.0 is exact: a sample inside the inner cone
+ *     has an ordinary light's bits, and so has every sample of an open cone, cos_inner = cos_outer = -1 (|c| <= 1 holds whenever the
+ *     axis has one non-zero component; for a general axis c can fall one rounding below -1 where d is exactly opposite to it).
+ *     The one-kernel path's shortcut for a light behind the surface (ambient term only) uses the scaled intensity as well.
+ *   A light with a cone is still ONE light: L = n_lights and the once-per-light reflected and refracted colour do not change, whatever
+ *   f is.  A point light with a cone keeps its light grid.
+ * Limits: RTC_ERR_INVALID for a `light` index out of range, two cones on one light, an axis that is zero or not finite (or whose length
+ * is, in f64), cosines not finite or outside [-1, 1], cos_outer > cos_inner, n_cones > 0 with NULL cones.
+ * Not covered: distance attenuation, textured (gobo) lights, more than one cone per light. */
+typedef struct rtc_light_cone {
+  uint32_t light;     /* index into the scene's light list */
+  uint32_t _pad;
+  double axis[3];     /* where the light points; normalised at scene creation */
+  double cos_inner;   /* cosine of the half-angle inside which the light is full */
+  double cos_outer;   /* cosine of the half-angle outside which it is dark; <= cos_inner */
+} rtc_light_cone;
+
 /* The sampled camera (not in the reference, whose Camera::ray_at_pixel sends one ray through each pixel centre from a pinhole): n x n
  * samples per pixel (anti-aliasing, box filter) and an optional thin lens (depth of field), for the rtc_render_sampled* entry points
  * and rtc_camera_rays.  Pixel i has x = i % hsize, y = i / hsize; sample k of its N = n * n has sx = k % n, sy = k / n.  Every step is
@@ -355,6 +387,14 @@ int rtc_scene_create_ex(const rtc_scene_desc* desc, const rtc_light_ex* lights, 
  * kernels, same bits); a scene with a UV node renders with kernel instantiations of its own on both device paths.  Every render
  * entry point takes the result. */
 int rtc_scene_create_ext(const rtc_scene_desc* desc, const rtc_scene_ext* ext, int device, rtc_scene** out);
+/* Same, with n_cones light cones (rtc_light_cone above; `light` indexes ext->lights, or desc->lights when ext is NULL or has none).
+ * Zero cones is exactly rtc_scene_create_ext (same kernels, same bits); a scene with a cone renders with kernel instantiations of its
+ * own on both device paths, whether or not it has an area light.  The cones' own numbers are checked before anything else, a device
+ * included.  Every render entry point takes the result. */
+int rtc_scene_create_ext2(const rtc_scene_desc* desc, const rtc_scene_ext* ext, const rtc_light_cone* cones, uint32_t n_cones, int device, rtc_scene** out);
+/* The cone factor f alone, for a light (or sample) at light_pos and a shading point `point`; `cone->light` is not read.  Host-only: no
+ * device needed (like rtc_ppm).  RTC_ERR_INVALID for NULL arguments and for a cone rtc_scene_create_ext2 would refuse. */
+int rtc_spot_factor(const rtc_light_cone* cone, const double light_pos[3], const double point[3], double* f);
 void rtc_scene_destroy(rtc_scene*);
 /* Size in bytes of the scene's device buffers (accelerator and texels included). */
 uint64_t rtc_scene_device_bytes(const rtc_scene*);
@@ -412,6 +452,9 @@ int rtc_multi_create(const rtc_scene_desc* desc, const int* devices, int n_devic
 int rtc_multi_create_ex(const rtc_scene_desc* desc, const rtc_light_ex* lights, uint32_t n_lights, const int* devices, int n_devices, rtc_multi** out);
 /* Same with the extensions of rtc_scene_create_ext (every replica uploads its own copy of the texels). */
 int rtc_multi_create_ext(const rtc_scene_desc* desc, const rtc_scene_ext* ext, const int* devices, int n_devices, rtc_multi** out);
+/* Same with the light cones of rtc_scene_create_ext2. */
+int rtc_multi_create_ext2(const rtc_scene_desc* desc, const rtc_scene_ext* ext, const rtc_light_cone* cones, uint32_t n_cones, const int* devices, int n_devices,
+                          rtc_multi** out);
 void rtc_multi_destroy(rtc_multi*);
 int rtc_multi_device_count(const rtc_multi*);
 /* Rows per band of the partition (default 8; 1 = single rows interleaved).  Waits for queued frames. */

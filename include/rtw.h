@@ -100,6 +100,11 @@ int rtw_world_add_light(rtw_world*, const double intensity[3], const double orig
  * oracle restates the reference, which has none); rendering such a world needs rtc_scene_create_ex. */
 int rtw_world_add_area_light(rtw_world*, const double intensity[3], const double corner[3], const double uvec[3], uint32_t usteps,
                              const double vvec[3], uint32_t vsteps, int jitter);
+/* A cone on the light added as number `light` (include/rtc.h rtc_light_cone; not in the reference): the light, point or area, becomes a
+ * spot light pointing along `axis` (any length), full inside the half-angle of cosine cos_inner, dark outside cos_outer's.  Fails for
+ * an index no light has yet, a second cone on one light and numbers rtc_scene_create_ext2 would refuse.  Product library only;
+ * rendering such a world needs rtc_scene_create_ext2. */
+int rtw_world_set_light_cone(rtw_world*, uint32_t light, const double axis[3], double cos_inner, double cos_outer);
 int rtw_world_add_element(rtw_world*, rtw_element*);                                    /* consumes */
 uint64_t rtw_world_primitive_count(const rtw_world*);
 void rtw_world_release(rtw_world*);

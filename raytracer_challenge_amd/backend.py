@@ -13,7 +13,7 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from .scene import (FUEL, GEOMETRY, GROUP_KINDS, JITTER_KINDS, MIXTURE_KINDS, Adaptive, AreaLight, Camera, Element, FILTER_KINDS, Filter, Material, Pattern, Sampling, World)
+from .scene import (FUEL, GEOMETRY, GROUP_KINDS, JITTER_KINDS, MIXTURE_KINDS, Adaptive, AreaLight, Camera, Cone, Element, FILTER_KINDS, Filter, Material, Pattern, Sampling, World)
 from .texture import UV_KINDS, UV_MAPS, Texture
 
 HIT_DTYPE = np.dtype([("t", "<f8"), ("prim", "<i4"), ("push_idx", "<i4")])
@@ -131,6 +131,11 @@ class Backend:
         if self.has_area_lights:
             lib.rtw_world_add_area_light.restype = i
             lib.rtw_world_add_area_light.argtypes = [vp, dp, dp, dp, C.c_uint32, dp, C.c_uint32, i]
+        # light cones: the same
+        self.has_light_cones = hasattr(lib, "rtw_world_set_light_cone")
+        if self.has_light_cones:
+            lib.rtw_world_set_light_cone.restype = i
+            lib.rtw_world_set_light_cone.argtypes = [vp, C.c_uint32, dp, d, d]
         # texture-mapped patterns: the same (the oracle has none)
         self.has_texture_map = hasattr(lib, "rtw_pattern_uv")
         if self.has_texture_map:
@@ -226,17 +231,23 @@ class Backend:
         cache: Dict[int, int] = {}
         owned: list = []
         try:
-            for l in world.lights:
+            for k, l in enumerate(world.lights):
                 inten = (C.c_double * 3)(l.intensity.r, l.intensity.g, l.intensity.b)
+                cone: Optional[Cone] = getattr(l, "cone", None)
+                if cone is not None and not self.has_light_cones:
+                    raise RtwError("light cones need librtc_amd.so (backend %r has no rtw_world_set_light_cone)" % self.name)
                 if isinstance(l, AreaLight):
                     if not self.has_area_lights:
                         raise RtwError("area lights need librtc_amd.so (backend %r has no rtw_world_add_area_light)" % self.name)
                     v3 = lambda v: (C.c_double * 3)(*v[:3])  # noqa: E731
                     self._check(lib.rtw_world_add_area_light(w, inten, v3(l.corner), v3(l.uvec), int(l.usteps), v3(l.vvec), int(l.vsteps),
                                                              1 if l.jitter else 0), "add_area_light")
-                    continue
-                org = (C.c_double * 3)(*l.origin[:3])
-                self._check(lib.rtw_world_add_light(w, inten, org), "add_light")
+                else:
+                    org = (C.c_double * 3)(*l.origin[:3])
+                    self._check(lib.rtw_world_add_light(w, inten, org), "add_light")
+                if cone is not None:
+                    axis = (C.c_double * 3)(*cone.direction[:3])
+                    self._check(lib.rtw_world_set_light_cone(w, k, axis, cone.cos_inner, cone.cos_outer), "set_light_cone")
             for e in world.elements:
                 self._check(lib.rtw_world_add_element(w, self._element(e, cache, owned)), "add_element")
         except Exception:

@@ -171,7 +171,8 @@ struct DScene {
                              // rgb (a Plain root pattern; else 0), 0}: what the wavefront path's shadow role reads of a material, in one row
   const int32_t* mat_pattern;
   const DPat* pats;
-  const double* lights;      // n_lights x {intensity rgb, origin xyz}; scenes with an area light (has_area): n_lights x RTC_ALIGHT doubles
+  const double* lights;      // n_lights x {intensity rgb, origin xyz}; scenes with an area light (has_area): n_lights x RTC_ALIGHT doubles;
+                             // scenes with a cone (has_spot): n_lights x RTC_SLIGHT doubles
   int32_t n_ops, n_prims, n_lights;
   int32_t all_cast_shadow;   // 1: every primitive casts a shadow -> shadow rays may stop at any hit
   int32_t has_mesh;          // 1: the program contains an OP_MESH
@@ -207,6 +208,8 @@ struct DScene {
   int32_t n_bvh, n_items, n_mtri, n_quirk, n_qitem, n_qcell, n_groups, n_qgrids;
   int32_t has_area;   // 1: some light is an area light: `lights` holds RTC_ALIGHT doubles per light and the area kernels render the scene
   int32_t has_uv;     // 1: some pattern node is an RTC_PAT_UV node: the UV kernel instantiations render the scene (DUv)
+  int32_t has_spot;   // 1: some light has a cone (include/rtc.h rtc_light_cone): `lights` holds RTC_SLIGHT doubles per light and the SPOT kernels
+                      // render the scene (in what was the struct's tail padding: the layout of everything else is unchanged)
 };
 
 // Which pixels a launch covers.
@@ -287,6 +290,9 @@ static inline RTC_HD double rtc_area_jitter(unsigned long long h, unsigned j) {
 // {intensity (area: / N) rgb, corner xyz, uc xyz, vc xyz, usteps, vsteps, kind (1 area, 0 point), area: jitter (0 / 1), point: its light
 // grid (index among the scene's point lights; scene_build.hpp build_arrays_ex)}.  Point-light-only scenes keep {intensity, origin}.
 #define RTC_ALIGHT 16
+// Light records of scenes with a cone (DScene.has_spot; the SPOT kernels read them), every light of the scene: the RTC_ALIGHT doubles
+// above -- a scene without an area light writes them too --, then {unit axis xyz, cos_inner, cos_outer, has a cone (1 / 0)}.
+#define RTC_SLIGHT 22
 
 // Wavefront path (rtc_device.hpp / rtc_kernels.hip, wf_* kernels): rays of one bounce level live in a queue; per level a traversal launch
 // (closest hits of the level + shadow rays and lighting of the previous level) and a shading launch (hit state, pattern

@@ -25,6 +25,18 @@
 
 namespace rth {
 
+// What is wrong with the numbers of a light cone (include/rtc.h rtc_light_cone: RTC_ERR_INVALID), or NULL; shared by scene creation
+// (scene_build.hpp) and rtw_world_set_light_cone.
+inline const char* cone_invalid(const double axis[3], double cos_inner, double cos_outer) {
+  for (int c = 0; c < 3; c++) if (!std::isfinite(axis[c])) return "the axis is not finite";
+  if (axis[0] == 0.0 && axis[1] == 0.0 && axis[2] == 0.0) return "the axis is zero";
+  const double m = std::sqrt((axis[0] * axis[0] + axis[1] * axis[1]) + axis[2] * axis[2]);
+  if (!(m > 0.0) || !std::isfinite(m)) return "the axis' length is zero or not finite in f64";
+  if (!(cos_inner >= -1.0 && cos_inner <= 1.0) || !(cos_outer >= -1.0 && cos_outer <= 1.0)) return "a cosine is not finite or outside [-1, 1]";
+  if (cos_outer > cos_inner) return "cos_outer is above cos_inner (the outer cone is the wider one)";
+  return nullptr;
+}
+
 constexpr double kInf = std::numeric_limits<double>::infinity();
 
 struct V4 { double x, y, z, w; };

@@ -23,6 +23,7 @@
 #include <algorithm>
 
 #include "device_scene.h"
+#include "spot_factor.h"
 
 #define EPS 0.00001
 #ifndef RTC_BLOCK
@@ -1644,13 +1645,17 @@ __device__ __forceinline__ void publish_counters(DStats* __restrict__ stats, con
 // rays walk the BVH (-1).
 // BEHIND: the one-kernel path's light_is_behind shortcut, per sample (its ambient-only term has the bits of the general case).
 // The one-kernel and the wavefront area kernels both run this function: same bits on both paths.
-template <int FEAT, bool KOPS, bool LDSC, bool BEHIND>
+// SPOT: scenes with a cone (include/rtc.h rtc_light_cone; DScene.has_spot: RTC_SLIGHT doubles per light, whether or not the scene has an
+// area light).  Per sample the factor f (spot_factor.h) from the shadow ray's direction; f == 0 ends the sample before it is counted,
+// tested for facing away or traversed; otherwise the sample's light is intensity * f (a light without a cone: f = 1.0, and x * 1.0 is
+// x).  Only f lives across the traversal beyond what the area code keeps.  Other scenes never run it.
+template <int FEAT, bool KOPS, bool LDSC, bool BEHIND, bool SPOT = false>
 __device__ __forceinline__ void shade_lights_area(const DScene& S, double px, double py, double pz, double nx, double ny, double nz, double ex, double ey,
                                                   double ez, double cr, double cg, double cb, double ambient, double diffuse, double specular, double shininess,
                                                   Counters& C, int* stack, int stride, unsigned& n_shadow, const LdsScene& Ls, double& sr, double& sg,
                                                   double& sb) {
   for (int l = 0; l < S.n_lights; l++) {
-    const double* LG = S.lights + RTC_ALIGHT * l;
+    const double* LG = S.lights + (SPOT ? RTC_SLIGHT : RTC_ALIGHT) * l;
     const bool area = LG[14] != 0.0, jitter = area && LG[15] != 0.0;
     const int us = (int)LG[12];
     const int ns = area ? us * (int)LG[13] : 1;
@@ -1665,6 +1670,28 @@ __device__ __forceinline__ void shade_lights_area(const DScene& S, double px, do
         lx = (LG[3] + LG[6] * fu) + LG[9] * fv;
         ly = (LG[4] + LG[7] * fu) + LG[10] * fv;
         lz = (LG[5] + LG[8] * fu) + LG[11] * fv;
+      }
+      if constexpr (SPOT) {
+        const ShadowRay s = shadow_ray(px, py, pz, lx, ly, lz);
+        double f = 1.0;
+        if (LG[21] != 0.0) f = rtc_spot_f(rtc_spot_cos(s.ray.dx, s.ray.dy, s.ray.dz, LG[16], LG[17], LG[18]), LG[19], LG[20]);
+        if (f == 0.0) continue;  // outside the cone: nothing to add, no shadow ray
+        n_shadow++;
+        if (BEHIND && light_is_behind(S, px, py, pz, lx, ly, lz, nx, ny, nz)) {
+          const double I[3] = {LG[0] * f, LG[1] * f, LG[2] * f};
+          ambient_add(I, cr, cg, cb, ambient, sr, sg, sb);
+          continue;
+        }
+        Trav Sh;
+        reset_closest(Sh, S.all_cast_shadow ? MODE_SHADOW_ANY : MODE_SHADOW_CLOSEST);
+        if (S.all_cast_shadow) { Sh.thi = s.distance; Sh.unordered = 1; }
+        Sh.light = area ? -1 : (int)LG[15]; Sh.c1_t = s.distance;
+        if (S.all_cast_shadow) traverse<FEAT, KOPS, MODE_SHADOW_ANY, LDSC>(S, s.ray, Sh, C, stack, stride, Ls);
+        else traverse<FEAT, KOPS, MODE_SHADOW_CLOSEST, LDSC>(S, s.ray, Sh, C, stack, stride, Ls);
+        const bool shadowed = shadow_result(S, Sh, s.distance, C);
+        const double I[3] = {LG[0] * f, LG[1] * f, LG[2] * f};
+        phong_add(I, s.ray.dx, s.ray.dy, s.ray.dz, shadowed, nx, ny, nz, ex, ey, ez, cr, cg, cb, ambient, diffuse, specular, shininess, sr, sg, sb);
+        continue;
       }
       n_shadow++;
       if (BEHIND && light_is_behind(S, px, py, pz, lx, ly, lz, nx, ny, nz)) {
@@ -1697,7 +1724,8 @@ __device__ __forceinline__ void shade_lights_area(const DScene& S, double px, do
 // scratch per lane instead of 1 648 (config 3 -3 %, config 4 -4 %: profiles/r3_partition_probe.txt).
 // AREA: scenes with an area light (DScene.has_area): the lights are shaded by shade_lights_area.  Point-light scenes never run it.
 // UV: scenes with a texture-mapped pattern (DScene.has_uv): the pattern walk with the RTC_PAT_UV branch.  Other scenes never run it.
-template <bool COUNT, int FEAT, bool KOPS, int WAVES = 0, bool LEAN = false, bool AREA = false, bool UV = false>
+// SPOT (with AREA): scenes with a cone (DScene.has_spot): shade_lights_area's SPOT build.
+template <bool COUNT, int FEAT, bool KOPS, int WAVES = 0, bool LEAN = false, bool AREA = false, bool UV = false, bool SPOT = false>
 __global__ void __launch_bounds__(RTC_BLOCK, WAVES ? WAVES : ((FEAT >= 2 && RTC_WAVES_PER_SIMD < 2) ? 2 : RTC_WAVES_PER_SIMD)) rtc_trace_kernel(DScene S, DCamera cam, DPixelMap pm, int fuel0, double* __restrict__ rgb, double* __restrict__ hit_t,
                                                         int* __restrict__ hit_prim, int* __restrict__ hit_k, DStats* __restrict__ stats) {
   RTC_LDS_STACK(lds_stack);
@@ -1777,7 +1805,7 @@ __global__ void __launch_bounds__(RTC_BLOCK, WAVES ? WAVES : ((FEAT >= 2 && RTC_
         // World::shade_hit (src/world.rs:50-82): per light, shadow test + Phong (src/shape.rs:429-462)
         double sr = 0.0, sg = 0.0, sb = 0.0;
         if constexpr (AREA) {
-          shade_lights_area<FEAT, KOPS, false, true>(S, st.px, st.py, st.pz, st.nx, st.ny, st.nz, st.ex, st.ey, st.ez, cr, cg, cb, ambient, diffuse, specular,
+          shade_lights_area<FEAT, KOPS, false, true, SPOT>(S, st.px, st.py, st.pz, st.nx, st.ny, st.nz, st.ex, st.ey, st.ez, cr, cg, cb, ambient, diffuse, specular,
                                                      shininess, C, stack, stride, n_shadow, LdsScene{}, sr, sg, sb);
         } else
         for (int l = 0; l < S.n_lights; l++) {
@@ -2013,7 +2041,7 @@ __device__ __forceinline__ void wf_shadow_rec(const DScene& S, const DCamera& ca
 
 // The shadow role for scenes with an area light (wf_ts<..., AREA>): the record's whole state is loaded first and every sample's shadow
 // ray is followed by its Phong terms (shade_lights_area), where wf_shadow_rec keeps one shadow bit per light.
-template <int FEAT, bool KOPS, bool LDSC>
+template <int FEAT, bool KOPS, bool LDSC, bool SPOT = false>
 __device__ __forceinline__ void wf_shadow_rec_area(const DScene& S, const DCamera& cam, const DPixelMap& pm, const DWave& W, const WorkMap& wm, int level, unsigned s,
                                                    int* stack, int stride, Counters& C, unsigned& n_shadow, const LdsScene& L) {
   const size_t cap = W.cap;
@@ -2024,7 +2052,7 @@ __device__ __forceinline__ void wf_shadow_rec_area(const DScene& S, const DCamer
   double cr, cg, cbl;
   const double* M = shade_rec_material(S, W, s, cr, cg, cbl);
   double sr = 0.0, sg = 0.0, sb = 0.0;
-  shade_lights_area<FEAT, KOPS, LDSC, false>(S, r[s], r[cap + s], r[2 * cap + s], r[3 * cap + s], r[4 * cap + s], r[5 * cap + s], v.ex, v.ey, v.ez, cr, cg, cbl, M[0], M[1],
+  shade_lights_area<FEAT, KOPS, LDSC, false, SPOT>(S, r[s], r[cap + s], r[2 * cap + s], r[3 * cap + s], r[4 * cap + s], r[5 * cap + s], v.ex, v.ey, v.ez, cr, cg, cbl, M[0], M[1],
                                              M[2], M[3], C, stack, stride, n_shadow, L, sr, sg, sb);
   cb[node] = v.weight * sr; cb[cap + node] = v.weight * sg; cb[2 * cap + node] = v.weight * sb;
 }
@@ -2044,8 +2072,8 @@ __device__ __forceinline__ void wf_shadow_rec_area(const DScene& S, const DCamer
 #ifndef RTC_LDS_BLOCK
 #define RTC_LDS_BLOCK (256 * RTC_WF_TS_WAVES)  // LDSC kernels: one block per CU with all the waves the register budget allows
 #endif
-// AREA: scenes with an area light (DScene.has_area): the shadow role is wf_shadow_rec_area.
-template <bool COUNT, int FEAT, bool KOPS, bool LDSC = false, bool AREA = false>
+// AREA: scenes with an area light (DScene.has_area): the shadow role is wf_shadow_rec_area.  SPOT (with AREA): its SPOT build.
+template <bool COUNT, int FEAT, bool KOPS, bool LDSC = false, bool AREA = false, bool SPOT = false>
 __global__ void __launch_bounds__(LDSC ? RTC_LDS_BLOCK : RTC_BLOCK, (KOPS || FEAT <= RTC_WF_TS_WAVES_MAXFEAT) ? RTC_WF_TS_WAVES : 2) wf_ts(DScene S, DCamera cam, DPixelMap pm, DWave W, int tl, int sl, unsigned n0, int slot, int fuel_left,
                                                                      double* __restrict__ hit_t, int* __restrict__ hit_prim, int* __restrict__ hit_k, DStats* __restrict__ stats) {
   RTC_LDS_STACK(lds_stack);
@@ -2096,7 +2124,7 @@ __global__ void __launch_bounds__(LDSC ? RTC_LDS_BLOCK : RTC_BLOCK, (KOPS || FEA
         const unsigned s = base + o + (unsigned)lane;
         if (s < ns) {
           DIAG_SPAN_BEGIN();
-          if constexpr (AREA) wf_shadow_rec_area<FEAT, KOPS, LDSC>(S, cam, pm, W, wm, sl, s, stack, stride, C, n_shadow, L);
+          if constexpr (AREA) wf_shadow_rec_area<FEAT, KOPS, LDSC, SPOT>(S, cam, pm, W, wm, sl, s, stack, stride, C, n_shadow, L);
           else wf_shadow_rec<FEAT, KOPS, LDSC>(S, cam, pm, W, wm, sl, s, stack, stride, C, n_shadow, L);
           DIAG_SPAN_END(7);
         }
@@ -2126,19 +2154,23 @@ struct RtcVariant {
   bool kops;  // the program is read from the kernel arguments (DScene.kops), not from memory (DScene.ops)
   bool area;  // area lights (DScene.has_area)
   bool uv;    // UV patterns (DScene.has_uv)
+  bool spot;  // light cones (DScene.has_spot); always with the `area` code path, which shades every light of such a scene
 };
 constexpr RtcVariant RTC_VARIANTS[] = {
-    {0, true, false, false},   // 0
-    {1, true, false, false},   // 1
-    {1, false, false, false},  // 2: also serves gate-free programs too long for the kernel arguments
-    {2, false, false, false},  // 3
-    {3, false, false, false},  // 4
-    {2, true, false, false},   // 5: grouped scenes on the fast path (scalar op fetches, LDS-resident tables, three waves per SIMD)
-    {3, false, true, false},   // 6: serves every scene with an area light that 7 does not
-    {1, true, true, false},    // 7: area-light scenes variants 0 and 1 would serve
-    {3, false, false, true},   // 8: the one-kernel path of every scene with a UV pattern (the wavefront path keeps its traversal
-                               //    variant and runs wf_shade's UV build)
-    {3, false, true, true},    // 9: the same with an area light
+    {0, true, false, false, false},  // 0
+    {1, true, false, false, false},  // 1
+    {1, false, false, false, false}, // 2: also serves gate-free programs too long for the kernel arguments
+    {2, false, false, false, false}, // 3
+    {3, false, false, false, false}, // 4
+    {2, true, false, false, false},  // 5: grouped scenes on the fast path (scalar op fetches, LDS-resident tables, three waves per SIMD)
+    {3, false, true, false, false},  // 6: serves every scene with an area light that 7 does not
+    {1, true, true, false, false},   // 7: area-light scenes variants 0 and 1 would serve
+    {3, false, false, true, false},  // 8: the one-kernel path of every scene with a UV pattern (the wavefront path keeps its traversal
+                                     //    variant and runs wf_shade's UV build)
+    {3, false, true, true, false},   // 9: the same with an area light
+    {3, false, true, false, true},   // 10: every scene with a light cone, area light or not (the most general feature level only: no
+                                     //     kernel-argument, LDS-resident or LEAN build for spot scenes)
+    {3, false, true, true, true},    // 11: the one-kernel path of a UV scene with a light cone
 };
 constexpr int RTC_N_VARIANTS = (int)(sizeof(RTC_VARIANTS) / sizeof(RTC_VARIANTS[0]));
 // What a row implies:
@@ -2148,8 +2180,9 @@ constexpr bool rtc_v_trace_3wave(RtcVariant r) { return r.feat == 1 && !r.area &
 constexpr bool rtc_v_trace_lean(RtcVariant r) { return r.feat <= 1 && !r.area && !r.uv; }   // one-kernel LEAN build
 
 // The variant that renders a scene on a device path: from the scene's feature level (0..3: DScene.has_csg / has_groups), whether its
-// program fits the kernel arguments (DScene.n_kops > 0), and DScene.has_area / has_uv.
-constexpr int rtc_pick_variant(int feat, bool kops, bool area, bool uv, bool wavefront) {
+// program fits the kernel arguments (DScene.n_kops > 0), and DScene.has_area / has_uv / has_spot.
+constexpr int rtc_pick_variant(int feat, bool kops, bool area, bool uv, bool spot, bool wavefront) {
+  if (spot) return (uv && !wavefront) ? 11 : 10;  // (wider light records: no other variant can read them)
   if (uv && !wavefront) return area ? 9 : 8;  // (the wavefront path of a UV scene: only wf_shade differs)
   // scenes with an area light: the AREA builds of the kernel-argument variants 0 / 1, or of the most general one (4) for the rest
   if (area) return (feat <= 1 && kops) ? 7 : 6;

@@ -30,15 +30,15 @@ void launch_trace(const RtcFrame& F, bool big_scene, unsigned grid, int fuel, do
     if (!F.count && F.S.all_plain && F.S.no_glass_mirror)  // the lean build (see rtc_trace_kernel)
       return launch_trace_kernel(rtc_trace_kernel<false, R.feat, R.kops, 0, true>, F, grid, fuel, rgb);
   }
-  if (F.count) launch_trace_kernel(rtc_trace_kernel<true, R.feat, R.kops, 0, false, R.area, R.uv>, F, grid, fuel, rgb);
-  else launch_trace_kernel(rtc_trace_kernel<false, R.feat, R.kops, 0, false, R.area, R.uv>, F, grid, fuel, rgb);
+  if (F.count) launch_trace_kernel(rtc_trace_kernel<true, R.feat, R.kops, 0, false, R.area, R.uv, R.spot>, F, grid, fuel, rgb);
+  else launch_trace_kernel(rtc_trace_kernel<false, R.feat, R.kops, 0, false, R.area, R.uv, R.spot>, F, grid, fuel, rgb);
 }
 
 template <int V>
 void launch_wf_ts(const RtcFrame& F, const RtcLevel& L) {
   constexpr RtcVariant R = RTC_VARIANTS[V];
-  if (F.count) launch_wf_ts_kernel(wf_ts<true, R.feat, R.kops, false, R.area>, RTC_BLOCK, rtc_stack_bytes(F.S), F, L);
-  else launch_wf_ts_kernel(wf_ts<false, R.feat, R.kops, false, R.area>, RTC_BLOCK, rtc_stack_bytes(F.S), F, L);
+  if (F.count) launch_wf_ts_kernel(wf_ts<true, R.feat, R.kops, false, R.area, R.spot>, RTC_BLOCK, rtc_stack_bytes(F.S), F, L);
+  else launch_wf_ts_kernel(wf_ts<false, R.feat, R.kops, false, R.area, R.spot>, RTC_BLOCK, rtc_stack_bytes(F.S), F, L);
 }
 
 #ifndef RTC_EMU
@@ -78,7 +78,7 @@ template <int V>
 int wf_ts_blocks_per_cu(unsigned lds_bytes) {
   constexpr RtcVariant R = RTC_VARIANTS[V];
   int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, wf_ts<false, R.feat, R.kops, false, R.area>, RTC_BLOCK, lds_bytes) != hipSuccess || nb <= 0) nb = 8;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, wf_ts<false, R.feat, R.kops, false, R.area, R.spot>, RTC_BLOCK, lds_bytes) != hipSuccess || nb <= 0) nb = 8;
   return nb;
 }
 #endif

@@ -10,7 +10,7 @@
 
 #ifdef RTC_EMU
 #include "rtc_feat.hip"  // the CPU emulator (tests/cpu_emu) compiles everything as one translation unit
-constexpr int RTC_VARIANTS_BUILT = 6;  // ... with variants 0..5 only: it has no entry point that creates an area-light or UV scene
+constexpr int RTC_VARIANTS_BUILT = 6;  // ... with variants 0..5 only: it has no entry point that creates an area-light, UV or spot scene
 #else
 constexpr int RTC_VARIANTS_BUILT = RTC_N_VARIANTS;
 #endif
@@ -24,7 +24,7 @@ static const RtcVariantOps& rtc_ops(int v) { return rtc_ops(v, std::make_integer
 // kernel variant that renders a scene on a device path (rtc_pick_variant)
 static int rtc_variant(const DScene& S, bool wavefront) {
   const int feat = S.has_csg ? 3 : (S.has_groups == 2 ? 2 : (S.has_groups ? 1 : 0));
-  return rtc_pick_variant(feat, S.n_kops > 0, S.has_area != 0, S.has_uv != 0, wavefront);
+  return rtc_pick_variant(feat, S.n_kops > 0, S.has_area != 0, S.has_uv != 0, S.has_spot != 0, wavefront);
 }
 
 #ifndef RTC_WF_SHADE_WAVES

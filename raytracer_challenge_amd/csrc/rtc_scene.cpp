@@ -25,6 +25,7 @@
 #include "device_scene.h"
 #include "filter_weights.h"
 #include "scene_build.hpp"
+#include "spot_factor.h"
 
 void rtc_launch_trace(const DScene& S, const DCamera& cam, const DPixelMap& pm, int fuel, double* rgb, double* hit_t, int* hit_prim, int* hit_k,
                       DStats* stats, bool count, hipStream_t stream, bool big_scene);
@@ -852,8 +853,9 @@ int rtc_device_count(void) {
 
 namespace {
 // rtc_scene_create (ex == false) and rtc_scene_create_ex (ex == true: the lights are `lx`, desc->lights must be empty); `uv`: the UV
-// pattern records and textures of rtc_scene_create_ext
-int scene_create(const rtc_scene_desc* desc, bool ex, const rtc_light_ex* lx, uint32_t n_lx, int device, rtc_scene** out, const rtb::UvInput& uv = rtb::UvInput{}) {
+// pattern records and textures of rtc_scene_create_ext; `cones`: the light cones of rtc_scene_create_ext2 (with ex == true only)
+int scene_create(const rtc_scene_desc* desc, bool ex, const rtc_light_ex* lx, uint32_t n_lx, int device, rtc_scene** out, const rtb::UvInput& uv = rtb::UvInput{},
+                 const rtb::ConeInput& cones = rtb::ConeInput{}) {
   if (!desc || !out) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
   *out = nullptr;
   int ndev = 0;
@@ -869,7 +871,7 @@ int scene_create(const rtc_scene_desc* desc, bool ex, const rtc_light_ex* lx, ui
   const char* dbe = std::getenv("RTC_DEVICE_BVH");
   const bool device_bvh = !(dbe && dbe[0] == '0');
   const size_t device_min = (dbe && dbe[0] == '1') ? 4096 : 100000;
-  int rc = ex ? rtb::build_arrays_ex(*desc, lx, n_lx, &H, &err, device_bvh ? rtc_bvh_build_device : nullptr, device_min, uv)
+  int rc = ex ? rtb::build_arrays_ex(*desc, lx, n_lx, &H, &err, device_bvh ? rtc_bvh_build_device : nullptr, device_min, uv, cones)
               : rtb::build_arrays(*desc, &H, &err, device_bvh ? rtc_bvh_build_device : nullptr, device_min, uv);
   if (rc != RTC_OK) return rtc_fail(rc, err);
   const bool timing = std::getenv("RTC_TIMING") != nullptr;
@@ -931,6 +933,7 @@ int scene_create(const rtc_scene_desc* desc, bool ex, const rtc_light_ex* lx, ui
     d.n_qitem = hv.n_qitem; d.n_qcell = hv.n_qcell; d.n_groups = hv.n_groups; d.n_qgrids = hv.n_qgrids;
     d.has_area = hv.has_area;
     d.has_uv = hv.has_uv;
+    d.has_spot = hv.has_spot;
   }
   s->n_prims_total = desc->n_prims;
   for (uint32_t i = 0; i < desc->n_prims; i++) {
@@ -992,6 +995,62 @@ int rtc_scene_create_ext(const rtc_scene_desc* desc, const rtc_scene_ext* ext, i
   if (!ext) return scene_create(desc, false, nullptr, 0, device, out);
   const rtb::UvInput uv{ext->uv_patterns, ext->n_uv_patterns, ext->textures, ext->n_textures};
   return scene_create(desc, ext->n_lights > 0, ext->lights, ext->n_lights, device, out, uv);
+}
+
+}  // extern "C"
+
+namespace {
+// What rtc_scene_create_ext2 / rtc_multi_create_ext2 hand on: the cones' own limits are checked first (no device needed); a scene whose
+// cones sit on desc->lights gets those lights as an rtc_light_ex list, the form build_arrays_ex takes.
+struct SpotArgs {
+  rtc_scene_desc desc;
+  std::vector<rtc_light_ex> lights;
+  const rtc_light_ex* lx = nullptr;
+  uint32_t n_lx = 0;
+  rtb::UvInput uv;
+  rtb::ConeInput cones;
+};
+int spot_args(const rtc_scene_desc* desc, const rtc_scene_ext* ext, const rtc_light_cone* cones, uint32_t n_cones, SpotArgs* a) {
+  if (!desc) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  a->desc = *desc;
+  a->cones = rtb::ConeInput{cones, n_cones};
+  if (ext) a->uv = rtb::UvInput{ext->uv_patterns, ext->n_uv_patterns, ext->textures, ext->n_textures};
+  const bool ext_lights = ext && ext->n_lights > 0;
+  std::string err;
+  if (const int rc = rtb::validate_cones(a->cones, ext_lights ? ext->n_lights : desc->n_lights, &err)) return rtc_fail(rc, err);
+  if (ext_lights) { a->lx = ext->lights; a->n_lx = ext->n_lights; return RTC_OK; }
+  if (desc->n_lights > 0 && !desc->lights) return rtc_fail(RTC_ERR_INVALID, "lights is NULL");
+  a->lights.resize(desc->n_lights);
+  for (uint32_t i = 0; i < desc->n_lights; i++) {
+    rtc_light_ex x{};
+    x.kind = RTC_LIGHT_POINT;
+    std::memcpy(x.intensity, desc->lights[i].intensity, sizeof(x.intensity));
+    std::memcpy(x.corner, desc->lights[i].origin, sizeof(x.corner));
+    a->lights[i] = x;
+  }
+  a->desc.n_lights = 0; a->desc.lights = nullptr;
+  a->lx = a->lights.data(); a->n_lx = desc->n_lights;
+  return RTC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rtc_scene_create_ext2(const rtc_scene_desc* desc, const rtc_scene_ext* ext, const rtc_light_cone* cones, uint32_t n_cones, int device, rtc_scene** out) {
+  if (n_cones == 0) return rtc_scene_create_ext(desc, ext, device, out);
+  if (out) *out = nullptr;
+  SpotArgs a;
+  if (const int rc = spot_args(desc, ext, cones, n_cones, &a)) return rc;
+  return scene_create(&a.desc, true, a.lx, a.n_lx, device, out, a.uv, a.cones);
+}
+
+int rtc_spot_factor(const rtc_light_cone* cone, const double light_pos[3], const double point[3], double* f) {
+  if (!cone || !light_pos || !point || !f) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  if (const char* why = rth::cone_invalid(cone->axis, cone->cos_inner, cone->cos_outer)) return rtc_fail(RTC_ERR_INVALID, std::string("cone: ") + why);
+  double a[3];
+  rtc_spot_axis(cone->axis, a);
+  *f = rtc_spot_factor_at(a, cone->cos_inner, cone->cos_outer, light_pos, point);
+  return RTC_OK;
 }
 
 void rtc_scene_destroy(rtc_scene* s) {
@@ -1666,13 +1725,13 @@ int render_multi(rtc_multi* m, const rtc_camera* cam, int32_t fuel, double* rgb_
 
 namespace {
 int multi_create(const rtc_scene_desc* desc, bool ex, const rtc_light_ex* lx, uint32_t n_lx, const int* devices, int n_devices, rtc_multi** out,
-                 const rtb::UvInput& uv = rtb::UvInput{}) {
+                 const rtb::UvInput& uv = rtb::UvInput{}, const rtb::ConeInput& cones = rtb::ConeInput{}) {
   if (!desc || !devices || !out || n_devices <= 0) return rtc_fail(RTC_ERR_INVALID, "NULL argument / no devices");
   *out = nullptr;
   std::unique_ptr<rtc_multi> m(new rtc_multi());
   for (int k = 0; k < n_devices; k++) {
     rtc_scene* s = nullptr;
-    int rc = scene_create(desc, ex, lx, n_lx, devices[k], &s, uv);
+    int rc = scene_create(desc, ex, lx, n_lx, devices[k], &s, uv, cones);
     if (rc != RTC_OK) { rtc_multi_destroy(m.release()); return rc; }
     m->scenes.push_back(s);
     m->tiles.push_back(nullptr);
@@ -1714,6 +1773,15 @@ int rtc_multi_create_ext(const rtc_scene_desc* desc, const rtc_scene_ext* ext, c
   if (!ext) return multi_create(desc, false, nullptr, 0, devices, n_devices, out);
   const rtb::UvInput uv{ext->uv_patterns, ext->n_uv_patterns, ext->textures, ext->n_textures};
   return multi_create(desc, ext->n_lights > 0, ext->lights, ext->n_lights, devices, n_devices, out, uv);
+}
+
+int rtc_multi_create_ext2(const rtc_scene_desc* desc, const rtc_scene_ext* ext, const rtc_light_cone* cones, uint32_t n_cones, const int* devices, int n_devices,
+                          rtc_multi** out) {
+  if (n_cones == 0) return rtc_multi_create_ext(desc, ext, devices, n_devices, out);
+  if (out) *out = nullptr;
+  SpotArgs a;
+  if (const int rc = spot_args(desc, ext, cones, n_cones, &a)) return rc;
+  return multi_create(&a.desc, true, a.lx, a.n_lx, devices, n_devices, out, a.uv, a.cones);
 }
 
 void rtc_multi_destroy(rtc_multi* m) {

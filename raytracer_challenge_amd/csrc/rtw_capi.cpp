@@ -21,6 +21,8 @@ using namespace rth;
 extern "C" int rtc_scene_create_ex(const rtc_scene_desc*, const rtc_light_ex*, uint32_t, int, rtc_scene**) __attribute__((weak));
 // (the same for texture-mapped patterns)
 extern "C" int rtc_scene_create_ext(const rtc_scene_desc*, const rtc_scene_ext*, int, rtc_scene**) __attribute__((weak));
+// (and for light cones)
+extern "C" int rtc_scene_create_ext2(const rtc_scene_desc*, const rtc_scene_ext*, const rtc_light_cone*, uint32_t, int, rtc_scene**) __attribute__((weak));
 
 struct rtw_pattern { PatRef p; };
 struct rtw_texture { TexRef t; };
@@ -31,6 +33,8 @@ struct rtw_world {
   int device = 0;
   std::unique_ptr<Flat> flat;  // rtw_world_flatten_desc: the arrays behind the descriptor it handed out
   std::vector<rtc_light_ex> lights_ex;  // every light in order (point and area) once an area light was added; empty otherwise
+  std::vector<rtc_light_cone> cones;    // rtw_world_set_light_cone: at most one per light, `light` = the light's place in the order
+  size_t n_lights() const { return lights_ex.empty() ? w.lights.size() : lights_ex.size(); }
   ~rtw_world() { if (scene) rtc_scene_destroy(scene); }
 };
 
@@ -59,7 +63,14 @@ static int ensure_scene(rtw_world* w) {
     rtc_scene_desc d = f.desc();
     if (timing) std::fprintf(stderr, "[rtc-timing] %-28s %.3f s\n", "flatten (host mirror -> desc)", since(t0));
     const auto t1 = std::chrono::steady_clock::now();
-    if (!f.uv_pats.empty()) {  // texture-mapped patterns: records and textures (and an area light's list) through the ext
+    if (!w->cones.empty()) {  // light cones: everything else the world has goes along in the ext
+      if (!rtc_scene_create_ext2) return fail("light cones need rtc_scene_create_ext2 (librtc_amd.so)");
+      rtc_scene_ext x{};
+      if (!w->lights_ex.empty()) { d.n_lights = 0; d.lights = nullptr; x.n_lights = (uint32_t)w->lights_ex.size(); x.lights = w->lights_ex.data(); }
+      x.n_uv_patterns = (uint32_t)f.uv_pats.size(); x.uv_patterns = f.uv_pats.data();
+      x.n_textures = (uint32_t)f.textures.size(); x.textures = f.textures.data();
+      rc = rtc_scene_create_ext2(&d, &x, w->cones.data(), (uint32_t)w->cones.size(), w->device, &w->scene);
+    } else if (!f.uv_pats.empty()) {  // texture-mapped patterns: records and textures (and an area light's list) through the ext
       if (!rtc_scene_create_ext) return fail("texture-mapped patterns need rtc_scene_create_ext (librtc_amd.so)");
       rtc_scene_ext x{};
       if (!w->lights_ex.empty()) { d.n_lights = 0; d.lights = nullptr; x.n_lights = (uint32_t)w->lights_ex.size(); x.lights = w->lights_ex.data(); }
@@ -255,6 +266,19 @@ int rtw_world_add_area_light(rtw_world* w, const double i[3], const double corne
   if (w->scene) { rtc_scene_destroy(w->scene); w->scene = nullptr; }
   return 0;
 }
+int rtw_world_set_light_cone(rtw_world* w, uint32_t light, const double axis[3], double cos_inner, double cos_outer) {
+  if (!w || !axis) return fail("set_light_cone: NULL argument");
+  if ((size_t)light >= w->n_lights()) return fail("set_light_cone: the world has no light " + std::to_string(light) + " yet");
+  for (const rtc_light_cone& c : w->cones) if (c.light == light) return fail("set_light_cone: light " + std::to_string(light) + " already has a cone");
+  if (const char* why = cone_invalid(axis, cos_inner, cos_outer)) return fail(std::string("set_light_cone: ") + why);
+  rtc_light_cone c{};
+  c.light = light;
+  std::memcpy(c.axis, axis, sizeof(c.axis));
+  c.cos_inner = cos_inner; c.cos_outer = cos_outer;
+  w->cones.push_back(c);
+  if (w->scene) { rtc_scene_destroy(w->scene); w->scene = nullptr; }
+  return 0;
+}
 int rtw_world_add_element(rtw_world* w, rtw_element* e) {
   if (!e || !e->e) return fail("add_element: NULL/consumed element");
   w->w.elements.push_back(std::move(e->e));
@@ -305,12 +329,16 @@ int rtw_make_camera(const rtw_camera* cam, rtc_camera* out) {
 static int refuse_area(const rtw_world* w) {
   return w->lights_ex.empty() ? 0 : fail("flatten: the world has area lights; its lights are an rtc_light_ex list for rtc_scene_create_ex, not desc->lights");
 }
+// ... a world with a light cone, which only rtc_scene_create_ext2 takes ...
+static int refuse_cones(const rtw_world* w) {
+  return w->cones.empty() ? 0 : fail("flatten: the world has light cones; they go to rtc_scene_create_ext2, not into a descriptor");
+}
 // ... and a world with a texture-mapped pattern, whose records and textures only rtc_scene_create_ext takes.
 static int refuse_uv(const Flat& f) {
   return f.uv_pats.empty() ? 0 : fail("flatten: the world has texture-mapped patterns; their records and textures go to rtc_scene_create_ext, not into a descriptor");
 }
 int rtw_world_flatten_counts(rtw_world* w, uint32_t counts[8]) {
-  if (refuse_area(w)) return 1;
+  if (refuse_area(w) || refuse_cones(w)) return 1;
   Flat f;
   Flattener fl(f);
   if (!fl.run(w->w)) return fail("flatten: " + f.error);
@@ -324,7 +352,7 @@ int rtw_world_flatten_counts(rtw_world* w, uint32_t counts[8]) {
 // Flatten only (no device): the descriptor a Rust shim would hand to rtc_scene_create; its arrays live in the world handle until
 // the next call / the world's release.  Works without a GPU (tests compare it with a foreign flattener's output).
 int rtw_world_flatten_desc(rtw_world* w, rtc_scene_desc* out) {
-  if (refuse_area(w)) return 1;
+  if (refuse_area(w) || refuse_cones(w)) return 1;
   w->flat.reset(new Flat());
   Flattener fl(*w->flat);
   if (!fl.run(w->w)) return fail("flatten: " + w->flat->error);

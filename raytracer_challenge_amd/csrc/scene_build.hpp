@@ -18,6 +18,7 @@
 #include "bvh_build.hpp"
 #include "device_scene.h"
 #include "host_scene.hpp"
+#include "spot_factor.h"
 
 namespace rtb {
 
@@ -701,6 +702,7 @@ struct HostArrays {
   int32_t n_lights = 0, all_cast_shadow = 1, bvh_depth = 0, bvh_stack = 8, csg_max_hits = 0, built_on_device = 0;
   int32_t has_area = 0;    // lights holds RTC_ALIGHT doubles per light (build_arrays_ex)
   int32_t has_uv = 0;      // some pattern node is an RTC_PAT_UV node
+  int32_t has_spot = 0;    // some light has a cone: lights holds RTC_SLIGHT doubles per light (build_arrays_ex)
   int32_t area_bounded = 1;  // every area light's sample positions lie below 1e30 in magnitude (the back-face scan's condition)
   double quirk_reach2 = 0.0, abvh_frame[4] = {0, 0, 0, 0};  // see DScene
 
@@ -812,6 +814,7 @@ struct HostArrays {
     }
     d.has_area = has_area;
     d.has_uv = has_uv;
+    d.has_spot = has_spot;
     d.has_recs = 0;
     for (size_t i = 0; i < ops.size(); i++) {
       const DOp& o = ops[i];
@@ -962,8 +965,8 @@ inline int build_arrays(const rtc_scene_desc& D, HostArrays* H, std::string* err
     // the 128-byte intersection records, one per primitive -- only if some op of the program reads them (DScene.has_recs): a mesh
     // and a few planes in the kernel arguments do not, and 10^6 triangles would carry 128 MB of them to the device for nothing
     // (scenes with a UV pattern always get them: the one-kernel path renders them with a build that reads the program from memory,
-    // rtc_feat.hip variants 8 and 9, whatever the program's own variant)
-    if (dv.has_recs || H->has_uv) {
+    // rtc_feat.hip variants 8 and 9, whatever the program's own variant; scenes with a light cone likewise, on both paths: variants 10, 11)
+    if (dv.has_recs || H->has_uv || H->has_spot) {
       // ... and only up to the last primitive an op can name: the program's own OP_PRIMs (CSG sub-programs included) and the analytic
       // BVH's primitives.  Mesh triangles are reached through their BVH's packed triangle array, never through a record; an OBJ
       // group at the end of the world -- where the bins put it -- leaves the array a few entries long.
@@ -995,8 +998,27 @@ inline int build_arrays(const rtc_scene_desc& D, HostArrays* H, std::string* err
 // with the POINT lights of the list alone, so light grids (sized by their count) exist for them only: grid g belongs to the g-th point
 // light, which its record names; area-light samples move with the shading point and walk the BVH.  `lights` then holds the
 // RTC_ALIGHT-double records the area kernels read, every light in list order (device_scene.h).
+// With cones (include/rtc.h rtc_light_cone) every light gets the wider RTC_SLIGHT-double record of the SPOT kernels, area light or not;
+// without an area light every point light keeps its grid, as above.
+struct ConeInput {
+  const rtc_light_cone* cones = nullptr;
+  uint32_t n = 0;
+};
+// The cones' own limits; needs no descriptor beyond the light count.
+inline int validate_cones(const ConeInput& K, uint32_t n_lights, std::string* err) {
+  if (K.n > 0 && !K.cones) { *err = "cones is NULL"; return RTC_ERR_INVALID; }
+  std::vector<char> seen(n_lights, 0);
+  for (uint32_t i = 0; i < K.n; i++) {
+    const rtc_light_cone& c = K.cones[i];
+    if (c.light >= n_lights) { *err = "cone " + std::to_string(i) + ": light index out of range"; return RTC_ERR_INVALID; }
+    if (seen[c.light]) { *err = "cone " + std::to_string(i) + ": light " + std::to_string(c.light) + " already has a cone"; return RTC_ERR_INVALID; }
+    seen[c.light] = 1;
+    if (const char* why = rth::cone_invalid(c.axis, c.cos_inner, c.cos_outer)) { *err = "cone " + std::to_string(i) + ": " + why; return RTC_ERR_INVALID; }
+  }
+  return RTC_OK;
+}
 inline int build_arrays_ex(const rtc_scene_desc& D, const rtc_light_ex* L, uint32_t n, HostArrays* H, std::string* err, bvh::DeviceBuildFn device_build = nullptr,
-                           size_t device_build_min = 4096, const UvInput& uv = UvInput{}) {
+                           size_t device_build_min = 4096, const UvInput& uv = UvInput{}, const ConeInput& cones = ConeInput{}) {
   if (D.n_lights != 0) { *err = "rtc_scene_create_ex: desc->n_lights must be 0 (the light list replaces desc->lights)"; return RTC_ERR_INVALID; }
   if (n > 0 && !L) { *err = "rtc_scene_create_ex: lights is NULL"; return RTC_ERR_INVALID; }
   bool area = false;
@@ -1012,6 +1034,9 @@ inline int build_arrays_ex(const rtc_scene_desc& D, const rtc_light_ex* L, uint3
       return RTC_ERR_UNSUPPORTED;
     }
   if (n > 64) { *err = "more than 64 lights (an area light is one)"; return RTC_ERR_UNSUPPORTED; }
+  if (const int rc = validate_cones(cones, n, err)) return rc;
+  const bool spot = cones.n > 0;
+  H->has_spot = spot ? 1 : 0;  // (before build_arrays: it decides whether the intersection records are built)
   std::vector<rtc_light> pts;  // all lights (no area light) or the point lights alone, in list order
   pts.reserve(n);
   for (uint32_t i = 0; i < n; i++) {
@@ -1025,14 +1050,22 @@ inline int build_arrays_ex(const rtc_scene_desc& D, const rtc_light_ex* L, uint3
   D2.n_lights = (uint32_t)pts.size();
   D2.lights = pts.empty() ? nullptr : pts.data();
   const int rc = build_arrays(D2, H, err, device_build, device_build_min, uv);
-  if (rc != RTC_OK || !area) return rc;
-  H->has_area = 1;
+  if (rc != RTC_OK || !(area || spot)) return rc;
+  H->has_area = area ? 1 : 0;
   H->n_lights = (int32_t)n;
   uint32_t grid = 0;  // index among the point lights = the light grid of a point light
-  H->lights.assign((size_t)n * RTC_ALIGHT, 0.0);
+  const size_t stride = spot ? RTC_SLIGHT : RTC_ALIGHT;
+  H->lights.assign((size_t)n * stride, 0.0);
+  for (uint32_t i = 0; i < cones.n; i++) {
+    double* q = &H->lights[(size_t)cones.cones[i].light * stride];
+    rtc_spot_axis(cones.cones[i].axis, q + 16);
+    q[19] = cones.cones[i].cos_inner;
+    q[20] = cones.cones[i].cos_outer;
+    q[21] = 1.0;
+  }
   for (uint32_t i = 0; i < n; i++) {
     const rtc_light_ex& l = L[i];
-    double* q = &H->lights[(size_t)i * RTC_ALIGHT];
+    double* q = &H->lights[(size_t)i * stride];
     const bool a = l.kind == RTC_LIGHT_AREA;
     const double N = a ? (double)l.usteps * (double)l.vsteps : 1.0;
     for (int c = 0; c < 3; c++) {

@@ -289,11 +289,67 @@ class PointLight:  # src/light.rs:5-8
 
 
 @dataclass(frozen=True)
+class Cone:
+    """A spot light's cone (include/rtc.h rtc_light_cone; not in the reference): the light points along ``direction`` (any length), is
+    full within ``inner_angle`` of it and dark beyond ``outer_angle`` (half-angles in radians, 0 <= inner <= outer <= pi), with a smooth
+    step between.  The library takes the cosines, :attr:`cos_inner` and :attr:`cos_outer` (``math.cos``)."""
+    direction: Vec4
+    inner_angle: float
+    outer_angle: float
+
+    def __post_init__(self):
+        try:
+            d = tuple(float(x) for x in self.direction[:3])
+            ok = len(d) == 3 and all(math.isfinite(x) for x in d)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError("a cone's direction must be three finite numbers")
+        if d == (0.0, 0.0, 0.0):
+            raise ValueError("a cone's direction must not be zero")
+        try:
+            ok = math.isfinite(self.inner_angle) and math.isfinite(self.outer_angle)
+        except TypeError:
+            ok = False
+        if not ok:
+            raise ValueError("a cone's angles must be finite")
+        if not (0.0 <= self.inner_angle <= self.outer_angle <= math.pi):
+            raise ValueError("a cone's angles must satisfy 0 <= inner_angle <= outer_angle <= pi")
+
+    @property
+    def cos_inner(self) -> float:
+        return math.cos(self.inner_angle)
+
+    @property
+    def cos_outer(self) -> float:
+        return math.cos(self.outer_angle)
+
+
+@dataclass(frozen=True)
+class SpotLight:
+    """A point light with a :class:`Cone` (not in the reference): a PointLight at ``origin`` whose intensity towards a point is scaled
+    by the cone's factor there.  The exact rules are in include/rtc.h (rtc_light_cone).  Rendered by the HIP library only."""
+    intensity: Color
+    origin: Vec4
+    direction: Vec4
+    inner_angle: float
+    outer_angle: float
+
+    def __post_init__(self):
+        Cone(self.direction, self.inner_angle, self.outer_angle)  # validates
+
+    @property
+    def cone(self) -> Cone:
+        return Cone(self.direction, self.inner_angle, self.outer_angle)
+
+
+@dataclass(frozen=True)
 class AreaLight:
     """Rectangular area light (the book's first bonus chapter; not in the reference): ``usteps x vsteps`` samples over
     ``corner + [0, uvec] x [0, vvec]``, at the cell centres or, with ``jitter``, at hashed offsets inside the cells.  Each sample
     shades like a PointLight of ``intensity / (usteps * vsteps)``; reflections and refractions count the light once.  The exact
-    rules are in include/rtc.h (rtc_light_ex).  Rendered by the HIP library only."""
+    rules are in include/rtc.h (rtc_light_ex).  With ``cone`` every sample is scaled by the cone's factor (rtc_light_cone).  Rendered by the
+    HIP library only."""
     intensity: Color
     corner: Vec4
     uvec: Vec4
@@ -301,6 +357,11 @@ class AreaLight:
     vvec: Vec4
     vsteps: int
     jitter: bool = False
+    cone: Optional[Cone] = None
+
+    def __post_init__(self):
+        if self.cone is not None and not isinstance(self.cone, Cone):
+            raise ValueError("AreaLight.cone must be a Cone or None")
 
     @property
     def samples(self) -> int:
@@ -308,7 +369,7 @@ class AreaLight:
 
 
 @dataclass
-class World:  # src/world.rs:12-15; lights: PointLight and AreaLight in any order (the order is kept)
+class World:  # src/world.rs:12-15; lights: PointLight, SpotLight and AreaLight in any order (the order is kept)
     lights: List[PointLight] = field(default_factory=list)
     elements: List[Element] = field(default_factory=list)
 

@@ -11,7 +11,7 @@ import math
 import os
 from typing import Tuple
 
-from .scene import (Camera, Color, Element, GroupKind, Material, Matrix, Noise, Pattern, PointLight, ShapeArgs, Vector, World)
+from .scene import (Camera, Color, Element, GroupKind, Material, Matrix, Noise, Pattern, PointLight, ShapeArgs, SpotLight, Vector, World)
 
 PI = math.pi
 ASSETS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets")
@@ -421,3 +421,24 @@ def texture_showcase(hsize=None, vsize=None) -> Tuple[Camera, World]:
         pattern=plain(Color.black()), diffuse=0.1, shininess=300.0, reflective=0.9, transparency=0.9, refractive_index=1.5)))
     world = World([PointLight(Color.white(), Vector.point(-8.0, 10.0, -10.0))], [floor, globe, can, box, earth, glass])
     return _cam(1920, 1080, PI / 3.0, (0.0, 2.5, -7.5), (0.0, 1.0, 1.0), (0.0, 1.0, 0.0), hsize, vsize), world
+
+
+def spot_showcase(hsize=None, vsize=None) -> Tuple[Camera, World]:
+    """Spot lights: a checkered floor with a matte, a mirror and a glass sphere under a narrow white spot with a smooth edge, a wide
+    warm one from the side, and a jittered 4x4 area light with a cone (a soft penumbra inside a soft-edged pool of light)."""
+    from .scene import AreaLight, Cone
+    c = Color.new
+    floor = Element.plane(ShapeArgs(material=Material(
+        pattern=Pattern.checkers(Matrix.id(), Pattern.plain(c(0.85, 0.85, 0.85)), Pattern.plain(c(0.25, 0.25, 0.3))), specular=0.0, reflective=0.1)))
+    matte = Element.sphere(ShapeArgs(transform=Matrix.translation(-2.2, 1.0, 0.5), material=Material(pattern=Pattern.plain(c(0.9, 0.3, 0.2)), diffuse=0.8, specular=0.3)))
+    mirror = Element.sphere(ShapeArgs(transform=Matrix.translation(0.0, 1.0, 2.0), material=Material(
+        pattern=Pattern.plain(c(0.1, 0.1, 0.1)), diffuse=0.3, specular=0.8, shininess=200.0, reflective=0.8)))
+    glass = Element.sphere(ShapeArgs(transform=Matrix.translation(2.0, 0.7, -0.8) * Matrix.scaling(0.7, 0.7, 0.7), material=Material(
+        pattern=Pattern.plain(Color.black()), diffuse=0.1, shininess=300.0, reflective=0.9, transparency=0.9, refractive_index=1.5)))
+    lights = [
+        SpotLight(c(0.9, 0.9, 0.9), Vector.point(0.0, 8.0, 0.0), Vector.vector(0.0, -1.0, 0.1), 0.25, 0.4),
+        SpotLight(c(0.5, 0.4, 0.25), Vector.point(-9.0, 5.0, -6.0), Vector.vector(9.0, -5.0, 6.0), 0.3, 0.7),
+        AreaLight(c(0.5, 0.55, 0.7), Vector.point(4.0, 6.0, -5.0), Vector.vector(1.5, 0.0, 0.0), 4, Vector.vector(0.0, 1.5, 0.0), 4, jitter=True,
+                  cone=Cone(Vector.vector(-4.0, -6.0, 5.0), 0.2, 0.45)),
+    ]
+    return _cam(1920, 1080, PI / 3.0, (0.0, 3.0, -8.5), (0.0, 1.0, 0.5), (0.0, 1.0, 0.0), hsize, vsize), World(lights, [floor, matte, mirror, glass])

@@ -124,6 +124,18 @@ pub struct RtcSceneExt {
     pub textures: *const RtcTexture,
 }
 
+// include/rtc.h rtc_light_cone: a spot light's cone on one light of the list (not in the reference), for rtc_scene_create_ext2 /
+// rtc_multi_create_ext2
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtcLightCone {
+    pub light: u32, // index into the scene's light list
+    pub _pad: u32,
+    pub axis: [f64; 3], // where the light points; any length
+    pub cos_inner: f64,
+    pub cos_outer: f64, // <= cos_inner
+}
+
 // include/rtc.h rtc_sampling: n x n samples per pixel and an optional thin lens (not in the reference) for rtc_render_sampled*
 #[allow(dead_code)]
 pub const RTC_SAMPLE_JITTER: u32 = 1;
@@ -265,6 +277,14 @@ extern "C" {
     fn rtc_scene_create_ext(desc: *const RtcSceneDesc, ext: *const RtcSceneExt, device: c_int, out: *mut *mut RtcScene) -> c_int;
     #[allow(dead_code)]
     fn rtc_multi_create_ext(desc: *const RtcSceneDesc, ext: *const RtcSceneExt, devices: *const c_int, n_devices: c_int, out: *mut *mut RtcMulti) -> c_int;
+    #[allow(dead_code)]
+    fn rtc_scene_create_ext2(desc: *const RtcSceneDesc, ext: *const RtcSceneExt, cones: *const RtcLightCone, n_cones: u32, device: c_int,
+                             out: *mut *mut RtcScene) -> c_int;
+    #[allow(dead_code)]
+    fn rtc_multi_create_ext2(desc: *const RtcSceneDesc, ext: *const RtcSceneExt, cones: *const RtcLightCone, n_cones: u32, devices: *const c_int,
+                             n_devices: c_int, out: *mut *mut RtcMulti) -> c_int;
+    #[allow(dead_code)] // host-only: the cone factor of one light position and shading point
+    fn rtc_spot_factor(cone: *const RtcLightCone, light_pos: *const f64, point: *const f64, f: *mut f64) -> c_int;
     fn rtc_multi_destroy(multi: *mut RtcMulti);
     fn rtc_render_multi(multi: *mut RtcMulti, camera: *const RtcCamera, fuel: i32, rgb: *mut f64, stats: *mut RtcStats) -> c_int;
     #[allow(dead_code)] // Color::clamp'ed pixels (what Image::ppm writes): 3 bytes per pixel cross xGMI instead of 24

@@ -1,0 +1,374 @@
+"""Spot lights (include/rtc.h rtc_light_cone), the parts that need no GPU: a Python-float restatement of the cone factor against
+rtc_spot_factor bit for bit, the limits (through C where the library checks them before it needs a device, and through the Python
+classes), the refusals of the oracle and of the emulator, the exports, the Rust mirror, and the fixture of the GPU file's partition
+test (test_spot_lights_gpu.py), checked from geometry alone."""
+import ctypes as C
+import math
+import os
+import struct
+
+import numpy as np
+import pytest
+
+import foreign_flattener as ff
+from raytracer_challenge_amd.backend import RtwError
+from raytracer_challenge_amd.scene import (EPSILON, AreaLight, Camera, Color, Cone, Element, Material, Matrix, Pattern, PointLight, Sampling, ShapeArgs, SpotLight,
+                                           Vector, World)
+from test_shim_layout import c_struct, rust_struct
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "raytracer_challenge_amd", "csrc", "librtc_amd.so")
+vp = C.c_void_p
+
+
+class RtcLightCone(C.Structure):  # include/rtc.h rtc_light_cone
+    _fields_ = [("light", C.c_uint32), ("_pad", C.c_uint32), ("axis", C.c_double * 3), ("cos_inner", C.c_double), ("cos_outer", C.c_double)]
+
+
+def cone_c(light, axis, cos_inner, cos_outer):
+    return RtcLightCone(int(light), 0, (C.c_double * 3)(*axis[:3]), float(cos_inner), float(cos_outer))
+
+
+def bind_spot(lib):
+    lib.rtc_last_error.restype = C.c_char_p
+    lib.rtc_spot_factor.restype = C.c_int
+    lib.rtc_spot_factor.argtypes = [C.POINTER(RtcLightCone), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.rtc_scene_create_ext2.restype = C.c_int
+    lib.rtc_scene_create_ext2.argtypes = [C.POINTER(ff.RtcSceneDesc), vp, C.POINTER(RtcLightCone), C.c_uint32, C.c_int, C.POINTER(vp)]
+    lib.rtc_multi_create_ext2.restype = C.c_int
+    lib.rtc_multi_create_ext2.argtypes = [C.POINTER(ff.RtcSceneDesc), vp, C.POINTER(RtcLightCone), C.c_uint32, C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
+    return lib
+
+
+def lib_spot_factor(lib, axis, cos_inner, cos_outer, light_pos, point):
+    """rtc_spot_factor; returns (status, f)."""
+    cone, f = cone_c(0, axis, cos_inner, cos_outer), C.c_double(-7.0)
+    rc = lib.rtc_spot_factor(C.byref(cone), (C.c_double * 3)(*light_pos[:3]), (C.c_double * 3)(*point[:3]), C.byref(f))
+    return rc, f.value
+
+
+# ---- the Python-float restatement of include/rtc.h rtc_light_cone (shared with test_spot_lights_gpu.py) ---------------------------
+def unit_axis(axis):
+    """m = sqrt((ax*ax + ay*ay) + az*az), a = axis / m: Vector::normalize's order."""
+    ax, ay, az = (float(x) for x in axis[:3])
+    m = math.sqrt((ax * ax + ay * ay) + az * az)
+    return (ax / m, ay / m, az / m)
+
+
+def shadow_dir(light_pos, point):
+    """shadow_ray()'s direction and distance: v = p_k - o, dist = sqrt(vx*vx + vy*vy + vz*vz), d = v / dist."""
+    vx, vy, vz = (float(light_pos[k]) - float(point[k]) for k in range(3))
+    dist = math.sqrt(vx * vx + vy * vy + vz * vz)
+    if dist == 0.0:            # IEEE: 0 / 0 is NaN (Python raises instead)
+        return (math.nan, math.nan, math.nan), dist
+    return (vx / dist, vy / dist, vz / dist), dist
+
+
+def spot_cos(d, a):
+    return ((-d[0]) * a[0] + (-d[1]) * a[1]) + (-d[2]) * a[2]
+
+
+def spot_f(c, cos_inner, cos_outer):
+    if c >= cos_inner:
+        return 1.0
+    if c <= cos_outer:
+        return 0.0
+    with np.errstate(all="ignore"):   # IEEE division: NaN / 0 at a hard edge is NaN (Python raises instead)
+        t = float(np.float64(c - cos_outer) / np.float64(cos_inner - cos_outer))
+    return (t * t) * (3.0 - 2.0 * t)
+
+
+def spot_factor(axis, cos_inner, cos_outer, light_pos, point):
+    d, _ = shadow_dir(light_pos, point)
+    return spot_f(spot_cos(d, unit_axis(axis)), cos_inner, cos_outer)
+
+
+def bits(x):
+    return struct.unpack("<Q", struct.pack("<d", float(x)))[0]
+
+
+# ---- the factor -------------------------------------------------------------------------------------------------------------------
+def test_restated_factor_is_rtc_spot_factor_bit_for_bit():
+    lib = bind_spot(C.CDLL(LIB))
+    rng = np.random.default_rng(2025)
+    seen = {"inner": 0, "band": 0, "outside": 0}
+    for _ in range(400):
+        axis = rng.uniform(-3.0, 3.0, 3) * rng.choice([1.0, 1e-3, 250.0])          # unnormalised, of any scale
+        ci = float(rng.uniform(-0.2, 1.0))
+        co = float(rng.uniform(-1.0, ci))
+        light, point = rng.uniform(-6.0, 6.0, 3), rng.uniform(-6.0, 6.0, 3)
+        if rng.random() < 0.5:     # aim near the cone's edge, so that all three branches are met
+            a = np.array(unit_axis(axis))
+            side = np.cross(a, rng.uniform(-1, 1, 3))
+            side /= np.linalg.norm(side)
+            ang = math.acos(rng.uniform(co, ci)) * rng.uniform(0.9, 1.1)
+            point = light + rng.uniform(0.5, 9.0) * (math.cos(ang) * a + math.sin(ang) * side)
+        want = spot_factor(axis, ci, co, light, point)
+        rc, got = lib_spot_factor(lib, axis, ci, co, light, point)
+        assert rc == 0 and bits(got) == bits(want), (axis, ci, co, light, point, got, want)
+        seen["inner" if want == 1.0 else "outside" if want == 0.0 else "band"] += 1
+    assert min(seen.values()) >= 40, seen
+
+
+def test_factor_on_the_axis_at_the_edges_hard_edge_and_nan():
+    lib = bind_spot(C.CDLL(LIB))
+    light = (0.0, 5.0, 0.0)
+
+    def f(axis, ci, co, point):
+        rc, got = lib_spot_factor(lib, axis, ci, co, light, point)
+        assert rc == 0
+        want = spot_factor(axis, ci, co, light, point)
+        assert bits(got) == bits(want) or (math.isnan(got) and math.isnan(want)), (axis, ci, co, point, got, want)
+        return got
+    # on the axis: c == 1 exactly, inside every inner cone -- cos_inner == 1 included
+    assert f((0.0, -1.0, 0.0), 0.9, 0.5, (0.0, 0.0, 0.0)) == 1.0
+    assert f((0.0, -1.0, 0.0), 1.0, 1.0, (0.0, -3.0, 0.0)) == 1.0
+    assert f((0.0, -7.5, 0.0), 1.0, 1.0, (0.0, 1.0, 0.0)) == 1.0                    # an unnormalised axis is normalised first
+    assert f((0.0, -1.0, 0.0), 1.0, 1.0, (1e-3, 0.0, 0.0)) == 0.0                   # cos_inner == cos_outer == 1: dark beside the axis
+    assert f((0.0, 1.0, 0.0), 0.9, 0.5, (0.0, 0.0, 0.0)) == 0.0                     # behind the light: c == -1
+    assert f((0.0, 1.0, 0.0), -1.0, -1.0, (0.0, 0.0, 0.0)) == 1.0                   # ... and inside an open cone
+    # exactly at c == cos_inner and c == cos_outer: a 3-4-5 triangle below the light gives c = 4/5 = 0.8 in one rounding each
+    p = (3.0, 1.0, 0.0)
+    d, dist = shadow_dir(light, p)
+    assert dist == 5.0 and spot_cos(d, (0.0, -1.0, 0.0)) == 0.8
+    assert f((0.0, -1.0, 0.0), 0.8, 0.5, p) == 1.0                                   # c == cos_inner: full
+    assert f((0.0, -1.0, 0.0), 0.9, 0.8, p) == 0.0                                   # c == cos_outer: dark
+    assert f((0.0, -1.0, 0.0), 0.8, 0.8, p) == 1.0                                   # a hard edge: the first test wins, nothing is divided
+    assert f((0.0, -1.0, 0.0), 0.8 + 2.0 ** -53, 0.8 + 2.0 ** -53, p) == 0.0
+    # the band: smoothstep, half-way is a half
+    assert abs(f((0.0, -1.0, 0.0), 0.9, 0.7, p) - 0.5) < 1e-12
+    band = f((0.0, -1.0, 0.0), 0.95, 0.75, p)
+    assert 0.0 < band < 1.0
+    # a NaN point fails both tests and comes back NaN; so does a point at the light (0 / 0)
+    assert math.isnan(f((0.0, -1.0, 0.0), 0.9, 0.5, (math.nan, 0.0, 0.0)))
+    assert math.isnan(f((0.0, -1.0, 0.0), 0.9, 0.5, light))
+    assert math.isnan(f((0.0, -1.0, 0.0), 0.8, 0.8, (0.0, math.nan, 0.0)))           # ... at a hard edge too
+
+
+def test_restated_direction_is_shadow_rays_order():
+    """d as include/rtc.h states it, against the obvious alternatives that round differently (a normalised sum of squares in another
+    association, a multiplication by the reciprocal): the restatement pins the order."""
+    rng = np.random.default_rng(5)
+    differs_recip = differs_assoc = 0
+    for _ in range(200):
+        l, o = rng.uniform(-9, 9, 3), rng.uniform(-9, 9, 3)
+        d, dist = shadow_dir(l, o)
+        v = [float(l[k]) - float(o[k]) for k in range(3)]
+        assert dist == math.sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2])          # left to right
+        assert d == (v[0] / dist, v[1] / dist, v[2] / dist)
+        differs_assoc += dist != math.sqrt(v[0] * v[0] + (v[1] * v[1] + v[2] * v[2]))
+        differs_recip += d != tuple(x * (1.0 / dist) for x in v)
+    assert differs_recip > 0 and differs_assoc > 0
+    # the over_point of a hit on the untransformed floor plane, as the GPU file restates it
+    o, dr, t = np.array([1.0, 3.0, -2.0]), np.array([0.6, -0.8, 0.0]), 3.75
+    over = (o + dr * t) + np.array([0.0, 1.0, 0.0]) * EPSILON
+    assert over[1] == (3.0 + -0.8 * 3.75) + EPSILON and over[0] == 1.0 + 0.6 * 3.75
+
+
+# ---- limits -----------------------------------------------------------------------------------------------------------------------
+def floor_world(lights):
+    return World(lights, [Element.plane(ShapeArgs())])
+
+
+def test_limits_through_c_need_no_device():
+    """The cones' own numbers are validated before the device is looked for: every limit answers RTC_ERR_INVALID (1) here, where
+    a valid cone gets as far as RTC_ERR_DEVICE (3) on a machine without one (or succeeds on one with)."""
+    lib = bind_spot(C.CDLL(LIB))
+    lib.rtc_scene_destroy.argtypes = [vp]
+    lib.rtc_multi_destroy.argtypes = [vp]
+    flat = ff.flatten(floor_world([PointLight(Color.white(), Vector.point(0, 5, 0)), PointLight(Color.white(), Vector.point(1, 5, 0))]))
+    desc = flat.desc()
+    devs = (C.c_int * 1)(0)
+
+    def create(cones, multi=False):
+        arr = (RtcLightCone * max(1, len(cones)))(*cones)
+        s = vp()
+        rc = (lib.rtc_multi_create_ext2(C.byref(desc), None, arr, len(cones), devs, 1, C.byref(s)) if multi else
+              lib.rtc_scene_create_ext2(C.byref(desc), None, arr, len(cones), 0, C.byref(s)))
+        if rc == 0:
+            (lib.rtc_multi_destroy if multi else lib.rtc_scene_destroy)(s)
+        return rc
+    down = (0.0, -1.0, 0.0)
+    bad = {
+        "light index out of range": [cone_c(2, down, 0.9, 0.5)],
+        "two cones on one light": [cone_c(1, down, 0.9, 0.5), cone_c(1, down, 0.8, 0.4)],
+        "zero axis": [cone_c(0, (0.0, 0.0, 0.0), 0.9, 0.5)],
+        "NaN axis": [cone_c(0, (0.0, math.nan, 1.0), 0.9, 0.5)],
+        "infinite axis": [cone_c(0, (math.inf, 0.0, 0.0), 0.9, 0.5)],
+        "NaN cosine": [cone_c(0, down, math.nan, 0.5)],
+        "infinite cosine": [cone_c(0, down, 0.9, -math.inf)],
+        "cos_inner above 1": [cone_c(0, down, 1.0 + 2.0 ** -52, 0.5)],
+        "cos_outer below -1": [cone_c(0, down, 0.9, -1.0 - 2.0 ** -52)],
+        "cos_outer above cos_inner": [cone_c(0, down, 0.5, 0.9)],
+    }
+    for multi in (False, True):
+        for why, cones in bad.items():
+            assert create(cones, multi) == 1, (why, multi)
+            assert lib.rtc_last_error(), why
+        for cones in ([cone_c(0, down, 0.9, 0.5)], [cone_c(1, (3.0, -4.0, 0.5), 1.0, -1.0), cone_c(0, down, 0.3, 0.3)]):
+            assert create(cones, multi) in (0, 3), multi
+    s = vp()
+    assert lib.rtc_scene_create_ext2(C.byref(desc), None, None, 1, 0, C.byref(s)) == 1       # n_cones > 0 with NULL cones
+    # rtc_spot_factor refuses what scene creation refuses, and NULL
+    assert lib_spot_factor(lib, (0.0, 0.0, 0.0), 0.9, 0.5, (0, 5, 0), (0, 0, 0))[0] == 1
+    assert lib_spot_factor(lib, down, 0.5, 0.9, (0, 5, 0), (0, 0, 0))[0] == 1
+    assert lib_spot_factor(lib, down, 1.5, 0.9, (0, 5, 0), (0, 0, 0))[0] == 1
+    assert lib.rtc_spot_factor(None, None, None, None) == 1
+
+
+def test_limits_through_the_python_classes_and_rtw():
+    P, V = Vector.point, Vector.vector
+    s = SpotLight(Color.white(), P(0, 5, 0), V(0, -2, 0), 0.3, 0.5)
+    assert s.cone == Cone(V(0, -2, 0), 0.3, 0.5) and s.cone.cos_inner == math.cos(0.3) and s.cone.cos_outer == math.cos(0.5)
+    assert Cone(V(0, -1, 0), math.pi, math.pi).cos_inner == -1.0 and Cone(V(0, -1, 0), 0.0, 0.0).cos_outer == 1.0
+    with pytest.raises(Exception):
+        s.inner_angle = 0.1                # frozen like PointLight
+    for args in ((V(0, 0, 0), 0.3, 0.5), (V(0, math.nan, 0), 0.3, 0.5), (V(math.inf, 0, 0), 0.3, 0.5), (V(0, -1, 0), math.nan, 0.5),
+                 (V(0, -1, 0), 0.3, math.inf), (V(0, -1, 0), 0.5, 0.3), (V(0, -1, 0), -0.1, 0.3), (V(0, -1, 0), 0.3, 3.2)):
+        with pytest.raises(ValueError):
+            Cone(*args)
+        with pytest.raises(ValueError):
+            SpotLight(Color.white(), P(0, 5, 0), *args)
+    a = AreaLight(Color.white(), P(0, 5, 0), V(1, 0, 0), 2, V(0, 0, 1), 3)
+    assert a.cone is None                  # existing constructions are unchanged
+    assert AreaLight(Color.white(), P(0, 5, 0), V(1, 0, 0), 2, V(0, 0, 1), 3, False) == a
+    c = AreaLight(Color.white(), P(0, 5, 0), V(1, 0, 0), 2, V(0, 0, 1), 3, cone=Cone(V(0, -1, 0), 0.2, 0.4))
+    assert c.cone.outer_angle == 0.4 and c.samples == 6
+    with pytest.raises(ValueError):
+        AreaLight(Color.white(), P(0, 5, 0), V(1, 0, 0), 2, V(0, 0, 1), 3, cone=(0, -1, 0))
+    w = World([s, a, PointLight(Color.white(), P(1, 1, 1)), c], [Element.sphere(ShapeArgs())])
+    assert w.lights == [s, a, w.lights[2], c]     # any mix, in order
+    # rtw_world_set_light_cone's own limits (no device: the world is only described)
+    import raytracer_challenge_amd as rt
+    hip = rt.hip_backend()
+    assert hip.has_light_cones
+    nw = hip.build_world(w)
+    lib = hip.lib
+    down = (C.c_double * 3)(0.0, -1.0, 0.0)
+    assert lib.rtw_world_set_light_cone(nw.handle, 4, down, 0.9, 0.5) != 0 and "no light 4" in hip._err()
+    assert lib.rtw_world_set_light_cone(nw.handle, 0, down, 0.9, 0.5) != 0 and "already has a cone" in hip._err()
+    assert lib.rtw_world_set_light_cone(nw.handle, 1, down, 0.5, 0.9) != 0 and "cos_outer" in hip._err()
+    assert lib.rtw_world_set_light_cone(nw.handle, 1, (C.c_double * 3)(0.0, 0.0, 0.0), 0.9, 0.5) != 0 and "zero" in hip._err()
+    assert lib.rtw_world_set_light_cone(nw.handle, 1, down, 0.9, 0.5) == 0
+    assert lib.rtw_world_set_light_cone(nw.handle, 2, down, 1.0, -1.0) == 0
+
+
+def test_flatten_helpers_refuse_worlds_with_cones():
+    import raytracer_challenge_amd as rt
+    hip = rt.hip_backend()
+    lib = hip.lib
+    lib.rtw_world_flatten_counts.restype = C.c_int
+    lib.rtw_world_flatten_counts.argtypes = [vp, C.POINTER(C.c_uint32)]
+    lib.rtw_world_flatten_desc.restype = C.c_int
+    lib.rtw_world_flatten_desc.argtypes = [vp, vp]
+    counts, desc = (C.c_uint32 * 8)(), C.create_string_buffer(256)
+    nw = hip.build_world(floor_world([PointLight(Color.white(), Vector.point(0, 5, 0))]))
+    assert lib.rtw_world_flatten_counts(nw.handle, counts) == 0 and counts[7] == 1
+    nw = hip.build_world(floor_world([SpotLight(Color.white(), Vector.point(0, 5, 0), Vector.vector(0, -1, 0), 0.3, 0.5)]))
+    assert lib.rtw_world_flatten_counts(nw.handle, counts) != 0 and "light cones" in hip._err()
+    assert lib.rtw_world_flatten_desc(nw.handle, desc) != 0 and "light cones" in hip._err()
+
+
+# ---- the libraries ----------------------------------------------------------------------------------------------------------------
+def test_exports_and_package_names():
+    lib = C.CDLL(LIB)
+    for name in ("rtc_scene_create_ext2", "rtc_multi_create_ext2", "rtc_spot_factor", "rtw_world_set_light_cone"):
+        assert hasattr(lib, name), name
+    import raytracer_challenge_amd as rt
+    assert rt.SpotLight is SpotLight and rt.Cone is Cone and rt.AreaLight is AreaLight
+    from raytracer_challenge_amd import scenes
+    cam, world = scenes.spot_showcase(32, 18)
+    assert (cam.hsize, cam.vsize) == (32, 18)
+    kinds = [type(l).__name__ for l in world.lights]
+    assert "SpotLight" in kinds and any(isinstance(l, AreaLight) and l.cone is not None for l in world.lights)
+
+
+def test_oracle_refuses_cones(orc):
+    assert not orc.has_light_cones
+    spot = SpotLight(Color.white(), Vector.point(0, 5, 0), Vector.vector(0, -1, 0), 0.3, 0.5)
+    with pytest.raises(RtwError, match="light cones need librtc_amd.so"):
+        orc.build_world(floor_world([spot]))
+    orc.build_world(floor_world([PointLight(Color.white(), Vector.point(0, 5, 0))]))       # point lights: as before
+
+
+def test_emulator_reports_cones_missing():
+    """tests/cpu_emu links the product's rtw_capi.cpp without rtc_scene_create_ext2 (the reference to it is weak): the library loads and
+    renders cone-less worlds; a world with a cone fails with a message."""
+    from emu_lib import emu
+    e = emu()
+    cam = Camera.new(8, 6, 1.0, Camera.transform(Vector.point(0, 1.5, -5), Vector.point(0, 1, 0), Vector.vector(0, 1, 0)))
+    rgb, _ = e.render(e.build_world(World.default()), cam, 1)
+    assert np.isfinite(rgb).all() and rgb.max() > 0.0
+    nw = e.build_world(floor_world([SpotLight(Color.white(), Vector.point(0, 5, 0), Vector.vector(0, -1, 0), 0.3, 0.5)]))
+    with pytest.raises(RtwError, match="rtc_scene_create_ext2"):
+        e.render(nw, cam, 1)
+
+
+def test_rust_shim_mirrors_rtc_light_cone():
+    h = open(os.path.join(ROOT, "include", "rtc.h")).read()
+    rs = open(os.path.join(ROOT, "shim", "gpu.rs")).read()
+    c, r = c_struct(h, "rtc_light_cone"), rust_struct(rs, "RtcLightCone")
+    assert c == r, (c, r)
+    assert [f[0] for f in c] == ["light", "_pad", "axis", "cos_inner", "cos_outer"]
+    assert C.sizeof(RtcLightCone) == 48 and RtcLightCone.axis.offset == 8 and RtcLightCone.cos_outer.offset == 40
+    assert "fn rtc_scene_create_ext2(" in rs and "fn rtc_multi_create_ext2(" in rs and "fn rtc_spot_factor(" in rs
+    # the structs the new call takes beside it keep their layout
+    assert c_struct(h, "rtc_scene_ext") == rust_struct(rs, "RtcSceneExt")
+
+
+# ---- the partition fixture of test_spot_lights_gpu.py -------------------------------------------------------------------------------
+PARTITION_LIGHT = (0.0, 5.0, 0.0)
+PARTITION_AXIS = (0.0, -1.0, 0.0)
+PARTITION_ANGLE = 0.53     # half-angle of the hard edge: a disc of radius 5 tan(0.53) = 2.9 on the floor
+PARTITION_SPHERE = (1.6, 1.0, 0.4)
+
+
+def partition_fixture(light):
+    """A matte floor, one unit sphere casting a shadow, the camera above, 32 x 24; `light` is the scene's one light."""
+    floor = Element.plane(ShapeArgs(material=Material(pattern=Pattern.plain(Color(0.9, 0.85, 0.8)), specular=0.0)))
+    ball = Element.sphere(ShapeArgs(transform=Matrix.translation(*PARTITION_SPHERE), material=Material(pattern=Pattern.plain(Color(0.3, 0.5, 0.9)), specular=0.0)))
+    cam = Camera.new(32, 24, 1.0, Camera.transform(Vector.point(0.0, 11.0, -3.0), Vector.point(0.0, 0.0, 0.0), Vector.vector(0.0, 0.0, 1.0)))
+    return cam, World([light], [floor, ball])
+
+
+def partition_lights():
+    """(the spot with the hard edge, the same light without a cone, the same light at intensity 0)"""
+    P, V, I = Vector.point(*PARTITION_LIGHT), Vector.vector(*PARTITION_AXIS), Color(1.0, 0.9, 0.8)
+    return SpotLight(I, P, V, PARTITION_ANGLE, PARTITION_ANGLE), PointLight(I, P), PointLight(Color(0.0, 0.0, 0.0), P)
+
+
+def partition_classes(rays, hits):
+    """From the camera's rays [n, 6] and the oracle's primary hits: c of every pixel's over_point (numpy, the rule's formulas) and the
+    three classes lit (c >= cos), dark, and excluded (|c - cos| < 1e-9, or no hit)."""
+    o, d, t = rays[:, :3], rays[:, 3:], hits["t"]
+    point = o + d * t[:, None]
+    normal = np.tile(np.array([0.0, 1.0, 0.0]), (len(t), 1))
+    on_ball = hits["prim"] == 1
+    nb = point[on_ball] - np.array(PARTITION_SPHERE)
+    normal[on_ball] = nb / np.sqrt((nb * nb).sum(1))[:, None]
+    over = point + normal * EPSILON
+    v = np.array(PARTITION_LIGHT) - over
+    dd = v / np.sqrt((v * v).sum(1))[:, None]
+    c = -(dd * np.array(PARTITION_AXIS)).sum(1)
+    cos = math.cos(PARTITION_ANGLE)
+    excluded = (np.abs(c - cos) < 1e-9) | (hits["prim"] < 0)
+    return c, (c >= cos) & ~excluded, (c < cos) & ~excluded, excluded
+
+
+def test_partition_fixture_meets_its_conditions(orc):
+    import raytracer_challenge_amd as rt
+    spot, plain, zero = partition_lights()
+    cam, world = partition_fixture(plain)
+    rays = rt.hip_backend().camera_rays(cam, Sampling()).reshape(-1, 6)          # host-side: no device
+    rgb, hits = orc.render(orc.build_world(world), cam, 0)
+    assert (hits["prim"] >= 0).all() and (hits["prim"] == 1).sum() >= 10          # every pixel sees the floor or the sphere
+    c, lit, dark, excluded = partition_classes(rays, hits)
+    n = float(len(c))
+    print("partition fixture: lit %.1f %%, dark %.1f %%, excluded %.2f %%" % (100 * lit.sum() / n, 100 * dark.sum() / n, 100 * excluded.sum() / n))
+    assert lit.sum() >= 0.15 * n and dark.sum() >= 0.15 * n and excluded.sum() <= 0.02 * n
+    assert 0.15 <= lit.sum() / n <= 0.40                                          # "about a quarter of the view"
+    # the two frames a pixel may come from differ wherever the light reaches: a lit pixel cannot pass for a dark one
+    zero_rgb, _ = orc.render(orc.build_world(partition_fixture(zero)[1]), cam, 0)
+    assert (zero_rgb == 0.0).all() and (rgb[lit] != 0.0).any(axis=1).all()
+    # some lit pixels lie in the sphere's shadow (ambient only) and some on the sphere: the partition is not the shadow's
+    assert (hits["prim"][lit] == 1).any() and (hits["prim"][dark] == 0).any()
