@@ -566,6 +566,23 @@ void rtc_scene_accel_info(const rtc_scene*, uint32_t* n_ops, uint32_t* n_bvh_nod
  * results-neutral: pixels and hit records do not depend on it. */
 int rtc_scene_bvh_built_on_device(const rtc_scene*);
 
+/* Test hook: ONE run of a binary-tree builder on the caller's boxes, handed back raw; no scene is involved and nothing about how scenes
+ * are built depends on it.  boxes = n records of 6 doubles (lo[3], hi[3]: an item's bounds); leaf_max = items per leaf (both builders
+ * clamp it to 1..8); base = index of the first item in the leaf references; where = 0: the host's binned-SAH builder (no device needed,
+ * like rtc_ppm), 1: the device's linear-BVH builder (csrc/bvh_device.hip).  Outputs, each with its capacity in records: nodes = the 64-byte
+ * node records verbatim (both children's boxes as f32 relative to frame[0..2], rounded outward; child references >= 0: node index,
+ * < 0: leaf, items [first, first + count) with first = (~ref) >> 3, count = ((~ref) & 7) + 1); order = the items in leaf order (n entries);
+ * keys = the n sorted 63-bit keys of the device builder (where = 1 only; NULL or capacity 0: not wanted); frame[4] = the tree's centre and
+ * inf-norm radius; *depth and *stack_need = levels of 4-wide nodes and worst-case traversal stack entries of that tree after the 4-wide
+ * collapse (-1 each if the tree cannot be walked).  *n_nodes receives the number of node records in every case where a tree was built.
+ * Returns RTC_OK; -1, the builder's own answer, when the device builder declines (n < 2, n <= leaf_max, an unbounded item, no device);
+ * RTC_ERR_INVALID for NULL arguments, n == 0, another `where`, or a capacity that is too small (nothing is written to that buffer). */
+int rtc_bvh_build_raw(const double* boxes, uint32_t n, int32_t leaf_max, uint32_t base, int32_t where, void* nodes, uint32_t nodes_cap, uint32_t* n_nodes,
+                      uint32_t* order, uint32_t order_cap, uint64_t* keys, uint32_t keys_cap, int32_t* root, double* frame, int32_t* depth, int32_t* stack_need);
+/* The 4-wide collapse alone on the caller's node records (the layout above): *depth and *stack_need as above.  Host only.  RTC_ERR_INVALID
+ * for NULL arguments, a root or child reference outside the array, or a node that is reached twice. */
+int rtc_bvh_collapse_raw(const void* nodes, uint32_t n_nodes, int32_t root, int32_t* depth, int32_t* stack_need);
+
 /* Dynamic LDS (bytes per block) the wavefront traversal kernel uses for this scene: > 0 = the scene's accelerator nodes, intersection
  * records and mesh triangles are copied into every CU's LDS and walks read them there (small scenes: the tables and the traversal
  * stacks fit 160 KB); 0 = they are read from memory.  bench.py's byte accounting counts LDS-resident records as 0 bytes. */

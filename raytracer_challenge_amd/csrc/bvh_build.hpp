@@ -317,4 +317,54 @@ inline int32_t collapse4(const std::vector<DBvhNode>& n2, int32_t root2, std::ve
   return r;
 }
 
+// The device builder with one more output: the sorted 63-bit keys of its radix tree (bvh_device.hip), for tests.
+typedef int32_t (*DeviceBuildKeysFn)(const std::vector<Item>& items, std::vector<DBvhNode>& nodes, std::vector<uint32_t>& order, uint32_t base, int leaf_max, double* frame,
+                                     std::vector<unsigned long long>* keys);
+
+// What collapse4 reads must be sound before it recurses over a caller's array: every reference inside the array, no node reached twice.
+inline bool tree_is_sound(const std::vector<DBvhNode>& n2, int32_t root2) {
+  if (root2 < 0 || (size_t)root2 >= n2.size()) return false;
+  std::vector<char> seen(n2.size(), 0);
+  std::vector<int32_t> todo(1, root2);
+  seen[(size_t)root2] = 1;
+  while (!todo.empty()) {
+    const DBvhNode& N = n2[(size_t)todo.back()];
+    todo.pop_back();
+    const bool have[2] = {N.lo0[0] <= N.hi0[0] && N.lo0[1] <= N.hi0[1] && N.lo0[2] <= N.hi0[2], N.lo1[0] <= N.hi1[0] && N.lo1[1] <= N.hi1[1] && N.lo1[2] <= N.hi1[2]};
+    const int32_t c[2] = {N.c0, N.c1};
+    for (int q = 0; q < 2; q++) {
+      if (!have[q] || c[q] < 0) continue;
+      if ((size_t)c[q] >= n2.size() || seen[(size_t)c[q]]) return false;
+      seen[(size_t)c[q]] = 1;
+      todo.push_back(c[q]);
+    }
+  }
+  return true;
+}
+
+// Test hook behind rtc_bvh_build_raw / rtc_bvh_collapse_raw (include/rtc.h): one builder run on the caller's boxes, nothing of a scene.
+// Returns the builder's root (>= 0) or -1 when the device builder declines.  depth and stack_need are collapse4's for that tree, -1
+// when the tree is not one collapse4 can walk (a reference outside the array, a node reached twice).
+struct Raw {
+  std::vector<DBvhNode> nodes;
+  std::vector<uint32_t> order;
+  std::vector<unsigned long long> keys;
+  double frame[4] = {0, 0, 0, 0};
+  int depth = 0, stack_need = 0;
+};
+inline int32_t build_raw(const double* boxes, size_t n, int leaf_max, uint32_t base, DeviceBuildKeysFn device, bool want_keys, Raw* out) {
+  std::vector<Item> items(n);
+  std::memcpy(items.data(), boxes, n * sizeof(Item));
+  int32_t root;
+  if (device) root = device(items, out->nodes, out->order, base, leaf_max, out->frame, want_keys ? &out->keys : nullptr);
+  else { int d2 = 0; root = build(items, out->nodes, out->order, base, &d2, false, leaf_max, out->frame); }
+  if (root < 0) return -1;
+  out->depth = out->stack_need = -1;
+  if (tree_is_sound(out->nodes, root)) {
+    std::vector<DBvhNode4> n4;
+    collapse4(out->nodes, root, n4, &out->depth, &out->stack_need);
+  }
+  return root;
+}
+
 }  // namespace bvh

@@ -223,9 +223,12 @@ struct Scratch {
 
 // bvh::DeviceBuildFn (bvh_build.hpp).  Returns the root node (index into n2, always an inner node) or -1: the caller then
 // builds on the host.  `order` receives the items in leaf order (appended), `frame` the centre and radius, as bvh::build does.
-int32_t rtc_bvh_build_device(const std::vector<bvh::Item>& items, std::vector<DBvhNode>& n2, std::vector<uint32_t>& order, uint32_t base, int leaf_max, double* frame) {
+// `keys` (tests: rtc_bvh_build_raw), when not null, receives the sorted 63-bit keys the radix tree was built over.
+int32_t rtc_bvh_build_device_keys(const std::vector<bvh::Item>& items, std::vector<DBvhNode>& n2, std::vector<uint32_t>& order, uint32_t base, int leaf_max, double* frame,
+                                  std::vector<unsigned long long>* keys) {
   static_assert(sizeof(bvh::Item) == sizeof(DevBox), "item layout");
   const size_t n = items.size();
+  leaf_max = leaf_max < 1 ? 1 : (leaf_max > 8 ? 8 : leaf_max);  // as bvh::build: a leaf reference has 3 bits for count - 1
   if (n < 2 || (int)n <= leaf_max || n > 0x0fffffffu) return -1;
   // bounds and frame on the host (one pass over data the host already holds): same centre / radius rule as bvh::build
   bvh::Builder::Range all = bvh::Builder::none(), cb = bvh::Builder::none();
@@ -289,6 +292,14 @@ int32_t rtc_bvh_build_device(const std::vector<bvh::Item>& items, std::vector<DB
   const size_t o0 = order.size();
   order.resize(o0 + n);
   if (hipMemcpy(order.data() + o0, d_v1, n * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) { n2.resize(at); order.resize(o0); return -1; }
+  if (keys) {
+    keys->resize(n);
+    if (hipMemcpy(keys->data(), d_k1, n * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) { n2.resize(at); order.resize(o0); keys->clear(); return -1; }
+  }
   if (frame) { frame[0] = center[0]; frame[1] = center[1]; frame[2] = center[2]; frame[3] = rad * (1.0 + 1e-6) + 1e-30; }
   return (int32_t)at;  // node 0 of the radix tree is the root, it is kept (n > leaf_max) and the prefix sum gives it index 0
+}
+
+int32_t rtc_bvh_build_device(const std::vector<bvh::Item>& items, std::vector<DBvhNode>& n2, std::vector<uint32_t>& order, uint32_t base, int leaf_max, double* frame) {
+  return rtc_bvh_build_device_keys(items, n2, order, base, leaf_max, frame, nullptr);
 }

@@ -50,6 +50,8 @@ void rtc_launch_resolve_samples_scatter(const double* ray_rgb, unsigned n_sample
 unsigned rtc_launch_resolve_filtered(const rtc_filter& f, const rtc_sampling& sp, unsigned long long hsize, unsigned long long row0, unsigned long long row1,
                                      unsigned long long out0, unsigned long long out1, const double* samples, double* dst, hipStream_t stream, unsigned* tile);
 int32_t rtc_bvh_build_device(const std::vector<bvh::Item>& items, std::vector<DBvhNode>& n2, std::vector<uint32_t>& order, uint32_t base, int leaf_max, double* frame);
+int32_t rtc_bvh_build_device_keys(const std::vector<bvh::Item>& items, std::vector<DBvhNode>& n2, std::vector<uint32_t>& order, uint32_t base, int leaf_max, double* frame,
+                                  std::vector<unsigned long long>* keys);
 
 static thread_local std::string g_rtc_err;
 static int rtc_fail(int code, const std::string& m) {
@@ -1857,6 +1859,20 @@ void rtc_scene_path_info(const rtc_scene* s, int32_t* choice, double* one_kernel
 }
 
 int rtc_scene_bvh_built_on_device(const rtc_scene* s) { return s ? s->built_on_device : 0; }
+
+// Test hooks: a builder's raw tree, no scene (include/rtc.h).
+int rtc_bvh_build_raw(const double* boxes, uint32_t n, int32_t leaf_max, uint32_t base, int32_t where, void* nodes, uint32_t nodes_cap, uint32_t* n_nodes, uint32_t* order,
+                      uint32_t order_cap, uint64_t* keys, uint32_t keys_cap, int32_t* root, double* frame, int32_t* depth, int32_t* stack_need) {
+  std::string err;
+  const int rc = rtb::bvh_build_raw(boxes, n, leaf_max, base, where, rtc_bvh_build_device_keys, nodes, nodes_cap, n_nodes, order, order_cap, keys, keys_cap, root, frame, depth,
+                                    stack_need, &err);
+  return rc > 0 ? rtc_fail(rc, err) : rc;
+}
+int rtc_bvh_collapse_raw(const void* nodes, uint32_t n_nodes, int32_t root, int32_t* depth, int32_t* stack_need) {
+  std::string err;
+  const int rc = rtb::bvh_collapse_raw(nodes, n_nodes, root, depth, stack_need, &err);
+  return rc > 0 ? rtc_fail(rc, err) : rc;
+}
 
 uint32_t rtc_scene_wavefront_lds_bytes(const rtc_scene* s) { return s ? rtc_wavefront_lds_bytes(s->d) : 0u; }
 

@@ -40,6 +40,45 @@ inline void parallel_for(size_t n, size_t grain, F fn) {
 }
 
 
+// rtc_bvh_build_raw / rtc_bvh_collapse_raw (include/rtc.h) but for the error text: shared by the library and tests/cpu_emu.
+inline int bvh_build_raw(const double* boxes, uint32_t n, int32_t leaf_max, uint32_t base, int32_t where, bvh::DeviceBuildKeysFn device, void* nodes, uint32_t nodes_cap,
+                         uint32_t* n_nodes, uint32_t* order, uint32_t order_cap, uint64_t* keys, uint32_t keys_cap, int32_t* root, double* frame, int32_t* depth,
+                         int32_t* stack_need, std::string* err) {
+  if (!boxes || !nodes || !n_nodes || !order || !root || !frame || !depth || !stack_need) { *err = "NULL argument"; return RTC_ERR_INVALID; }
+  if (n == 0 || (where != 0 && where != 1)) { *err = "rtc_bvh_build_raw: n == 0, or where is neither 0 nor 1"; return RTC_ERR_INVALID; }
+  if (where == 1 && !device) return -1;  // no device builder here: declined
+  bvh::Raw R;
+  const bool want_keys = where == 1 && keys && keys_cap > 0;
+  const int32_t r = bvh::build_raw(boxes, n, leaf_max, base, where == 1 ? device : nullptr, want_keys, &R);
+  if (r < 0) return -1;
+  *n_nodes = (uint32_t)R.nodes.size();
+  if (R.nodes.size() > nodes_cap || R.order.size() > order_cap || (want_keys && R.keys.size() > keys_cap)) {
+    *err = "rtc_bvh_build_raw: a capacity is too small";
+    return RTC_ERR_INVALID;
+  }
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "key type");
+  std::memcpy(nodes, R.nodes.data(), R.nodes.size() * sizeof(DBvhNode));
+  std::memcpy(order, R.order.data(), R.order.size() * sizeof(uint32_t));
+  if (want_keys) std::memcpy(keys, R.keys.data(), R.keys.size() * sizeof(uint64_t));
+  *root = r;
+  std::memcpy(frame, R.frame, sizeof(R.frame));
+  *depth = R.depth;
+  *stack_need = R.stack_need;
+  return RTC_OK;
+}
+inline int bvh_collapse_raw(const void* nodes, uint32_t n_nodes, int32_t root, int32_t* depth, int32_t* stack_need, std::string* err) {
+  if (!nodes || !depth || !stack_need) { *err = "NULL argument"; return RTC_ERR_INVALID; }
+  std::vector<DBvhNode> n2(n_nodes);
+  std::memcpy(n2.data(), nodes, (size_t)n_nodes * sizeof(DBvhNode));
+  if (!bvh::tree_is_sound(n2, root)) { *err = "rtc_bvh_collapse_raw: a reference outside the array, or a node reached twice"; return RTC_ERR_INVALID; }
+  std::vector<DBvhNode4> n4;
+  int d = 0, need = 0;
+  bvh::collapse4(n2, root, n4, &d, &need);
+  *depth = d;
+  *stack_need = need;
+  return RTC_OK;
+}
+
 struct ProgramBuilder {
   const rtc_scene_desc& D;
   std::vector<DOp> ops;
@@ -353,14 +392,17 @@ struct ProgramBuilder {
       // pipeline (4-wide collapse, stack bound, leaf packing) is shared, and a tree too deep for the stack falls to the median build
       const bool on_device = attempt == 0 && mesh && device_build && items.size() >= device_build_min;
       if (on_device) root2 = device_build(items, n2, order, base, leaf_size(mesh), frame);
-      if (root2 >= 0) built_on_device++;
-      else { n2.clear(); order.resize(o0); root2 = bvh::build(items, n2, order, base, &depth2, attempt == 1, leaf_size(mesh), frame); }
+      const bool from_device = root2 >= 0;
+      if (!from_device) { n2.clear(); order.resize(o0); root2 = bvh::build(items, n2, order, base, &depth2, attempt == 1, leaf_size(mesh), frame); }
       auto t1_ = std::chrono::steady_clock::now();
       root = bvh::collapse4(n2, root2, bvh_nodes, &depth, &need);
       if (std::getenv("RTC_TIMING") && items.size() > 100000)
-        std::fprintf(stderr, "[rtc-timing]   %s build %.3f s, collapse4 %.3f s (%zu items)\n", on_device && built_on_device ? "device LBVH" : "host SAH", std::chrono::duration<double>(t1_ - t0_).count(),
+        std::fprintf(stderr, "[rtc-timing]   %s build %.3f s, collapse4 %.3f s (%zu items)\n", from_device ? "device LBVH" : "host SAH", std::chrono::duration<double>(t1_ - t0_).count(),
                      std::chrono::duration<double>(std::chrono::steady_clock::now() - t1_).count(), items.size());
-      if (need <= RTC_BVH_STACK - 1) break;
+      if (need <= RTC_BVH_STACK - 1) {
+        if (from_device) built_on_device++;  // counted only when this attempt's tree is the one kept
+        break;
+      }
     }
     if (need > RTC_BVH_STACK - 1) { error = "BVH too deep for the traversal stack"; status = RTC_ERR_UNSUPPORTED; }
     *frame_index = (int32_t)(bvh_frame.size() / 4);

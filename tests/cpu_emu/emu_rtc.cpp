@@ -195,6 +195,18 @@ void rtc_scene_path_info(const rtc_scene*, int32_t* choice, double* one_kernel_m
 }
 uint32_t rtc_scene_wavefront_lds_bytes(const rtc_scene*) { return 0; }
 int rtc_scene_bvh_built_on_device(const rtc_scene*) { return 0; }
+// the builder hooks: the host builder as in the product; there is no device builder, so where = 1 is always declined
+int rtc_bvh_build_raw(const double* boxes, uint32_t n, int32_t leaf_max, uint32_t base, int32_t where, void* nodes, uint32_t nodes_cap, uint32_t* n_nodes, uint32_t* order,
+                      uint32_t order_cap, uint64_t* keys, uint32_t keys_cap, int32_t* root, double* frame, int32_t* depth, int32_t* stack_need) {
+  std::string err;
+  const int rc = rtb::bvh_build_raw(boxes, n, leaf_max, base, where, nullptr, nodes, nodes_cap, n_nodes, order, order_cap, keys, keys_cap, root, frame, depth, stack_need, &err);
+  return rc > 0 ? efail(rc, err) : rc;
+}
+int rtc_bvh_collapse_raw(const void* nodes, uint32_t n_nodes, int32_t root, int32_t* depth, int32_t* stack_need) {
+  std::string err;
+  const int rc = rtb::bvh_collapse_raw(nodes, n_nodes, root, depth, stack_need, &err);
+  return rc > 0 ? efail(rc, err) : rc;
+}
 void rtc_scene_accel_info(const rtc_scene* s, uint32_t* n_ops, uint32_t* n_bvh_nodes, uint32_t* n_mesh_tris, uint32_t* bvh_depth) {
   if (n_ops) *n_ops = (uint32_t)s->H.ops.size();
   if (n_bvh_nodes) *n_bvh_nodes = (uint32_t)s->H.bvh.size();

@@ -1,0 +1,221 @@
+"""The device BVH builder (csrc/bvh_device.hip) checked on its tree, not on its consequences: through the library's builder hook
+(include/rtc.h rtc_bvh_build_raw, where = 1) every input family of tests/bvh_cases.py is built on an MI355X and the result must satisfy
+the format's invariants (tests/bvh_ref.py check_tree: exact, outward-rounded boxes, leaves tiling the items once), its sorted keys
+must equal the restatement's, and its node bytes and leaf order must equal ref_lbvh's.  Then the cases where the builder must decline,
+the leaf sizes it must clamp, and four small meshes rendered through both builders and against the oracle, with the count of device-built
+trees checked -- among them a tree too deep for the traversal stack, which must be replaced by the host's."""
+import ctypes as C
+import re
+
+import numpy as np
+import pytest
+
+import bvh_cases
+import bvh_ref
+from bvh_cases import RTC_BVH_STACK, boxes_of, build_raw, case_id, reference
+from parity import assert_parity, oracle_reference
+from raytracer_challenge_amd.scene import Camera, Color, Element, GroupKind, Material, Matrix, Pattern, PointLight, ShapeArgs, Vector, World
+
+pytestmark = pytest.mark.gpu
+CASES = bvh_cases.cases(65537)
+_built = {}
+
+
+@pytest.fixture(scope="module")
+def lib(hip):
+    return bvh_cases.bind(hip.lib)
+
+
+@pytest.fixture(scope="module")
+def hip_error(hip):
+    """hipPeekAtLastError of the HIP runtime the library is linked to."""
+    path = [line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line][0]
+    rt = C.CDLL(path)
+    rt.hipPeekAtLastError.restype = C.c_int
+    return rt.hipPeekAtLastError
+
+
+def device_tree(lib, case):
+    """One device build per case, shared by the tests below."""
+    if case not in _built:
+        family, n, leaf_max, base = case
+        _built[case] = build_raw(lib, boxes_of(family, n), leaf_max, base, 1)
+    return _built[case]
+
+
+def same_bytes(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
+
+
+# ---- every family x size ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", CASES, ids=case_id)
+def test_device_tree_passes_the_checker(lib, case):
+    family, n, leaf_max, base = case
+    t = device_tree(lib, case)
+    if n <= leaf_max:
+        assert t.rc == -1 and t.untouched
+        return
+    assert t.rc == 0, lib.rtc_last_error()
+    assert t.root == 0
+    bvh_ref.check_tree(t.nodes, t.root, t.order, boxes_of(family, n), base, leaf_max, t.frame)
+    assert t.depth > 0 and t.stack_need > 0
+
+
+@pytest.mark.parametrize("case", [c for c in CASES if c[1] > c[2]], ids=case_id)
+def test_device_sorted_keys_equal_the_reference(lib, case):
+    t = device_tree(lib, case)
+    assert t.rc == 0
+    keys = reference(*case)[2]
+    bad = np.flatnonzero(t.keys != keys)
+    assert not len(bad), "%d of %d sorted keys differ, first at position %d: %#x, want %#x" % (len(bad), len(keys), bad[0], t.keys[bad[0]], keys[bad[0]])
+
+
+@pytest.mark.parametrize("case", [c for c in CASES if c[1] > c[2]], ids=case_id)
+def test_device_tree_equals_the_reference_bytes(lib, case):
+    t = device_tree(lib, case)
+    assert t.rc == 0
+    nodes, order, keys, frame = reference(*case)
+    assert np.array_equal(t.order, order), "leaf order differs at %d positions" % int((t.order != order).sum())
+    assert len(t.nodes) == len(nodes), "%d node records, want %d" % (len(t.nodes), len(nodes))
+    rows = np.flatnonzero((t.nodes.view(np.uint8).reshape(-1, 64) != nodes.view(np.uint8).reshape(-1, 64)).any(axis=1))
+    assert not len(rows), "%d of %d node records differ, first %d: %s, want %s" % (len(rows), len(nodes), rows[0], t.nodes[rows[0]], nodes[rows[0]])
+    assert same_bytes(t.nodes, nodes) and same_bytes(t.frame, frame)
+
+
+def test_deep_chain_needs_more_stack_than_a_lane_has(lib):
+    """What makes the rendered family-(h) mesh below meaningful, on the device's own tree."""
+    t = device_tree(lib, ("h_chain", bvh_cases.H_DEEP, 4, 0))
+    assert t.rc == 0 and t.stack_need > RTC_BVH_STACK - 1, t.stack_need
+
+
+def test_two_builds_of_one_input_are_identical(lib):
+    boxes = boxes_of("a_uniform", 65537)
+    first = build_raw(lib, boxes, 4, 0, 1)
+    second = build_raw(lib, boxes, 4, 0, 1)
+    assert first.rc == 0 and second.rc == 0
+    assert same_bytes(first.nodes, second.nodes) and same_bytes(first.order, second.order) and same_bytes(first.keys, second.keys)
+
+
+# ---- declined builds -------------------------------------------------------------------------------------------------------------------
+def _unbounded():
+    b = boxes_of("a_uniform", 257).copy()
+    b[100, 4] = np.inf
+    return b
+
+
+@pytest.mark.parametrize("name,boxes,leaf_max", [("n <= leaf_max", lambda: boxes_of("a_uniform", 5)[:4], 4), ("n == leaf_max, 8", lambda: boxes_of("a_uniform", 255)[:8], 8),
+                                                 ("one item", lambda: boxes_of("a_uniform", 5)[:1], 1), ("an unbounded item", _unbounded, 4)])
+def test_builder_declines_and_leaves_no_error_behind(lib, hip_error, name, boxes, leaf_max):
+    t = build_raw(lib, boxes(), leaf_max, 0, 1)
+    assert t.rc == -1 and t.untouched, name
+    assert hip_error() == 0, "%s: the declined build left HIP error %d in the runtime" % (name, hip_error())
+    case = ("a_uniform", 513, 4, 0)
+    after = build_raw(lib, boxes_of(*case[:2]), 4, 0, 1)
+    nodes, order, keys, frame = reference(*case)
+    assert after.rc == 0 and same_bytes(after.nodes, nodes) and same_bytes(after.order, order) and same_bytes(after.keys, keys), name
+    assert hip_error() == 0
+
+
+@pytest.mark.parametrize("leaf_max,used", [(0, 1), (9, 8), (16, 8)])
+def test_device_builder_clamps_leaf_max(lib, leaf_max, used):
+    """A leaf reference has 3 bits for count - 1: both builders clamp leaf_max to 1..8.  Through the hook only: a tree with a malformed
+    leaf reference must never reach a traversal kernel."""
+    boxes = boxes_of("c_runs", 4099)
+    t = build_raw(lib, boxes, leaf_max, 0, 1)
+    assert t.rc == 0
+    bvh_ref.check_tree(t.nodes, t.root, t.order, boxes, 0, used, t.frame)
+    nodes, order, keys, frame = bvh_ref.ref_lbvh(boxes, used, 0)
+    assert same_bytes(t.nodes, nodes) and same_bytes(t.order, order)
+    host = build_raw(lib, boxes, leaf_max, 0, 0)
+    assert host.rc == 0
+    bvh_ref.check_tree(host.nodes, host.root, host.order, boxes, 0, used, host.frame)
+
+
+# ---- render level ----------------------------------------------------------------------------------------------------------------------
+def built_on_device(hip, nw):
+    lib = hip.lib
+    lib.rtw_world_scene.restype = C.c_void_p
+    lib.rtw_world_scene.argtypes = [C.c_void_p, C.c_int]
+    lib.rtc_scene_bvh_built_on_device.restype = C.c_int
+    lib.rtc_scene_bvh_built_on_device.argtypes = [C.c_void_p]
+    return lib.rtc_scene_bvh_built_on_device(lib.rtw_world_scene(nw.handle, 0))
+
+
+def _camera(frm, to):
+    return Camera.new(64, 36, 0.9, Camera.transform(Vector.point(*frm), Vector.point(*to), Vector.vector(0, 1, 0)))
+
+
+def _world(elements):
+    floor = Element.plane(ShapeArgs(transform=Matrix.translation(0.0, -3.0, 0.0), material=Material(pattern=Pattern.plain(Color.new(0.4, 0.4, 0.5)), reflective=0.3)))
+    return World([PointLight(Color.new(0.9, 0.9, 0.9), Vector.point(-6.0, 9.0, -7.0))], [floor] + elements)
+
+
+MAT = Material(pattern=Pattern.plain(Color.new(0.8, 0.5, 0.3)), reflective=0.2)
+
+
+def scene_repeated(tmp):
+    obj = bvh_cases.write_obj(str(tmp / "repeated.obj"), bvh_cases.mesh_repeated(np.random.RandomState(11)))
+    return _camera((0.5, 2.0, -7.0), (0.0, 0.3, 0.0)), _world([Element.obj(obj, Matrix.id(), MAT)]), 1
+
+
+def scene_flat(tmp):
+    obj = bvh_cases.write_obj(str(tmp / "flat.obj"), bvh_cases.mesh_flat_grid())
+    return _camera((1.0, 4.0, -8.0), (0.0, 0.0, 0.0)), _world([Element.obj(obj, Matrix.id(), MAT)]), 1
+
+
+def scene_two_meshes(tmp):
+    rng = np.random.RandomState(12)
+    cloud = bvh_cases.write_obj(str(tmp / "cloud.obj"), bvh_cases.tris_around(rng.uniform(-1.5, 1.5, (200, 3)), rng.uniform(0.05, 0.4, (200, 3))))
+    flat = bvh_cases.write_obj(str(tmp / "flat8.obj"), bvh_cases.mesh_flat_grid(cells=8, size=2.0))
+    group = Element.composite(Matrix.translation(1.5, 0.5, 1.0) * Matrix.rotation_z(0.4) * Matrix.rotation_y(0.7) * Matrix.scaling(1.3, 0.6, 0.9), None, GroupKind.Aggregation,
+                              [Element.obj(flat, Matrix.id(), MAT)])
+    return _camera((0.0, 2.5, -8.0), (0.0, 0.0, 0.0)), _world([Element.obj(cloud, Matrix.translation(-1.5, 0.0, 0.0), MAT), group]), 2
+
+
+SCENES = {"repeated_triangle": scene_repeated, "flat_grid": scene_flat, "two_meshes_one_in_a_group": scene_two_meshes}
+
+
+def _both_builders(hip, orc, monkeypatch, cam, world, label):
+    """RTC_DEVICE_BVH=0 and =1: each against the oracle (hit records and digests bit for bit), and the two against each other bit for
+    bit.  Returns the count of device-built trees under =1."""
+    monkeypatch.setenv("RTC_DEVICE_BVH_MIN", "64")
+    ref = oracle_reference(orc, world, cam, 2)
+    out, count = {}, {}
+    for flag in ("0", "1"):
+        monkeypatch.setenv("RTC_DEVICE_BVH", flag)
+        assert_parity(hip, orc, world, cam, 2, label="%s, RTC_DEVICE_BVH=%s" % (label, flag), ref=ref)
+        nw = hip.build_world(world)
+        out[flag] = hip.render(nw, cam, 2)
+        count[flag] = built_on_device(hip, nw)
+    assert np.array_equal(out["0"][1], out["1"][1]), label + ": primary-hit records differ between the two builders"
+    assert np.array_equal(out["0"][0].view(np.uint64), out["1"][0].view(np.uint64)), label + ": pixels differ between the two builders"
+    assert (out["1"][1]["prim"] >= 0).sum() > 64, label + ": the camera sees too little of the scene"
+    assert count["0"] == 0, label
+    return count["1"]
+
+
+@pytest.mark.parametrize("name", sorted(SCENES))
+def test_small_meshes_render_the_same_bits_through_both_builders(hip, orc, monkeypatch, tmp_path, name):
+    cam, world, meshes = SCENES[name](tmp_path)
+    assert _both_builders(hip, orc, monkeypatch, cam, world, name) == meshes
+
+
+def test_tree_too_deep_for_the_stack_is_rebuilt_on_the_host(hip, orc, lib, monkeypatch, tmp_path, capfd):
+    """Family (h) as a mesh: the device's tree needs more traversal stack than a lane has (asserted on the mesh's own boxes), so the
+    scene keeps the host's second attempt -- and must say so: no device-built tree is counted, and the timing line of the kept build
+    names the host."""
+    tris = bvh_cases.mesh_chain(513)
+    t = build_raw(lib, bvh_cases.tri_boxes(tris), 4, 0, 1)
+    assert t.rc == 0 and t.stack_need > RTC_BVH_STACK - 1, t.stack_need
+    world = _world([Element.obj(bvh_cases.write_obj(str(tmp_path / "chain.obj"), tris), Matrix.translation(-1.0, 0.0, 0.0) * Matrix.scaling(2.0, 2.0, 2.0), MAT)])
+    assert _both_builders(hip, orc, monkeypatch, _camera((0.5, 1.5, -5.0), (0.0, 0.5, 0.0)), world, "deep chain") == 0
+    # the timing line is printed for meshes of more than 100 000 items: the same chain with that many copies, built but not rendered
+    big = _world([Element.obj(bvh_cases.write_obj(str(tmp_path / "chain_big.obj"), bvh_cases.mesh_chain(100100)), Matrix.id(), MAT)])
+    monkeypatch.setenv("RTC_DEVICE_BVH", "1")
+    monkeypatch.setenv("RTC_TIMING", "1")
+    capfd.readouterr()
+    count = built_on_device(hip, hip.build_world(big))       # (the scene is created on first use)
+    lines = re.findall(r"\[rtc-timing\]\s+(device LBVH|host SAH) build .*\((\d+) items\)", capfd.readouterr().err)
+    assert lines == [("device LBVH", "100100"), ("host SAH", "100100")], lines
+    assert count == 0
