@@ -588,6 +588,38 @@ int rtc_bvh_collapse_raw(const void* nodes, uint32_t n_nodes, int32_t root, int3
  * stacks fit 160 KB); 0 = they are read from memory.  bench.py's byte accounting counts LDS-resident records as 0 bytes. */
 uint32_t rtc_scene_wavefront_lds_bytes(const rtc_scene*);
 
+/* Test hook: which build of each ray kernel a launch of this scene takes, read-only.  The ray kernels are compiled in several builds
+ * (DESIGN.md "Kernel builds"); the launchers and this query call the same selection functions, so what is reported is what runs -- with one exception, decided
+ * at launch time: a device that refuses the dynamic LDS size runs wf_ts's memory build (lds_refused below tells).
+ * path = 1: the one-kernel path (trace_build is set, the wf_* fields are -1); 4: the wavefront path (the reverse); count != 0: a launch
+ * with counters (a stats pointer, rtc_render_hit_digest).  RTC_NO_KOPS (set: the program is read from memory), RTC_KOPS_GROUPS=0
+ * (programs with per-primitive gates are read from memory) and RTC_WF_LDS=0 (tables are read from memory) are read when a scene is
+ * created and hold for that scene, as RTC_KERNEL does.  Returns RTC_ERR_INVALID for a NULL argument or another path. */
+enum { RTC_TRACE_DEFAULT = 0, RTC_TRACE_COUNT = 1, RTC_TRACE_LEAN = 2, RTC_TRACE_3WAVE = 3 };
+enum { RTC_WF_TS_MEM = 0, RTC_WF_TS_MEM_COUNT = 1, RTC_WF_TS_LDS = 2, RTC_WF_TS_LDS_COUNT = 3 };
+enum { RTC_SHADE_COUNT = 0, RTC_SHADE_COUNT_UV = 1, RTC_SHADE_UV = 2, RTC_SHADE_PIPE_LV0 = 3, RTC_SHADE_PIPE = 4, RTC_SHADE_PAT = 5 };
+typedef struct rtc_kernel_info {
+  int32_t variant;          /* row of the variant table (csrc/rtc_device.hpp RTC_VARIANTS) */
+  int32_t n_kops;           /* ops of the program in the kernel arguments (0: the program is read from memory) */
+  int32_t n_kplanes;        /* plane records in the kernel arguments */
+  int32_t n_kaux;           /* accelerator roots in the kernel arguments */
+  int32_t has_recs;         /* some op reads the intersection-record table */
+  int32_t all_plain;        /* every material's root pattern is a Plain colour */
+  int32_t no_glass_mirror;  /* no material both reflects and refracts */
+  int32_t big_scene;        /* the scene's tables exceed 32 MiB */
+  uint32_t lds_bytes;       /* path 4: dynamic LDS of the traversal kernel, 0 = tables in memory */
+  int32_t trace_build;      /* path 1: RTC_TRACE_* */
+  int32_t wf_ts_build;      /* path 4: RTC_WF_TS_* */
+  int32_t wf_shade_build0;  /* path 4: RTC_SHADE_* of level 0 */
+  int32_t wf_shade_build;   /* path 4: RTC_SHADE_* of the levels above */
+  /* what the LDS size is computed from: 112 B per accelerator node, 128 B per intersection record if has_recs, 76 B per mesh
+   * triangle (rounded up to 16) if has_mesh, and 4 * bvh_stack bytes of traversal stack for each of the block's 768 threads */
+  int32_t n_bvh_nodes, n_recs, n_mesh_tris, has_mesh, bvh_stack;
+  int32_t lds_refused;      /* path 4, lds_bytes > 0: the scene's device has refused that much dynamic LDS in an earlier launch, so
+                               its launches run the RTC_WF_TS_MEM* build instead of the one reported (0 before any launch) */
+} rtc_kernel_info;
+int rtc_scene_kernel_info(const rtc_scene*, int32_t path, int32_t count, rtc_kernel_info* out);
+
 /* Which device path renders whole-row launches of this scene (both give bit-identical pixels and hits):
  *   1  one kernel: a lane walks its pixel's whole ray tree (rtc_trace_kernel);
  *   4  wavefront: per bounce level a closest-hit + shadow kernel and a shading kernel over ray queues (wf_* kernels).

@@ -2191,6 +2191,39 @@ constexpr int rtc_pick_variant(int feat, bool kops, bool area, bool uv, bool spo
   return feat <= 1 ? 2 : feat + 1;
 }
 
+// The build of each ray kernel that a launch takes: every choice between instantiations is one of the pure functions below, called by the
+// launchers (rtc_feat.hip, rtc_kernels.hip) and by the dispatch query (rtc_kernel_info_fill -> rtc.h rtc_scene_kernel_info), so the query
+// reports what runs.  The values are include/rtc.h's RTC_TRACE_* / RTC_WF_TS_* / RTC_SHADE_*.
+enum RtcTraceBuild { RTC_TB_DEFAULT = 0, RTC_TB_COUNT = 1, RTC_TB_LEAN = 2, RTC_TB_3WAVE = 3 };
+enum RtcWfTsBuild { RTC_TS_MEM = 0, RTC_TS_MEM_COUNT = 1, RTC_TS_LDS = 2, RTC_TS_LDS_COUNT = 3 };
+enum RtcWfShadeBuild { RTC_SH_COUNT = 0, RTC_SH_COUNT_UV = 1, RTC_SH_UV = 2, RTC_SH_PIPE_LV0 = 3, RTC_SH_PIPE = 4, RTC_SH_PAT = 5 };
+// feature level of a scene (RtcVariant.feat)
+static inline int rtc_scene_feat(const DScene& S) { return S.has_csg ? 3 : (S.has_groups == 2 ? 2 : (S.has_groups ? 1 : 0)); }
+// one-kernel path: mesh scenes larger than the L2s take the 3-waves-per-SIMD build, all-Plain scenes without a glass mirror the LEAN
+// build (see rtc_trace_kernel); neither has a counting form
+constexpr RtcTraceBuild rtc_pick_trace_build(RtcVariant r, bool count, bool big_scene, bool all_plain, bool no_glass_mirror) {
+  if (rtc_v_trace_3wave(r) && big_scene && !count) return RTC_TB_3WAVE;
+  if (rtc_v_trace_lean(r) && !count && all_plain && no_glass_mirror) return RTC_TB_LEAN;
+  return count ? RTC_TB_COUNT : RTC_TB_DEFAULT;
+}
+// one-kernel path: the scene's tables do not fit the L2s
+constexpr bool rtc_big_scene(unsigned long long scene_bytes) { return scene_bytes > (32ull << 20); }
+// wavefront traversal: dynamic LDS of the LDSC build, or 0 = the build that reads the tables from memory (the row has no LDSC build,
+// RTC_WF_LDS=0 at scene creation, or tables + stacks beyond 158 KB)
+constexpr unsigned rtc_pick_lds_bytes(RtcVariant r, bool lds_enabled, unsigned long long table_bytes, int bvh_stack) {
+  if (!lds_enabled || !rtc_v_lds(r)) return 0u;
+  const unsigned long long need = table_bytes + (unsigned long long)RTC_LDS_BLOCK * (unsigned)bvh_stack * sizeof(int);
+  return need <= 158ull * 1024 ? (unsigned)need : 0u;
+}
+constexpr RtcWfTsBuild rtc_pick_wf_ts_build(bool count, bool lds) { return lds ? (count ? RTC_TS_LDS_COUNT : RTC_TS_LDS) : (count ? RTC_TS_MEM_COUNT : RTC_TS_MEM); }
+// wavefront shading of one level (see wf_shade)
+constexpr RtcWfShadeBuild rtc_pick_wf_shade_build(bool count, bool has_uv, bool all_plain, bool level0) {
+  if (has_uv) return count ? RTC_SH_COUNT_UV : RTC_SH_UV;
+  if (count) return RTC_SH_COUNT;
+  if (all_plain) return level0 ? RTC_SH_PIPE_LV0 : RTC_SH_PIPE;
+  return RTC_SH_PAT;
+}
+
 // Launch arguments (host side): what every ray kernel of a frame receives, and what one level of the wavefront path adds.
 struct RtcFrame {
   const DScene& S;
@@ -2216,6 +2249,7 @@ struct RtcVariantOps {
   void (*launch_wf_ts)(const RtcFrame& F, const RtcLevel& L);
   bool (*launch_wf_ts_lds)(const RtcFrame& F, const RtcLevel& L);  // false: this device refuses the dynamic LDS size, nothing was launched
   int (*wf_ts_blocks_per_cu)(unsigned lds_bytes);
+  bool (*wf_ts_lds_refused)(int device);  // a launch on that device was refused the dynamic LDS size: its launches take launch_wf_ts
 };
 template <int V>
 RtcVariantOps rtc_variant_ops();  // defined and explicitly instantiated by the translation unit of variant V

@@ -22,26 +22,35 @@ void launch_wf_ts_kernel(K kernel, unsigned block, unsigned lds_bytes, const Rtc
 template <int V>
 void launch_trace(const RtcFrame& F, bool big_scene, unsigned grid, int fuel, double* rgb) {
   constexpr RtcVariant R = RTC_VARIANTS[V];
-  if constexpr (rtc_v_trace_3wave(R)) {
-    // mesh scenes larger than the L2s: the 3-waves-per-SIMD build (see rtc_trace_kernel)
-    if (big_scene && !F.count) return launch_trace_kernel(rtc_trace_kernel<false, R.feat, R.kops, 3>, F, grid, fuel, rgb);
+  switch (rtc_pick_trace_build(R, F.count, big_scene, F.S.all_plain != 0, F.S.no_glass_mirror != 0)) {
+    case RTC_TB_3WAVE:  // (instantiated for the rows that can be told to take it only)
+      if constexpr (rtc_v_trace_3wave(R)) launch_trace_kernel(rtc_trace_kernel<false, R.feat, R.kops, 3>, F, grid, fuel, rgb);
+      return;
+    case RTC_TB_LEAN:
+      if constexpr (rtc_v_trace_lean(R)) launch_trace_kernel(rtc_trace_kernel<false, R.feat, R.kops, 0, true>, F, grid, fuel, rgb);
+      return;
+    case RTC_TB_COUNT: return launch_trace_kernel(rtc_trace_kernel<true, R.feat, R.kops, 0, false, R.area, R.uv, R.spot>, F, grid, fuel, rgb);
+    case RTC_TB_DEFAULT: return launch_trace_kernel(rtc_trace_kernel<false, R.feat, R.kops, 0, false, R.area, R.uv, R.spot>, F, grid, fuel, rgb);
   }
-  if constexpr (rtc_v_trace_lean(R)) {
-    if (!F.count && F.S.all_plain && F.S.no_glass_mirror)  // the lean build (see rtc_trace_kernel)
-      return launch_trace_kernel(rtc_trace_kernel<false, R.feat, R.kops, 0, true>, F, grid, fuel, rgb);
-  }
-  if (F.count) launch_trace_kernel(rtc_trace_kernel<true, R.feat, R.kops, 0, false, R.area, R.uv, R.spot>, F, grid, fuel, rgb);
-  else launch_trace_kernel(rtc_trace_kernel<false, R.feat, R.kops, 0, false, R.area, R.uv, R.spot>, F, grid, fuel, rgb);
 }
 
 template <int V>
 void launch_wf_ts(const RtcFrame& F, const RtcLevel& L) {
   constexpr RtcVariant R = RTC_VARIANTS[V];
-  if (F.count) launch_wf_ts_kernel(wf_ts<true, R.feat, R.kops, false, R.area, R.spot>, RTC_BLOCK, rtc_stack_bytes(F.S), F, L);
+  if (rtc_pick_wf_ts_build(F.count, false) == RTC_TS_MEM_COUNT) launch_wf_ts_kernel(wf_ts<true, R.feat, R.kops, false, R.area, R.spot>, RTC_BLOCK, rtc_stack_bytes(F.S), F, L);
   else launch_wf_ts_kernel(wf_ts<false, R.feat, R.kops, false, R.area, R.spot>, RTC_BLOCK, rtc_stack_bytes(F.S), F, L);
 }
 
 #ifndef RTC_EMU
+// Per device (rtc_multi renders on several from one process), one bit each: the dynamic-LDS attribute of this variant's LDSC kernels was
+// raised / was refused.
+template <int V>
+struct WfLdsState {
+  static inline std::atomic<unsigned long long> raised{0ull}, refused{0ull};
+};
+template <int V>
+bool wf_ts_lds_refused(int dev) { return dev >= 0 && dev < 64 && ((WfLdsState<V>::refused.load(std::memory_order_acquire) >> dev) & 1ull) != 0; }
+
 // The same kernel with the scene's accelerator nodes and intersection records copied into LDS by every block (variants with a
 // kernel-argument program only: those are the small scenes); one block of RTC_LDS_BLOCK threads per CU, L.lds_bytes of dynamic LDS.
 // Returns false when this device refuses the dynamic LDS size (nothing was launched: the caller takes the kernel that reads the tables from memory).
@@ -49,8 +58,8 @@ template <int V>
 bool launch_wf_ts_lds(const RtcFrame& F, const RtcLevel& L) {
   constexpr RtcVariant R = RTC_VARIANTS[V];
   // More than 64 KB of dynamic LDS has to be asked for, and the attribute belongs to the function object of the CURRENT device:
-  // one bit per device (rtc_multi renders on several from one process), 1 = raised, in the second word 1 = refused.
-  static std::atomic<unsigned long long> raised{0ull}, refused{0ull};
+  // one bit per device in WfLdsState.
+  std::atomic<unsigned long long>&raised = WfLdsState<V>::raised, &refused = WfLdsState<V>::refused;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
   const unsigned long long bit = 1ull << dev;
@@ -68,7 +77,7 @@ bool launch_wf_ts_lds(const RtcFrame& F, const RtcLevel& L) {
     }
     raised.fetch_or(bit, std::memory_order_acq_rel);
   }
-  if (F.count) launch_wf_ts_kernel(wf_ts<true, R.feat, R.kops, true>, RTC_LDS_BLOCK, L.lds_bytes, F, L);
+  if (rtc_pick_wf_ts_build(F.count, true) == RTC_TS_LDS_COUNT) launch_wf_ts_kernel(wf_ts<true, R.feat, R.kops, true>, RTC_LDS_BLOCK, L.lds_bytes, F, L);
   else launch_wf_ts_kernel(wf_ts<false, R.feat, R.kops, true>, RTC_LDS_BLOCK, L.lds_bytes, F, L);
   return true;
 }
@@ -88,10 +97,10 @@ int wf_ts_blocks_per_cu(unsigned lds_bytes) {
 template <int V>
 RtcVariantOps rtc_variant_ops() {
   constexpr RtcVariant R = RTC_VARIANTS[V];
-  RtcVariantOps ops = {launch_trace<V>, nullptr, nullptr, nullptr};
+  RtcVariantOps ops = {launch_trace<V>, nullptr, nullptr, nullptr, nullptr};
   if constexpr (rtc_v_wavefront(R)) ops.launch_wf_ts = launch_wf_ts<V>;
 #ifndef RTC_EMU
-  if constexpr (rtc_v_lds(R)) ops.launch_wf_ts_lds = launch_wf_ts_lds<V>;
+  if constexpr (rtc_v_lds(R)) { ops.launch_wf_ts_lds = launch_wf_ts_lds<V>; ops.wf_ts_lds_refused = wf_ts_lds_refused<V>; }
   if constexpr (rtc_v_wavefront(R)) ops.wf_ts_blocks_per_cu = wf_ts_blocks_per_cu<V>;
 #endif
   return ops;

@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <utility>
 
+#include "../../include/rtc.h"
 #include "rtc_device.hpp"
 
 #ifdef RTC_EMU
@@ -23,8 +24,7 @@ static const RtcVariantOps& rtc_ops(int v, std::integer_sequence<int, V...>) {
 static const RtcVariantOps& rtc_ops(int v) { return rtc_ops(v, std::make_integer_sequence<int, RTC_VARIANTS_BUILT>{}); }
 // kernel variant that renders a scene on a device path (rtc_pick_variant)
 static int rtc_variant(const DScene& S, bool wavefront) {
-  const int feat = S.has_csg ? 3 : (S.has_groups == 2 ? 2 : (S.has_groups ? 1 : 0));
-  return rtc_pick_variant(feat, S.n_kops > 0, S.has_area != 0, S.has_uv != 0, S.has_spot != 0, wavefront);
+  return rtc_pick_variant(rtc_scene_feat(S), S.n_kops > 0, S.has_area != 0, S.has_uv != 0, S.has_spot != 0, wavefront);
 }
 
 #ifndef RTC_WF_SHADE_WAVES
@@ -263,15 +263,53 @@ __global__ void __launch_bounds__(256) wf_gather(DCamera cam, DPixelMap pm, DWav
 }
 
 
-#ifndef RTC_EMU
 // LDS-resident scene (rtc_device.hpp, LdsScene): bytes of dynamic LDS a block of the LDSC traversal kernel needs, or 0 when the
-// scene does not qualify (program not in the kernel arguments, tables + stacks beyond a CU's 160 KB) or RTC_WF_LDS=0.
-unsigned rtc_wavefront_lds_bytes(const DScene& S) {
-  static const bool off = [] { const char* e = std::getenv("RTC_WF_LDS"); return e && e[0] == '0'; }();
-  if (off || !rtc_v_lds(RTC_VARIANTS[rtc_variant(S, true)])) return 0;
-  const unsigned long long need = rtc_lds_table_bytes(S) + (unsigned long long)RTC_LDS_BLOCK * (unsigned)S.bvh_stack * sizeof(int);
-  return need <= 158ull * 1024 ? (unsigned)need : 0u;
+// scene does not qualify (program not in the kernel arguments, tables + stacks beyond a CU's 160 KB) or `enabled` is false (RTC_WF_LDS=0
+// when the scene was created; the emulator, which has no LDSC build).
+unsigned rtc_wavefront_lds_bytes(const DScene& S, bool enabled) {
+#ifdef RTC_EMU
+  enabled = false;
+#endif
+  return rtc_pick_lds_bytes(RTC_VARIANTS[rtc_variant(S, true)], enabled, rtc_lds_table_bytes(S), S.bvh_stack);
 }
+// wf_shade build of one level of a frame (the emulator has no UV builds: no entry point of it creates a UV scene)
+static RtcWfShadeBuild rtc_scene_shade_build(const DScene& S, bool count, bool level0) {
+#ifdef RTC_EMU
+  const bool uv = false;
+#else
+  const bool uv = S.has_uv != 0;
+#endif
+  return rtc_pick_wf_shade_build(count, uv, S.all_plain != 0, level0);
+}
+
+// The dispatch of a launch of scene S, read-only (rtc.h rtc_scene_kernel_info): the same functions the launchers below call.
+// lds_bytes: rtc_wavefront_lds_bytes of the scene; big_scene: rtc_big_scene of its device bytes; device: the scene's.
+void rtc_kernel_info_fill(const DScene& S, bool wavefront, bool count, bool big_scene, unsigned lds_bytes, int device, rtc_kernel_info* out) {
+  const int v = rtc_variant(S, wavefront);
+  out->variant = v;
+  out->n_kops = S.n_kops; out->n_kplanes = S.n_kplanes; out->n_kaux = 0;
+  for (int i = 0; i < S.n_kops; i++) if ((S.kops[i].op == OP_BVH || S.kops[i].op == OP_MESH) && S.kops[i].pad[0] >= 0) out->n_kaux++;
+  out->has_recs = S.has_recs; out->all_plain = S.all_plain; out->no_glass_mirror = S.no_glass_mirror;
+  out->big_scene = big_scene ? 1 : 0;
+  out->n_bvh_nodes = S.n_bvh; out->n_recs = S.n_recs; out->n_mesh_tris = S.n_mtri; out->has_mesh = S.has_mesh; out->bvh_stack = S.bvh_stack;
+  out->lds_bytes = wavefront ? lds_bytes : 0u;
+  out->lds_refused = 0;
+#ifndef RTC_EMU
+  // (the one choice that is made at launch time: a device that refuses the LDS size gets the memory build, rtc_launch_wavefront)
+  if (wavefront && lds_bytes && rtc_ops(v).wf_ts_lds_refused && rtc_ops(v).wf_ts_lds_refused(device)) out->lds_refused = 1;
+#endif
+  out->trace_build = out->wf_ts_build = out->wf_shade_build0 = out->wf_shade_build = -1;
+  if (wavefront) {
+    out->wf_ts_build = rtc_pick_wf_ts_build(count, lds_bytes != 0);
+    out->wf_shade_build0 = rtc_scene_shade_build(S, count, true);
+    out->wf_shade_build = rtc_scene_shade_build(S, count, false);
+  } else {
+    out->trace_build = rtc_pick_trace_build(RTC_VARIANTS[v], count, big_scene, S.all_plain != 0, S.no_glass_mirror != 0);
+  }
+}
+bool rtc_scene_is_big(unsigned long long scene_bytes) { return rtc_big_scene(scene_bytes); }
+
+#ifndef RTC_EMU
 
 // Grid of the wavefront traversal kernel: as many one-wave blocks as the chip holds at once (the kernel hands out chunks
 // itself), from the occupancy the runtime reports for this scene's variant and LDS stack size.
@@ -288,15 +326,14 @@ uint64_t rtc_wavefront_work(const DCamera& cam, const DPixelMap& pm) {
 
 // One frame through the wavefront kernels.  The caller zeroed W.counts (RTC_WF_COUNTS entries) on the stream and sized the
 // arrays for W.cap >= the work ids of the launch and fuel + 1 levels; `blocks` / `shade_blocks` = grid sizes of the traversal /
-// shading kernels.
+// shading kernels; `lds` = the scene's rtc_wavefront_lds_bytes (0, the default: tables in memory -- all a caller without LDSC builds can ask for).
 void rtc_launch_wavefront(const DScene& S, const DCamera& cam, const DPixelMap& pm, int fuel, const DWave& W, double* rgb, double* hit_t, int* hit_prim, int* hit_k,
-                          DStats* stats, bool count, hipStream_t stream, unsigned blocks, unsigned shade_blocks) {
+                          DStats* stats, bool count, hipStream_t stream, unsigned blocks, unsigned shade_blocks, unsigned lds = 0u) {
   if (pm.n == 0) return;
   const RtcVariantOps& ops = rtc_ops(rtc_variant(S, true));
   const RtcFrame F = {S, cam, pm, hit_t, hit_prim, hit_k, stats, stream, count};
   const unsigned n0 = (unsigned)rtc_wavefront_work(cam, pm);
 #ifndef RTC_EMU
-  const unsigned lds = rtc_wavefront_lds_bytes(S);
   const unsigned lds_blocks = std::max(1u, shade_blocks / 2u);  // one block per CU (the shading grid is two per CU)
 #endif
   const dim3 sgrid(std::max(1u, shade_blocks)), sblock(RTC_WF_SHADE_BLOCK);
@@ -309,17 +346,18 @@ void rtc_launch_wavefront(const DScene& S, const DCamera& cam, const DPixelMap& 
 #endif
     ops.launch_wf_ts(F, RtcLevel{W, tl, sl, n0, level, fuel - level, blocks, 0u});
     if (level <= fuel) {
+      switch (rtc_scene_shade_build(S, count, level == 0)) {
 #ifndef RTC_EMU
-      if (S.has_uv) {
-        if (count) hipLaunchKernelGGL((wf_shade<true, true, true>), sgrid, sblock, 0, stream, S, cam, pm, W, level, n0, fuel, stats);
-        else hipLaunchKernelGGL((wf_shade<false, true, true>), sgrid, sblock, 0, stream, S, cam, pm, W, level, n0, fuel, stats);
-        continue;
-      }
+        case RTC_SH_COUNT_UV: hipLaunchKernelGGL((wf_shade<true, true, true>), sgrid, sblock, 0, stream, S, cam, pm, W, level, n0, fuel, stats); break;
+        case RTC_SH_UV: hipLaunchKernelGGL((wf_shade<false, true, true>), sgrid, sblock, 0, stream, S, cam, pm, W, level, n0, fuel, stats); break;
+#else
+        case RTC_SH_COUNT_UV: case RTC_SH_UV: break;  // (never picked here: rtc_scene_shade_build)
 #endif
-      if (count) hipLaunchKernelGGL((wf_shade<true>), sgrid, sblock, 0, stream, S, cam, pm, W, level, n0, fuel, stats);
-      else if (S.all_plain && level == 0) hipLaunchKernelGGL((wf_shade<false, false, false, true, true>), sgrid, sblock, 0, stream, S, cam, pm, W, level, n0, fuel, stats);
-      else if (S.all_plain) hipLaunchKernelGGL((wf_shade<false, false, false, true, false>), sgrid, sblock, 0, stream, S, cam, pm, W, level, n0, fuel, stats);
-      else hipLaunchKernelGGL((wf_shade<false>), sgrid, sblock, 0, stream, S, cam, pm, W, level, n0, fuel, stats);
+        case RTC_SH_COUNT: hipLaunchKernelGGL((wf_shade<true>), sgrid, sblock, 0, stream, S, cam, pm, W, level, n0, fuel, stats); break;
+        case RTC_SH_PIPE_LV0: hipLaunchKernelGGL((wf_shade<false, false, false, true, true>), sgrid, sblock, 0, stream, S, cam, pm, W, level, n0, fuel, stats); break;
+        case RTC_SH_PIPE: hipLaunchKernelGGL((wf_shade<false, false, false, true, false>), sgrid, sblock, 0, stream, S, cam, pm, W, level, n0, fuel, stats); break;
+        case RTC_SH_PAT: hipLaunchKernelGGL((wf_shade<false>), sgrid, sblock, 0, stream, S, cam, pm, W, level, n0, fuel, stats); break;
+      }
     }
   }
   hipLaunchKernelGGL(wf_gather, dim3(std::max(1u, std::min(blocks, (n0 + 255u) / 256u))), dim3(256), 0, stream, cam, pm, W, n0, rgb);

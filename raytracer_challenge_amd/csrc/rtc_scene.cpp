@@ -34,10 +34,12 @@ void rtc_launch_pack_hits(const double* t, const int* prim, const int* k, DHit* 
 void rtc_launch_deinterleave(const double* slab, double* image, unsigned rowlen, unsigned vsize, unsigned n, unsigned max_rows, unsigned band, hipStream_t stream);
 void rtc_launch_deinterleave8(const unsigned char* slab, unsigned char* image, unsigned rowlen, unsigned vsize, unsigned n, unsigned max_rows, unsigned band, hipStream_t stream);
 void rtc_launch_wavefront(const DScene& S, const DCamera& cam, const DPixelMap& pm, int fuel, const DWave& W, double* rgb, double* hit_t, int* hit_prim, int* hit_k,
-                          DStats* stats, bool count, hipStream_t stream, unsigned blocks, unsigned shade_blocks);
+                          DStats* stats, bool count, hipStream_t stream, unsigned blocks, unsigned shade_blocks, unsigned lds);
+void rtc_kernel_info_fill(const DScene& S, bool wavefront, bool count, bool big_scene, unsigned lds_bytes, int device, rtc_kernel_info* out);
+bool rtc_scene_is_big(unsigned long long scene_bytes);
 uint64_t rtc_wavefront_work(const DCamera& cam, const DPixelMap& pm);
 unsigned rtc_wavefront_grid(const DScene& S, int n_cu);
-unsigned rtc_wavefront_lds_bytes(const DScene& S);
+unsigned rtc_wavefront_lds_bytes(const DScene& S, bool enabled);
 void rtc_launch_gen_rays(const DCamera& cam, const DPixelMap& pm, const rtc_sampling& sp, unsigned long long slot_first, unsigned long long n_slots, double* rays,
                          hipStream_t stream);
 void rtc_launch_resolve_samples(const double* ray_rgb, unsigned n_samples, unsigned long long n_slots, double* dst, hipStream_t stream);
@@ -119,6 +121,7 @@ struct rtc_scene {
   uint64_t wave_cap = 0;
   int wave_levels = 0;
   unsigned wave_blocks = 0, shade_blocks = 0;
+  unsigned lds_bytes = 0;     // dynamic LDS of the wavefront traversal kernel (0: tables in memory; RTC_WF_LDS=0 at creation pins that)
   unsigned wave_eighths = 9;  // queue capacity per level, in eighths of the launch's level-0 work ids
   int bvh_depth = 0;
   int built_on_device = 0;  // mesh accelerators of this scene whose tree came from bvh_device.hip
@@ -351,9 +354,9 @@ int run(rtc_scene* s, const DCamera& cam, DPixelMap pm, int fuel, double* d_rgb,
     }
     HIP_OK(hipMemsetAsync(s->wave.counts, 0, RTC_WF_COUNTS * sizeof(uint32_t), s->stream));
     HIP_OK(hipEventRecord(s->ev0, s->stream));
-    rtc_launch_wavefront(s->d, cam, pm, fuel, s->wave, d_rgb, want_hits ? s->d_hit_t : nullptr, s->d_hit_prim, s->d_hit_k, s->d_stats, count, s->stream, s->wave_blocks, s->shade_blocks);
+    rtc_launch_wavefront(s->d, cam, pm, fuel, s->wave, d_rgb, want_hits ? s->d_hit_t : nullptr, s->d_hit_prim, s->d_hit_k, s->d_stats, count, s->stream, s->wave_blocks, s->shade_blocks, s->lds_bytes);
   } else {
-    rtc_launch_trace(s->d, cam, pm, fuel, d_rgb, want_hits ? s->d_hit_t : nullptr, s->d_hit_prim, s->d_hit_k, s->d_stats, count, s->stream, s->bytes > (32ull << 20));
+    rtc_launch_trace(s->d, cam, pm, fuel, d_rgb, want_hits ? s->d_hit_t : nullptr, s->d_hit_prim, s->d_hit_k, s->d_stats, count, s->stream, rtc_scene_is_big(s->bytes));
   }
   HIP_OK(hipGetLastError());
   HIP_OK(hipEventRecord(s->ev1, s->stream));
@@ -972,6 +975,9 @@ int scene_create(const rtc_scene_desc* desc, bool ex, const rtc_light_ex* lx, ui
     const char* kv = std::getenv("RTC_KERNEL");
     const int kvi = kv ? std::atoi(kv) : 0;
     s->kernel_version = (kvi == 1 || kvi == 4) ? kvi : 0;
+    // RTC_WF_LDS=0: the wavefront traversal reads this scene's tables from memory (A/B runs, the build tests); pinned here likewise
+    const char* le = std::getenv("RTC_WF_LDS");
+    s->lds_bytes = rtc_wavefront_lds_bytes(s->d, !(le && le[0] == '0'));
     // hipDeviceGetAttribute, not hipGetDeviceProperties: the property struct's layout differs between ROCm releases and
     // this library may run on the HIP runtime PyTorch loaded first.
     int n_cu = 0;
@@ -1874,7 +1880,14 @@ int rtc_bvh_collapse_raw(const void* nodes, uint32_t n_nodes, int32_t root, int3
   return rc > 0 ? rtc_fail(rc, err) : rc;
 }
 
-uint32_t rtc_scene_wavefront_lds_bytes(const rtc_scene* s) { return s ? rtc_wavefront_lds_bytes(s->d) : 0u; }
+uint32_t rtc_scene_wavefront_lds_bytes(const rtc_scene* s) { return s ? s->lds_bytes : 0u; }
+
+int rtc_scene_kernel_info(const rtc_scene* s, int32_t path, int32_t count, rtc_kernel_info* out) {
+  if (!s || !out) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  if (path != 1 && path != 4) return rtc_fail(RTC_ERR_INVALID, "path must be 1 (one kernel) or 4 (wavefront)");
+  rtc_kernel_info_fill(s->d, path == 4, count != 0, rtc_scene_is_big(s->bytes), s->lds_bytes, s->device, out);
+  return RTC_OK;
+}
 
 void rtc_scene_accel_info(const rtc_scene* s, uint32_t* n_ops, uint32_t* n_bvh_nodes, uint32_t* n_mesh_tris, uint32_t* bvh_depth) {
   if (n_ops) *n_ops = s ? (uint32_t)s->d.n_ops : 0;

@@ -766,7 +766,8 @@ struct HostArrays {
     if (std::getenv("RTC_NO_KOPS")) return;
     // (per-primitive gates — has_groups == 2 — do not change the op sequence: the gate is part of a primitive's own test.  Kernel
     // variant 5 serves such programs; RTC_KOPS_GROUPS=0 sends them back to the program in memory.)
-    static const bool kops_groups = [] { const char* e = std::getenv("RTC_KOPS_GROUPS"); return !(e && e[0] == '0'); }();
+    const char* kg = std::getenv("RTC_KOPS_GROUPS");  // (read per scene, as RTC_NO_KOPS is)
+    const bool kops_groups = !(kg && kg[0] == '0');
     if (ops.size() > RTC_KOPS || d.has_csg || (d.has_groups == 2 && !kops_groups)) return;
     for (const DOp& o : ops) if (o.op == OP_GROUP || o.op == OP_CSG || o.op == OP_CSG_END) return;
     int n_aux = 0;

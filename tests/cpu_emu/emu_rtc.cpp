@@ -27,6 +27,7 @@ static int efail(int c, const std::string& m) { g_err = m; return c; }
 
 static int run(rtc_scene* s, const DCamera& cam, DPixelMap pm, int fuel, double* rgb, rtc_hit* hits, rtc_stats* stats, unsigned long long* digest = nullptr) {
   pm.digest = digest;
+  const bool count = stats != nullptr || digest != nullptr;  // as the product: the counting builds only where counters or digests are wanted
   if (fuel < 0) fuel = 0;
   if (fuel > RTC_MAX_FUEL) return efail(RTC_ERR_UNSUPPORTED, "fuel exceeds RTC_MAX_FUEL");
   if (s->d.n_lights == 0) fuel = 0;  // as rtc_scene.cpp run(): no lights, no secondary rays (src/world.rs:58-79)
@@ -55,16 +56,16 @@ static int run(rtc_scene* s, const DCamera& cam, DPixelMap pm, int fuel, double*
       if (digest) W.dig = dig.data();
       std::memset(W.counts, 0, RTC_WF_COUNTS * sizeof(uint32_t));
       std::memset(&st, 0, sizeof(st));
-      rtc_launch_wavefront(s->d, cam, pm, fuel, W, rgb, hits ? t.data() : nullptr, p.data(), k.data(), &st, true, nullptr, 5, 3);
+      rtc_launch_wavefront(s->d, cam, pm, fuel, W, rgb, hits ? t.data() : nullptr, p.data(), k.data(), &st, count, nullptr, 5, 3);
       done = W.counts[RTC_WF_OVERFLOW] == 0;
       if (done) n_launches = 2u * (unsigned)fuel + 4u;
     }
     if (!done) {  // as the product does beyond its memory budget: render again with the one-kernel path
       std::memset(&st, 0, sizeof(st));
-      rtc_launch_trace(s->d, cam, pm, fuel, rgb, hits ? t.data() : nullptr, p.data(), k.data(), &st, true, nullptr, false);
+      rtc_launch_trace(s->d, cam, pm, fuel, rgb, hits ? t.data() : nullptr, p.data(), k.data(), &st, count, nullptr, false);
     }
   } else {
-    rtc_launch_trace(s->d, cam, pm, fuel, rgb, hits ? t.data() : nullptr, p.data(), k.data(), &st, true, nullptr, false);
+    rtc_launch_trace(s->d, cam, pm, fuel, rgb, hits ? t.data() : nullptr, p.data(), k.data(), &st, count, nullptr, false);
   }
   if (hits) for (uint64_t i = 0; i < pm.n; i++) hits[i] = {t[i], p[i], k[i]};
   if (stats) {
@@ -194,6 +195,12 @@ void rtc_scene_path_info(const rtc_scene*, int32_t* choice, double* one_kernel_m
   if (wavefront_ms) *wavefront_ms = -1.0;
 }
 uint32_t rtc_scene_wavefront_lds_bytes(const rtc_scene*) { return 0; }
+// the dispatch query through the product's own selection functions (no LDS-resident build here, and no scene is called big: run() above)
+int rtc_scene_kernel_info(const rtc_scene* s, int32_t path, int32_t count, rtc_kernel_info* out) {
+  if (!s || !out || (path != 1 && path != 4)) return efail(RTC_ERR_INVALID, "bad argument");
+  rtc_kernel_info_fill(s->d, path == 4, count != 0, false, 0u, 0, out);
+  return RTC_OK;
+}
 int rtc_scene_bvh_built_on_device(const rtc_scene*) { return 0; }
 // the builder hooks: the host builder as in the product; there is no device builder, so where = 1 is always declined
 int rtc_bvh_build_raw(const double* boxes, uint32_t n, int32_t leaf_max, uint32_t base, int32_t where, void* nodes, uint32_t nodes_cap, uint32_t* n_nodes, uint32_t* order,
