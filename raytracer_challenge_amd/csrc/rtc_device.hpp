@@ -1931,6 +1931,15 @@ __device__ __forceinline__ const double* shade_rec_material(const DScene& S, con
   else { cr = r[6 * cap + s]; cg = r[7 * cap + s]; cb = r[8 * cap + s]; }
   return M;
 }
+// The same for a record whose sr_mat the caller has already loaded.
+__device__ __forceinline__ const double* shade_rec_material_row(const DScene& S, const DWave& W, unsigned s, int mrow, double& cr, double& cg, double& cb) {
+  const double* r = W.sr;
+  const size_t cap = W.cap;
+  const double* M = S.mat + 8 * (mrow & (RTC_SR_PLAIN - 1));
+  if (mrow & RTC_SR_PLAIN) { cr = M[4]; cg = M[5]; cb = M[6]; }
+  else { cr = r[6 * cap + s]; cg = r[7 * cap + s]; cb = r[8 * cap + s]; }
+  return M;
+}
 
 }  // namespace
 
@@ -1990,13 +1999,18 @@ __device__ __forceinline__ void wf_trace_ray(const DScene& S, const DCamera& cam
 }
 
 // wf_ts work item of the shadow role: shade record s of `level` (per light: shadow ray, then the Phong terms).
-template <int FEAT, bool KOPS, bool LDSC>
+// EARLY: the record's two indices (DWave.sr_mat, sr_node) are loaded with its point, in front of the shadow rays, so that behind the
+// last traversal the normal, the material row and the view rows are requested together and not in two dependent trips.  Two VGPRs
+// more are live across the traversals: the builds that would pay for them with scratch load the indices where they are used.
+template <int FEAT, bool KOPS, bool LDSC, bool EARLY>
 __device__ __forceinline__ void wf_shadow_rec(const DScene& S, const DCamera& cam, const DPixelMap& pm, const DWave& W, const WorkMap& wm, int level, unsigned s, int* stack,
                                               int stride, Counters& C, unsigned& n_shadow, const LdsScene& L) {
   const size_t cap = W.cap;
   double* cb = W.contrib + (size_t)level * 3 * cap;
   const double* r = W.sr;
   const double px = r[s], py = r[cap + s], pz = r[2 * cap + s];
+  int mrow_early = 0, node_early = 0;
+  if constexpr (EARLY) { mrow_early = W.sr_mat[s]; node_early = W.sr_node[s]; }
   // World::shade_hit (src/world.rs:50-82): per light, shadow test + Phong (src/shape.rs:429-462).  First every shadow
   // ray (only the point is live across the traversals), then the Phong terms with the rest of the record.
   // (light_is_behind() is not used here: on the scenes this path serves few lights are behind their surfaces -- most hits are on the
@@ -2022,8 +2036,15 @@ __device__ __forceinline__ void wf_shadow_rec(const DScene& S, const DCamera& ca
   DIAG_SPAN_BEGIN();
   const double nx = r[3 * cap + s], ny = r[4 * cap + s], nz = r[5 * cap + s];
   double cr, cg, cbl;
-  const double* M = shade_rec_material(S, W, s, cr, cg, cbl);
-  const int node = W.sr_node[s];
+  const double* M;
+  int node;
+  if constexpr (EARLY) {
+    M = shade_rec_material_row(S, W, s, mrow_early, cr, cg, cbl);
+    node = node_early;
+  } else {
+    M = shade_rec_material(S, W, s, cr, cg, cbl);
+    node = W.sr_node[s];
+  }
   const RecView v = shade_rec_view(cam, pm, W, wm, level, node);
   double sr = 0.0, sg = 0.0, sb = 0.0;
   for (int l = 0; l < S.n_lights * ((RTC_PROBE & 8) ? 2 : 1); l++) {
@@ -2125,7 +2146,7 @@ __global__ void __launch_bounds__(LDSC ? RTC_LDS_BLOCK : RTC_BLOCK, (KOPS || FEA
         if (s < ns) {
           DIAG_SPAN_BEGIN();
           if constexpr (AREA) wf_shadow_rec_area<FEAT, KOPS, LDSC, SPOT>(S, cam, pm, W, wm, sl, s, stack, stride, C, n_shadow, L);
-          else wf_shadow_rec<FEAT, KOPS, LDSC>(S, cam, pm, W, wm, sl, s, stack, stride, C, n_shadow, L);
+          else wf_shadow_rec<FEAT, KOPS, LDSC, KOPS && !COUNT && FEAT <= RTC_WF_TS_WAVES_MAXFEAT>(S, cam, pm, W, wm, sl, s, stack, stride, C, n_shadow, L);
           DIAG_SPAN_END(7);
         }
       }
