@@ -583,6 +583,19 @@ int rtc_bvh_build_raw(const double* boxes, uint32_t n, int32_t leaf_max, uint32_
  * for NULL arguments, a root or child reference outside the array, or a node that is reached twice. */
 int rtc_bvh_collapse_raw(const void* nodes, uint32_t n_nodes, int32_t root, int32_t* depth, int32_t* stack_need);
 
+/* Test hook: ONE light-grid build on the caller's primitives and one light position, handed back raw, through the
+ * function a scene's build calls; host only, no device, no scene.  Primitive k is geometry[k] (RTC_SPHERE..; no planes), limits[2k..2k+1]
+ * (cylinder / cone {min, max}, finite; others: ignored), transform_inv + 16 k (world -> object, row major, as rtc_xform) and, for triangles,
+ * tris + 9 k ({p1, e1, e2}; tris may be NULL when there is no triangle).  n = cells per face edge (2..512); max_list = the longest list
+ * a cell may hold (at least 8; a scene takes its traversal stack's depth); tight = 0: the rectangle lists of RTC_LIGHT_GRID_TIGHT=0.
+ * Outputs: cells[6 n n + 1] = per cell (face, v, u) the index of its first item, the last entry = *n_items; items = *n_items pairs
+ * {leaf reference = ~(k << 3), f32 bits of the lower bound of the primitive's distance from the light}, per cell sorted by (distance,
+ * k); a cell with more than max_list candidates holds the one reference 0x7fffffff (its rays walk the BVH).  *n_items is written
+ * whenever a grid was built.  Returns RTC_OK; -1 when the build declines (over its work budget, or most cells over-full);
+ * RTC_ERR_INVALID for NULL arguments, n out of range, a primitive without bounds, or a capacity that is too small. */
+int rtc_light_grid_build_raw(const int32_t* geometry, const double* limits, const double* transform_inv, const double* tris, uint32_t n_prims, const double* light, int32_t n,
+                             int32_t max_list, int32_t tight, uint32_t* cells, uint32_t cells_cap, int32_t* items, uint32_t items_cap, uint32_t* n_items);
+
 /* Dynamic LDS (bytes per block) the wavefront traversal kernel uses for this scene: > 0 = the scene's accelerator nodes, intersection
  * records and mesh triangles are copied into every CU's LDS and walks read them there (small scenes: the tables and the traversal
  * stacks fit 160 KB); 0 = they are read from memory.  bench.py's byte accounting counts LDS-resident records as 0 bytes. */

@@ -1879,6 +1879,12 @@ int rtc_bvh_collapse_raw(const void* nodes, uint32_t n_nodes, int32_t root, int3
   const int rc = rtb::bvh_collapse_raw(nodes, n_nodes, root, depth, stack_need, &err);
   return rc > 0 ? rtc_fail(rc, err) : rc;
 }
+int rtc_light_grid_build_raw(const int32_t* geometry, const double* limits, const double* transform_inv, const double* tris, uint32_t n_prims, const double* light, int32_t n,
+                             int32_t max_list, int32_t tight, uint32_t* cells, uint32_t cells_cap, int32_t* items, uint32_t items_cap, uint32_t* n_items) {
+  std::string err;
+  const int rc = rtb::light_grid_build_raw(geometry, limits, transform_inv, tris, n_prims, light, n, max_list, tight, cells, cells_cap, items, items_cap, n_items, &err);
+  return rc > 0 ? rtc_fail(rc, err) : rc;
+}
 
 uint32_t rtc_scene_wavefront_lds_bytes(const rtc_scene* s) { return s ? s->lds_bytes : 0u; }
 

@@ -266,6 +266,145 @@ struct ProgramBuilder {
   // references the BVH itself would hand the walk: a shadow ray looks its cell up, puts the list on its traversal stack and runs
   // the walk's leaf loop — no frame, no node steps.  The lists are supersets of what the walk would reach (the walk also culls by
   // distance), the exact tests are the same, so the results are.  Returns 1 + index of light 0's grid in qgrids, 0 = not built.
+  //
+  // "Bounds" are two things.  The primitive's world box gives a rectangle of cells per cube-map face: the outer bound, and what the
+  // work budget counts.  Inside the rectangle the primitive is entered only into the cells that the outline of a convex polytope K
+  // touches (RTC_LIGHT_GRID_TIGHT=0: into all of them).  K holds every point the exact test can report, the same set
+  // local_bounds(for_accel) bounds, so seen from the light no such point lies outside K's outline; a box seen along its diagonal
+  // fills little more than half of its rectangle.  Where the construction is not safe the rectangle stands (silhouette_vertices,
+  // silhouette_spans below).
+  struct LightRect { int32_t face, u0, u1, v0, v1, ref; float dmin; int32_t span; };  // span: first of v1 - v0 + 1 {first, last} cell pairs in `spans`; -1: every cell
+  static constexpr int kSilhouetteMax = 32;
+
+  // The vertices of K in world space -> out, their number; 0: no K (the rectangle stands).  Object-space vertices through the
+  // primitive's forward matrix, then moved away from their centroid by a relative 1e-6 (the exact tests round in f64).
+  //   cube: the corners of the padded box;  cylinder, cone: two rings of a 12-gon around the circle of local_bounds' radius;
+  //   triangle: its vertices;  sphere: with l' the light in object space, the tangent cone from l' touches the unit sphere in a circle
+  //   of radius sqrt(1 - 1/|l'|^2) in the plane at 1/|l'| from the centre: a 16-gon around that circle.  The cone from l' over the
+  //   polygon contains the cone over the circle, which contains the sphere, and an affine map keeps both containments: the polygon's
+  //   outline seen from the light contains the ellipsoid's.
+  int silhouette_vertices(const rtc_prim& p, const double o[3], double out[kSilhouetteMax][3]) const {
+    double lo[3], hi[3], q[kSilhouetteMax][3];
+    if (!local_bounds(p, lo, hi, true)) return 0;
+    const rth::M4 inv = rth::M4::from(D.xforms[p.xform].transform_inv);
+    rth::M4 fwd;
+    if (!inv.invert(&fwd)) return 0;
+    const double kPi = 3.14159265358979323846;
+    int nv = 0;
+    switch (p.geometry) {
+      case RTC_CUBE:
+        for (int k = 0; k < 8; k++, nv++) { q[nv][0] = (k & 4) ? hi[0] : lo[0]; q[nv][1] = (k & 2) ? hi[1] : lo[1]; q[nv][2] = (k & 1) ? hi[2] : lo[2]; }
+        break;
+      case RTC_CYLINDER:
+      case RTC_CONE: {
+        const int K = 12;
+        const double r = hi[0] / std::cos(kPi / K);
+        for (int ring = 0; ring < 2; ring++)
+          for (int k = 0; k < K; k++, nv++) { q[nv][0] = r * std::cos(2.0 * kPi * k / K); q[nv][1] = ring ? hi[1] : lo[1]; q[nv][2] = r * std::sin(2.0 * kPi * k / K); }
+        break;
+      }
+      case RTC_SPHERE: {
+        const int K = 16;
+        const rth::V4 lp = inv.apply(rth::pt(o[0], o[1], o[2]));
+        const double d = std::sqrt(lp.x * lp.x + lp.y * lp.y + lp.z * lp.z);
+        if (!(d > 1.0 + 1e-3) || !std::isfinite(d)) return 0;  // the light is inside the sphere or nearly on it
+        const double a[3] = {lp.x / d, lp.y / d, lp.z / d}, h = 1.0 / d, rho = std::sqrt(1.0 - h * h) / std::cos(kPi / K);
+        const int t = std::fabs(a[0]) <= std::fabs(a[1]) && std::fabs(a[0]) <= std::fabs(a[2]) ? 0 : (std::fabs(a[1]) <= std::fabs(a[2]) ? 1 : 2);
+        double e1[3], e2[3], x[3] = {0.0, 0.0, 0.0};  // e1 = a x axis t (the axis a is furthest from), e2 = a x e1
+        x[t] = 1.0;
+        e1[0] = a[1] * x[2] - a[2] * x[1]; e1[1] = a[2] * x[0] - a[0] * x[2]; e1[2] = a[0] * x[1] - a[1] * x[0];
+        const double l1 = std::sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]);
+        if (!(l1 > 0.5)) return 0;
+        for (int c = 0; c < 3; c++) e1[c] /= l1;
+        e2[0] = a[1] * e1[2] - a[2] * e1[1]; e2[1] = a[2] * e1[0] - a[0] * e1[2]; e2[2] = a[0] * e1[1] - a[1] * e1[0];
+        for (int k = 0; k < K; k++, nv++) {
+          const double cs = rho * std::cos(2.0 * kPi * k / K), sn = rho * std::sin(2.0 * kPi * k / K);
+          for (int c = 0; c < 3; c++) q[nv][c] = h * a[c] + cs * e1[c] + sn * e2[c];
+        }
+        break;
+      }
+      case RTC_PLANE: return 0;
+      default: {
+        const double* g = D.tri_p1e1e2 + 9 * (size_t)p.data;
+        for (int k = 0; k < 3; k++, nv++)
+          for (int c = 0; c < 3; c++) q[nv][c] = k == 0 ? g[c] : g[c] + g[3 * k + c];
+        break;
+      }
+    }
+    double cen[3] = {0.0, 0.0, 0.0};
+    for (int k = 0; k < nv; k++) {
+      const rth::V4 w = fwd.apply(rth::pt(q[k][0], q[k][1], q[k][2]));
+      out[k][0] = w.x; out[k][1] = w.y; out[k][2] = w.z;
+      for (int c = 0; c < 3; c++) { if (!std::isfinite(out[k][c])) return 0; cen[c] += out[k][c] / nv; }
+    }
+    for (int k = 0; k < nv; k++)
+      for (int c = 0; c < 3; c++) { out[k][c] = cen[c] + (out[k][c] - cen[c]) * (1.0 + 1e-6); if (!std::isfinite(out[k][c])) return 0; }
+    return nv;
+  }
+
+  // K's outline on one face of the light's cube map, as cells: per row of r's rectangle the first and last cell (within the
+  // rectangle) that the outline touches, appended to `spans` (first > last: none).  The vertices, all in front of the face plane,
+  // project to points whose convex hull is the outline (a projection from a point keeps convexity on its near side); the hull cut
+  // by a row's band is convex, so the extent in u of the hull's edges clipped to the band is exact: rows x hull edges, no test per
+  // cell.  false, nothing appended: a vertex not clearly in front of the plane (the light is inside K, on it, or K reaches round the
+  // light), or a value that is not finite: the rectangle stands.
+  static bool silhouette_spans(const double (*vtx)[3], int nv, const double o[3], int n, const LightRect& r, std::vector<int32_t>& spans) {
+    const int ax = r.face >> 1, iu = ax == 0 ? 1 : 0, iv = ax == 2 ? 1 : 2;
+    const double s = (r.face & 1) ? -1.0 : 1.0;
+    double ext = 0.0;
+    for (int k = 1; k < nv; k++)
+      for (int c = 0; c < 3; c++) ext = std::fmax(ext, std::fabs(vtx[k][c] - vtx[0][c]));
+    struct P2 { double u, v; };
+    P2 pt[kSilhouetteMax], hull[2 * kSilhouetteMax];
+    for (int k = 0; k < nv; k++) {
+      const double m = s * (o[ax] - vtx[k][ax]);
+      if (!(m > 1e-6 * ext) || !(m > 0.0)) return false;
+      pt[k] = {(o[iu] - vtx[k][iu]) / m, (o[iv] - vtx[k][iv]) / m};
+      if (!std::isfinite(pt[k].u) || !std::isfinite(pt[k].v)) return false;
+    }
+    std::sort(pt, pt + nv, [](const P2& x, const P2& y) { return x.u < y.u || (x.u == y.u && x.v < y.v); });
+    auto cross = [](const P2& a, const P2& b, const P2& c) { return (b.u - a.u) * (c.v - a.v) - (b.v - a.v) * (c.u - a.u); };
+    int nh = 0;
+    for (int k = 0; k < nv; k++) {  // monotone chain: lower hull, then upper
+      while (nh >= 2 && cross(hull[nh - 2], hull[nh - 1], pt[k]) <= 0.0) nh--;
+      hull[nh++] = pt[k];
+    }
+    for (int k = nv - 2, low = nh + 1; k >= 0; k--) {
+      while (nh >= low && cross(hull[nh - 2], hull[nh - 1], pt[k]) <= 0.0) nh--;
+      hull[nh++] = pt[k];
+    }
+    if (nh > 1) nh--;  // (the first point again)
+    const double tol = 1e-9;  // device and host may disagree on the cell of a direction on an edge
+    auto cell = [n](double u) {
+      int i = (int)((u + 1.0) * 0.5 * (double)n);
+      return i < 0 ? 0 : (i >= n ? n - 1 : i);
+    };
+    for (int row = r.v0; row <= r.v1; row++) {
+      double b0 = 2.0 * row / (double)n - 1.0, b1 = 2.0 * (row + 1) / (double)n - 1.0;
+      b0 -= tol * (1.0 + std::fabs(b0)); b1 += tol * (1.0 + std::fabs(b1));
+      double umin = rth::kInf, umax = -rth::kInf;
+      for (int k = 0; k < nh; k++) {
+        const P2 &a = hull[k], &b = hull[(k + 1) % nh];
+        if ((a.v < b0 && b.v < b0) || (a.v > b1 && b.v > b1)) continue;
+        double t0 = 0.0, t1 = 1.0;
+        if (a.v != b.v) {
+          const double ta = (b0 - a.v) / (b.v - a.v), tb = (b1 - a.v) / (b.v - a.v);
+          t0 = std::fmax(0.0, std::fmin(ta, tb)); t1 = std::fmin(1.0, std::fmax(ta, tb));
+        }
+        const double ua = a.u + t0 * (b.u - a.u), ub = a.u + t1 * (b.u - a.u);
+        umin = std::fmin(umin, std::fmin(ua, ub)); umax = std::fmax(umax, std::fmax(ua, ub));
+      }
+      int32_t c0 = 1, c1 = 0;
+      if (umin <= umax) {
+        umin -= tol * (1.0 + std::fabs(umin)); umax += tol * (1.0 + std::fabs(umax));
+        if (umin <= 1.0 && umax >= -1.0) { c0 = std::max(r.u0, cell(umin)); c1 = std::min(r.u1, cell(umax)); }  // (beyond the face: cell() would clamp it onto the border)
+      }
+      spans.push_back(c0);
+      spans.push_back(c1);
+    }
+    return true;
+  }
+
   int32_t build_light_grids(const std::vector<bvh::Item>& boxes, const std::vector<int32_t>& ids) {
     const char* e = std::getenv("RTC_LIGHT_GRID");
     if ((e && e[0] == '0') || D.n_lights == 0 || boxes.size() < 16) return 0;
@@ -275,6 +414,11 @@ struct ProgramBuilder {
     // ... and while the build stays cheap: a scene of 10^4-10^5 bounded primitives gets coarser grids
     int n = en ? std::min(512, std::max(2, std::atoi(en))) : (D.n_lights <= 4 ? 256 : (D.n_lights <= 16 ? 128 : 64));
     if (!en && boxes.size() > 8192) n = std::min(n, boxes.size() > 65536 ? 64 : 128);
+    const char* et = std::getenv("RTC_LIGHT_GRID_TIGHT");
+    return build_light_grids_n(boxes, ids, n, !(et && et[0] == '0'));
+  }
+  // (the builder hook of include/rtc.h, rtc_light_grid_build_raw, enters here)
+  int32_t build_light_grids_n(const std::vector<bvh::Item>& boxes, const std::vector<int32_t>& ids, const int n, const bool tight) {
     // Work budget: every box is counted into (and later written to) every cell its projection covers, so a light inside a cloud of
     // large boxes costs boxes x cells; beyond 64 entries per cell on average the lists would be thrown away as RTC_LIGHT_CELL_WALK
     // anyway: no grids then (shadow rays walk the BVH, as they did before round 2), whatever the scene.
@@ -286,11 +430,20 @@ struct ProgramBuilder {
     for (uint32_t l = 0; l < D.n_lights; l++) {
       const double* o = D.lights[l].origin;
       std::vector<uint32_t> count((size_t)6 * n * n + 1, 0u);
-      struct Rect { int32_t face, u0, u1, v0, v1, ref; float dmin; };
+      using Rect = LightRect;
       std::vector<Rect> rects;
+      std::vector<int32_t> spans;
+      size_t by_outline = 0;
       auto cell = [&](double u) {
         int i = (int)((u + 1.0) * 0.5 * (double)n);
         return i < 0 ? 0 : (i >= n ? n - 1 : i);
+      };
+      // fn(cell index) over the cells of r that the primitive is entered into: count[] and the fill pass see the same cells
+      auto for_cells = [&](const Rect& r, auto fn) {
+        for (int v = r.v0; v <= r.v1; v++) {
+          const int32_t* sp = r.span < 0 ? nullptr : &spans[(size_t)r.span + 2 * (size_t)(v - r.v0)];
+          for (int u = sp ? sp[0] : r.u0, u1 = sp ? sp[1] : r.u1; u <= u1; u++) fn(((size_t)r.face * n + v) * n + u);
+        }
       };
       bool ok = std::isfinite(o[0]) && std::isfinite(o[1]) && std::isfinite(o[2]);
       unsigned long long area = 0;
@@ -304,6 +457,8 @@ struct ProgramBuilder {
         for (int c = 0; c < 3; c++) { const double g = a[c] > 0.0 ? a[c] : (b[c] < 0.0 ? -b[c] : 0.0); d2 += g * g; }
         float dmin = (float)(std::sqrt(d2) * (1.0 - 1e-6));
         dmin = dmin > 0.0f ? std::nextafterf(dmin, 0.0f) : 0.0f;
+        double vtx[kSilhouetteMax][3];
+        int nv = -1;  // K's vertices: made for the first face that needs them
         for (int face = 0; face < 6 && ok; face++) {
           const int ax = face >> 1;
           const double m_lo = (face & 1) ? -b[ax] : a[ax], m_hi = (face & 1) ? -a[ax] : b[ax];  // range of the dominant |component|
@@ -321,12 +476,16 @@ struct ProgramBuilder {
             lo2[c] = std::fmax(lo, -1.0); hi2[c] = std::fmin(hi, 1.0);
           }
           if (none) continue;
-          Rect r{face, cell(lo2[0]), cell(hi2[0]), cell(lo2[1]), cell(hi2[1]), ref, dmin};
+          Rect r{face, cell(lo2[0]), cell(hi2[0]), cell(lo2[1]), cell(hi2[1]), ref, dmin, -1};
           area += (unsigned long long)(r.u1 - r.u0 + 1) * (unsigned long long)(r.v1 - r.v0 + 1);
           if (area > area_budget) { ok = false; break; }
+          if (tight && (r.u1 > r.u0 || r.v1 > r.v0)) {  // (one cell: nothing to leave out)
+            if (nv < 0) nv = silhouette_vertices(D.prims[ids[k]], o, vtx);
+            const size_t at = spans.size();
+            if (nv > 0 && at < 0x7fffffffu && silhouette_spans(vtx, nv, o, n, r, spans)) { r.span = (int32_t)at; by_outline++; }
+          }
           rects.push_back(r);
-          for (int v = r.v0; v <= r.v1; v++)
-            for (int u = r.u0; u <= r.u1; u++) count[((size_t)face * n + v) * n + u]++;
+          for_cells(r, [&](size_t c) { count[c]++; });
         }
       }
       if (!ok) {
@@ -345,7 +504,7 @@ struct ProgramBuilder {
         return 0;
       }
       if (std::getenv("RTC_TIMING"))
-        std::fprintf(stderr, "[rtc-timing]   light grid %u: n %d, %llu items, longest list %u, %u cells left to the BVH walk (more than %d candidates)\n", l, n, total, longest, walks, max_list);
+        std::fprintf(stderr, "[rtc-timing]   light grid %u: n %d, %llu items, longest list %u, %u cells left to the BVH walk (more than %d candidates), %zu of %zu rectangles cut to the outline\n", l, n, total, longest, walks, max_list, by_outline, rects.size());
       // a cell's items: pairs {leaf reference, dmin as f32 bits}, nearest to the light first (8-byte aligned for one load each)
       if (items.size() & 1u) items.push_back(0);
       DQuirkGrid g{n, (int32_t)qcell.size(), 0, 0};
@@ -356,14 +515,13 @@ struct ProgramBuilder {
       for (size_t c = 0; c < count.size(); c++) if (count[c] & 0x80000000u) { items[at[c]] = RTC_LIGHT_CELL_WALK; items[at[c] + 1] = 0; at[c] = 0xffffffffu; }
       std::sort(rects.begin(), rects.end(), [](const Rect& x, const Rect& y) { return x.dmin < y.dmin || (x.dmin == y.dmin && x.ref > y.ref); });
       for (const Rect& r : rects)
-        for (int v = r.v0; v <= r.v1; v++)
-          for (int u = r.u0; u <= r.u1; u++) {
-            uint32_t& w = at[((size_t)r.face * n + v) * n + u];
-            if (w == 0xffffffffu) continue;
-            items[w] = r.ref;
-            std::memcpy(&items[w + 1], &r.dmin, 4);
-            w += 2;
-          }
+        for_cells(r, [&](size_t c) {
+          uint32_t& w = at[c];
+          if (w == 0xffffffffu) return;
+          items[w] = r.ref;
+          std::memcpy(&items[w + 1], &r.dmin, 4);
+          w += 2;
+        });
       qgrids.push_back(g);
     }
     return (int32_t)g0 + 1;
@@ -605,6 +763,50 @@ struct ProgramBuilder {
     return true;
   }
 };
+
+// rtc_light_grid_build_raw (include/rtc.h) but for the error text: ONE light's grid over the caller's primitives through the scene
+// build's own build_light_grids_n; shared by the library and tests/cpu_emu.
+inline int light_grid_build_raw(const int32_t* geometry, const double* limits, const double* transform_inv, const double* tris, uint32_t n_prims, const double* light, int32_t n,
+                                int32_t max_list, int32_t tight, uint32_t* cells, uint32_t cells_cap, int32_t* items, uint32_t items_cap, uint32_t* n_items, std::string* err) {
+  if (!geometry || !limits || !transform_inv || !light || !cells || !items || !n_items) { *err = "NULL argument"; return RTC_ERR_INVALID; }
+  if (n_prims == 0 || n < 2 || n > 512) { *err = "rtc_light_grid_build_raw: no primitives, or n outside 2..512"; return RTC_ERR_INVALID; }
+  std::vector<rtc_prim> prims(n_prims);
+  std::vector<rtc_xform> xf(n_prims);
+  for (uint32_t k = 0; k < n_prims; k++) {
+    if (geometry[k] < RTC_SPHERE || geometry[k] > RTC_SMOOTH_TRIANGLE || (geometry[k] >= RTC_TRIANGLE && !tris)) { *err = "rtc_light_grid_build_raw: unknown geometry, or a triangle without vertices"; return RTC_ERR_INVALID; }
+    prims[k] = rtc_prim{};
+    prims[k].geometry = geometry[k];
+    prims[k].xform = (int32_t)k;
+    prims[k].data = (int32_t)k;  // limits and triangle records are per primitive here
+    std::memcpy(xf[k].transform_inv, transform_inv + 16 * (size_t)k, sizeof(xf[k].transform_inv));
+    std::memcpy(xf[k].material_inv, xf[k].transform_inv, sizeof(xf[k].material_inv));
+  }
+  rtc_light lt{};
+  std::memcpy(lt.origin, light, sizeof(lt.origin));
+  rtc_scene_desc D{};
+  D.n_prims = n_prims; D.prims = prims.data();
+  D.n_xforms = n_prims; D.xforms = xf.data();
+  D.n_limits = n_prims; D.limits = limits;
+  D.n_tris = tris ? n_prims : 0; D.tri_p1e1e2 = tris;
+  D.n_lights = 1; D.lights = &lt;
+  ProgramBuilder pb{D};
+  std::vector<bvh::Item> boxes(n_prims);
+  std::vector<int32_t> ids(n_prims);
+  for (uint32_t k = 0; k < n_prims; k++) {
+    if (!pb.world_bounds(prims[k], &boxes[k])) { *err = "rtc_light_grid_build_raw: a primitive without bounds (a plane, an unbounded cylinder or cone, a singular matrix)"; return RTC_ERR_INVALID; }
+    ids[k] = (int32_t)k;
+  }
+  pb.max_stack = max_list - 1;
+  if (pb.build_light_grids_n(boxes, ids, n, tight != 0) == 0) return -1;
+  const size_t n_cells = (size_t)6 * n * n + 1;
+  if (pb.qcell.size() != n_cells) { *err = "rtc_light_grid_build_raw: the build left another number of cells"; return RTC_ERR_INVALID; }
+  const uint32_t first = pb.qcell[0];
+  *n_items = (pb.qcell[n_cells - 1] - first) / 2u;
+  if (n_cells > cells_cap || *n_items > items_cap) { *err = "rtc_light_grid_build_raw: a capacity is too small"; return RTC_ERR_INVALID; }
+  for (size_t c = 0; c < n_cells; c++) cells[c] = (pb.qcell[c] - first) / 2u;
+  std::memcpy(items, pb.items.data() + first, (size_t)*n_items * 2 * sizeof(int32_t));
+  return RTC_OK;
+}
 
 // Texture mapping (include/rtc.h RTC_PAT_UV): the UV pattern records and textures of rtc_scene_create_ext (none for the other entry
 // points, so a UV node there has no records and is RTC_ERR_INVALID).

@@ -1,0 +1,379 @@
+"""Inputs for the light-grid builder tests (test_light_grid_silhouettes_cpu.py) and the ctypes side of the library's builder hook
+(include/rtc.h rtc_light_grid_build_raw): one light-grid build of scene_build.hpp build_light_grids on a list of primitives and one
+light, the numpy restatement of the exact intersection tests (csrc/rtc_device.hpp prim_hits) and of the cell function (dir_grid_cell),
+and the cases at which the silhouette construction can go wrong."""
+import ctypes as C
+import math
+
+import numpy as np
+
+vp = C.c_void_p
+SPHERE, PLANE, CUBE, CYLINDER, CONE, TRIANGLE = 0, 1, 2, 3, 4, 5
+WALK = 0x7fffffff        # csrc/device_scene.h RTC_LIGHT_CELL_WALK
+EPS = 0.00001            # the reference's EPSILON
+CUBE_PAD = 0.015625      # scene_build.hpp cube_pad
+REACH = 400.0            # length of the test rays: below cube_pad / EPSILON, the reach up to which a leaf serves a cube's quirk rays
+
+
+# ---- primitives -----------------------------------------------------------------------------------------------------------------------
+class Prim:
+    def __init__(self, kind, fwd, mn=0.0, mx=0.0, closed=False, tri=None):
+        self.kind, self.fwd, self.mn, self.mx, self.closed = kind, np.asarray(fwd, dtype=np.float64), float(mn), float(mx), closed
+        self.tri = np.zeros(9) if tri is None else np.asarray(tri, dtype=np.float64).reshape(9)     # {p1, e1, e2}
+        self.inv = np.linalg.inv(self.fwd)
+
+
+def T(x, y, z):
+    m = np.eye(4); m[:3, 3] = (x, y, z); return m
+
+
+def S(x, y=None, z=None):
+    return np.diag([x, x if y is None else y, x if z is None else z, 1.0])
+
+
+def R(axis, a):
+    c, s = math.cos(a), math.sin(a)
+    m = np.eye(4)
+    i, j = [(1, 2), (2, 0), (0, 1)][axis]
+    m[i, i] = c; m[i, j] = -s; m[j, i] = s; m[j, j] = c
+    return m
+
+
+def Sh(xy, xz, yx, yz, zx, zy):
+    m = np.eye(4); m[0, 1], m[0, 2], m[1, 0], m[1, 2], m[2, 0], m[2, 1] = xy, xz, yx, yz, zx, zy; return m
+
+
+def sphere(fwd): return Prim(SPHERE, fwd)
+def cube(fwd): return Prim(CUBE, fwd)
+def cylinder(fwd, mn, mx, closed): return Prim(CYLINDER, fwd, mn, mx, closed)
+def cone(fwd, mn, mx, closed): return Prim(CONE, fwd, mn, mx, closed)
+
+
+def triangle(p1, p2, p3):
+    p1, p2, p3 = (np.asarray(p, dtype=np.float64) for p in (p1, p2, p3))
+    return Prim(TRIANGLE, np.eye(4), tri=np.concatenate([p1, p2 - p1, p3 - p1]))
+
+
+# ---- the hook -------------------------------------------------------------------------------------------------------------------------
+def bind(lib):
+    lib.rtc_light_grid_build_raw.restype = C.c_int
+    lib.rtc_light_grid_build_raw.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_uint32, vp, C.c_uint32, vp]
+    lib.rtc_last_error.restype = C.c_char_p
+    return lib
+
+
+class Grid:
+    """cells[6 n n + 1]: first item of each cell; prim / dmin: the items; walk: cells left to the BVH walk (their one item is not a primitive)."""
+    def __init__(self, n, n_prims, cells, items):
+        self.n, self.n_prims, self.cells = n, n_prims, cells
+        self.ref = items[:, 0].copy()
+        self.dmin = items[:, 1].copy().view(np.float32)
+        self.prim = (~self.ref) >> 3
+        self.cell_of_item = np.repeat(np.arange(len(cells) - 1), np.diff(cells.astype(np.int64)))
+        self.walk = np.zeros(len(cells) - 1, dtype=bool)
+        self.walk[self.cell_of_item[self.ref == WALK]] = True
+
+    def member(self):
+        """[cell, primitive] -> listed, and the listed item's dmin (inf where not listed)."""
+        m = np.zeros((len(self.cells) - 1, self.n_prims), dtype=bool)
+        d = np.full((len(self.cells) - 1, self.n_prims), np.inf, dtype=np.float32)
+        ok = self.ref != WALK
+        m[self.cell_of_item[ok], self.prim[ok]] = True
+        d[self.cell_of_item[ok], self.prim[ok]] = self.dmin[ok]
+        return m, d
+
+
+def build_raw(lib, prims, light, n, tight=1, max_list=8, items_cap=None):
+    """One call of the hook -> (rc, Grid or None)."""
+    geometry = np.array([p.kind for p in prims], dtype=np.int32)
+    limits = np.array([[p.mn, p.mx] for p in prims], dtype=np.float64)
+    inv = np.ascontiguousarray(np.stack([p.inv for p in prims]).reshape(-1, 16))
+    tris = np.ascontiguousarray(np.stack([p.tri for p in prims]))
+    light = np.array(light, dtype=np.float64)
+    n_cells = 6 * n * n + 1
+    cells = np.zeros(n_cells, dtype=np.uint32)
+    items_cap = 64 * n_cells if items_cap is None else items_cap          # the builder's own budget: 64 entries per cell on average
+    items = np.zeros((items_cap, 2), dtype=np.int32)
+    n_items = C.c_uint32(0)
+    rc = lib.rtc_light_grid_build_raw(geometry.ctypes.data, limits.ctypes.data, inv.ctypes.data, tris.ctypes.data, len(prims), light.ctypes.data, n, max_list,
+                                      tight, cells.ctypes.data, n_cells, items.ctypes.data, items_cap, C.addressof(n_items))
+    if rc != 0:
+        return rc, None
+    return rc, Grid(n, len(prims), cells, items[:n_items.value])
+
+
+# ---- csrc/rtc_device.hpp dir_grid_cell ---------------------------------------------------------------------------------------------------
+def cell_of(d, n):
+    a = np.abs(d)
+    fx = (a[:, 0] >= a[:, 1]) & (a[:, 0] >= a[:, 2])
+    fy = ~fx & (a[:, 1] >= a[:, 2])
+    ax = np.where(fx, 0, np.where(fy, 1, 2))
+    k = np.arange(len(d))
+    m = a[k, ax]
+    face = 2 * ax + (d[k, ax] <= 0.0)
+    u = d[k, np.where(ax == 0, 1, 0)] / m
+    v = d[k, np.where(ax == 2, 1, 2)] / m
+    iu = np.clip(((u + 1.0) * 0.5 * n).astype(np.int64), 0, n - 1)
+    iv = np.clip(((v + 1.0) * 0.5 * n).astype(np.int64), 0, n - 1)
+    return (face * n + iv) * n + iu
+
+
+# ---- csrc/rtc_device.hpp prim_hits, to_object --------------------------------------------------------------------------------------------
+def prim_hits(p, org, dirs):
+    """The t of every intersection the exact test of primitive p reports for world rays (org, dirs): [rays, 4], NaN = no such push.
+    Second value: the rays a BVH leaf does NOT serve for this primitive (a cone's rays with |a| < EPSILON: visit_prim policy 1)."""
+    with np.errstate(all="ignore"):
+        m = p.inv
+        o = org @ m[:3, :3].T + m[:3, 3]
+        d = dirs @ m[:3, :3].T
+        N = len(d)
+        t = np.full((N, 4), np.nan)
+        unserved = np.zeros(N, dtype=bool)
+        if p.kind == CUBE:
+            lo, hi = [], []
+            for c in range(3):
+                big = np.abs(d[:, c]) >= EPS
+                a = np.where(big, (-1.0 - o[:, c]) / d[:, c], (-1.0 - o[:, c]) * np.inf)
+                b = np.where(big, (1.0 - o[:, c]) / d[:, c], (1.0 - o[:, c]) * np.inf)
+                sw = a > b
+                lo.append(np.where(sw, b, a)); hi.append(np.where(sw, a, b))
+            tmin = np.fmax(np.fmax(lo[0], lo[1]), lo[2])
+            tmax = np.fmin(np.fmin(hi[0], hi[1]), hi[2])
+            ok = tmin <= tmax
+            t[ok, 0] = tmin[ok]; t[ok, 1] = tmax[ok]
+            return t, unserved
+        if p.kind >= TRIANGLE:
+            p1, e1, e2 = p.tri[0:3], p.tri[3:6], p.tri[6:9]
+            cx = np.cross(d, e2)
+            det = cx @ e1
+            ok = ~(np.abs(det) < EPS)
+            f = 1.0 / det
+            s = o - p1
+            u = f * np.einsum("ij,ij->i", s, cx)
+            ok &= ~((u < 0.0) | (u > 1.0))
+            q = np.cross(s, e1)
+            v = f * np.einsum("ij,ij->i", d, q)
+            ok &= ~((v < 0.0) | (u + v > 1.0))
+            t[ok, 0] = (f * (q @ e2))[ok]
+            return t, unserved
+        sph, con = p.kind == SPHERE, p.kind == CONE
+        ys = 1.0 if sph else (-1.0 if con else 0.0)
+        a = d[:, 0] ** 2 + ys * d[:, 1] ** 2 + d[:, 2] ** 2
+        b = 2.0 * (d[:, 0] * o[:, 0] + ys * d[:, 1] * o[:, 1] + d[:, 2] * o[:, 2])
+        c = o[:, 0] ** 2 + ys * o[:, 1] ** 2 + o[:, 2] ** 2 - (0.0 if con else 1.0)
+        a0 = np.abs(a) < EPS
+        if con:
+            unserved = a0
+        disc = b * b - 4.0 * a * c
+        sq = np.sqrt(disc)
+        t0, t1 = (-b - sq) / (2.0 * a), (-b + sq) / (2.0 * a)
+        if sph:
+            ok = ~(disc < 0.0)
+            t[ok, 0] = t0[ok]; t[ok, 1] = t1[ok]
+            return t, unserved
+        ok = ~a0 & (disc >= 0.0)
+        for k, tk in enumerate((t0, t1)):
+            y = o[:, 1] + tk * d[:, 1]
+            w = ok & (p.mn < y) & (y < p.mx)
+            t[w, k] = tk[w]
+        if p.closed:
+            for k, (lim, r) in enumerate(((p.mn, p.mn if con else 1.0), (p.mx, p.mx if con else 1.0))):
+                tc = (lim - o[:, 1]) / d[:, 1]
+                x, z = o[:, 0] + tc * d[:, 0], o[:, 2] + tc * d[:, 2]
+                w = ~(np.abs(d[:, 1]) < EPS) & (x * x + z * z <= r * r)
+                t[w, 2 + k] = tc[w]
+        return t, unserved
+
+
+# ---- directions -------------------------------------------------------------------------------------------------------------------------
+def _unit(v):
+    return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+
+def surface_points(p, light, rng, count):
+    """World-space points on (and a hair inside) primitive p: random ones, its corners, rims and edges, and its outline as the light sees it."""
+    g = rng.normal(size=(count, 3))
+    if p.kind == SPHERE:
+        q = _unit(g)
+        lp = p.inv[:3, :3] @ light + p.inv[:3, 3]
+        dl = np.linalg.norm(lp)
+        if dl > 1.0:                                      # the tangent circle from the light
+            a = lp / dl
+            e1 = _unit(np.cross(a, [[1.0, 0.3, -0.2]]))[0]
+            e2 = np.cross(a, e1)
+            th = np.linspace(0.0, 2 * np.pi, 97)[:-1, None]
+            q = np.concatenate([q, a / dl + math.sqrt(1.0 - 1.0 / dl ** 2) * (np.cos(th) * e1 + np.sin(th) * e2)])
+    elif p.kind == CUBE:
+        q = rng.uniform(-1.0, 1.0, (count, 3))
+        k = np.arange(count)
+        q[k, k % 3] = np.where(rng.uniform(size=count) < 0.5, -1.0, 1.0)                   # faces
+        q[: count // 3, (k[: count // 3] + 1) % 3] = np.sign(q[: count // 3, (k[: count // 3] + 1) % 3])   # edges
+        q = np.concatenate([q, np.array([[x, y, z] for x in (-1.0, 1.0) for y in (-1.0, 1.0) for z in (-1.0, 1.0)])])
+    elif p.kind in (CYLINDER, CONE):
+        th = rng.uniform(0.0, 2 * np.pi, count)
+        y = rng.uniform(p.mn, p.mx, count)
+        y[: count // 4] = p.mn; y[count // 4: count // 2] = p.mx                             # the rims
+        r = np.abs(y) if p.kind == CONE else np.ones(count)
+        q = np.stack([r * np.cos(th), y, r * np.sin(th)], axis=1)
+        q[: count // 8] *= [rng.uniform(0.0, 1.0), 1.0, rng.uniform(0.0, 1.0)]               # inside the caps
+    else:
+        w = rng.dirichlet([0.4, 0.4, 0.4], count)                                            # near the edges and corners mostly
+        w[:3] = np.eye(3)
+        p1, e1, e2 = p.tri[0:3], p.tri[3:6], p.tri[6:9]
+        q = p1 + w[:, 1:2] * e1 + w[:, 2:3] * e2
+    return q @ p.fwd[:3, :3].T + p.fwd[:3, 3]
+
+
+def directions(prims, light, n, rng, extra=None):
+    """~20 000 unit directions (l - x) / |l - x|: random ones, directions on the edges and corners of the n-grid's cells, exact and moved
+    by 1 ulp and 1e-9 either way, and directions through points of every primitive's surface and outline."""
+    light = np.asarray(light, dtype=np.float64)
+    out = [_unit(rng.normal(size=(6000, 3)))]
+    k = 4000
+    line = lambda: -1.0 + 2.0 * rng.integers(0, n + 1, k) / n
+    u, v = line(), np.where(rng.uniform(size=k) < 0.5, line(), rng.uniform(-1.0, 1.0, k))     # edges, and corners
+    nudge = rng.integers(0, 5, k)
+    u = np.where(nudge == 1, np.nextafter(u, 2.0), np.where(nudge == 2, np.nextafter(u, -2.0), np.where(nudge == 3, u + 1e-9, np.where(nudge == 4, u - 1e-9, u))))
+    swap = rng.uniform(size=k) < 0.5
+    u, v = np.where(swap, v, u), np.where(swap, u, v)
+    face = rng.integers(0, 6, k)
+    d = np.zeros((k, 3))
+    idx = np.arange(k)
+    ax = face >> 1
+    d[idx, ax] = np.where(face & 1, -1.0, 1.0)
+    d[idx, np.where(ax == 0, 1, 0)] = u
+    d[idx, np.where(ax == 2, 1, 2)] = v
+    out.append(_unit(np.clip(d, -1.0, 1.0)))
+    per = max(64, 10000 // len(prims))
+    for p in prims:
+        w = light - surface_points(p, light, rng, per)
+        w = w[np.linalg.norm(w, axis=1) > 1e-12]
+        out.append(_unit(w))
+    if extra is not None:
+        out.append(_unit(np.asarray(extra, dtype=np.float64)))
+    return np.concatenate(out)
+
+
+# ---- the cases --------------------------------------------------------------------------------------------------------------------------
+def _rot(rng):
+    return R(2, rng.uniform(0, 2 * np.pi)) @ R(1, rng.uniform(0, 2 * np.pi)) @ R(0, rng.uniform(0, 2 * np.pi))
+
+
+def _filler(rng, count, centre=(0.0, 0.0, 0.0), spread=6.0, size=(0.2, 0.9)):
+    """A small cloud of mixed primitives, randomly turned: what the special primitives of a case stand among."""
+    out = []
+    for i in range(count):
+        f = T(*(np.asarray(centre) + rng.uniform(-spread, spread, 3))) @ _rot(rng) @ S(rng.uniform(*size))
+        out.append([sphere(f), cube(f), cylinder(f, 0.0, 1.0, True), cone(f, -1.0, 0.0, True)][i % 4])
+    return out
+
+
+def cases():
+    """{name: (primitives, light, extra directions or None)}; 16-40 primitives each."""
+    rng = np.random.default_rng(20240)
+    c = {}
+    boxes = [cube(T(*rng.uniform(-6, 6, 3)) @ S(rng.uniform(0.4, 1.2))) for _ in range(12)]            # axis-aligned boxes, light on their body diagonal
+    c["light_on_a_body_diagonal"] = (boxes + _filler(rng, 12), (-100.0, 100.0, -100.0), None)
+    c["light_on_a_face_axis"] = (boxes + _filler(rng, 12), (0.0, 100.0, 0.0), None)
+    # around a light at the origin: primitives across two faces, three faces, and the cube map's corner itself
+    st = []
+    for dirn in ((1, 1, 0), (1, -1, 0), (0, 1, 1), (-1, 0, 1), (1, 1, 1), (-1, 1, -1), (1, -1, -1), (1, 1, 0.97), (1, 0.99, 0.2)):
+        f = T(*(8.0 * np.asarray(dirn, dtype=np.float64))) @ _rot(rng) @ S(1.5)
+        st += [cube(f), sphere(T(*(14.0 * np.asarray(dirn, dtype=np.float64))) @ S(1.0, 2.5, 0.6)), cylinder(T(*(20.0 * np.asarray(dirn, dtype=np.float64))) @ _rot(rng) @ S(1.2), -1.0, 2.0, True)]
+    c["across_faces_and_the_corner"] = (st + _filler(rng, 6, (0, -30, 0)), (0.0, 0.0, 0.0), None)
+    # smaller than a cell of any of the grids, on a corner that all of them share (u, v multiples of 1/4)
+    tiny = []
+    for k, dirn in enumerate(((1, 0.25, 0.5), (-0.5, 1, 0.25), (0.25, -0.75, -1), (-1, -0.5, 0.5), (0.5, 0.25, 1), (0.75, -1, 0.5))):
+        at = 10.0 * np.asarray(dirn, dtype=np.float64)
+        f = T(*at) @ _rot(rng) @ S(1e-4)
+        tiny += [sphere(f), cube(f), cylinder(f, -1.0, 1.0, True), triangle(at + [1e-4, 0, 0], at + [0, 1e-4, 0], at + [0, -1e-4, 1e-4])][k % 4:k % 4 + 1]
+        tiny.append([cube, sphere][k % 2](T(*(2.0 * at)) @ S(3e-3)))
+    c["smaller_than_a_cell_on_a_cell_corner"] = (tiny + _filler(rng, 8, (0, 0, 25)), (0.0, 0.0, 0.0), None)
+    c["covering_a_whole_face"] = ([cube(T(0, 0, 3) @ S(50, 50, 1)), sphere(T(0, -40, 0) @ S(35)), cylinder(T(-6, 0, 0) @ R(2, np.pi / 2) @ S(30, 1, 30), -2.0, 2.0, True)] +
+                                  _filler(rng, 15, (0, 0, 0), 20.0), (0.0, 0.0, 0.0), None)
+    # the light inside a primitive's box but outside it, inside it, on its surface, and just off a sphere
+    near = [sphere(T(1.0, 1.0, 1.0) @ S(1.6)),                             # |(1,1,1)| = 1.73 > 1.6: inside the box only
+            cube(T(-1.5, 0.0, 0.0) @ R(1, np.pi / 4) @ S(1.0)),            # a turned cube's world box holds the origin, the cube does not (its edge is at x = -0.086)
+            cube(T(0.3, 0.2, -0.1) @ _rot(rng) @ S(2.0)),                  # inside
+            sphere(T(0.0, -2.0, 0.0) @ S(2.0)),                            # on the surface
+            sphere(T(0.0, 0.0, 3.0003) @ S(3.0)),                          # at 1 + 1e-4 radii
+            cylinder(T(0.0, 0.0, 0.0) @ R(0, 0.3), -1.0, 1.0, True),       # inside a cylinder
+            cube(T(0.0, 3.0 + CUBE_PAD * 2.0, 0.0) @ S(2.0)),              # on the padded face of a cube: inside K's tolerance
+            cone(T(0.0, 0.0, -0.5) @ S(2.0), -1.0, 1.0, True)]
+    c["light_inside_on_and_near"] = (near + _filler(rng, 12, (0, 0, 0), 9.0), (0.0, 0.0, 0.0), None)
+    flat = [sphere(T(*rng.uniform(-8, 8, 3)) @ _rot(rng) @ Sh(0.4, -0.3, 0.2, 0.5, -0.6, 0.1) @ S(1.0, 100.0, 0.01)) for _ in range(6)]
+    flat += [sphere(T(*rng.uniform(-8, 8, 3)) @ Sh(1.5, 0, 0, 0, 0, 0.7) @ _rot(rng) @ S(0.05, 2.0, 5.0)) for _ in range(6)]
+    c["squashed_turned_sheared_spheres"] = (flat + _filler(rng, 8), (30.0, 40.0, -20.0), None)
+    # a face of the cube's K (the PADDED cube) in a plane through the light: it projects to a segment
+    al = [cube(T(0, 0, 0)), cube(T(4, 1.0 + CUBE_PAD - 0.5 * (1 + CUBE_PAD), 6) @ S(0.5)), cube(T(-5, 0, 0) @ S(1, 1, 3)), cube(T(0, 1.0 + CUBE_PAD + 2.0 * (1 + CUBE_PAD), 9) @ S(2.0)),
+          cube(T(30.0 - 3.0 * (1 + CUBE_PAD) - 8.0, 0, 0) @ S(3.0))]
+    c["cube_aligned_with_the_light"] = (al + _filler(rng, 12, (0, 0, 0), 10.0), (30.0, 1.0 + CUBE_PAD, 0.0), None)
+    cy = []
+    for k in range(10):
+        f = T(*rng.uniform(-7, 7, 3)) @ _rot(rng) @ S(rng.uniform(0.3, 1.5), rng.uniform(0.3, 3.0), rng.uniform(0.3, 1.5))
+        cy.append(cylinder(f, *[(-1.0, 1.0), (0.0, 1.0), (-3.0, -2.5), (0.5, 0.50001)][k % 4], closed=k % 2 == 0))
+    c["closed_and_open_cylinders"] = (cy + _filler(rng, 8), (-40.0, 25.0, 10.0), None)
+    co = []
+    for k in range(12):
+        f = T(*rng.uniform(-7, 7, 3)) @ _rot(rng) @ S(rng.uniform(0.3, 1.5), rng.uniform(0.3, 2.0), rng.uniform(0.3, 1.5))
+        co.append(cone(f, *[(-1.0, 2.0), (-1.0, 0.0), (0.5, 2.0), (-2.0, -0.25), (-0.5, 0.5), (0.0, 1.5)][k % 6], closed=k % 3 != 0))
+    c["cones_two_sided_and_truncated"] = (co + _filler(rng, 8), (15.0, 60.0, -35.0), None)
+    tr = []
+    for k in range(20):
+        at = rng.uniform(-8, 8, 3)
+        tr.append(triangle(at, at + rng.normal(size=3) * 2.0, at + rng.normal(size=3) * (2.0 if k % 5 else 1e-3)))
+    tr.append(triangle((0, 0, 5), (3, 0, 5), (1, 0, 9)))                  # edge-on to the light below: y = 0 holds the light
+    c["loose_triangles"] = (tr + _filler(rng, 6), (0.5, 0.0, -30.0), None)
+    # cube quirk rays: an object-space direction component below EPSILON needs only the ORIGIN inside that slab pair, and the points
+    # reported drift out of the cube by |t| EPSILON, into the pad.  Light just outside the slab x <= 1 of a unit cube, rays almost along z.
+    qc = [cube(T(0, 0, 0)), cube(T(0.3, 4.0, 20.0)), cube(T(-3.0, 0.5, -40.0) @ S(4.0, 1.0, 1.0))]
+    dx, dy = np.meshgrid(np.linspace(-1.2e-5, 1.2e-5, 241), np.linspace(-6e-3, 6e-3, 13))
+    extra = np.stack([dx.ravel(), dy.ravel(), -np.ones(dx.size)], axis=1)
+    extra = np.concatenate([extra, extra[:, [1, 0, 2]]])
+    c["cube_quirk_rays_in_the_pad"] = (qc + _filler(rng, 14, (0, 0, 0), 10.0), (1.003, 0.0, -100.0), extra)
+    for name, (prims, _, _) in c.items():
+        assert 16 <= len(prims) <= 40, (name, len(prims))
+    return c
+
+
+def world_prims(world):
+    """The bounded primitives of a scene.World (top-level shapes only) as Prims, in order."""
+    out = []
+    for e in world.elements:
+        assert e.tag == "shape"
+        f = np.array(e.args.transform.m, dtype=np.float64)
+        if e.geometry == "sphere": out.append(sphere(f))
+        elif e.geometry == "cube": out.append(cube(f))
+        elif e.geometry == "cylinder": out.append(cylinder(f, e.params[0], e.params[1], bool(e.params[2])))
+        elif e.geometry == "cone": out.append(cone(f, e.params[0], e.params[1], bool(e.params[2])))
+        else: assert e.geometry == "plane", e.geometry
+    return out
+
+
+# ---- renders under every setting of the grids ------------------------------------------------------------------------------------------
+def both_ways(be, world, cam, fuel, monkeypatch, idx=None, kernels=("1", "4")):
+    """tests/test_light_grids.py both_ways with RTC_LIGHT_GRID_TIGHT added to the grid of settings."""
+    out = {}
+    for k in kernels:
+        monkeypatch.setenv("RTC_KERNEL", k)
+        for grid, tight in (("0", "1"), ("1", "0"), ("1", "1")):
+            monkeypatch.setenv("RTC_LIGHT_GRID", grid)
+            monkeypatch.setenv("RTC_LIGHT_GRID_TIGHT", tight)
+            out[k, grid, tight] = be.render(be.build_world(world), cam, fuel, idx)
+    ref = out[kernels[0], "0", "1"]
+    for key, (rgb, hits) in out.items():
+        assert np.array_equal(hits, ref[1]), key
+        assert np.array_equal(rgb, ref[0]), key
+    monkeypatch.delenv("RTC_LIGHT_GRID")
+    monkeypatch.delenv("RTC_LIGHT_GRID_TIGHT")
+    monkeypatch.delenv("RTC_KERNEL")
+
+
+def lights_inside_scene():
+    """The scene of test_light_grids.py's lights-inside test: a light inside primitives' bounds, one on the floor plane."""
+    from raytracer_challenge_amd import scenes
+    from raytracer_challenge_amd.scene import Color, PointLight, Vector
+    cam, world = scenes.synthetic_analytic(n_primitives=64, seed=3, hsize=64, vsize=36)
+    world.lights.append(PointLight(Color.new(0.5, 0.5, 0.5), Vector.point(0.0, 1.0, 0.0)))
+    world.lights.append(PointLight(Color.new(0.2, 0.2, 0.2), Vector.point(0.3, 0.0, 0.2)))
+    return cam, world
