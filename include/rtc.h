@@ -218,6 +218,43 @@ typedef struct rtc_light_cone {
   double cos_outer;   /* cosine of the half-angle outside which it is dark; <= cos_inner */
 } rtc_light_cone;
 
+/* The scene's background (not in the reference, where a ray that leaves the scene is Color::BLACK): what a ray that hits nothing sees --
+ * a pattern, a UV map or a skybox --, for rtc_scene_create_ext3 / rtc_multi_create_ext3.  A background belongs to the world, not to its
+ * geometry: no dome is intersected, no bound grows.
+ *   `pattern` is the index of a root node in the scene's pattern-node array.  It may be any tag, RTC_PAT_UV included.
+ *   `projection` is one of:
+ *     RTC_BG_DIRECTION: the point is (dx, dy, dz, 1.0), the ray's direction as it is, with no normalisation.
+ *     RTC_BG_CUBE:      c = max(|dx|, |dy|, |dz|), with the NaN-skipping max that the CUBE uv map uses.  The point is
+ *                       (dx / c, dy / c, dz / c, 1.0), three divisions.  The direction lands on the unit cube's surface, where
+ *                       RTC_UVMAP_CUBE expects its point.  This is a skybox.
+ *     (csrc/background_point.h, one function for device and host.)
+ *   For a ray of the ray tree, camera ray or child ray, whose closest-hit pass finds nothing:
+ *     B = the pattern's colour at that point.  Root-level transform_inv matrices apply as ever, and w = 1.0, so translations count.
+ *     The ray contributes weight * B[ch] per channel, one multiplication each.
+ *     `weight` is the path weight the ray already carries: 1.0 at level 0, and child_rays()' wr / wt below that (the reflective or
+ *     transparency factors down the path, each times L = n_lights, as for a hit's surface colour).
+ *     The contribution is added at the place in the one-kernel path's depth-first order where a hit's surface colour would have been
+ *     added.  Both device paths give the same bits.
+ *   A background traces no ray and changes no hit; changes no hit-tree digest; is not a light: no ambient term, no factor per light of
+ *   its own, and shadow rays never see it; changes none of rtc_stats' counters (n_launches counts the wavefront path's extra kernel,
+ *   one per level).  A scene without lights still shows its background to the camera rays (fuel is 0 there, as ever).
+ *   A scene without a background is exactly today's scene: the same kernels, the same builds, the same kernel arguments.
+ * Which kernels: on the wavefront path every existing kernel runs as it does without the background, and wf_background
+ * (csrc/rtc_background.hip) runs once per level behind that level's closest-hit pass.  On the one-kernel path a background scene takes
+ * the BG build of the general kernel that reads the program from memory (feature level 3) with the scene's own area / uv / spot flags:
+ * there is no LEAN, 3-wave or kernel-argument one-kernel build for background scenes.  rtc_scene_kernel_info describes the scene as it
+ * would run without its background (on path 4 that is what runs); rtc_scene_background_info says what the background adds or replaces.
+ * Limits: RTC_ERR_INVALID for a pattern index out of range, an unknown projection, or a NULL where a background is announced
+ * (rtc_background_point, rtc_background_colors, rtc_scene_background_info); checked before anything else, a device included.  The
+ * pattern tree's own limits apply as they do for a material: RTC_MAX_PATTERN_DEPTH, UV records, textures.
+ * Not covered: importance-sampled environment lighting; a background that only the camera sees; a per-channel or per-level tint;
+ * filtered texture lookups. */
+enum { RTC_BG_DIRECTION = 0, RTC_BG_CUBE = 1 };
+typedef struct rtc_background {
+  int32_t pattern;     /* index of a root rtc_pattern_node */
+  int32_t projection;  /* RTC_BG_* */
+} rtc_background;
+
 /* The sampled camera (not in the reference, whose Camera::ray_at_pixel sends one ray through each pixel centre from a pinhole): n x n
  * samples per pixel (anti-aliasing, box filter) and an optional thin lens (depth of field), for the rtc_render_sampled* entry points
  * and rtc_camera_rays.  Pixel i has x = i % hsize, y = i / hsize; sample k of its N = n * n has sx = k % n, sy = k / n.  Every step is
@@ -392,6 +429,30 @@ int rtc_scene_create_ext(const rtc_scene_desc* desc, const rtc_scene_ext* ext, i
  * own on both device paths, whether or not it has an area light.  The cones' own numbers are checked before anything else, a device
  * included.  Every render entry point takes the result. */
 int rtc_scene_create_ext2(const rtc_scene_desc* desc, const rtc_scene_ext* ext, const rtc_light_cone* cones, uint32_t n_cones, int device, rtc_scene** out);
+/* Same, with a background (rtc_background above).  bg == NULL is exactly rtc_scene_create_ext2 (same kernels, same bits).  The
+ * background's own numbers are checked before anything else, a device included.  Every render entry point takes the result. */
+int rtc_scene_create_ext3(const rtc_scene_desc* desc, const rtc_scene_ext* ext, const rtc_light_cone* cones, uint32_t n_cones, const rtc_background* bg, int device,
+                          rtc_scene** out);
+/* The projection rule alone: point = where a ray of direction dir looks the background up.  Host-only: no device needed (like
+ * rtc_spot_factor).  RTC_ERR_INVALID for NULL arguments or an unknown projection. */
+int rtc_background_point(int32_t projection, const double dir[3], double point[3]);
+/* The whole rule on the device for n directions (dirs: n x {x, y, z}, rgb: n x 3, both host): rgb[i] = B of a ray with direction
+ * dirs[i] -- to a background what rtc_camera_rays is to the camera.  RTC_ERR_INVALID for a scene without a background. */
+int rtc_background_colors(rtc_scene*, const double* dirs, uint64_t n, double* rgb);
+/* Test hook, read-only: what a launch of this scene takes for its background.  has_background == 0: pattern, projection and the
+ * builds are -1.  trace_build: path 1, the row of RTC_BG_BUILDS (csrc/rtc_device.hpp) whose BG instantiation of rtc_trace_kernel
+ * replaces the build rtc_scene_kernel_info reports, with that row's flags; wf_background_build: path 4, RTC_WF_BG_*. */
+enum { RTC_WF_BG_PLAIN = 0, RTC_WF_BG_UV = 1 };
+typedef struct rtc_background_info {
+  int32_t has_background;
+  int32_t pattern, projection;
+  int32_t plain_root;           /* the root is a Plain colour: no pattern walk, no projection */
+  int32_t trace_build;          /* path 1: row of RTC_BG_BUILDS (feature level 3, program read from memory) */
+  int32_t trace_area, trace_uv, trace_spot;  /* ... and its flags */
+  int32_t wf_background_build;  /* path 4: RTC_WF_BG_PLAIN (pattern_color) or RTC_WF_BG_UV (pattern_color_uv, scenes with a UV node) */
+  int32_t _pad;
+} rtc_background_info;
+int rtc_scene_background_info(const rtc_scene*, rtc_background_info* out);
 /* The cone factor f alone, for a light (or sample) at light_pos and a shading point `point`; `cone->light` is not read.  Host-only: no
  * device needed (like rtc_ppm).  RTC_ERR_INVALID for NULL arguments and for a cone rtc_scene_create_ext2 would refuse. */
 int rtc_spot_factor(const rtc_light_cone* cone, const double light_pos[3], const double point[3], double* f);
@@ -455,6 +516,9 @@ int rtc_multi_create_ext(const rtc_scene_desc* desc, const rtc_scene_ext* ext, c
 /* Same with the light cones of rtc_scene_create_ext2. */
 int rtc_multi_create_ext2(const rtc_scene_desc* desc, const rtc_scene_ext* ext, const rtc_light_cone* cones, uint32_t n_cones, const int* devices, int n_devices,
                           rtc_multi** out);
+/* Same with the background of rtc_scene_create_ext3. */
+int rtc_multi_create_ext3(const rtc_scene_desc* desc, const rtc_scene_ext* ext, const rtc_light_cone* cones, uint32_t n_cones, const rtc_background* bg, const int* devices,
+                          int n_devices, rtc_multi** out);
 void rtc_multi_destroy(rtc_multi*);
 int rtc_multi_device_count(const rtc_multi*);
 /* Rows per band of the partition (default 8; 1 = single rows interleaved).  Waits for queued frames. */

@@ -105,6 +105,11 @@ int rtw_world_add_area_light(rtw_world*, const double intensity[3], const double
  * an index no light has yet, a second cone on one light and numbers rtc_scene_create_ext2 would refuse.  Product library only;
  * rendering such a world needs rtc_scene_create_ext2. */
 int rtw_world_set_light_cone(rtw_world*, uint32_t light, const double axis[3], double cos_inner, double cos_outer);
+/* The world's background (include/rtc.h rtc_background; not in the reference, where a ray that leaves the scene is black): a ray that
+ * hits nothing sees `pattern` (borrowed, any kind) at the point `projection` (RTC_BG_DIRECTION / RTC_BG_CUBE) makes of its direction.
+ * A second call replaces the first.  Fails for a NULL pattern and an unknown projection.  Product library only; rendering such a
+ * world needs rtc_scene_create_ext3. */
+int rtw_world_set_background(rtw_world*, const rtw_pattern* pattern, int32_t projection);
 int rtw_world_add_element(rtw_world*, rtw_element*);                                    /* consumes */
 uint64_t rtw_world_primitive_count(const rtw_world*);
 void rtw_world_release(rtw_world*);

@@ -13,7 +13,7 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from .scene import (FUEL, GEOMETRY, GROUP_KINDS, JITTER_KINDS, MIXTURE_KINDS, Adaptive, AreaLight, Camera, Cone, Element, FILTER_KINDS, Filter, Material, Pattern, Sampling, World)
+from .scene import (BACKGROUND_PROJECTIONS, FUEL, GEOMETRY, GROUP_KINDS, JITTER_KINDS, MIXTURE_KINDS, Adaptive, AreaLight, Camera, Cone, Element, FILTER_KINDS, Filter, Material, Pattern, Sampling, World)
 from .texture import UV_KINDS, UV_MAPS, Texture
 
 HIT_DTYPE = np.dtype([("t", "<f8"), ("prim", "<i4"), ("push_idx", "<i4")])
@@ -136,6 +136,11 @@ class Backend:
         if self.has_light_cones:
             lib.rtw_world_set_light_cone.restype = i
             lib.rtw_world_set_light_cone.argtypes = [vp, C.c_uint32, dp, d, d]
+        # a background: the same
+        self.has_background = hasattr(lib, "rtw_world_set_background")
+        if self.has_background:
+            lib.rtw_world_set_background.restype = i
+            lib.rtw_world_set_background.argtypes = [vp, vp, C.c_int32]
         # texture-mapped patterns: the same (the oracle has none)
         self.has_texture_map = hasattr(lib, "rtw_pattern_uv")
         if self.has_texture_map:
@@ -250,6 +255,11 @@ class Backend:
                     self._check(lib.rtw_world_set_light_cone(w, k, axis, cone.cos_inner, cone.cos_outer), "set_light_cone")
             for e in world.elements:
                 self._check(lib.rtw_world_add_element(w, self._element(e, cache, owned)), "add_element")
+            bg = getattr(world, "background", None)
+            if bg is not None:
+                if not self.has_background:
+                    raise RtwError("a background needs librtc_amd.so (backend %r has no rtw_world_set_background)" % self.name)
+                self._check(lib.rtw_world_set_background(w, self._pattern(bg.pattern, cache, owned), BACKGROUND_PROJECTIONS.index(bg.projection)), "set_background")
         except Exception:
             lib.rtw_world_release(w)
             raise

@@ -194,6 +194,7 @@ struct DScene {
   int32_t has_recs;          // 1: some op reads intersection records (pisect): analytic BVH, quirk scans, primitives outside the kernel arguments
   int32_t n_recs;            // entries of pisect: 0, or 1 + the last primitive an op can name (scene_build.hpp build_arrays) -- NOT n_prims: the
                              // triangles of a mesh at the end of the world have no record
+                             // (0 too where the records exist for a background's one-kernel build alone: HostArrays.recs_bg_only)
   // Kernel-argument copy of a short traversal program (kernargs are read with scalar loads: the op fetch and the plane
   // records stop being per-lane vector loads on every ray's dependency chain).  Used when n_kops > 0: the whole program
   // has <= RTC_KOPS ops, no OP_GROUP / OP_CSG, no per-primitive gates (so every lane runs the same op sequence); an
@@ -210,6 +211,17 @@ struct DScene {
   int32_t has_uv;     // 1: some pattern node is an RTC_PAT_UV node: the UV kernel instantiations render the scene (DUv)
   int32_t has_spot;   // 1: some light has a cone (include/rtc.h rtc_light_cone): `lights` holds RTC_SLIGHT doubles per light and the SPOT kernels
                       // render the scene (in what was the struct's tail padding: the layout of everything else is unchanged)
+};
+
+// A scene's background (include/rtc.h rtc_background): what a ray that hits nothing contributes.  DScene has no padding left, and no
+// kernel of a scene without a background may see its arguments move: the two ints travel as an argument that only the background
+// builds have -- rtc_trace_kernel's BG build takes a DSceneBg where the others take a DScene, wf_background takes a DBackground.
+struct DBackground {
+  int32_t pattern;     // root node in DScene.pats
+  int32_t projection;  // RTC_BG_DIRECTION (0) / RTC_BG_CUBE (1): background_point.h
+};
+struct DSceneBg : DScene {
+  DBackground bg;
 };
 
 // Which pixels a launch covers.

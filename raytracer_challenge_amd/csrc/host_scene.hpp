@@ -531,6 +531,8 @@ class Flattener {
       if (!walk(*e)) return false;
     return true;
   }
+  // The node index of a pattern tree no material names (a background's, include/rtc.h rtc_background): emitted like any other, after run().
+  int32_t root_pattern(const PatRef& p) { return pattern(p); }
 
  private:
   Flat& f_;

@@ -21,7 +21,9 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <type_traits>
 
+#include "background_point.h"
 #include "device_scene.h"
 #include "spot_factor.h"
 
@@ -1257,6 +1259,18 @@ __device__ __noinline__ void pattern_color(const DScene& S, int root, double px,
 __device__ __noinline__ void pattern_color_uv(const DScene& S, int root, double px, double py, double pz, double pw, double& r, double& g, double& b) {
   pattern_walk<true>(S, root, px, py, pz, pw, r, g, b);
 }
+// The background's colour for a ray of direction d that hit nothing (include/rtc.h rtc_background): the pattern tree under `bg.pattern`
+// at background_point.h's point with w = 1.0, so root-level translations count.  A Plain root is its colour, without a walk.
+// UV as for pattern_at: scenes with DScene.has_uv walk with the RTC_PAT_UV branch.
+template <bool UV>
+__device__ __forceinline__ void background_color(const DScene& S, const DBackground bg, double dx, double dy, double dz, double& r, double& g, double& b) {
+  const DPat& root = S.pats[bg.pattern];
+  if (root.tag == 1) { r = root.color[0]; g = root.color[1]; b = root.color[2]; return; }
+  double p[3];
+  rtc_background_point_at(bg.projection, dx, dy, dz, p);
+  if (UV) pattern_color_uv(S, bg.pattern, p[0], p[1], p[2], 1.0, r, g, b);
+  else pattern_color(S, bg.pattern, p[0], p[1], p[2], 1.0, r, g, b);
+}
 
 // ---- hit state (Intersection::prepare_state, src/intersection.rs:50-121) --------------------------------
 struct State {
@@ -1725,8 +1739,11 @@ __device__ __forceinline__ void shade_lights_area(const DScene& S, double px, do
 // AREA: scenes with an area light (DScene.has_area): the lights are shaded by shade_lights_area.  Point-light scenes never run it.
 // UV: scenes with a texture-mapped pattern (DScene.has_uv): the pattern walk with the RTC_PAT_UV branch.  Other scenes never run it.
 // SPOT (with AREA): scenes with a cone (DScene.has_spot): shade_lights_area's SPOT build.
-template <bool COUNT, int FEAT, bool KOPS, int WAVES = 0, bool LEAN = false, bool AREA = false, bool UV = false, bool SPOT = false>
-__global__ void __launch_bounds__(RTC_BLOCK, WAVES ? WAVES : ((FEAT >= 2 && RTC_WAVES_PER_SIMD < 2) ? 2 : RTC_WAVES_PER_SIMD)) rtc_trace_kernel(DScene S, DCamera cam, DPixelMap pm, int fuel0, double* __restrict__ rgb, double* __restrict__ hit_t,
+// BG: scenes with a background (include/rtc.h rtc_background): a ray that hits nothing adds weight * the background's colour where a
+// hit's surface colour would have been added.  Only these builds take a DSceneBg; they are instantiated by rtc_background.hip, not by
+// a row of RTC_VARIANTS.  Scenes without a background never run them.
+template <bool COUNT, int FEAT, bool KOPS, int WAVES = 0, bool LEAN = false, bool AREA = false, bool UV = false, bool SPOT = false, bool BG = false>
+__global__ void __launch_bounds__(RTC_BLOCK, WAVES ? WAVES : ((FEAT >= 2 && RTC_WAVES_PER_SIMD < 2) ? 2 : RTC_WAVES_PER_SIMD)) rtc_trace_kernel(std::conditional_t<BG, DSceneBg, DScene> S, DCamera cam, DPixelMap pm, int fuel0, double* __restrict__ rgb, double* __restrict__ hit_t,
                                                         int* __restrict__ hit_prim, int* __restrict__ hit_k, DStats* __restrict__ stats) {
   RTC_LDS_STACK(lds_stack);
   int* stack = lds_stack + threadIdx.x;
@@ -1847,6 +1864,10 @@ __global__ void __launch_bounds__(RTC_BLOCK, WAVES ? WAVES : ((FEAT >= 2 && RTC_
             continue;
           }
         }
+      } else if constexpr (BG) {
+        double br, bgr, bb;
+        background_color<UV>(S, S.bg, ray.dx, ray.dy, ray.dz, br, bgr, bb);
+        acc_r += weight * br; acc_g += weight * bgr; acc_b += weight * bb;
       }
       DIAG_REGION(5);
       if (np == 0) {
@@ -2274,3 +2295,20 @@ struct RtcVariantOps {
 };
 template <int V>
 RtcVariantOps rtc_variant_ops();  // defined and explicitly instantiated by the translation unit of variant V
+
+// Scenes with a background (include/rtc.h rtc_background) on the one-kernel path: rtc_trace_kernel's BG build of the general
+// memory-program kernel (feature level 3, KOPS = false: DScene.ops is always in memory, as variant 10 relies on) with the scene's own
+// area / uv / spot flags.  These are not rows of RTC_VARIANTS: rtc_background.hip instantiates them, one object per build (-DRTC_BG_BUILD=<b>),
+// each with its counting form.  No LEAN, 3-wave or kernel-argument build serves a background scene.
+constexpr RtcVariant RTC_BG_BUILDS[] = {
+    {3, false, false, false, false},  // 0
+    {3, false, true, false, false},   // 1: an area light
+    {3, false, false, true, false},   // 2: a UV pattern
+    {3, false, true, true, false},    // 3: both
+    {3, false, true, false, true},    // 4: a light cone (always with the `area` code path)
+    {3, false, true, true, true},     // 5: a light cone and a UV pattern
+};
+constexpr int RTC_N_BG_BUILDS = (int)(sizeof(RTC_BG_BUILDS) / sizeof(RTC_BG_BUILDS[0]));
+constexpr int rtc_pick_bg_build(bool area, bool uv, bool spot) { return spot ? (uv ? 5 : 4) : ((uv ? 2 : 0) + (area ? 1 : 0)); }
+template <int B>
+void rtc_launch_trace_bg_build(const RtcFrame& F, const DBackground& bg, unsigned grid, int fuel, double* rgb);  // defined by the object of build B

@@ -327,8 +327,13 @@ uint64_t rtc_wavefront_work(const DCamera& cam, const DPixelMap& pm) {
 // One frame through the wavefront kernels.  The caller zeroed W.counts (RTC_WF_COUNTS entries) on the stream and sized the
 // arrays for W.cap >= the work ids of the launch and fuel + 1 levels; `blocks` / `shade_blocks` = grid sizes of the traversal /
 // shading kernels; `lds` = the scene's rtc_wavefront_lds_bytes (0, the default: tables in memory -- all a caller without LDSC builds can ask for).
+// `bg` (optional): the scene's background: wf_background (rtc_background.hip) runs once per level, behind that level's trace role.
+#ifndef RTC_EMU
+void rtc_launch_wf_background(const DScene& S, const DCamera& cam, const DPixelMap& pm, const DWave& W, int level, unsigned n0, const DBackground& bg, unsigned blocks,
+                              hipStream_t stream);
+#endif
 void rtc_launch_wavefront(const DScene& S, const DCamera& cam, const DPixelMap& pm, int fuel, const DWave& W, double* rgb, double* hit_t, int* hit_prim, int* hit_k,
-                          DStats* stats, bool count, hipStream_t stream, unsigned blocks, unsigned shade_blocks, unsigned lds = 0u) {
+                          DStats* stats, bool count, hipStream_t stream, unsigned blocks, unsigned shade_blocks, unsigned lds = 0u, const DBackground* bg = nullptr) {
   if (pm.n == 0) return;
   const RtcVariantOps& ops = rtc_ops(rtc_variant(S, true));
   const RtcFrame F = {S, cam, pm, hit_t, hit_prim, hit_k, stats, stream, count};
@@ -345,6 +350,9 @@ void rtc_launch_wavefront(const DScene& S, const DCamera& cam, const DPixelMap& 
     if (!lds || !ops.launch_wf_ts_lds(F, RtcLevel{W, tl, sl, n0, level, fuel - level, lds_blocks, lds}))
 #endif
     ops.launch_wf_ts(F, RtcLevel{W, tl, sl, n0, level, fuel - level, blocks, 0u});
+#ifndef RTC_EMU
+    if (bg && level <= fuel) rtc_launch_wf_background(S, cam, pm, W, level, n0, *bg, 4u * std::max(1u, shade_blocks), stream);
+#endif
     if (level <= fuel) {
       switch (rtc_scene_shade_build(S, count, level == 0)) {
 #ifndef RTC_EMU

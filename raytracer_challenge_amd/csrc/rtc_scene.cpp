@@ -21,6 +21,7 @@
 
 #include "../../include/rtc.h"
 #include "adaptive_contrast.h"
+#include "background_point.h"
 #include "camera_sampling.h"
 #include "device_scene.h"
 #include "filter_weights.h"
@@ -34,7 +35,11 @@ void rtc_launch_pack_hits(const double* t, const int* prim, const int* k, DHit* 
 void rtc_launch_deinterleave(const double* slab, double* image, unsigned rowlen, unsigned vsize, unsigned n, unsigned max_rows, unsigned band, hipStream_t stream);
 void rtc_launch_deinterleave8(const unsigned char* slab, unsigned char* image, unsigned rowlen, unsigned vsize, unsigned n, unsigned max_rows, unsigned band, hipStream_t stream);
 void rtc_launch_wavefront(const DScene& S, const DCamera& cam, const DPixelMap& pm, int fuel, const DWave& W, double* rgb, double* hit_t, int* hit_prim, int* hit_k,
-                          DStats* stats, bool count, hipStream_t stream, unsigned blocks, unsigned shade_blocks, unsigned lds);
+                          DStats* stats, bool count, hipStream_t stream, unsigned blocks, unsigned shade_blocks, unsigned lds, const DBackground* bg);
+void rtc_launch_trace_bg(const DScene& S, const DBackground& bg, const DCamera& cam, const DPixelMap& pm, int fuel, double* rgb, double* hit_t, int* hit_prim, int* hit_k,
+                         DStats* stats, bool count, hipStream_t stream);
+void rtc_launch_background_colors(const DScene& S, const DBackground& bg, const double* dirs, unsigned long long n, double* rgb, hipStream_t stream);
+int rtc_background_trace_build(const DScene& S);
 void rtc_kernel_info_fill(const DScene& S, bool wavefront, bool count, bool big_scene, unsigned lds_bytes, int device, rtc_kernel_info* out);
 bool rtc_scene_is_big(unsigned long long scene_bytes);
 uint64_t rtc_wavefront_work(const DCamera& cam, const DPixelMap& pm);
@@ -75,6 +80,9 @@ struct rtc_scene {
   std::vector<void*> allocs;
   uint64_t bytes = 0;
   DScene d{};
+  bool has_bg = false;  // the scene has a background (rtc_scene_create_ext3): its launches take the BG builds (rtc_background.hip)
+  DBackground bg{0, 0};
+  bool bg_plain = false;  // its root is a Plain colour: no pattern walk
   DStats* d_stats = nullptr;
   // scratch output buffers (grown on demand)
   double* d_rgb = nullptr;
@@ -291,7 +299,7 @@ int fill_stats(rtc_scene* s, const DStats& h, uint64_t pixels, rtc_stats* stats)
   stats->accel_nodes_kernarg = h.knodes; stats->analytic_tests_kernarg = h.kplanes; stats->light_grid_cells = h.light_cells;
   stats->group_tests_uniform = h.kgroups;
   stats->kernel_ms = ms;
-  stats->n_launches = s->last_wavefront ? 2u * (uint32_t)s->last_fuel + 4u : 1u;
+  stats->n_launches = s->last_wavefront ? 2u * (uint32_t)s->last_fuel + 4u + (s->has_bg ? (uint32_t)s->last_fuel + 1u : 0u) : 1u;  // (wf_background: one per level)
   return RTC_OK;
 }
 
@@ -354,7 +362,10 @@ int run(rtc_scene* s, const DCamera& cam, DPixelMap pm, int fuel, double* d_rgb,
     }
     HIP_OK(hipMemsetAsync(s->wave.counts, 0, RTC_WF_COUNTS * sizeof(uint32_t), s->stream));
     HIP_OK(hipEventRecord(s->ev0, s->stream));
-    rtc_launch_wavefront(s->d, cam, pm, fuel, s->wave, d_rgb, want_hits ? s->d_hit_t : nullptr, s->d_hit_prim, s->d_hit_k, s->d_stats, count, s->stream, s->wave_blocks, s->shade_blocks, s->lds_bytes);
+    rtc_launch_wavefront(s->d, cam, pm, fuel, s->wave, d_rgb, want_hits ? s->d_hit_t : nullptr, s->d_hit_prim, s->d_hit_k, s->d_stats, count, s->stream, s->wave_blocks, s->shade_blocks, s->lds_bytes,
+                         s->has_bg ? &s->bg : nullptr);
+  } else if (s->has_bg) {
+    rtc_launch_trace_bg(s->d, s->bg, cam, pm, fuel, d_rgb, want_hits ? s->d_hit_t : nullptr, s->d_hit_prim, s->d_hit_k, s->d_stats, count, s->stream);
   } else {
     rtc_launch_trace(s->d, cam, pm, fuel, d_rgb, want_hits ? s->d_hit_t : nullptr, s->d_hit_prim, s->d_hit_k, s->d_stats, count, s->stream, rtc_scene_is_big(s->bytes));
   }
@@ -859,15 +870,21 @@ int rtc_device_count(void) {
 namespace {
 // rtc_scene_create (ex == false) and rtc_scene_create_ex (ex == true: the lights are `lx`, desc->lights must be empty); `uv`: the UV
 // pattern records and textures of rtc_scene_create_ext; `cones`: the light cones of rtc_scene_create_ext2 (with ex == true only)
+// `bg`: the background of rtc_scene_create_ext3 (NULL: none)
 int scene_create(const rtc_scene_desc* desc, bool ex, const rtc_light_ex* lx, uint32_t n_lx, int device, rtc_scene** out, const rtb::UvInput& uv = rtb::UvInput{},
-                 const rtb::ConeInput& cones = rtb::ConeInput{}) {
+                 const rtb::ConeInput& cones = rtb::ConeInput{}, const rtc_background* bg = nullptr) {
   if (!desc || !out) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
   *out = nullptr;
+  if (bg) {  // (its own limits first: they need no device)
+    std::string why;
+    if (const int rc = rtb::validate_background(*bg, desc->n_pattern_nodes, &why)) return rtc_fail(rc, why);
+  }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return rtc_fail(RTC_ERR_DEVICE, "no HIP device available (this library has no CPU path)");
   if (device < 0 || device >= ndev) return rtc_fail(RTC_ERR_DEVICE, "device index out of range");
   HIP_OK(hipSetDevice(device));
   rtb::HostArrays H;
+  H.has_bg = bg ? 1 : 0;
   std::string err;
   // Mesh accelerators of at least 100 000 triangles are built on the device (LBVH over extent-aware bisection keys, bvh_device.hip)
   // instead of by the host's binned SAH: same pixels (the accelerator is results-neutral), a quarter of the build time, frames
@@ -886,6 +903,7 @@ int scene_create(const rtc_scene_desc* desc, bool ex, const rtc_light_ex* lx, ui
   struct SceneDeleter { void operator()(rtc_scene* p) const { rtc_scene_destroy(p); } };
   std::unique_ptr<rtc_scene, SceneDeleter> s(new rtc_scene());
   s->device = device;
+  if (bg) { s->has_bg = true; s->bg = DBackground{bg->pattern, bg->projection}; s->bg_plain = desc->pattern_nodes[bg->pattern].tag == RTC_PAT_PLAIN; }
   HIP_OK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
   HIP_OK(hipEventCreate(&s->ev0));
   HIP_OK(hipEventCreate(&s->ev1));
@@ -910,7 +928,7 @@ int scene_create(const rtc_scene_desc* desc, bool ex, const rtc_light_ex* lx, ui
 #undef UP
   d.n_ops = (int32_t)H.ops.size();
   d.n_prims = (int32_t)H.prims.size();
-  d.n_recs = (int32_t)H.pisect.size();
+  d.n_recs = H.recs_bg_only ? 0 : (int32_t)H.pisect.size();
   d.n_lights = H.n_lights;
   d.all_cast_shadow = H.all_cast_shadow;
   {
@@ -1050,6 +1068,66 @@ int rtc_scene_create_ext2(const rtc_scene_desc* desc, const rtc_scene_ext* ext, 
   SpotArgs a;
   if (const int rc = spot_args(desc, ext, cones, n_cones, &a)) return rc;
   return scene_create(&a.desc, true, a.lx, a.n_lx, device, out, a.uv, a.cones);
+}
+
+int rtc_scene_create_ext3(const rtc_scene_desc* desc, const rtc_scene_ext* ext, const rtc_light_cone* cones, uint32_t n_cones, const rtc_background* bg, int device,
+                          rtc_scene** out) {
+  if (!bg) return rtc_scene_create_ext2(desc, ext, cones, n_cones, device, out);
+  if (out) *out = nullptr;
+  if (!desc) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  std::string why;
+  if (const int rc = rtb::validate_background(*bg, desc->n_pattern_nodes, &why)) return rtc_fail(rc, why);
+  if (n_cones > 0) {
+    SpotArgs a;
+    if (const int rc = spot_args(desc, ext, cones, n_cones, &a)) return rc;
+    return scene_create(&a.desc, true, a.lx, a.n_lx, device, out, a.uv, a.cones, bg);
+  }
+  if (!ext) return scene_create(desc, false, nullptr, 0, device, out, rtb::UvInput{}, rtb::ConeInput{}, bg);
+  const rtb::UvInput uv{ext->uv_patterns, ext->n_uv_patterns, ext->textures, ext->n_textures};
+  return scene_create(desc, ext->n_lights > 0, ext->lights, ext->n_lights, device, out, uv, rtb::ConeInput{}, bg);
+}
+
+int rtc_background_point(int32_t projection, const double dir[3], double point[3]) {
+  if (!dir || !point) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  if (projection != RTC_BG_DIRECTION && projection != RTC_BG_CUBE) return rtc_fail(RTC_ERR_INVALID, "background: unknown projection");
+  rtc_background_point_at(projection, dir[0], dir[1], dir[2], point);
+  return RTC_OK;
+}
+
+int rtc_background_colors(rtc_scene* s, const double* dirs, uint64_t n, double* rgb) {
+  if (!s || (!dirs && n) || (!rgb && n)) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  if (!s->has_bg) return rtc_fail(RTC_ERR_INVALID, "the scene has no background");
+  if (n == 0) return RTC_OK;
+  HIP_OK(hipSetDevice(s->device));
+  int rc = ensure_px(s, n, false);  // d_rgb: n x 3 doubles
+  if (rc != RTC_OK) return rc;
+  if ((n + 1) / 2 > s->cap_rays) {  // d_rays holds 6 doubles per ray: n directions need half as many
+    if (s->d_rays) (void)hipFree(s->d_rays);
+    s->d_rays = nullptr; s->cap_rays = 0;
+    HIP_OK(hipMalloc((void**)&s->d_rays, ((n + 1) / 2) * 6 * sizeof(double)));
+    s->cap_rays = (n + 1) / 2;
+  }
+  HIP_OK(hipMemcpyAsync(s->d_rays, dirs, n * 3 * sizeof(double), hipMemcpyHostToDevice, s->stream));
+  rtc_launch_background_colors(s->d, s->bg, s->d_rays, n, s->d_rgb, s->stream);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(rgb, s->d_rgb, n * 3 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  HIP_OK(hipStreamSynchronize(s->stream));
+  return RTC_OK;
+}
+
+int rtc_scene_background_info(const rtc_scene* s, rtc_background_info* out) {
+  if (!s || !out) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  std::memset(out, 0, sizeof(*out));
+  out->pattern = out->trace_build = out->wf_background_build = -1;
+  out->projection = -1;
+  if (!s->has_bg) return RTC_OK;
+  out->has_background = 1;
+  out->pattern = s->bg.pattern; out->projection = s->bg.projection;
+  out->trace_build = rtc_background_trace_build(s->d);
+  out->trace_area = s->d.has_area || s->d.has_spot; out->trace_uv = s->d.has_uv; out->trace_spot = s->d.has_spot;
+  out->wf_background_build = s->d.has_uv ? RTC_WF_BG_UV : RTC_WF_BG_PLAIN;
+  out->plain_root = s->bg_plain ? 1 : 0;
+  return RTC_OK;
 }
 
 int rtc_spot_factor(const rtc_light_cone* cone, const double light_pos[3], const double point[3], double* f) {
@@ -1733,13 +1811,13 @@ int render_multi(rtc_multi* m, const rtc_camera* cam, int32_t fuel, double* rgb_
 
 namespace {
 int multi_create(const rtc_scene_desc* desc, bool ex, const rtc_light_ex* lx, uint32_t n_lx, const int* devices, int n_devices, rtc_multi** out,
-                 const rtb::UvInput& uv = rtb::UvInput{}, const rtb::ConeInput& cones = rtb::ConeInput{}) {
+                 const rtb::UvInput& uv = rtb::UvInput{}, const rtb::ConeInput& cones = rtb::ConeInput{}, const rtc_background* bg = nullptr) {
   if (!desc || !devices || !out || n_devices <= 0) return rtc_fail(RTC_ERR_INVALID, "NULL argument / no devices");
   *out = nullptr;
   std::unique_ptr<rtc_multi> m(new rtc_multi());
   for (int k = 0; k < n_devices; k++) {
     rtc_scene* s = nullptr;
-    int rc = scene_create(desc, ex, lx, n_lx, devices[k], &s, uv, cones);
+    int rc = scene_create(desc, ex, lx, n_lx, devices[k], &s, uv, cones, bg);
     if (rc != RTC_OK) { rtc_multi_destroy(m.release()); return rc; }
     m->scenes.push_back(s);
     m->tiles.push_back(nullptr);
@@ -1790,6 +1868,23 @@ int rtc_multi_create_ext2(const rtc_scene_desc* desc, const rtc_scene_ext* ext, 
   SpotArgs a;
   if (const int rc = spot_args(desc, ext, cones, n_cones, &a)) return rc;
   return multi_create(&a.desc, true, a.lx, a.n_lx, devices, n_devices, out, a.uv, a.cones);
+}
+
+int rtc_multi_create_ext3(const rtc_scene_desc* desc, const rtc_scene_ext* ext, const rtc_light_cone* cones, uint32_t n_cones, const rtc_background* bg, const int* devices,
+                          int n_devices, rtc_multi** out) {
+  if (!bg) return rtc_multi_create_ext2(desc, ext, cones, n_cones, devices, n_devices, out);
+  if (out) *out = nullptr;
+  if (!desc) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  std::string why;
+  if (const int rc = rtb::validate_background(*bg, desc->n_pattern_nodes, &why)) return rtc_fail(rc, why);
+  if (n_cones > 0) {
+    SpotArgs a;
+    if (const int rc = spot_args(desc, ext, cones, n_cones, &a)) return rc;
+    return multi_create(&a.desc, true, a.lx, a.n_lx, devices, n_devices, out, a.uv, a.cones, bg);
+  }
+  if (!ext) return multi_create(desc, false, nullptr, 0, devices, n_devices, out, rtb::UvInput{}, rtb::ConeInput{}, bg);
+  const rtb::UvInput uv{ext->uv_patterns, ext->n_uv_patterns, ext->textures, ext->n_textures};
+  return multi_create(desc, ext->n_lights > 0, ext->lights, ext->n_lights, devices, n_devices, out, uv, rtb::ConeInput{}, bg);
 }
 
 void rtc_multi_destroy(rtc_multi* m) {

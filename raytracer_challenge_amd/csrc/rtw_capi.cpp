@@ -24,6 +24,9 @@ extern "C" int rtc_scene_create_ext(const rtc_scene_desc*, const rtc_scene_ext*,
 // (and for light cones)
 extern "C" int rtc_scene_create_ext2(const rtc_scene_desc*, const rtc_scene_ext*, const rtc_light_cone*, uint32_t, int, rtc_scene**) __attribute__((weak));
 
+// (and for a background)
+extern "C" int rtc_scene_create_ext3(const rtc_scene_desc*, const rtc_scene_ext*, const rtc_light_cone*, uint32_t, const rtc_background*, int, rtc_scene**) __attribute__((weak));
+
 struct rtw_pattern { PatRef p; };
 struct rtw_texture { TexRef t; };
 struct rtw_element { std::unique_ptr<Elem> e; };
@@ -34,6 +37,8 @@ struct rtw_world {
   std::unique_ptr<Flat> flat;  // rtw_world_flatten_desc: the arrays behind the descriptor it handed out
   std::vector<rtc_light_ex> lights_ex;  // every light in order (point and area) once an area light was added; empty otherwise
   std::vector<rtc_light_cone> cones;    // rtw_world_set_light_cone: at most one per light, `light` = the light's place in the order
+  PatRef background;                    // rtw_world_set_background: the pattern a ray that hits nothing sees (null: none)
+  int32_t background_projection = RTC_BG_DIRECTION;
   size_t n_lights() const { return lights_ex.empty() ? w.lights.size() : lights_ex.size(); }
   ~rtw_world() { if (scene) rtc_scene_destroy(scene); }
 };
@@ -63,7 +68,16 @@ static int ensure_scene(rtw_world* w) {
     rtc_scene_desc d = f.desc();
     if (timing) std::fprintf(stderr, "[rtc-timing] %-28s %.3f s\n", "flatten (host mirror -> desc)", since(t0));
     const auto t1 = std::chrono::steady_clock::now();
-    if (!w->cones.empty()) {  // light cones: everything else the world has goes along in the ext
+    if (w->background) {  // a background: its pattern tree joins the node array; everything else the world has goes along
+      if (!rtc_scene_create_ext3) return fail("a background needs rtc_scene_create_ext3 (librtc_amd.so)");
+      rtc_background bg{fl.root_pattern(w->background), w->background_projection};
+      d = f.desc();  // (the node array grew)
+      rtc_scene_ext x{};
+      if (!w->lights_ex.empty()) { d.n_lights = 0; d.lights = nullptr; x.n_lights = (uint32_t)w->lights_ex.size(); x.lights = w->lights_ex.data(); }
+      x.n_uv_patterns = (uint32_t)f.uv_pats.size(); x.uv_patterns = f.uv_pats.data();
+      x.n_textures = (uint32_t)f.textures.size(); x.textures = f.textures.data();
+      rc = rtc_scene_create_ext3(&d, &x, w->cones.empty() ? nullptr : w->cones.data(), (uint32_t)w->cones.size(), &bg, w->device, &w->scene);
+    } else if (!w->cones.empty()) {  // light cones: everything else the world has goes along in the ext
       if (!rtc_scene_create_ext2) return fail("light cones need rtc_scene_create_ext2 (librtc_amd.so)");
       rtc_scene_ext x{};
       if (!w->lights_ex.empty()) { d.n_lights = 0; d.lights = nullptr; x.n_lights = (uint32_t)w->lights_ex.size(); x.lights = w->lights_ex.data(); }
@@ -279,6 +293,14 @@ int rtw_world_set_light_cone(rtw_world* w, uint32_t light, const double axis[3],
   if (w->scene) { rtc_scene_destroy(w->scene); w->scene = nullptr; }
   return 0;
 }
+int rtw_world_set_background(rtw_world* w, const rtw_pattern* pattern, int32_t projection) {
+  if (!w || !pattern || !pattern->p) return fail("set_background: NULL argument");
+  if (projection != RTC_BG_DIRECTION && projection != RTC_BG_CUBE) return fail("set_background: unknown projection of the background");
+  w->background = pattern->p;
+  w->background_projection = projection;
+  if (w->scene) { rtc_scene_destroy(w->scene); w->scene = nullptr; }
+  return 0;
+}
 int rtw_world_add_element(rtw_world* w, rtw_element* e) {
   if (!e || !e->e) return fail("add_element: NULL/consumed element");
   w->w.elements.push_back(std::move(e->e));
@@ -333,12 +355,16 @@ static int refuse_area(const rtw_world* w) {
 static int refuse_cones(const rtw_world* w) {
   return w->cones.empty() ? 0 : fail("flatten: the world has light cones; they go to rtc_scene_create_ext2, not into a descriptor");
 }
+// ... a world with a background, which only rtc_scene_create_ext3 takes ...
+static int refuse_background(const rtw_world* w) {
+  return !w->background ? 0 : fail("flatten: the world has a background; it goes to rtc_scene_create_ext3, not into a descriptor");
+}
 // ... and a world with a texture-mapped pattern, whose records and textures only rtc_scene_create_ext takes.
 static int refuse_uv(const Flat& f) {
   return f.uv_pats.empty() ? 0 : fail("flatten: the world has texture-mapped patterns; their records and textures go to rtc_scene_create_ext, not into a descriptor");
 }
 int rtw_world_flatten_counts(rtw_world* w, uint32_t counts[8]) {
-  if (refuse_area(w) || refuse_cones(w)) return 1;
+  if (refuse_area(w) || refuse_cones(w) || refuse_background(w)) return 1;
   Flat f;
   Flattener fl(f);
   if (!fl.run(w->w)) return fail("flatten: " + f.error);
@@ -352,7 +378,7 @@ int rtw_world_flatten_counts(rtw_world* w, uint32_t counts[8]) {
 // Flatten only (no device): the descriptor a Rust shim would hand to rtc_scene_create; its arrays live in the world handle until
 // the next call / the world's release.  Works without a GPU (tests compare it with a foreign flattener's output).
 int rtw_world_flatten_desc(rtw_world* w, rtc_scene_desc* out) {
-  if (refuse_area(w) || refuse_cones(w)) return 1;
+  if (refuse_area(w) || refuse_cones(w) || refuse_background(w)) return 1;
   w->flat.reset(new Flat());
   Flattener fl(*w->flat);
   if (!fl.run(w->w)) return fail("flatten: " + w->flat->error);

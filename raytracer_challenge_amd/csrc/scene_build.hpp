@@ -947,6 +947,9 @@ struct HostArrays {
   int32_t has_area = 0;    // lights holds RTC_ALIGHT doubles per light (build_arrays_ex)
   int32_t has_uv = 0;      // some pattern node is an RTC_PAT_UV node
   int32_t has_spot = 0;    // some light has a cone: lights holds RTC_SLIGHT doubles per light (build_arrays_ex)
+  int32_t has_bg = 0;      // the scene has a background (rtc_scene_create_ext3; set before build_arrays): its one-kernel launches read the
+                           // program from memory, whatever the program's own variant, so the intersection records are built
+  int32_t recs_bg_only = 0;  // ... and nothing else reads them: DScene.n_recs stays 0, as without the background (rtc_kernel_info reports it)
   int32_t area_bounded = 1;  // every area light's sample positions lie below 1e30 in magnitude (the back-face scan's condition)
   double quirk_reach2 = 0.0, abvh_frame[4] = {0, 0, 0, 0};  // see DScene
 
@@ -1006,7 +1009,7 @@ struct HostArrays {
     d.item_prim = items.data(); d.quirk_prim = items.data(); d.qgrids = qgrids.data(); d.qcell = qcell.data(); d.bvh_frame = bvh_frame.data(); d.csg = csg.data(); d.qitem = items.data(); d.prims = prims.data(); d.pisect = pisect.data(); d.xf_inv = xf_inv.data(); d.xf_matinv = xf_matinv.data(); d.limits = limits.data();
     d.tri_geo = tri_geo.data(); d.tri_nrm = tri_nrm.data(); d.mat = mat.data(); d.mat_pattern = mat_pattern.data(); d.pats = pats.data();
     d.lights = lights.data();
-    d.n_ops = (int32_t)ops.size(); d.n_prims = (int32_t)prims.size(); d.n_recs = (int32_t)pisect.size(); d.n_lights = n_lights; d.all_cast_shadow = all_cast_shadow;
+    d.n_ops = (int32_t)ops.size(); d.n_prims = (int32_t)prims.size(); d.n_recs = recs_bg_only ? 0 : (int32_t)pisect.size(); d.n_lights = n_lights; d.all_cast_shadow = all_cast_shadow;
     d.n_bvh = (int32_t)bvh.size(); d.n_items = (int32_t)items.size(); d.n_mtri = (int32_t)mtri_prim.size(); d.n_quirk = (int32_t)items.size();
     d.n_qitem = (int32_t)items.size(); d.n_qcell = (int32_t)qcell.size(); d.n_groups = (int32_t)(group_box.size() / 6); d.n_qgrids = (int32_t)qgrids.size();
     d.bvh_stack = bvh_stack;
@@ -1211,7 +1214,9 @@ inline int build_arrays(const rtc_scene_desc& D, HostArrays* H, std::string* err
     // and a few planes in the kernel arguments do not, and 10^6 triangles would carry 128 MB of them to the device for nothing
     // (scenes with a UV pattern always get them: the one-kernel path renders them with a build that reads the program from memory,
     // rtc_feat.hip variants 8 and 9, whatever the program's own variant; scenes with a light cone likewise, on both paths: variants 10, 11)
-    if (dv.has_recs || H->has_uv || H->has_spot) {
+    // ... and scenes with a background, for their one-kernel path's BG build: rtc_background.hip)
+    H->recs_bg_only = (H->has_bg && !(dv.has_recs || H->has_uv || H->has_spot)) ? 1 : 0;
+    if (dv.has_recs || H->has_uv || H->has_spot || H->has_bg) {
       // ... and only up to the last primitive an op can name: the program's own OP_PRIMs (CSG sub-programs included) and the analytic
       // BVH's primitives.  Mesh triangles are reached through their BVH's packed triangle array, never through a record; an OBJ
       // group at the end of the world -- where the bins put it -- leaves the array a few entries long.
@@ -1249,6 +1254,12 @@ struct ConeInput {
   const rtc_light_cone* cones = nullptr;
   uint32_t n = 0;
 };
+// A background's own limits (include/rtc.h rtc_background); needs no descriptor beyond the pattern-node count.
+inline int validate_background(const rtc_background& b, uint32_t n_pattern_nodes, std::string* err) {
+  if (b.projection != RTC_BG_DIRECTION && b.projection != RTC_BG_CUBE) { *err = "background: unknown projection"; return RTC_ERR_INVALID; }
+  if (b.pattern < 0 || (uint32_t)b.pattern >= n_pattern_nodes) { *err = "background: pattern index out of range"; return RTC_ERR_INVALID; }
+  return RTC_OK;
+}
 // The cones' own limits; needs no descriptor beyond the light count.
 inline int validate_cones(const ConeInput& K, uint32_t n_lights, std::string* err) {
   if (K.n > 0 && !K.cones) { *err = "cones is NULL"; return RTC_ERR_INVALID; }

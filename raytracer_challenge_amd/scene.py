@@ -368,10 +368,34 @@ class AreaLight:
         return self.usteps * self.vsteps
 
 
+BACKGROUND_PROJECTIONS = ("direction", "cube")  # include/rtc.h RTC_BG_*, in enum order
+
+
+@dataclass(frozen=True)
+class Background:
+    """What a ray that hits nothing sees (include/rtc.h rtc_background; not in the reference, where it is black): ``pattern`` -- any
+    Pattern, a texture map included -- evaluated at the ray's direction (``projection="direction"``) or at the direction scaled onto
+    the unit cube's surface (``"cube"``: a skybox for a cube map).  It is weighted like a surface colour down the ray tree, is no
+    light and casts no shadow.  Rendered by the HIP library only."""
+    pattern: Pattern
+    projection: str = "direction"
+
+    def __post_init__(self):
+        if not isinstance(self.pattern, Pattern):
+            raise TypeError("Background.pattern must be a Pattern")
+        if self.projection not in BACKGROUND_PROJECTIONS:
+            raise ValueError("Background.projection must be one of %r" % (BACKGROUND_PROJECTIONS,))
+
+
 @dataclass
 class World:  # src/world.rs:12-15; lights: PointLight, SpotLight and AreaLight in any order (the order is kept)
     lights: List[PointLight] = field(default_factory=list)
     elements: List[Element] = field(default_factory=list)
+    background: Optional[Background] = None  # not in the reference: see Background
+
+    def __post_init__(self):
+        if self.background is not None and not isinstance(self.background, Background):
+            raise TypeError("World.background must be a Background or None")
 
     @staticmethod
     def default() -> "World":  # src/world.rs:152-183

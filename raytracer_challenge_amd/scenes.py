@@ -442,3 +442,29 @@ def spot_showcase(hsize=None, vsize=None) -> Tuple[Camera, World]:
                   cone=Cone(Vector.vector(-4.0, -6.0, 5.0), 0.2, 0.45)),
     ]
     return _cam(1920, 1080, PI / 3.0, (0.0, 3.0, -8.5), (0.0, 1.0, 0.5), (0.0, 1.0, 0.0), hsize, vsize), World(lights, [floor, matte, mirror, glass])
+
+
+def sky_showcase(hsize=None, vsize=None, skybox: bool = False) -> Tuple[Camera, World]:
+    """A scene background: a checkered floor with a mirror, a glass and a matte ball under an open sky.  The sky is a gradient over
+    the ray direction's height, horizon haze to zenith blue, so the mirror and the glass show a sky instead of a void; with
+    ``skybox`` it is a cube map of six seeded image textures looked up on the unit cube's surface (projection "cube")."""
+    from .scene import Background
+    c = Color.new
+    floor = Element.plane(ShapeArgs(material=Material(
+        pattern=Pattern.checkers(Matrix.id(), Pattern.plain(c(0.8, 0.8, 0.75)), Pattern.plain(c(0.3, 0.3, 0.35))), specular=0.0, reflective=0.15)))
+    mirror = Element.sphere(ShapeArgs(transform=Matrix.translation(-1.6, 1.0, 1.0), material=Material(
+        pattern=Pattern.plain(c(0.05, 0.05, 0.05)), diffuse=0.2, specular=0.9, shininess=300.0, reflective=0.9)))
+    glass = Element.sphere(ShapeArgs(transform=Matrix.translation(1.3, 0.8, -0.6) * Matrix.scaling(0.8, 0.8, 0.8), material=Material(
+        pattern=Pattern.plain(Color.black()), diffuse=0.1, shininess=300.0, reflective=0.9, transparency=0.9, refractive_index=1.5)))
+    matte = Element.sphere(ShapeArgs(transform=Matrix.translation(0.2, 0.5, -2.2) * Matrix.scaling(0.5, 0.5, 0.5), material=Material(
+        pattern=Pattern.plain(c(0.9, 0.35, 0.2)), diffuse=0.8, specular=0.2)))
+    if skybox:
+        from .texture import UvPattern
+        faces = [UvPattern.image(procedural_texture(32, 32, seed=100 + k)) for k in range(6)]
+        background = Background(Pattern.cube_map(Matrix.id(), *faces), "cube")
+    else:
+        # the gradient runs along x of its own space: turn the direction's height into x in (0, 1), horizon at 0.5
+        up = Matrix.translation(0.0, -1.0, 0.0) * Matrix.scaling(2.0001, 2.0001, 2.0001) * Matrix.rotation_z(PI / 2.0)
+        background = Background(Pattern.gradient(up, Pattern.plain(c(0.95, 0.9, 0.8)), Pattern.plain(c(0.2, 0.45, 0.9))), "direction")
+    lights = [PointLight(c(0.9, 0.9, 0.85), Vector.point(-6.0, 9.0, -8.0))]
+    return _cam(1920, 1080, PI / 3.0, (0.0, 1.8, -7.0), (0.0, 1.0, 0.5), (0.0, 1.0, 0.0), hsize, vsize), World(lights, [floor, mirror, glass, matte], background)

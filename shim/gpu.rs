@@ -136,6 +136,34 @@ pub struct RtcLightCone {
     pub cos_outer: f64, // <= cos_inner
 }
 
+// include/rtc.h rtc_background: what a ray that hits nothing sees (not in the reference, where it is black), for rtc_scene_create_ext3 /
+// rtc_multi_create_ext3
+#[allow(dead_code)]
+pub const RTC_BG_DIRECTION: i32 = 0;
+#[allow(dead_code)]
+pub const RTC_BG_CUBE: i32 = 1;
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtcBackground {
+    pub pattern: i32,    // index of a root RtcPatternNode
+    pub projection: i32, // RTC_BG_*
+}
+// include/rtc.h rtc_background_info: which builds a launch of a background scene takes (test hook)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtcBackgroundInfo {
+    pub has_background: i32,
+    pub pattern: i32,
+    pub projection: i32,
+    pub plain_root: i32,
+    pub trace_build: i32,
+    pub trace_area: i32,
+    pub trace_uv: i32,
+    pub trace_spot: i32,
+    pub wf_background_build: i32,
+    pub _pad: i32,
+}
+
 // include/rtc.h rtc_sampling: n x n samples per pixel and an optional thin lens (not in the reference) for rtc_render_sampled*
 #[allow(dead_code)]
 pub const RTC_SAMPLE_JITTER: u32 = 1;
@@ -285,6 +313,18 @@ extern "C" {
                              n_devices: c_int, out: *mut *mut RtcMulti) -> c_int;
     #[allow(dead_code)] // host-only: the cone factor of one light position and shading point
     fn rtc_spot_factor(cone: *const RtcLightCone, light_pos: *const f64, point: *const f64, f: *mut f64) -> c_int;
+    #[allow(dead_code)]
+    fn rtc_scene_create_ext3(desc: *const RtcSceneDesc, ext: *const RtcSceneExt, cones: *const RtcLightCone, n_cones: u32, bg: *const RtcBackground,
+                             device: c_int, out: *mut *mut RtcScene) -> c_int;
+    #[allow(dead_code)]
+    fn rtc_multi_create_ext3(desc: *const RtcSceneDesc, ext: *const RtcSceneExt, cones: *const RtcLightCone, n_cones: u32, bg: *const RtcBackground,
+                             devices: *const c_int, n_devices: c_int, out: *mut *mut RtcMulti) -> c_int;
+    #[allow(dead_code)] // host-only: where a ray of direction dir looks the background up
+    fn rtc_background_point(projection: i32, dir: *const f64, point: *mut f64) -> c_int;
+    #[allow(dead_code)] // the background's colour for n directions, evaluated on the device
+    fn rtc_background_colors(scene: *mut RtcScene, dirs: *const f64, n: u64, rgb: *mut f64) -> c_int;
+    #[allow(dead_code)]
+    fn rtc_scene_background_info(scene: *const RtcScene, out: *mut RtcBackgroundInfo) -> c_int;
     fn rtc_multi_destroy(multi: *mut RtcMulti);
     fn rtc_render_multi(multi: *mut RtcMulti, camera: *const RtcCamera, fuel: i32, rgb: *mut f64, stats: *mut RtcStats) -> c_int;
     #[allow(dead_code)] // Color::clamp'ed pixels (what Image::ppm writes): 3 bytes per pixel cross xGMI instead of 24
