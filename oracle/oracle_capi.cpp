@@ -26,7 +26,11 @@ static Material to_material(const rtw_material* m) {
 extern "C" {
 
 const char* rtw_last_error(void) { return g_err.c_str(); }
+#ifdef ORC_EXT
+const char* rtw_backend(void) { return "oracle-ext-cpu"; }  // liboracle_ext.so (oracle_ext_capi.cpp)
+#else
 const char* rtw_backend(void) { return "oracle-cpu"; }
+#endif
 
 rtw_pattern* rtw_pattern_debug(void) { return new rtw_pattern{Pattern::debug()}; }
 rtw_pattern* rtw_pattern_plain(double r, double g, double b) { return new rtw_pattern{Pattern::plain({r, g, b})}; }

@@ -368,13 +368,22 @@ enum MixtureKind { Blend = 0, Checkers = 1, RingGradient = 2, Ring = 3, Gradient
 struct Pattern;
 using PatternPtr = std::shared_ptr<const Pattern>;  // Box<Pattern>; trees are immutable so clones may share
 struct Pattern {                                    // material.rs:60-65
-  enum Tag { Debug = 0, Plain = 1, Jitter = 2, Mixture = 3 } tag = Plain;
+  enum Tag {
+    Debug = 0, Plain = 1, Jitter = 2, Mixture = 3,
+#ifdef ORC_EXT
+    UV = 4,  // include/rtc.h RTC_PAT_UV (rt_oracle_ext.hpp)
+#endif
+  } tag = Plain;
   Color color{1, 1, 1};
   JitterKind jkind = JitterPoint;
   Noise noise;
   MixtureKind mkind = Blend;
   Matrix transform_inv = Matrix::id();
   PatternPtr left, right;  // Jitter uses `left` as its child
+#ifdef ORC_EXT
+  std::shared_ptr<const struct UvNode> uv;  // UV: the map and its records; transform_inv as a Mixture's
+  Color uv_color_at(Vector point) const;    // rt_oracle_ext.hpp
+#endif
 
   static PatternPtr debug() { auto p = std::make_shared<Pattern>(); p->tag = Debug; return p; }
   static PatternPtr plain(Color c) { auto p = std::make_shared<Pattern>(); p->tag = Plain; p->color = c; return p; }
@@ -406,6 +415,9 @@ struct Pattern {                                    // material.rs:60-65
           return left->color_at(Vector::point(nx, ny, nz));
         }
       }
+#ifdef ORC_EXT
+      case UV: return uv_color_at(point);
+#endif
       default: {
         Vector p = transform_inv * point;
         return mix(p);
@@ -945,6 +957,11 @@ struct Counters {
 struct World {  // :12-15
   std::vector<PointLight> lights;
   std::vector<ElementPtr> elements;
+#ifdef ORC_EXT
+  // Area lights, light cones and the background (include/rtc.h; not in the reference), rt_oracle_ext.hpp.  Null for a world
+  // that has none of them: such a world takes every step below as liboracle.so takes it.
+  std::shared_ptr<struct WorldExt> ext;
+#endif
 
   static World default_world() {  // :152-183
     World w;
@@ -981,6 +998,10 @@ struct World {  // :12-15
     int repeat = 0;      // > 0: inside a subtree the reference re-traces for a light other than the first
     int next_kind = 0;   // kind of the ray the next color_at call traces
   };
+#ifdef ORC_EXT
+  Color shade_hit_ext(const State& st, int fuel, Ctx& c) const;
+  Color miss_color_ext(const Ray& ray, int fuel, const Ctx& c) const;
+#endif
 
   void intersect(const Ray& ray, Ctx& c) const {  // :18-24
     c.xs.clear();
@@ -997,6 +1018,9 @@ struct World {  // :12-15
     return h ? (h->shape->casts_shadow && h->t < distance) : false;
   }
   Color shade_hit(const State& st, int fuel, Ctx& c) const {  // :50-82
+#ifdef ORC_EXT
+    if (ext) return shade_hit_ext(st, fuel, c);
+#endif
     Color color = Color::black();
     int depth = c.fuel0 - fuel;
     bool first_light = true;
@@ -1058,6 +1082,9 @@ struct World {  // :12-15
       State st = prepare_state(self, ray, c.xs);
       return shade_hit(st, fuel, c);
     }
+#ifdef ORC_EXT
+    if (ext) return miss_color_ext(ray, fuel, c);
+#endif
     return Color::black();
   }
 
@@ -1401,3 +1428,7 @@ inline ObjResult parse_obj_file(const std::string& path, const Matrix& transform
 }
 
 }  // namespace orc
+
+#ifdef ORC_EXT
+#include "rt_oracle_ext.hpp"  // liboracle_ext.so only: the extensions' bodies
+#endif

@@ -26,10 +26,24 @@ def oracle_reference(orc, world, camera, fuel=5, pixel_indices=None, threads=0):
     return orc.render_with_digest(orc.build_world(world), camera, fuel, pixel_indices, threads=threads)
 
 
-def assert_parity(test_backend, orc, world, camera, fuel=5, pixel_indices=None, label="", digest=True, ref=None, rel=False):
+def unmasked(rgb, ref_rgb, color_mask):
+    """The rows a colour comparison keeps.  Of the rows left out only the values are: where the reference is NaN or infinite the device
+    must still be, masked or not (the rows go through rgb_error's first check with their finite values set equal)."""
+    if color_mask is None:
+        return rgb, ref_rgb
+    m = np.asarray(color_mask, dtype=bool)
+    assert m.shape == (len(rgb),), "the colour mask needs one flag per pixel or ray"
+    rgb = rgb.copy()
+    fin = np.isfinite(rgb[m]) & np.isfinite(ref_rgb[m])
+    rgb[m] = np.where(fin, ref_rgb[m], rgb[m])
+    return rgb, ref_rgb
+
+
+def assert_parity(test_backend, orc, world, camera, fuel=5, pixel_indices=None, label="", digest=True, ref=None, rel=False, color_mask=None):
     """Hit records must be bit-exact: the primary hit of every pixel (t as u64 bits, primitive sequence number, push index) and,
     through the hit-tree digest (include/rtc.h rtc_render_hit_digest), every closest hit of every pixel's ray tree — reflected and
-    refracted rays at every depth; colours within RGB_TOL."""
+    refracted rays at every depth; colours within RGB_TOL.  color_mask (default: none) names pixels left out of the COLOUR comparison
+    only: their hit records, digests and NaN / infinity pattern are held like everyone's."""
     nw_t = test_backend.build_world(world)
     rgb, hits = test_backend.render(nw_t, camera, fuel, pixel_indices)
     ref_dig = None
@@ -47,18 +61,18 @@ def assert_parity(test_backend, orc, world, camera, fuel=5, pixel_indices=None, 
         bad_d = dig != ref_dig
         assert not bad_d.any(), "%s: the hit-tree digests of %d/%d pixels differ (a closest hit somewhere below the primary one), first at %s" % (
             label, int(bad_d.sum()), bad_d.size, np.flatnonzero(bad_d)[:5])
-    err = rgb_error(rgb, ref_rgb, label, rel)
+    err = rgb_error(*unmasked(rgb, ref_rgb, color_mask), label, rel)
     assert err <= RGB_TOL, "%s: max |dRGB| = %.3e > %.0e" % (label, err, RGB_TOL)
     return err
 
 
-def assert_ray_parity(test_backend, orc, world, rays, fuel=5, label="", rel=False):
+def assert_ray_parity(test_backend, orc, world, rays, fuel=5, label="", rel=False, color_mask=None):
     nw_t, nw_o = test_backend.build_world(world), orc.build_world(world)
     rgb, hits = test_backend.color_at(nw_t, rays, fuel)
     ref_rgb, ref_hits = orc.color_at(nw_o, rays, fuel)
     bad = (hits["prim"] != ref_hits["prim"]) | (hits["push_idx"] != ref_hits["push_idx"]) | (hits["t"].view(np.uint64) != ref_hits["t"].view(np.uint64))
     assert not bad.any(), "%s: %d/%d hit records differ: got %s want %s" % (label, int(bad.sum()), bad.size, hits[bad][:3], ref_hits[bad][:3])
-    err = rgb_error(rgb, ref_rgb, label, rel)
+    err = rgb_error(*unmasked(rgb, ref_rgb, color_mask), label, rel)
     assert err <= RGB_TOL, "%s: max |dRGB| = %.3e" % (label, err)
     return err
 
@@ -73,7 +87,7 @@ def _raises(backend, nw, rays, fuel):
         return True
 
 
-def assert_ray_parity_with_panics(test_backend, orc, world, rays, fuel=5, label="", max_panics=64, rel=False):
+def assert_ray_parity_with_panics(test_backend, orc, world, rays, fuel=5, label="", max_panics=64, rel=False, color_mask=None):
     """assert_ray_parity for ray sets that may hold rays on which the reference PANICS (a NaN t reaches its sort,
     src/intersection.rs:123-125): those rays are found with the oracle (bisection), the device must refuse each of them alone with
     RTC_ERR_NAN, and the rest of the set must match hit for hit.  Returns (max |dRGB|, number of panicking rays)."""
@@ -96,4 +110,5 @@ def assert_ray_parity_with_panics(test_backend, orc, world, rays, fuel=5, label=
         assert _raises(test_backend, nw_t, rays[i:i + 1], fuel), "%s: the reference panics on ray %d %s, the device does not" % (label, i, rays[i])
     keep = np.ones(len(rays), dtype=bool)
     keep[panics] = False
-    return assert_ray_parity(test_backend, orc, world, rays[keep], fuel, label=label, rel=rel), len(panics)
+    mask = None if color_mask is None else np.asarray(color_mask, dtype=bool)[keep]
+    return assert_ray_parity(test_backend, orc, world, rays[keep], fuel, label=label, rel=rel, color_mask=mask), len(panics)
