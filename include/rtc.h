@@ -343,6 +343,35 @@ typedef struct rtc_filter {
   double alpha;           /* GAUSSIAN's falloff; read by no other kind */
 } rtc_filter;
 
+/* The shutter (not in the reference, whose frame sees one scene from one camera): motion blur over K poses of the scene and the camera,
+ * the accumulation-buffer way, for the rtc_render_shutter* entry points and, the dealing alone, rtc_shutter_deal.  The caller supplies K
+ * poses; pose p of K has scenes[p] and cameras[p] (the pointers may repeat: a moving camera over a static scene passes one scene K
+ * times).  Every sample of every pixel is dealt to ONE pose and traced there; the pixel stays the mean of its N samples (a box shutter).
+ * All cameras share hsize and vsize; transform_inv, half_width, half_height and pixel_size may differ from pose to pose.
+ *   Pixel i, sample k of N = side * side, h = m(m(m(seed) ^ i) ^ k) and rtc_area_jitter are rtc_sampling's above.
+ *   Pose s of sample (i, k) (csrc/shutter_pose.h, one function for device and host):
+ *     without RTC_SHUTTER_HASHED: s = (uint32_t)(((uint64_t)k * K) / N) -- sequential: the pixel's samples in K runs of floor(N / K) or
+ *       ceil(N / K); K > N is refused, some poses would never be sampled.
+ *     with RTC_SHUTTER_HASHED: u = rtc_area_jitter(h, 4u), the draw after the lens's two; t = u * (double)K; s = (uint32_t)t, held to
+ *       K - 1.  Hashed whether or not RTC_SAMPLE_JITTER is set, as the lens draws are.  Nothing of the launch, chunk, device or device
+ *       path enters.
+ *   Ray of sample (i, k): rtc_sampling's ray of (i, k) through cameras[s], unchanged, lens included.
+ *   Colour: c_k = World::color_at(that ray, fuel) in scenes[s].
+ *   Pixel colour: (((c_0 + c_1) + c_2) + ... + c_{N-1}) / (double)N per channel, k ascending: rtc_render_sampled's sum.
+ *   Identities: K = 1 is rtc_render_sampled bit for bit; so are K equal poses under either flag -- the same pointers repeated, or equal
+ *     scenes created twice.
+ * Limits: RTC_ERR_INVALID for K == 0, NULL arrays or entries, unknown flag bits, cameras whose hsize or vsize differ, scenes on different
+ * devices, K > N without RTC_SHUTTER_HASHED, and everything rtc_sampling refuses; RTC_ERR_UNSUPPORTED for K > RTC_SHUTTER_MAX_POSES.  The
+ * shutter's own numbers are checked before anything else, a device included.
+ * Not covered: bands, rtc_render_rows_device and rtc_multi; adaptive and filtered renders; hit records and digests; a time stratified
+ * jointly with the sub-pixel cell; interpolated transforms inside one scene; shutters other than the box. */
+enum { RTC_SHUTTER_HASHED = 1u };
+#define RTC_SHUTTER_MAX_POSES 64
+typedef struct rtc_shutter {
+  uint32_t flags;         /* RTC_SHUTTER_HASHED */
+  uint32_t _pad;
+} rtc_shutter;
+
 /* The Element tree (src/shape.rs:31-34, :181-185) in DFS pre-order.  A group node carries the world-space
  * bounding box the reference computed for it (Element::composite + propagate_inverses; NaN/inf included,
  * SURVEY Q9) and `skip` = index of the first node after its subtree.  The device evaluates
@@ -593,6 +622,32 @@ int rtc_render_filtered_rgb8(rtc_scene*, const rtc_camera*, const rtc_sampling*,
  * kernel filters, the frame is copied back; scene == NULL: evaluated on the host by the same function, no device needed (like
  * rtc_contrast_pixels).  Of `sampling` only side, flags and seed are read (its lens is validated). */
 int rtc_filter_frame(rtc_scene*, uint64_t hsize, uint64_t vsize, const rtc_sampling*, const rtc_filter*, const double* sample_rgb, double* rgb);
+
+/* ---- the shutter (rtc_shutter above) -------------------------------------------------------------------------------------------------
+ * rtc_render_sampled over n_poses poses: pixels as in rtc_render (a range or a list, of the cameras' common frame).  On one device, in
+ * rtc_render_sampled's chunks (RTC_SAMPLED_MAX_RAYS as there; the buffers are scenes[0]'s).  Per chunk, on scenes[0]'s stream: two small
+ * kernels and a scan (csrc/rtc_shutter.hip) deal the chunk's samples to the poses and sort their ids by pose -- ballots, ranks within the
+ * wave, a pose-major table of per-block counts, ONE exclusive scan: no atomic orders the list, it is ascending within a pose --; the host
+ * must know the runs to launch over them: ONE read-back of the n_poses + 1 offsets is the synchronisation this feature adds per chunk.
+ * Then, per pose with a non-empty run, a generator kernel writes the run's rays through that pose's camera and that pose's scene traces
+ * them as explicit rays (every scene kind, both device paths; ordered against scenes[0]'s stream by an event before, and by the end of
+ * the synchronous trace after); a last kernel gathers each pixel's N colours back in k order and WRITES their mean.  Only pixels leave the device.
+ * Device path of a run: RTC_KERNEL pins as ever; otherwise its scene's first guess (rtc_scene_path_info) over the run's rays -- the runs
+ * change with the seed, so nothing is measured.  rtc_stats: pixels = n, rays_primary = n * N, counters summed over poses and chunks,
+ * kernel_ms = dealing + generators + traces + resolve, n_launches counts those kernels too.  No hit records or digests. */
+int rtc_render_shutter(rtc_scene* const* scenes, const rtc_camera* cameras, uint32_t n_poses, const rtc_shutter*, const rtc_sampling*,
+                       int32_t fuel, const uint64_t* pixel_indices, uint64_t first, uint64_t n, double* rgb, rtc_stats* stats);
+/* The whole frame, quantised on the device (Color::clamp): rgb8 = hsize*vsize*3 bytes (host). */
+int rtc_render_shutter_rgb8(rtc_scene* const* scenes, const rtc_camera* cameras, uint32_t n_poses, const rtc_shutter*, const rtc_sampling*,
+                            int32_t fuel, uint8_t* rgb8, rtc_stats* stats);
+/* The dealing alone, for pixels as in rtc_render_shutter (of a frame hsize wide; one chunk: n * N below 2^31): order[0 .. n*N-1] = the
+ * sample ids (slot * N + k, slot = the pixel's place in the range or list) pose-major, ascending within a pose; offsets[0 .. n_poses] =
+ * where each pose's run starts (offsets[n_poses] = n*N).  scene != NULL: the device kernels above, copied back; scene == NULL: the same
+ * rule on the host (a stable counting sort), no device needed -- like rtc_contrast_pixels. */
+int rtc_shutter_deal(rtc_scene* scene, uint64_t hsize, uint32_t n_poses, const rtc_shutter*, const rtc_sampling*,
+                     const uint64_t* pixel_indices, uint64_t first, uint64_t n, uint32_t* order, uint64_t* offsets);
+/* Test hook: the pose of a hashed draw u in [0, 1) among n_poses (>= 1) -- (uint32_t)(u * (double)n_poses), held to n_poses - 1.  Host only. */
+uint32_t rtc_shutter_draw_pose(double u, uint32_t n_poses);
 
 /* ---- the step after the path: Color::clamp and Image::ppm ---------------------------------
  * Color::clamp (src/color.rs:42-46): u8 = round(min(max(c, 0), 1) * 255), round half away from zero, NaN -> 255 (Rust's

@@ -9,11 +9,11 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Dict, Optional
+from typing import Dict, Optional, Sequence
 
 import numpy as np
 
-from .scene import (BACKGROUND_PROJECTIONS, FUEL, GEOMETRY, GROUP_KINDS, JITTER_KINDS, MIXTURE_KINDS, Adaptive, AreaLight, Camera, Cone, Element, FILTER_KINDS, Filter, Material, Pattern, Sampling, World)
+from .scene import (BACKGROUND_PROJECTIONS, FUEL, GEOMETRY, GROUP_KINDS, JITTER_KINDS, MIXTURE_KINDS, Adaptive, AreaLight, Camera, Cone, Element, FILTER_KINDS, Filter, Material, Pattern, SHUTTER_MAX_POSES, Sampling, Shutter, World)
 from .texture import UV_KINDS, UV_MAPS, Texture
 
 HIT_DTYPE = np.dtype([("t", "<f8"), ("prim", "<i4"), ("push_idx", "<i4")])
@@ -59,6 +59,14 @@ class FilterC(C.Structure):  # include/rtc.h rtc_filter
     @staticmethod
     def of(f: Filter) -> "FilterC":
         return FilterC(FILTER_KINDS.index(f.kind), 0, float(f.radius), float(f.alpha))
+
+
+class ShutterC(C.Structure):  # include/rtc.h rtc_shutter
+    _fields_ = [("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+    @staticmethod
+    def of(s: Shutter) -> "ShutterC":
+        return ShutterC(1 if s.hashed else 0, 0)
 
 
 RTW_SYMBOLS = [
@@ -481,6 +489,80 @@ class Backend:
         if lib.rtc_filter_frame(scene, int(hsize), int(vsize), C.byref(sp), C.byref(fl), samples.ctypes.data, rgb.ctypes.data) != 0:
             raise RtwError("rtc_filter_frame: %s" % (lib.rtc_last_error() or b"").decode())
         return rgb
+
+    def _shutter_lib(self):
+        """The rtc_* entry points of the shutter, bound; RtwError for a library that has none (the CPU emulator, the oracle)."""
+        lib = self.lib
+        if not (hasattr(lib, "rtc_render_shutter") and hasattr(lib, "rtc_shutter_deal")):
+            raise RtwError("a shutter needs librtc_amd.so (backend %r has no rtc_render_shutter)" % self.name)
+        vp = C.c_void_p
+        lib.rtw_world_scene.restype, lib.rtw_world_scene.argtypes = vp, [vp, C.c_int]
+        lib.rtw_make_camera.restype, lib.rtw_make_camera.argtypes = C.c_int, [vp, vp]
+        lib.rtc_render_shutter.restype = C.c_int
+        lib.rtc_render_shutter.argtypes = [vp, vp, C.c_uint32, C.POINTER(ShutterC), C.POINTER(SamplingC), C.c_int32, vp, C.c_uint64, C.c_uint64, vp, vp]
+        lib.rtc_shutter_deal.restype = C.c_int
+        lib.rtc_shutter_deal.argtypes = [vp, C.c_uint64, C.c_uint32, C.POINTER(ShutterC), C.POINTER(SamplingC), vp, C.c_uint64, C.c_uint64, vp, vp]
+        lib.rtc_last_error.restype = C.c_char_p
+        return lib
+
+    def render_shutter(self, nws: Sequence[NativeWorld], cameras: Sequence[Camera], sampling: Sampling, shutter: Shutter, fuel: int = FUEL,
+                       pixel_indices: Optional[np.ndarray] = None, stats=None, device: int = 0) -> np.ndarray:
+        """include/rtc.h rtc_render_shutter: pose p is (nws[p], cameras[p]); every pixel (row-major) or the listed pixel indices as the
+        mean of `sampling`'s rays, each traced in the pose `shutter` deals it to.  A world given several times is one scene.  stats: an
+        rtc_stats structure (ctypes) to fill.  Returns rgb[n,3]."""
+        if len(nws) != len(cameras):
+            raise ValueError("render_shutter: as many worlds as cameras")
+        if not 1 <= len(nws) <= SHUTTER_MAX_POSES:
+            raise ValueError("render_shutter: 1 to %d poses" % SHUTTER_MAX_POSES)
+        if any((c.hsize, c.vsize) != (cameras[0].hsize, cameras[0].vsize) for c in cameras):
+            raise ValueError("render_shutter: the cameras' hsize or vsize differ")
+        lib = self._shutter_lib()
+        K = len(nws)
+        scenes = (C.c_void_p * K)()
+        for p, nw in enumerate(nws):
+            scenes[p] = lib.rtw_world_scene(nw.handle, int(device))
+            if not scenes[p]:
+                raise RtwError("scene upload failed: %s" % self._err())
+        cams = ((C.c_double * 21) * K)()   # rtc_camera: 2 x u64 + 3 + 16 doubles
+        for p, cam in enumerate(cameras):
+            cc = self.camera_c(cam)
+            if lib.rtw_make_camera(C.byref(cc), C.byref(cams[p])) != 0:
+                raise RtwError("camera: %s" % self._err())
+        sp, sh = SamplingC.of(sampling), ShutterC.of(shutter)
+        if pixel_indices is None:
+            n, idx_p = cameras[0].hsize * cameras[0].vsize, None
+        else:
+            pixel_indices = np.ascontiguousarray(pixel_indices, dtype=np.uint64)
+            n, idx_p = pixel_indices.size, pixel_indices.ctypes.data
+        rgb = np.empty((n, 3), dtype=np.float64)
+        if lib.rtc_render_shutter(scenes, cams, K, C.byref(sh), C.byref(sp), int(fuel), idx_p, 0, n, rgb.ctypes.data, None if stats is None else C.addressof(stats)) != 0:
+            raise RtwError("rtc_render_shutter: %s" % (lib.rtc_last_error() or b"").decode())
+        return rgb
+
+    def shutter_deal(self, hsize: int, n_poses: int, sampling: Sampling, shutter: Shutter, pixel_indices: Optional[np.ndarray] = None, first: int = 0,
+                     n: Optional[int] = None, nw: Optional[NativeWorld] = None, device: int = 0):
+        """include/rtc.h rtc_shutter_deal: the dealing alone for the pixels first .. first + n - 1 or the listed ones of a frame `hsize`
+        wide.  Returns (order[n * side * side] of uint32: the sample ids pose-major, offsets[n_poses + 1] of uint64: the runs' starts).
+        With a world the device kernels deal, without one the same rule is evaluated on the host (no GPU needed)."""
+        lib = self._shutter_lib()
+        scene = None
+        if nw is not None:
+            scene = lib.rtw_world_scene(nw.handle, int(device))
+            if not scene:
+                raise RtwError("scene upload failed: %s" % self._err())
+        if pixel_indices is None:
+            if n is None:
+                raise ValueError("shutter_deal: give pixel_indices or n")
+            idx_p = None
+        else:
+            pixel_indices = np.ascontiguousarray(pixel_indices, dtype=np.uint64)
+            n, idx_p = pixel_indices.size, pixel_indices.ctypes.data
+        sp, sh = SamplingC.of(sampling), ShutterC.of(shutter)
+        order = np.empty(int(n) * sampling.samples, dtype=np.uint32)
+        offsets = np.empty(max(0, int(n_poses)) + 1, dtype=np.uint64)
+        if lib.rtc_shutter_deal(scene, int(hsize), int(n_poses), C.byref(sh), C.byref(sp), idx_p, int(first), int(n), order.ctypes.data, offsets.ctypes.data) != 0:
+            raise RtwError("rtc_shutter_deal: %s" % (lib.rtc_last_error() or b"").decode())
+        return order, offsets
 
     def color_at(self, nw: NativeWorld, rays: np.ndarray, fuel: int = FUEL):
         """World::color_at for rays given as rows {ox,oy,oz,dx,dy,dz}.  Returns (rgb[n,3], hits[n])."""

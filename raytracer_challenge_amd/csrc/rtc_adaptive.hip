@@ -95,11 +95,35 @@ __global__ void __launch_bounds__(RTC_ADAPT_BLOCK) rtc_resolve_samples_scatter(c
 // Blocks of the flag / scatter kernels for a frame of n pixels, and of one scan level over m entries.
 unsigned long long rtc_contrast_blocks(unsigned long long n) { return (n + RTC_ADAPT_BLOCK - 1) / RTC_ADAPT_BLOCK; }
 
-// Device words (8 bytes each) rtc_launch_contrast_compact needs in `work` for a frame of n pixels: the wave masks, then the scan's levels.
-unsigned long long rtc_contrast_work_words(unsigned long long n) {
-  unsigned long long m = rtc_contrast_blocks(n), words = m * RTC_ADAPT_WAVES + m;
+// The exclusive scan of v[0 .. n - 1] in place, for any caller with a table of counts (the compaction below, rtc_shutter.hip's counting
+// sort): `levels` = rtc_scan_work_words(n) device words for the tile sums of every level above v, *total = the sum of all of v (one
+// device word).  Returns the number of kernels queued.
+unsigned long long rtc_scan_work_words(unsigned long long n) {
+  unsigned long long m = n, words = 0;
   do { m = rtc_contrast_blocks(m); words += m; } while (m > 1);
   return words;
+}
+unsigned rtc_launch_scan(unsigned long long* v, unsigned long long n, unsigned long long* levels, unsigned long long* total, hipStream_t stream) {
+  unsigned long long* level[18];
+  unsigned long long size[17];
+  int top = 0;
+  level[0] = v; size[0] = n;
+  level[1] = levels;
+  do { size[top + 1] = rtc_contrast_blocks(size[top]); level[top + 2] = level[top + 1] + size[top + 1]; top++; } while (size[top] > 1);  // 256^8 entries before 16 levels
+  unsigned launches = 0;
+  // up: level k's tiles scanned in place, their sums = level k + 1; the last level is one word, the total (`total` may be that word's copy)
+  for (int k = 0; k < top; k++, launches++)
+    hipLaunchKernelGGL(rtc_scan_tiles, dim3((unsigned)size[k + 1]), dim3(RTC_ADAPT_BLOCK), 0, stream, level[k], size[k], k + 1 == top ? total : level[k + 1]);
+  // down: level top - 1 is one tile and complete; every level below adds its tile's finished prefix
+  for (int k = top - 2; k >= 0; k--, launches++)
+    hipLaunchKernelGGL(rtc_scan_add_base, dim3((unsigned)size[k + 1]), dim3(RTC_ADAPT_BLOCK), 0, stream, level[k], size[k], level[k + 1]);
+  return launches;
+}
+
+// Device words (8 bytes each) rtc_launch_contrast_compact needs in `work` for a frame of n pixels: the wave masks, then the scan's levels.
+unsigned long long rtc_contrast_work_words(unsigned long long n) {
+  const unsigned long long m = rtc_contrast_blocks(n);
+  return m * RTC_ADAPT_WAVES + m + rtc_scan_work_words(m);
 }
 
 // Queues the whole detect-and-compact step for the n = hsize * vsize pixels of `frame`: list[0 .. *count - 1] = the refined pixels'
@@ -108,21 +132,11 @@ unsigned rtc_launch_contrast_compact(const double* frame, unsigned long long hsi
                                      unsigned long long* work, unsigned long long* list, unsigned long long* count, hipStream_t stream) {
   const unsigned long long n = hsize * vsize, nb = rtc_contrast_blocks(n);
   unsigned long long* mask = work;
-  unsigned long long* level[16];
-  unsigned long long size[16];
-  int top = 0;
-  level[0] = work + nb * RTC_ADAPT_WAVES; size[0] = nb;
-  do { level[top + 1] = level[top] + size[top]; size[top + 1] = rtc_contrast_blocks(size[top]); top++; } while (size[top] > 1);  // 256^8 blocks before 16 levels
-  unsigned launches = 2;
-  hipLaunchKernelGGL(rtc_contrast_flags, dim3((unsigned)nb), dim3(RTC_ADAPT_BLOCK), 0, stream, frame, hsize, vsize, threshold, neighbours, mask, level[0]);
-  // up: level k's tiles scanned in place, their sums = level k + 1; the last level is one word, the total (count may be that word's copy)
-  for (int k = 0; k < top; k++, launches++)
-    hipLaunchKernelGGL(rtc_scan_tiles, dim3((unsigned)size[k + 1]), dim3(RTC_ADAPT_BLOCK), 0, stream, level[k], size[k], k + 1 == top ? count : level[k + 1]);
-  // down: level top - 1 is one tile and complete; every level below adds its tile's finished prefix
-  for (int k = top - 2; k >= 0; k--, launches++)
-    hipLaunchKernelGGL(rtc_scan_add_base, dim3((unsigned)size[k + 1]), dim3(RTC_ADAPT_BLOCK), 0, stream, level[k], size[k], level[k + 1]);
-  hipLaunchKernelGGL(rtc_contrast_scatter, dim3((unsigned)nb), dim3(RTC_ADAPT_BLOCK), 0, stream, mask, level[0], list);
-  return launches;
+  unsigned long long* block_count = work + nb * RTC_ADAPT_WAVES;
+  hipLaunchKernelGGL(rtc_contrast_flags, dim3((unsigned)nb), dim3(RTC_ADAPT_BLOCK), 0, stream, frame, hsize, vsize, threshold, neighbours, mask, block_count);
+  const unsigned scans = rtc_launch_scan(block_count, nb, block_count + nb, count, stream);
+  hipLaunchKernelGGL(rtc_contrast_scatter, dim3((unsigned)nb), dim3(RTC_ADAPT_BLOCK), 0, stream, mask, block_count, list);
+  return 2 + scans;
 }
 
 void rtc_launch_resolve_samples_scatter(const double* ray_rgb, unsigned n_samples, unsigned long long n_slots, const unsigned long long* indices, double* frame,

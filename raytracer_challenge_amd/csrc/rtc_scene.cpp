@@ -26,6 +26,7 @@
 #include "device_scene.h"
 #include "filter_weights.h"
 #include "scene_build.hpp"
+#include "shutter_pose.h"
 #include "spot_factor.h"
 
 void rtc_launch_trace(const DScene& S, const DCamera& cam, const DPixelMap& pm, int fuel, double* rgb, double* hit_t, int* hit_prim, int* hit_k,
@@ -56,6 +57,13 @@ void rtc_launch_resolve_samples_scatter(const double* ray_rgb, unsigned n_sample
                                         hipStream_t stream);
 unsigned rtc_launch_resolve_filtered(const rtc_filter& f, const rtc_sampling& sp, unsigned long long hsize, unsigned long long row0, unsigned long long row1,
                                      unsigned long long out0, unsigned long long out1, const double* samples, double* dst, hipStream_t stream, unsigned* tile);
+unsigned long long rtc_shutter_work_words(unsigned long long m);
+unsigned long long* rtc_shutter_offsets(unsigned long long* work, unsigned long long m);
+unsigned rtc_launch_shutter_deal(const rtc_shutter& sh, const rtc_sampling& sp, unsigned K, const DPixelMap& pm, const DCamera& cam, unsigned long long slot_first,
+                                 unsigned long long m, unsigned long long* work, unsigned* order, unsigned* where, hipStream_t stream);
+void rtc_launch_shutter_gen_rays(const DCamera& cam, const DPixelMap& pm, const rtc_sampling& sp, unsigned long long slot_first, const unsigned* order, unsigned off, unsigned len,
+                                 unsigned m, double* rays, hipStream_t stream);
+void rtc_launch_shutter_resolve(const double* ray_rgb, const unsigned* where, unsigned n_samples, unsigned long long n_slots, double* dst, hipStream_t stream);
 int32_t rtc_bvh_build_device(const std::vector<bvh::Item>& items, std::vector<DBvhNode>& n2, std::vector<uint32_t>& order, uint32_t base, int leaf_max, double* frame);
 int32_t rtc_bvh_build_device_keys(const std::vector<bvh::Item>& items, std::vector<DBvhNode>& n2, std::vector<uint32_t>& order, uint32_t base, int leaf_max, double* frame,
                                   std::vector<unsigned long long>* keys);
@@ -109,6 +117,12 @@ struct rtc_scene {
   unsigned long long* d_awork = nullptr;
   unsigned long long* d_acount = nullptr;
   uint64_t cap_alist = 0;
+  // the shutter (run_shutter, rtc_shutter_deal; this scene as scenes[0]): per sample of the largest chunk so far the pose-major list of
+  // sample ids and each id's position in it; the pose-major count table, its scan levels and the offsets
+  unsigned* d_shorder = nullptr;
+  unsigned* d_shwhere = nullptr;
+  unsigned long long* d_shwork = nullptr;
+  uint64_t cap_shutter = 0;
   int kernel_version = 0;  // 0: measured choice between the one-kernel (1) and the wavefront (4) path, per launch signature
   uint64_t tune_sig = 0;
   double tune_ms[2] = {-1.0, -1.0};
@@ -423,15 +437,15 @@ int run(rtc_scene* s, const DCamera& cam, DPixelMap pm, int fuel, double* d_rgb,
 }
 
 // The pixel map of a host-side launch over pixels first .. first + n - 1 or the n listed indices (uploaded to the scene's index buffer).
-int make_pixel_map(rtc_scene* s, const rtc_camera* cam, const uint64_t* pixel_indices, uint64_t first, uint64_t n, DPixelMap* pm, std::vector<uint64_t>* range_idx) {
-  const uint64_t total = cam->hsize * cam->vsize;
+// (`total`: the frame's pixel count, the bound of a listed index)
+int make_pixel_map(rtc_scene* s, uint64_t hsize, uint64_t total, const uint64_t* pixel_indices, uint64_t first, uint64_t n, DPixelMap* pm, std::vector<uint64_t>* range_idx) {
   *pm = DPixelMap{};
   pm->n = n;
   // A contiguous range is expressed through the two pixel maps the kernels are validated with on hardware: whole rows ->
   // interleaved-row map with step 1; anything else -> an explicit index list.
   if (!pixel_indices) {
-    if (first % cam->hsize == 0 && n % cam->hsize == 0) {
-      pm->mode = 2; pm->row_first = (uint32_t)(first / cam->hsize); pm->row_step = 1;
+    if (first % hsize == 0 && n % hsize == 0) {
+      pm->mode = 2; pm->row_first = (uint32_t)(first / hsize); pm->row_step = 1;
     } else {
       range_idx->resize(n);
       for (uint64_t i = 0; i < n; i++) (*range_idx)[i] = first + i;
@@ -451,6 +465,9 @@ int make_pixel_map(rtc_scene* s, const rtc_camera* cam, const uint64_t* pixel_in
     pm->mode = 1; pm->indices = s->d_idx;
   }
   return RTC_OK;
+}
+int make_pixel_map(rtc_scene* s, const rtc_camera* cam, const uint64_t* pixel_indices, uint64_t first, uint64_t n, DPixelMap* pm, std::vector<uint64_t>* range_idx) {
+  return make_pixel_map(s, cam->hsize, cam->hsize * cam->vsize, pixel_indices, first, n, pm, range_idx);
 }
 
 // ---- the sampled camera (include/rtc.h rtc_sampling; kernels in rtc_camera.hip) ---------------------------------------------------
@@ -705,6 +722,147 @@ int run_adaptive(rtc_scene* s, const DCamera& cam, const rtc_adaptive& ad, int f
   return RTC_OK;
 }
 
+// ---- the shutter (include/rtc.h rtc_shutter; kernels in rtc_shutter.hip, the rule in shutter_pose.h) ---------------------------------
+// The shutter's own numbers, with the sampling they deal: no device is looked at.
+int check_shutter(const rtc_shutter* sh, uint32_t n_poses, const rtc_sampling* sp) {
+  if (!sh) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  if (n_poses == 0) return rtc_fail(RTC_ERR_INVALID, "shutter: n_poses must be >= 1");
+  if (sh->flags & ~(uint32_t)RTC_SHUTTER_HASHED) return rtc_fail(RTC_ERR_INVALID, "shutter: unknown flag bits");
+  if (n_poses > RTC_SHUTTER_MAX_POSES) return rtc_fail(RTC_ERR_UNSUPPORTED, "shutter: n_poses exceeds RTC_SHUTTER_MAX_POSES (64)");
+  const int rc = check_sampling(sp);
+  if (rc != RTC_OK) return rc;
+  if (!(sh->flags & RTC_SHUTTER_HASHED) && n_poses > sp->side * sp->side)
+    return rtc_fail(RTC_ERR_INVALID, "shutter: more poses than samples per pixel without RTC_SHUTTER_HASHED (some poses would never be sampled)");
+  return RTC_OK;
+}
+
+// The poses' arrays: entries, one frame size, one device.
+int check_poses(rtc_scene* const* scenes, const rtc_camera* cameras, uint32_t n_poses) {
+  if (!scenes || !cameras) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  if (cameras[0].hsize == 0 || cameras[0].vsize == 0) return rtc_fail(RTC_ERR_INVALID, "empty camera");
+  for (uint32_t p = 1; p < n_poses; p++)
+    if (cameras[p].hsize != cameras[0].hsize || cameras[p].vsize != cameras[0].vsize) return rtc_fail(RTC_ERR_INVALID, "shutter: the cameras' hsize or vsize differ");
+  for (uint32_t p = 0; p < n_poses; p++)
+    if (!scenes[p]) return rtc_fail(RTC_ERR_INVALID, "shutter: a NULL scene among the poses");
+  for (uint32_t p = 1; p < n_poses; p++)
+    if (scenes[p]->device != scenes[0]->device) return rtc_fail(RTC_ERR_INVALID, "shutter: the poses' scenes are on different devices");
+  return RTC_OK;
+}
+
+// The dealing's buffers for a chunk of m samples, grown like d_srays.
+int ensure_shutter(rtc_scene* s, uint64_t m) {
+  if (m > s->cap_shutter) {
+    HIP_OK(hipStreamSynchronize(s->stream));
+    (void)hipFree(s->d_shorder); (void)hipFree(s->d_shwhere); (void)hipFree(s->d_shwork);
+    s->d_shorder = nullptr; s->d_shwhere = nullptr; s->d_shwork = nullptr; s->cap_shutter = 0;
+    HIP_OK(hipMalloc((void**)&s->d_shorder, m * sizeof(unsigned)));
+    HIP_OK(hipMalloc((void**)&s->d_shwhere, m * sizeof(unsigned)));
+    HIP_OK(hipMalloc((void**)&s->d_shwork, rtc_shutter_work_words(m) * sizeof(unsigned long long)));
+    s->cap_shutter = m;
+  }
+  return RTC_OK;
+}
+
+// Deal the m samples of the output slots slot_first .. of `pm` on s's stream (ensure_shutter'ed for m), then the ONE read-back the host
+// needs: offsets[0 .. K], checked before anybody launches over them.  `timed`: evs0 / evs1 around the kernels.
+int shutter_deal(rtc_scene* s, const rtc_shutter& sh, const rtc_sampling& sp, uint32_t K, const DPixelMap& pm, const DCamera& cam, uint64_t slot_first, uint64_t m,
+                 unsigned long long* offsets, unsigned* n_kernels, bool timed) {
+  if (timed) HIP_OK(hipEventRecord(s->evs0, s->stream));
+  *n_kernels = rtc_launch_shutter_deal(sh, sp, K, pm, cam, slot_first, m, s->d_shwork, s->d_shorder, s->d_shwhere, s->stream);
+  HIP_OK(hipGetLastError());
+  if (timed) HIP_OK(hipEventRecord(s->evs1, s->stream));
+  HIP_OK(hipMemcpyAsync(offsets, rtc_shutter_offsets(s->d_shwork, m), (K + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
+  HIP_OK(hipStreamSynchronize(s->stream));
+  bool ok = offsets[0] == 0 && offsets[K] == m;
+  for (uint32_t p = 0; p < K && ok; p++) ok = offsets[p] <= offsets[p + 1];
+  if (!ok) return rtc_fail(RTC_ERR_DEVICE, "shutter: the dealing's offsets do not partition the chunk's samples");
+  return RTC_OK;
+}
+
+// run_sampled over K poses: the pixel set `pm` (mode 1 or 2; a list lives in scenes[0]'s index buffer) in run_sampled's chunks; the
+// buffers and the shutter's own kernels are scenes[0]'s, on its stream.  Per chunk: deal and read the offsets back (shutter_deal); per
+// pose with a non-empty run its generator, then run() of ITS scene over the run's rays -- synchronously, so a run whose wavefront queues
+// overflowed is traced again before anything else touches its colours, and so that the trace is over before scenes[0]'s stream goes
+// on; a trace on another scene's stream waits for the generator through an event --; then the resolve.
+// Path of a run: a pinned scene's own; otherwise that scene's first guess over the run's rays (nothing is measured: the runs change
+// with the seed), the one-kernel path after a refusal of the queues.  `after`: behind the last chunk's resolve (see run()).
+int run_shutter(rtc_scene* const* scenes, const DCamera* cams, uint32_t K, const rtc_shutter& sh, const DPixelMap& pm, const rtc_sampling& sp, int fuel, double* d_rgb,
+                rtc_stats* stats, const AfterLaunch* after) {
+  rtc_scene* s = scenes[0];
+  if (fuel < 0) fuel = 0;
+  HIP_OK(hipSetDevice(s->device));
+  const uint64_t N = (uint64_t)sp.side * sp.side;
+  const uint64_t unit = pm.mode == 2 ? cams[0].hsize : 1;  // pixels a chunk grows by
+  const uint64_t chunk_px = std::min<uint64_t>(pm.n / unit, std::max<uint64_t>(1, sampled_max_rays() / (unit * N))) * unit;
+  if (chunk_px * N > 0x7fffff00ull) return rtc_fail(RTC_ERR_UNSUPPORTED, "one row of this sampled launch exceeds 2^31 rays");
+  int rc = ensure_sampled(s, chunk_px * N, true);
+  if (rc == RTC_OK) rc = ensure_shutter(s, chunk_px * N);
+  if (rc != RTC_OK) return rc;
+  const bool count = stats != nullptr;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  DCamera ray_cam{};
+  ray_cam.hsize = 1; ray_cam.vsize = 1;
+  unsigned long long offsets[RTC_SHUTTER_MAX_POSES + 1];
+  for (uint64_t p0 = 0; p0 < pm.n; p0 += chunk_px) {
+    const uint64_t np = std::min(chunk_px, pm.n - p0);
+    const bool last = p0 + np == pm.n;
+    unsigned n_kernels = 0;
+    rc = shutter_deal(s, sh, sp, K, pm, cams[0], p0, np * N, offsets, &n_kernels, stats != nullptr);
+    if (rc != RTC_OK) return rc;
+    float ms = 0.f, deal_ms = 0.f;
+    double gen_ms = 0.0, trace_ms = 0.0;
+    if (stats) {
+      HIP_OK(hipEventElapsedTime(&deal_ms, s->evs0, s->evs1));
+      stats->kernel_ms += deal_ms;
+      stats->n_launches += n_kernels;
+    }
+    for (uint32_t p = 0; p < K; p++) {
+      const uint64_t off = offsets[p], len = offsets[p + 1] - off;
+      if (len == 0) continue;  // an empty run launches nothing
+      rtc_scene* t = scenes[p];
+      if (stats) HIP_OK(hipEventRecord(s->evs0, s->stream));
+      rtc_launch_shutter_gen_rays(cams[p], pm, sp, p0, s->d_shorder, (unsigned)off, (unsigned)len, (unsigned)(np * N), s->d_srays, s->stream);
+      HIP_OK(hipGetLastError());
+      HIP_OK(hipEventRecord(s->evs1, s->stream));
+      if (t->stream != s->stream) HIP_OK(hipStreamWaitEvent(t->stream, s->evs1, 0));
+      DPixelMap rm{};
+      rm.n = len; rm.mode = 3; rm.rays = s->d_srays + 6 * off;
+      int force = 0;
+      if (t->kernel_version == 0) force = t->wave_alloc_failed ? 1 : first_guess(t, len, fuel);
+      rtc_stats st;
+      rc = run(t, ray_cam, rm, fuel, s->d_srgb + 3 * off, false, stats ? &st : nullptr, count, true, force);
+      if (rc == RTC_ERR_UNSUPPORTED && force == 4) {  // the queues were refused: the one-kernel path (same bits)
+        rc = run(t, ray_cam, rm, fuel, s->d_srgb + 3 * off, false, stats ? &st : nullptr, count, true, 1);
+      }
+      if (rc != RTC_OK) return rc;
+      // (run() waited for t's stream: whatever scenes[0]'s stream does next comes after the trace)
+      if (stats) {
+        HIP_OK(hipEventElapsedTime(&ms, s->evs0, s->evs1));
+        add_stats(stats, st);
+        stats->kernel_ms += ms;
+        stats->n_launches += 1u;
+        gen_ms += ms; trace_ms += st.kernel_ms;
+      }
+    }
+    if (stats) HIP_OK(hipEventRecord(s->evs0, s->stream));
+    rtc_launch_shutter_resolve(s->d_srgb, s->d_shwhere, (unsigned)N, np, d_rgb + 3 * p0, s->stream);
+    HIP_OK(hipGetLastError());
+    if (stats) HIP_OK(hipEventRecord(s->evs1, s->stream));
+    if (last && after) { rc = (*after)(); if (rc != RTC_OK) return rc; }
+    if (stats || last) HIP_OK(hipStreamSynchronize(s->stream));
+    if (stats) {
+      HIP_OK(hipEventElapsedTime(&ms, s->evs0, s->evs1));
+      if (std::getenv("RTC_SAMPLED_TIMING"))  // debug aid (scripts/shutter_probe.py)
+        std::fprintf(stderr, "[rtc-shutter] chunk of %llu rays: dealing %.3f ms (%u kernels), generators %.3f ms, traces %.3f ms, resolve %.3f ms\n",
+                     (unsigned long long)(np * N), deal_ms, n_kernels, gen_ms, trace_ms, ms);
+      stats->kernel_ms += ms;
+      stats->n_launches += 1u;
+    }
+  }
+  if (stats) stats->pixels = pm.n;
+  return RTC_OK;
+}
+
 // ---- reconstruction filters (include/rtc.h rtc_filter; kernel in rtc_filter.hip, the rule in filter_weights.h) ------------------------
 int check_filter(const rtc_filter* f) {
   if (!f) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
@@ -821,9 +979,11 @@ int run_filtered(rtc_scene* s, const DCamera& cam, const DPixelMap& pm, const rt
 // copies are queued behind the kernels (see pretouch_pages above).
 // `sp`: the launch goes through run_sampled (no hit records).  `ad`: the whole frame through run_adaptive (pm covers it).
 // `sp` and `fl`: whole rows through run_filtered.
+// `sp` and `shu`: run_shutter over the poses (s = scenes[0], dc = its camera).
 struct AdaptiveOut { const rtc_adaptive* rule; uint8_t* mask; uint64_t* n_refined; };
+struct ShutterIn { rtc_scene* const* scenes; const DCamera* cams; uint32_t n_poses; const rtc_shutter* rule; };
 int render_to_host(rtc_scene* s, const DCamera& dc, const DPixelMap& pm, int fuel, double* rgb, uint8_t* rgb8, rtc_hit* hits, rtc_stats* stats,
-                   const rtc_sampling* sp = nullptr, const AdaptiveOut* ad = nullptr, const rtc_filter* fl = nullptr) {
+                   const rtc_sampling* sp = nullptr, const AdaptiveOut* ad = nullptr, const rtc_filter* fl = nullptr, const ShutterIn* shu = nullptr) {
   static_assert(sizeof(DHit) == sizeof(rtc_hit) && offsetof(DHit, prim) == offsetof(rtc_hit, prim) && offsetof(DHit, k) == offsetof(rtc_hit, push_idx), "hit layout");
   const uint64_t n = pm.n;
   std::vector<std::thread> pool;
@@ -846,6 +1006,7 @@ int render_to_host(rtc_scene* s, const DCamera& dc, const DPixelMap& pm, int fue
     return RTC_OK;
   };
   const int rc = ad ? run_adaptive(s, dc, *ad->rule, fuel, stats, ad->mask, ad->n_refined, &after)
+                 : shu ? run_shutter(shu->scenes, shu->cams, shu->n_poses, *shu->rule, pm, *sp, fuel, s->d_rgb, stats, &after)
                  : fl ? run_filtered(s, dc, pm, *sp, *fl, fuel, s->d_rgb, stats, stats != nullptr, true, &after)
                  : sp ? run_sampled(s, dc, pm, *sp, fuel, s->d_rgb, stats, stats != nullptr, true, &after)
                     : run(s, dc, pm, fuel, s->d_rgb, hits != nullptr, stats, stats != nullptr, true, 0, &after);
@@ -1153,6 +1314,7 @@ void rtc_scene_destroy(rtc_scene* s) {
   if (s->d_rays) (void)hipFree(s->d_rays);
   (void)hipFree(s->d_srays); (void)hipFree(s->d_srgb);
   (void)hipFree(s->d_alist); (void)hipFree(s->d_awork); (void)hipFree(s->d_acount);
+  (void)hipFree(s->d_shorder); (void)hipFree(s->d_shwhere); (void)hipFree(s->d_shwork);
   if (s->evs0) (void)hipEventDestroy(s->evs0);
   if (s->evs1) (void)hipEventDestroy(s->evs1);
   for (auto& m : s->marker) if (m) (void)hipEventDestroy(m);
@@ -1452,6 +1614,90 @@ int rtc_contrast_pixels(rtc_scene* s, uint64_t hsize, uint64_t vsize, const doub
   *n = refined;
   return RTC_OK;
 }
+
+// ---- the shutter's entry points (include/rtc.h) ---------------------------------------------------------------------------------------
+static int render_shutter(rtc_scene* const* scenes, const rtc_camera* cameras, uint32_t n_poses, const rtc_shutter* sh, const rtc_sampling* sp, int32_t fuel,
+                          const uint64_t* pixel_indices, uint64_t first, uint64_t n, bool whole, double* rgb, uint8_t* rgb8, rtc_stats* stats) {
+  int rc = check_shutter(sh, n_poses, sp);  // (the rule first: it is checked without a device)
+  if (rc == RTC_OK) rc = check_poses(scenes, cameras, n_poses);
+  if (rc != RTC_OK) return rc;
+  const uint64_t total = cameras[0].hsize * cameras[0].vsize;
+  if (whole) n = total;
+  if ((!rgb && !rgb8) && n) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  if (!pixel_indices && (first > total || n > total - first)) return rtc_fail(RTC_ERR_INVALID, "pixel range exceeds the image");
+  if (n == 0) { if (stats) std::memset(stats, 0, sizeof(*stats)); return RTC_OK; }
+  rtc_scene* s = scenes[0];
+  HIP_OK(hipSetDevice(s->device));
+  rc = ensure_px(s, n, false);
+  if (rc != RTC_OK) return rc;
+  if (rgb8 && 3 * n > s->cap_rgb8) {
+    (void)hipFree(s->d_rgb8);
+    s->d_rgb8 = nullptr; s->cap_rgb8 = 0;
+    HIP_OK(hipMalloc((void**)&s->d_rgb8, 3 * n));
+    s->cap_rgb8 = 3 * n;
+  }
+  DPixelMap pm{};
+  std::vector<uint64_t> range_idx;
+  rc = make_pixel_map(s, &cameras[0], pixel_indices, first, n, &pm, &range_idx);
+  if (rc != RTC_OK) return rc;
+  std::vector<DCamera> cams(n_poses);
+  for (uint32_t p = 0; p < n_poses; p++) to_dcam(cameras[p], &cams[p]);
+  const ShutterIn in{scenes, cams.data(), n_poses, sh};
+  return render_to_host(s, cams[0], pm, fuel, rgb, rgb8, nullptr, stats, sp, nullptr, nullptr, &in);
+}
+
+int rtc_render_shutter(rtc_scene* const* scenes, const rtc_camera* cameras, uint32_t n_poses, const rtc_shutter* sh, const rtc_sampling* sp, int32_t fuel,
+                       const uint64_t* pixel_indices, uint64_t first, uint64_t n, double* rgb, rtc_stats* stats) {
+  return render_shutter(scenes, cameras, n_poses, sh, sp, fuel, pixel_indices, first, n, false, rgb, nullptr, stats);
+}
+
+int rtc_render_shutter_rgb8(rtc_scene* const* scenes, const rtc_camera* cameras, uint32_t n_poses, const rtc_shutter* sh, const rtc_sampling* sp, int32_t fuel,
+                            uint8_t* rgb8, rtc_stats* stats) {
+  if (!rgb8) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  return render_shutter(scenes, cameras, n_poses, sh, sp, fuel, nullptr, 0, 0, true, nullptr, rgb8, stats);
+}
+
+int rtc_shutter_deal(rtc_scene* s, uint64_t hsize, uint32_t n_poses, const rtc_shutter* sh, const rtc_sampling* sp, const uint64_t* pixel_indices, uint64_t first,
+                     uint64_t n, uint32_t* order, uint64_t* offsets) {
+  int rc = check_shutter(sh, n_poses, sp);
+  if (rc != RTC_OK) return rc;
+  if (!offsets || (!order && n)) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  if (hsize == 0) return rtc_fail(RTC_ERR_INVALID, "empty frame");
+  const uint64_t N = (uint64_t)sp->side * sp->side;
+  if (n > 0x7fffff00ull / N) return rtc_fail(RTC_ERR_UNSUPPORTED, "shutter: a dealing of 2^31 samples or more");
+  if (!pixel_indices && first > ~0ull - n) return rtc_fail(RTC_ERR_INVALID, "pixel range exceeds the image");
+  const uint64_t m = n * N;
+  if (n == 0) { for (uint32_t p = 0; p <= n_poses; p++) offsets[p] = 0; return RTC_OK; }
+  if (!s) {  // the same rule on the host: count, prefix sums, place in id order (stable)
+    std::vector<uint32_t> pose(m);
+    std::vector<uint64_t> next(n_poses + 1, 0);
+    for (uint64_t j = 0; j < n; j++) {
+      const uint64_t i = pixel_indices ? pixel_indices[j] : first + j;
+      for (uint64_t k = 0; k < N; k++) next[(pose[j * N + k] = rtc_shutter_pose(*sh, *sp, n_poses, i, (uint32_t)k)) + 1]++;
+    }
+    for (uint32_t p = 0; p < n_poses; p++) next[p + 1] += next[p];
+    for (uint32_t p = 0; p <= n_poses; p++) offsets[p] = next[p];
+    for (uint64_t id = 0; id < m; id++) order[next[pose[id]]++] = (uint32_t)id;
+    return RTC_OK;
+  }
+  HIP_OK(hipSetDevice(s->device));
+  DPixelMap pm{};
+  std::vector<uint64_t> range_idx;
+  rc = make_pixel_map(s, hsize, ~0ull, pixel_indices, first, n, &pm, &range_idx);
+  if (rc == RTC_OK) rc = ensure_shutter(s, m);
+  if (rc != RTC_OK) return rc;
+  DCamera dc{};
+  dc.hsize = hsize; dc.vsize = 1;  // (of the camera only hsize enters a slot's pixel)
+  unsigned long long offs[RTC_SHUTTER_MAX_POSES + 1];
+  unsigned n_kernels = 0;
+  rc = shutter_deal(s, *sh, *sp, n_poses, pm, dc, 0, m, offs, &n_kernels, false);
+  if (rc != RTC_OK) return rc;
+  for (uint32_t p = 0; p <= n_poses; p++) offsets[p] = offs[p];
+  HIP_OK(hipMemcpy(order, s->d_shorder, m * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return RTC_OK;
+}
+
+uint32_t rtc_shutter_draw_pose(double u, uint32_t n_poses) { return n_poses ? rtc_shutter_draw_pose_of(u, n_poses) : 0u; }
 
 // ---- the reconstruction filters' entry points (include/rtc.h) ------------------------------------------------------------------------
 static int render_filtered(rtc_scene* s, const rtc_camera* cam, const rtc_sampling* sp, const rtc_filter* f, int32_t fuel, uint64_t row_first, uint64_t n_rows,

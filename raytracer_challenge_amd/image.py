@@ -7,10 +7,11 @@ the library's host code.
 from __future__ import annotations
 
 import ctypes as C
+from typing import Sequence, Tuple
 
 import numpy as np
 
-from .scene import FUEL, Adaptive, Camera, Color, Filter, Sampling, World
+from .scene import FUEL, Adaptive, Camera, Color, Filter, Sampling, Shutter, World
 
 
 class Image:
@@ -42,6 +43,35 @@ class Image:
             return Image(camera.hsize, camera.vsize, be.render_sampled(nw, camera, sampling, fuel), (be, nw))
         rgb, _ = be.render(nw, camera, fuel, want_hits=False)
         return Image(camera.hsize, camera.vsize, rgb, (be, nw))
+
+    @staticmethod
+    def par_render_shutter(poses: Sequence[Tuple[Camera, World]], sampling: Sampling, shutter: Shutter = Shutter(), fuel: int = FUEL, backend=None) -> "Image":
+        """Motion blur: `poses` are (camera, world) pairs over the shutter's opening, all cameras of one frame size; every sample of
+        `sampling` is traced in the pose `shutter` deals it to and a pixel is the mean of its samples.  World objects that are the same
+        object are built once and passed as one scene (a moving camera over a static world costs no memory)."""
+        poses = list(poses)
+        if not poses:
+            raise ValueError("par_render_shutter: at least one pose")
+        if not isinstance(sampling, Sampling) or not isinstance(shutter, Shutter):
+            raise ValueError("par_render_shutter: `sampling` must be a Sampling and `shutter` a Shutter")
+        for pose in poses:
+            if not (isinstance(pose, tuple) and len(pose) == 2 and isinstance(pose[0], Camera) and isinstance(pose[1], World)):
+                raise ValueError("par_render_shutter: every pose is a (Camera, World) pair")
+        cam0 = poses[0][0]
+        if any((c.hsize, c.vsize) != (cam0.hsize, cam0.vsize) for c, _ in poses):
+            raise ValueError("par_render_shutter: the cameras' hsize or vsize differ")
+        if not shutter.hashed and len(poses) > sampling.samples:
+            raise ValueError("par_render_shutter: more poses than samples per pixel need Shutter(hashed=True)")
+        from . import hip_backend
+        be = backend or hip_backend()
+        built = {}
+        nws = []
+        for _, world in poses:
+            if id(world) not in built:
+                built[id(world)] = be.build_world(world)
+            nws.append(built[id(world)])
+        rgb = be.render_shutter(nws, [c for c, _ in poses], sampling, shutter, fuel)
+        return Image(cam0.hsize, cam0.vsize, rgb, (be, nws[0]))
 
     def _idx(self, x: int, y: int) -> int:  # :114-116
         return y * self.hsize + x

@@ -512,6 +512,22 @@ class Filter:
         return cls("mitchell", radius)
 
 
+SHUTTER_MAX_POSES = 64  # include/rtc.h RTC_SHUTTER_MAX_POSES
+
+
+@dataclass(frozen=True)
+class Shutter:
+    """The shutter (include/rtc.h rtc_shutter; not in the reference): motion blur over K poses, each a camera and a world.  Every
+    sample of a pixel is traced in ONE pose and the pixel stays the mean of its samples.  ``hashed``: a sample's pose is a hashed draw
+    (any number of poses up to 64); otherwise the pixel's samples are split into K runs in sample order, which needs K <= side * side.
+    Rendered by the HIP library only."""
+    hashed: bool = True
+
+    def __post_init__(self):
+        if not isinstance(self.hashed, bool):
+            raise ValueError("Shutter.hashed must be a bool")
+
+
 @dataclass(frozen=True)
 class Camera:  # src/camera.rs:5-13; derived fields are computed natively from `transform`
     hsize: int

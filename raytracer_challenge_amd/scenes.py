@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Tuple
+from typing import List, Tuple
 
 from .scene import (Camera, Color, Element, GroupKind, Material, Matrix, Noise, Pattern, PointLight, ShapeArgs, SpotLight, Vector, World)
 
@@ -468,3 +468,27 @@ def sky_showcase(hsize=None, vsize=None, skybox: bool = False) -> Tuple[Camera, 
         background = Background(Pattern.gradient(up, Pattern.plain(c(0.95, 0.9, 0.8)), Pattern.plain(c(0.2, 0.45, 0.9))), "direction")
     lights = [PointLight(c(0.9, 0.9, 0.85), Vector.point(-6.0, 9.0, -8.0))]
     return _cam(1920, 1080, PI / 3.0, (0.0, 1.8, -7.0), (0.0, 1.0, 0.5), (0.0, 1.0, 0.0), hsize, vsize), World(lights, [floor, mirror, glass, matte], background)
+
+
+def motion_showcase(hsize=None, vsize=None, poses: int = 8) -> List[Tuple[Camera, World]]:
+    """The shutter's showcase (not in the reference): `poses` (camera, world) pairs over the shutter's opening for
+    Image.par_render_shutter.  A checkered floor, a glass and a matte sphere that move linearly across the poses, a mirror that stands
+    still, one point light, a camera that pans slightly.  A few primitives: K scene creations stay cheap."""
+    if int(poses) != poses or poses < 1:
+        raise ValueError("motion_showcase: poses must be an integer >= 1")
+    light = PointLight(Color(1.0, 1.0, 1.0), Vector.point(-6.0, 8.0, -6.0))
+    floor = Element.plane(ShapeArgs(material=Material(
+        pattern=Pattern.checkers(Matrix.id(), Pattern.plain(Color(0.85, 0.85, 0.85)), Pattern.plain(Color(0.2, 0.2, 0.25))), specular=0.0, reflective=0.1)))
+    mirror = Element.cube(ShapeArgs(transform=Matrix.translation(0.0, 1.5, 4.0) * Matrix.scaling(3.5, 1.5, 0.05),
+                                    material=Material(pattern=Pattern.plain(Color(0.05, 0.05, 0.05)), diffuse=0.1, specular=0.9, shininess=300.0, reflective=0.9)))
+    out = []
+    for p in range(int(poses)):
+        t = p / (poses - 1) if poses > 1 else 0.0   # 0 .. 1 over the opening
+        glass = Element.sphere(ShapeArgs(transform=Matrix.translation(-2.0 + 1.5 * t, 1.0, 0.5),
+                                         material=Material(pattern=Pattern.plain(Color(0.05, 0.05, 0.1)), diffuse=0.1, specular=1.0, shininess=300.0, reflective=0.9,
+                                                           transparency=0.9, refractive_index=1.5)))
+        matte = Element.sphere(ShapeArgs(transform=Matrix.translation(2.2 - 1.0 * t, 0.6 + 0.8 * t, -0.5) * Matrix.scaling(0.6, 0.6, 0.6),
+                                         material=Material(pattern=Pattern.plain(Color(0.9, 0.25, 0.2)), specular=0.2)))
+        cam = _cam(400, 200, math.pi / 3.0, (-0.3 + 0.6 * t, 2.5, -7.0), (0.0, 1.0, 0.0), (0.0, 1.0, 0.0), hsize, vsize)
+        out.append((cam, World([light], [floor, mirror, glass, matte])))
+    return out

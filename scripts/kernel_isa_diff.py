@@ -4,7 +4,7 @@
     scripts/kernel_isa_diff.py OLD_TREE NEW_TREE [--rename 'REGEX=>REPLACEMENT']... [--jobs N] [--keep DIR [--reuse]]
 
 For each tree: rtc_feat.hip for every variant id of its csrc/Makefile, rtc_kernels.hip and, where the tree has them,
-rtc_camera.hip, rtc_adaptive.hip, rtc_filter.hip and rtc_background.hip (once plain, once per BG build id) are compiled to device-only assembly with that Makefile's FLAGS.  The assembly is split per function; comments, directives and label definitions
+rtc_camera.hip, rtc_adaptive.hip, rtc_filter.hip, rtc_shutter.hip and rtc_background.hip (once plain, once per BG build id) are compiled to device-only assembly with that Makefile's FLAGS.  The assembly is split per function; comments, directives and label definitions
 are dropped, local label references (.LBB<fn>_<n> ...) lose their function number, the function's own symbol becomes
 <self>; what remains is counted and hashed.  Printed per function of NEW_TREE: unit, demangled name, instruction
 count, hash, next_free_vgpr, next_free_sgpr, private segment size (device functions that are not kernels: the
@@ -39,7 +39,7 @@ def units(tree):
     flags = make_var(mk, "FLAGS")
     out = [("feat%s" % v, "rtc_feat.hip", flags + ["-DRTC_VARIANT=%s" % v]) for v in make_var(mk, "VARIANT_IDS", "VARIANTS")]
     out.append(("kernels", "rtc_kernels.hip", flags))
-    for unit, src in (("camera", "rtc_camera.hip"), ("adaptive", "rtc_adaptive.hip"), ("filter", "rtc_filter.hip")):   # the small kernels beside the ray kernels, where a tree has them
+    for unit, src in (("camera", "rtc_camera.hip"), ("adaptive", "rtc_adaptive.hip"), ("filter", "rtc_filter.hip"), ("shutter", "rtc_shutter.hip")):   # the small kernels beside the ray kernels, where a tree has them
         if os.path.exists(os.path.join(tree, CSRC, src)):
             out.append((unit, src, flags))
     if os.path.exists(os.path.join(tree, CSRC, "rtc_background.hip")):   # the background's kernels, and one unit per BG build of the one-kernel path

@@ -211,6 +211,18 @@ pub struct RtcFilter {
     pub alpha: f64,  // the Gaussian's falloff; read by no other kind
 }
 
+// include/rtc.h rtc_shutter: motion blur over K poses, each a scene and a camera (not in the reference), for rtc_render_shutter*
+#[allow(dead_code)]
+pub const RTC_SHUTTER_HASHED: u32 = 1;
+#[allow(dead_code)]
+pub const RTC_SHUTTER_MAX_POSES: u32 = 64;
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtcShutter {
+    pub flags: u32, // RTC_SHUTTER_HASHED: a sample's pose is a hashed draw; 0: the pixel's samples in K runs, K <= side * side
+    pub _pad: u32,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct RtcNode {
@@ -362,6 +374,13 @@ extern "C" {
     #[allow(dead_code)]
     fn rtc_render_filtered_rgb8(scene: *mut RtcScene, camera: *const RtcCamera, sampling: *const RtcSampling, filter: *const RtcFilter, fuel: i32, rgb8: *mut u8,
                                 stats: *mut RtcStats) -> c_int;
+    // the shutter: rtc_render_sampled / rtc_render_sampled_rgb8 over n_poses poses, pose p = (scenes[p], cameras[p]); the pointers may repeat
+    #[allow(dead_code)]
+    fn rtc_render_shutter(scenes: *const *mut RtcScene, cameras: *const RtcCamera, n_poses: u32, shutter: *const RtcShutter, sampling: *const RtcSampling,
+                          fuel: i32, pixel_indices: *const u64, first: u64, n: u64, rgb: *mut f64, stats: *mut RtcStats) -> c_int;
+    #[allow(dead_code)]
+    fn rtc_render_shutter_rgb8(scenes: *const *mut RtcScene, cameras: *const RtcCamera, n_poses: u32, shutter: *const RtcShutter, sampling: *const RtcSampling,
+                               fuel: i32, rgb8: *mut u8, stats: *mut RtcStats) -> c_int;
     #[allow(dead_code)] // the filter step alone on host sample colours; scene = null: evaluated on the host, no device needed
     fn rtc_filter_frame(scene: *mut RtcScene, hsize: u64, vsize: u64, sampling: *const RtcSampling, filter: *const RtcFilter, sample_rgb: *const f64,
                         rgb: *mut f64) -> c_int;

@@ -1,0 +1,252 @@
+"""The shutter (include/rtc.h rtc_shutter), the parts that need no GPU: a Python-int restatement of the dealing rule, compared with the
+library's own host evaluation (rtc_shutter_deal without a scene: the function the dealing kernels are compiled from), the clamp of the
+hashed draw, the sequential split, every limit through C, the argument errors of `Shutter` / `Image.par_render_shutter`, and the mirrors
+of the record."""
+import ctypes as C
+import math
+import os
+
+import numpy as np
+import pytest
+
+import foreign_flattener as ff
+from raytracer_challenge_amd import scenes
+from raytracer_challenge_amd.backend import Backend, RtwError, SamplingC, ShutterC
+from raytracer_challenge_amd.image import Image
+from raytracer_challenge_amd.scene import Camera, Matrix, Sampling, Shutter
+from test_area_lights_cpu import jitter as draw_of
+from test_sampled_camera_cpu import sample_hash
+from test_shim_layout import c_struct, rust_struct
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "raytracer_challenge_amd", "csrc", "librtc_amd.so")
+vp = C.c_void_p
+OK, INVALID, UNSUPPORTED = 0, 1, 2
+
+FRAME = (37, 19)
+LIST7 = np.array([702, 0, 36, 37, 350, 350, 1], dtype=np.uint64)   # 7 pixels of the 37x19 frame, one of them twice
+
+
+# ---- the restatement of include/rtc.h rtc_shutter (shared with test_shutter_gpu.py) -------------------------------------------------
+def draw_pose(u: float, K: int) -> int:
+    """s = (uint32_t)(u * (double)K), held to K - 1."""
+    return min(int(u * float(K)), K - 1)
+
+
+_draws = {}
+
+
+def time_draws(sp: Sampling, pixels) -> list:
+    """u = rtc_area_jitter(h, 4) of every (pixel, k), pixel-major; SplitMix64 in Python ints.  Kept per (seed, side, pixels): K does not enter."""
+    key = (sp.seed, sp.side, tuple(int(i) for i in pixels))
+    if key not in _draws:
+        _draws[key] = [draw_of(sample_hash(sp.seed, i, k), 4) for i in key[2] for k in range(sp.samples)]
+    return _draws[key]
+
+
+def poses_of(sp: Sampling, hashed: bool, K: int, pixels) -> np.ndarray:
+    """Pose of every sample id (slot * N + k) of the listed pixels."""
+    N = sp.samples
+    if hashed:
+        return np.array([draw_pose(u, K) for u in time_draws(sp, pixels)], dtype=np.int64)
+    return np.array([(k * K) // N for _ in pixels for k in range(N)], dtype=np.int64)
+
+
+def deal(poses: np.ndarray, K: int):
+    """(order, offsets): the ids pose-major and ascending within a pose -- a stable sort by pose --, and where each pose's run starts."""
+    order = np.argsort(poses, kind="stable").astype(np.uint32)
+    offsets = np.concatenate(([0], np.cumsum(np.bincount(poses, minlength=K)))).astype(np.uint64)
+    return order, offsets
+
+
+def bind(lib):
+    lib.rtc_last_error.restype = C.c_char_p
+    lib.rtc_shutter_deal.restype = C.c_int
+    lib.rtc_shutter_deal.argtypes = [vp, C.c_uint64, C.c_uint32, vp, vp, vp, C.c_uint64, C.c_uint64, vp, vp]
+    lib.rtc_render_shutter.restype = C.c_int
+    lib.rtc_render_shutter.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_int32, vp, C.c_uint64, C.c_uint64, vp, vp]
+    lib.rtc_render_shutter_rgb8.restype = C.c_int
+    lib.rtc_render_shutter_rgb8.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_int32, vp, vp]
+    lib.rtc_shutter_draw_pose.restype = C.c_uint32
+    lib.rtc_shutter_draw_pose.argtypes = [C.c_double, C.c_uint32]
+    return lib
+
+
+@pytest.fixture(scope="module")
+def host():
+    """librtc_amd.so without a device: loading it and the host-only entry points need none."""
+    be = Backend(LIB)
+    bind(be.lib)
+    return be
+
+
+# ---- the rule ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("hashed", [False, True])
+@pytest.mark.parametrize("side", [1, 3, 4, 16])
+def test_host_dealing_is_the_restatement(host, side, hashed):
+    frame_pixels = list(range(FRAME[0] * FRAME[1]))
+    for seed in (0, 0x9E3779B97F4A7C15):
+        sp = Sampling(side=side, seed=seed)
+        N = sp.samples
+        for K in (1, 2, 3, 5, 64):
+            for pixels, kw in ((frame_pixels, dict(n=len(frame_pixels))), ([int(i) for i in LIST7], dict(pixel_indices=LIST7))):
+                if not hashed and K > N:   # some poses would never be sampled
+                    with pytest.raises(RtwError):
+                        host.shutter_deal(FRAME[0], K, sp, Shutter(hashed), **kw)
+                    continue
+                order, offsets = host.shutter_deal(FRAME[0], K, sp, Shutter(hashed), **kw)
+                want_order, want_offsets = deal(poses_of(sp, hashed, K, pixels), K)
+                m = len(pixels) * N
+                assert offsets.shape == (K + 1,) and offsets[0] == 0 and offsets[K] == m and (np.diff(offsets.astype(np.int64)) >= 0).all()
+                assert np.array_equal(np.sort(order), np.arange(m, dtype=np.uint32))          # a permutation
+                assert np.array_equal(offsets, want_offsets), (side, hashed, seed, K)
+                assert np.array_equal(order, want_order), (side, hashed, seed, K)
+    # a range that is not whole rows deals like the same pixels listed; nothing but the pixel index and k enter
+    sp = Sampling(side=3, seed=11)
+    a = host.shutter_deal(FRAME[0], 5, sp, Shutter(hashed), first=40, n=50)
+    b = host.shutter_deal(FRAME[0], 5, sp, Shutter(hashed), pixel_indices=np.arange(40, 90, dtype=np.uint64))
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+
+
+def test_hashed_poses_depend_on_the_seed_and_not_on_jitter(host):
+    a = host.shutter_deal(FRAME[0], 5, Sampling(side=3, seed=1), Shutter(), n=703)
+    b = host.shutter_deal(FRAME[0], 5, Sampling(side=3, seed=2), Shutter(), n=703)
+    c = host.shutter_deal(FRAME[0], 5, Sampling(side=3, seed=1, jitter=True, lens_radius=0.2, focal_distance=3.0), Shutter(), n=703)
+    assert not np.array_equal(a[0], b[0]) and np.array_equal(a[0], c[0]) and np.array_equal(a[1], c[1])
+    # every pose gets about a fifth: 6 327 draws, binomial sigma = sqrt(6327 * 0.2 * 0.8) = 31.8; 6 sigma
+    assert (np.abs(np.diff(a[1].astype(np.int64)) - 6327 / 5.0) <= 6.0 * math.sqrt(6327 * 0.2 * 0.8)).all()
+
+
+def test_the_clamp(host):
+    u = 1.0 - 2.0 ** -53   # the largest draw
+    for K in (3, 7, 64):
+        assert draw_pose(u, K) <= K - 1
+        assert host.lib.rtc_shutter_draw_pose(u, K) == draw_pose(u, K) <= K - 1
+        assert host.lib.rtc_shutter_draw_pose(0.0, K) == 0
+        assert host.lib.rtc_shutter_draw_pose(1.0, K) == K - 1     # not a draw: what the clamp is for
+    assert [host.lib.rtc_shutter_draw_pose(p / 3.0 + 1e-9, 3) for p in range(3)] == [0, 1, 2]
+
+
+@pytest.mark.parametrize("side,K", [(1, 1), (3, 2), (3, 9), (4, 3), (4, 5), (4, 16), (16, 64), (16, 5)])
+def test_sequential_mode_splits_every_pixel_evenly(host, side, K):
+    sp = Sampling(side=side, seed=3)
+    N = sp.samples
+    order, offsets = host.shutter_deal(FRAME[0], K, sp, Shutter(hashed=False), pixel_indices=LIST7)
+    for p in range(K):
+        run = order[int(offsets[p]):int(offsets[p + 1])].astype(np.int64)
+        per_pixel = np.bincount(run // N, minlength=len(LIST7))
+        assert ((per_pixel == N // K) | (per_pixel == -(-N // K))).all(), (side, K, p, per_pixel)
+        assert (np.diff(run) > 0).all()                    # ascending within the pose
+        k = run % N
+        assert ((k * K) // N == p).all()
+
+
+# ---- limits ------------------------------------------------------------------------------------------------------------------------
+def test_every_limit_through_c_without_a_device(host):
+    lib = host.lib
+    order, offsets = np.zeros(7 * 256, dtype=np.uint32), np.zeros(66, dtype=np.uint64)
+
+    def deal_code(K=3, flags=1, sh=True, sp=True, side=3, sflags=0, R=0.0, F=1.0, hsize=37, n=7, order_p=order.ctypes.data, offsets_p=offsets.ctypes.data):
+        shc, spc = ShutterC(flags, 0), SamplingC(side, sflags, 0, R, F)
+        return lib.rtc_shutter_deal(None, hsize, K, C.byref(shc) if sh else None, C.byref(spc) if sp else None, LIST7.ctypes.data, 0, n, order_p, offsets_p)
+    assert deal_code() == OK and deal_code(flags=0) == OK and deal_code(K=64) == OK and deal_code(K=9, flags=0) == OK
+    assert deal_code(K=0) == INVALID and b"n_poses" in lib.rtc_last_error()
+    assert deal_code(sh=False) == INVALID and deal_code(sp=False) == INVALID
+    assert deal_code(flags=2) == INVALID and deal_code(flags=0x80000001) == INVALID and b"flag" in lib.rtc_last_error()
+    assert deal_code(K=10, flags=0) == INVALID and b"more poses than samples" in lib.rtc_last_error()       # K > N, sequential
+    assert deal_code(K=2, flags=0, side=1) == INVALID and deal_code(K=2, flags=1, side=1) == OK
+    assert deal_code(K=65) == UNSUPPORTED and deal_code(K=65, flags=0, side=16) == UNSUPPORTED and b"RTC_SHUTTER_MAX_POSES" in lib.rtc_last_error()
+    # everything check_sampling refuses
+    assert deal_code(side=0) == INVALID and deal_code(sflags=2) == INVALID and deal_code(R=-0.1) == INVALID and deal_code(R=math.nan) == INVALID
+    assert deal_code(R=0.1, F=0.0) == INVALID and deal_code(R=0.1, F=math.inf) == INVALID and deal_code(side=17) == UNSUPPORTED
+    # the dealing's own arguments
+    assert deal_code(order_p=None) == INVALID and deal_code(offsets_p=None) == INVALID and deal_code(hsize=0) == INVALID
+    assert deal_code(n=0, order_p=None) == OK and not offsets[:4].any()
+
+    # the render entry points: the shutter's own numbers before anything else, then the arrays; no device is touched
+    cam = Camera.new(37, 19, 1.0, Matrix.id())
+    cams = (ff.RtcCamera * 3)(*[ff.make_camera(cam)] * 3)
+    scenes_null = (vp * 3)()      # three NULL entries
+    rgb = np.zeros((7, 3))
+    rgb8 = np.zeros(703 * 3, dtype=np.uint8)
+
+    def render_code(K=3, flags=1, sh=True, side=3, scenes_p=scenes_null, cams_p=cams, out=rgb.ctypes.data):
+        shc, spc = ShutterC(flags, 0), SamplingC(side, 0, 0, 0.0, 1.0)
+        a = lib.rtc_render_shutter(scenes_p, cams_p, K, C.byref(shc) if sh else None, C.byref(spc), 5, LIST7.ctypes.data, 0, 7, out, None)
+        err = lib.rtc_last_error()
+        b = lib.rtc_render_shutter_rgb8(scenes_p, cams_p, K, C.byref(shc) if sh else None, C.byref(spc), 5, rgb8.ctypes.data, None)
+        assert a == b, (a, b)
+        return a, err
+    assert render_code(K=0)[0] == INVALID and render_code(sh=False)[0] == INVALID and render_code(flags=4)[0] == INVALID
+    assert render_code(K=65, scenes_p=None, cams_p=None)[0] == UNSUPPORTED         # before the NULL arrays are looked at
+    assert render_code(K=3, flags=0, side=1, scenes_p=None)[0] == INVALID and b"more poses" in lib.rtc_last_error()
+    assert render_code(side=0)[0] == INVALID and render_code(side=17, scenes_p=None)[0] == UNSUPPORTED
+    code, err = render_code(scenes_p=None)
+    assert code == INVALID and b"NULL argument" in err
+    code, err = render_code(cams_p=None)
+    assert code == INVALID and b"NULL argument" in err
+    code, err = render_code()
+    assert code == INVALID and b"NULL scene" in err                                # NULL entries
+    odd = (ff.RtcCamera * 3)(ff.make_camera(cam), ff.make_camera(Camera.new(37, 20, 1.0, Matrix.id())), ff.make_camera(cam))
+    code, err = render_code(cams_p=odd)
+    assert code == INVALID and b"hsize or vsize differ" in err
+    odd = (ff.RtcCamera * 3)(ff.make_camera(cam), ff.make_camera(cam), ff.make_camera(Camera.new(36, 19, 1.0, Matrix.id())))
+    code, err = render_code(cams_p=odd)
+    assert code == INVALID and b"hsize or vsize differ" in err
+    assert lib.rtc_render_shutter_rgb8(scenes_null, cams, 3, C.byref(ShutterC(1, 0)), C.byref(SamplingC(3, 0, 0, 0.0, 1.0)), 5, None, None) == INVALID
+
+
+# ---- the Python layer ---------------------------------------------------------------------------------------------------------------
+def test_shutter_and_par_render_shutter_argument_errors(host):
+    assert Shutter().hashed is True and Shutter(hashed=False).hashed is False
+    for bad in (1, 0, None, "yes"):
+        with pytest.raises(ValueError):
+            Shutter(hashed=bad)
+    with pytest.raises(Exception):
+        Shutter().hashed = False   # frozen
+    assert (ShutterC.of(Shutter()).flags, ShutterC.of(Shutter(hashed=False)).flags) == (1, 0)
+    poses = scenes.motion_showcase(8, 8, 3)
+    assert len(poses) == 3 and all(isinstance(c, Camera) and (c.hsize, c.vsize) == (8, 8) for c, _ in poses)
+    assert poses[0][1] is not poses[1][1] and poses[0][0].transform_matrix.flat() != poses[2][0].transform_matrix.flat()
+    with pytest.raises(ValueError):
+        scenes.motion_showcase(8, 8, 0)
+    sp = Sampling(side=2)
+    for bad_poses in ([], [poses[0][0]], [(poses[0][1], poses[0][0])], [poses[0], (Camera.new(9, 8, 1.0, Matrix.id()), poses[1][1])]):
+        with pytest.raises(ValueError):
+            Image.par_render_shutter(bad_poses, sp, backend=host)
+    with pytest.raises(ValueError):
+        Image.par_render_shutter(poses, None, backend=host)
+    with pytest.raises(ValueError):
+        Image.par_render_shutter(poses, sp, shutter=True, backend=host)
+    with pytest.raises(ValueError):
+        Image.par_render_shutter(scenes.motion_showcase(8, 8, 5), sp, shutter=Shutter(hashed=False), backend=host)   # K = 5 > N = 4
+    with pytest.raises(ValueError):
+        host.render_shutter([], [], sp, Shutter())
+    with pytest.raises(ValueError):
+        host.shutter_deal(37, 3, sp, Shutter())   # neither a list nor a count
+
+
+def test_libraries_without_the_entry_points_refuse(orc):
+    poses = scenes.motion_showcase(8, 8, 2)
+    with pytest.raises(RtwError):
+        orc.shutter_deal(8, 2, Sampling(side=2), Shutter(), n=4)
+    with pytest.raises(RtwError):
+        Image.par_render_shutter(poses, Sampling(side=2), backend=orc)
+
+
+def test_exports_and_mirrors():
+    lib = C.CDLL(LIB)
+    names = ("rtc_render_shutter", "rtc_render_shutter_rgb8", "rtc_shutter_deal")
+    for name in names + ("rtc_shutter_draw_pose",):
+        assert hasattr(lib, name), name
+    h = open(os.path.join(ROOT, "include", "rtc.h")).read()
+    rs = open(os.path.join(ROOT, "shim", "gpu.rs")).read()
+    c, r = c_struct(h, "rtc_shutter"), rust_struct(rs, "RtcShutter")
+    assert c == r == [("flags", "u32", 0), ("_pad", "u32", 0)]
+    assert C.sizeof(ShutterC) == 4 * len(c) == 8 and [f[0] for f in ShutterC._fields_] == [f[0] for f in c]
+    assert "RTC_SHUTTER_HASHED = 1u" in h and "pub const RTC_SHUTTER_HASHED: u32 = 1;" in rs
+    assert "#define RTC_SHUTTER_MAX_POSES 64" in h and "pub const RTC_SHUTTER_MAX_POSES: u32 = 64;" in rs
+    for name in ("rtc_render_shutter", "rtc_render_shutter_rgb8"):
+        assert "fn %s(" % name in rs, name
+    from raytracer_challenge_amd.scene import SHUTTER_MAX_POSES
+    assert SHUTTER_MAX_POSES == 64
