@@ -715,6 +715,16 @@ int rtc_bvh_collapse_raw(const void* nodes, uint32_t n_nodes, int32_t root, int3
 int rtc_light_grid_build_raw(const int32_t* geometry, const double* limits, const double* transform_inv, const double* tris, uint32_t n_prims, const double* light, int32_t n,
                              int32_t max_list, int32_t tight, uint32_t* cells, uint32_t cells_cap, int32_t* items, uint32_t items_cap, uint32_t* n_items);
 
+/* Test hook, not part of the rendering surface: the exclusive scan that orders the work lists of adaptive sampling (the compaction's block
+ * counts) and of the shutter (the dealing's pose-major count table), alone, on the caller's words.  values[0 .. n - 1] are replaced by their
+ * exclusive prefix sums (values[i] = the sum of the former values[0 .. i - 1], modulo 2^64) and *total receives the sum of all n.  With a
+ * scene the device's scan runs on that scene's device and stream (csrc/rtc_adaptive.hip rtc_launch_scan: tiles of 256 entries, one
+ * level per factor of 256 in n, so 1 level up to 256 entries, 2 up to 65 536, 3 up to 2^24, ...) in device buffers of the call's own
+ * (n + the levels' words + 1, freed before it returns; nothing of the scene is touched); with scene == NULL the same sums are formed in a
+ * plain loop on the host, no device needed.  n == 0 sets *total = 0 and reads nothing.  RTC_ERR_INVALID for a NULL `total`, or NULL
+ * `values` with n > 0; RTC_ERR_UNSUPPORTED for n >= 2^39 with a scene (the limit of the frames the compaction accepts). */
+int rtc_scan_raw(rtc_scene* scene, uint64_t* values, uint64_t n, uint64_t* total);
+
 /* Dynamic LDS (bytes per block) the wavefront traversal kernel uses for this scene: > 0 = the scene's accelerator nodes, intersection
  * records and mesh triangles are copied into every CU's LDS and walks read them there (small scenes: the tables and the traversal
  * stacks fit 160 KB); 0 = they are read from memory.  bench.py's byte accounting counts LDS-resident records as 0 bytes. */

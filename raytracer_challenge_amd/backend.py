@@ -564,6 +564,28 @@ class Backend:
             raise RtwError("rtc_shutter_deal: %s" % (lib.rtc_last_error() or b"").decode())
         return order, offsets
 
+    def scan_raw(self, values: np.ndarray, nw: Optional[NativeWorld] = None, device: int = 0):
+        """include/rtc.h rtc_scan_raw (test infrastructure): (the exclusive prefix sums of `values` as a new uint64 array, their total),
+        sums modulo 2^64.  With a world the device's scan kernels form them, without one a plain loop on the host (no GPU needed)."""
+        lib = self.lib
+        if not hasattr(lib, "rtc_scan_raw"):
+            raise RtwError("the scan hook needs librtc_amd.so (backend %r has no rtc_scan_raw)" % self.name)
+        vp = C.c_void_p
+        lib.rtw_world_scene.restype, lib.rtw_world_scene.argtypes = vp, [vp, C.c_int]
+        lib.rtc_scan_raw.restype = C.c_int
+        lib.rtc_scan_raw.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+        lib.rtc_last_error.restype = C.c_char_p
+        scene = None
+        if nw is not None:
+            scene = lib.rtw_world_scene(nw.handle, int(device))
+            if not scene:
+                raise RtwError("scene upload failed: %s" % self._err())
+        out = np.array(values, dtype=np.uint64, order="C", copy=True).reshape(-1)
+        total = C.c_uint64(0)
+        if lib.rtc_scan_raw(scene, out.ctypes.data if out.size else None, out.size, C.byref(total)) != 0:
+            raise RtwError("rtc_scan_raw: %s" % (lib.rtc_last_error() or b"").decode())
+        return out, int(total.value)
+
     def color_at(self, nw: NativeWorld, rays: np.ndarray, fuel: int = FUEL):
         """World::color_at for rays given as rows {ox,oy,oz,dx,dy,dz}.  Returns (rgb[n,3], hits[n])."""
         rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)

@@ -51,6 +51,8 @@ void rtc_launch_gen_rays(const DCamera& cam, const DPixelMap& pm, const rtc_samp
 void rtc_launch_resolve_samples(const double* ray_rgb, unsigned n_samples, unsigned long long n_slots, double* dst, hipStream_t stream);
 unsigned long long rtc_contrast_blocks(unsigned long long n);
 unsigned long long rtc_contrast_work_words(unsigned long long n);
+unsigned long long rtc_scan_work_words(unsigned long long n);
+unsigned rtc_launch_scan(unsigned long long* v, unsigned long long n, unsigned long long* levels, unsigned long long* total, hipStream_t stream);
 unsigned rtc_launch_contrast_compact(const double* frame, unsigned long long hsize, unsigned long long vsize, double threshold, unsigned neighbours,
                                      unsigned long long* work, unsigned long long* list, unsigned long long* count, hipStream_t stream);
 void rtc_launch_resolve_samples_scatter(const double* ray_rgb, unsigned n_samples, unsigned long long n_slots, const unsigned long long* indices, double* frame,
@@ -2225,6 +2227,38 @@ int rtc_light_grid_build_raw(const int32_t* geometry, const double* limits, cons
   std::string err;
   const int rc = rtb::light_grid_build_raw(geometry, limits, transform_inv, tris, n_prims, light, n, max_list, tight, cells, cells_cap, items, items_cap, n_items, &err);
   return rc > 0 ? rtc_fail(rc, err) : rc;
+}
+
+// Test hook: the shared scan (rtc_adaptive.hip rtc_launch_scan) alone on the caller's words, in buffers of its own (include/rtc.h).
+int rtc_scan_raw(rtc_scene* s, uint64_t* values, uint64_t n, uint64_t* total) {
+  if (!total || (!values && n)) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  *total = 0;
+  if (n == 0) return RTC_OK;
+  if (!s) {  // the same sums on the host
+    uint64_t sum = 0;
+    for (uint64_t i = 0; i < n; i++) { const uint64_t v = values[i]; values[i] = sum; sum += v; }
+    *total = sum;
+    return RTC_OK;
+  }
+  if (n >= (1ull << 39)) return rtc_fail(RTC_ERR_UNSUPPORTED, "scan: 2^39 words or more");
+  HIP_OK(hipSetDevice(s->device));
+  const uint64_t words = n + rtc_scan_work_words(n) + 1;  // the values, the levels above them, the total
+  unsigned long long* d = nullptr;
+  HIP_OK(hipMalloc((void**)&d, words * sizeof(unsigned long long)));
+  hipError_t e = hipMemcpyAsync(d, values, n * sizeof(uint64_t), hipMemcpyHostToDevice, s->stream);
+  if (e == hipSuccess) {
+    (void)rtc_launch_scan(d, n, d + n, d + words - 1, s->stream);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(values, d, n * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream);
+  unsigned long long sum = 0;
+  if (e == hipSuccess) e = hipMemcpyAsync(&sum, d + words - 1, sizeof(sum), hipMemcpyDeviceToHost, s->stream);
+  const hipError_t e_sync = hipStreamSynchronize(s->stream);  // (before the buffer goes, whatever happened)
+  (void)hipFree(d);
+  HIP_OK(e);
+  HIP_OK(e_sync);
+  *total = sum;
+  return RTC_OK;
 }
 
 uint32_t rtc_scene_wavefront_lds_bytes(const rtc_scene* s) { return s ? s->lds_bytes : 0u; }

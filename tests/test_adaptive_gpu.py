@@ -240,3 +240,62 @@ def test_other_routes_and_buffer_reuse(hip, path, monkeypatch):
     assert np.array_equal(bits(hip.render_adaptive(nw, cam, ad, 5)), bits(whole))
     img = Image.par_render(cam, scenes.cover(48, 32)[1], adaptive=ad)
     assert (img.hsize, img.vsize) == (48, 32) and np.array_equal(bits(np.asarray(img.pixels).reshape(-1, 3)), bits(whole))
+
+
+# ---- 6. the compaction past 2^24 pixels: three scan levels ---------------------------------------------------------------------------
+WIDE = (4096, 4097)   # 16 781 312 pixels in 65 552 blocks: block counts -> 257 tile sums -> 2 -> 1, one entry past a tile at the second level
+WIDE_PLANTED = (0, 255, 256, 65535, 65536, (1 << 24) - 1, 1 << 24, 4096 * 4097 - 1,   # the seams of the first and second level, 2^24, the last pixel
+                5000, 5001,                    # pairs that touch: in a row,
+                9000000, 9000000 + 4096,       #   in a column,
+                12345678, 12345678 + 4097)     #   across a corner
+
+
+@pytest.fixture(scope="module")
+def wide(hip):
+    """(the frame: 0.5 everywhere but the planted pixels' green, a scene to compact it on); the frame is 403 MB on the host and on the device
+    and the list 134 MB more, so the scene is released when the module is done."""
+    w, h = WIDE
+    frame = np.full((w * h, 3), 0.5)
+    frame[np.array(WIDE_PLANTED), 1] = 1.0
+    nw = hip.build_world(scenes.chapter11_glass_air_bubble(8, 8)[1])
+    yield frame, nw
+    nw.close()
+
+
+def planted_and_neighbours(planted, w, h, neighbours):
+    """The sorted union of the planted pixels and their neighbours inside the frame, from the planted set alone."""
+    p = np.array(planted, dtype=np.int64)
+    x, y = p % w, p // w
+    steps = [(-1, 0), (1, 0), (0, -1), (0, 1)] + ([(-1, -1), (1, -1), (-1, 1), (1, 1)] if neighbours == 8 else [])
+    out = [p]
+    for dx, dy in steps:
+        inside = (x + dx >= 0) & (x + dx < w) & (y + dy >= 0) & (y + dy < h)
+        out.append(((y + dy) * w + (x + dx))[inside])
+    return np.unique(np.concatenate(out)).astype(np.uint64)
+
+
+@pytest.mark.parametrize("neighbours", [4, 8])
+def test_compaction_of_a_sparse_frame_past_2_to_24_pixels(hip, wide, neighbours):
+    """A bright pixel differs by 0.5 from every dark neighbour and by 0 from a bright one, and none is surrounded by bright ones: at 0.25
+    the refined pixels are the planted ones and their neighbours."""
+    frame, nw = wide
+    w, h = WIDE
+    want = planted_and_neighbours(WIDE_PLANTED, w, h, neighbours)
+    assert want.size < len(WIDE_PLANTED) * (neighbours + 1) and int(want[-1]) == w * h - 1 and int(want[0]) == 0
+    host = hip.contrast_pixels(frame, w, h, 0.25, neighbours)
+    assert host.size == want.size and np.array_equal(host, want), (host.size, want.size)
+    dev = hip.contrast_pixels(frame, w, h, 0.25, neighbours, nw=nw)
+    assert dev.size == want.size and np.array_equal(dev, want), (dev.size, want.size, dev[:40], want[:40])
+
+
+def test_compaction_of_every_pixel_past_2_to_24_pixels(hip, wide):
+    """Threshold -1 refines every pixel: every block count is 256 and the prefix sums reach 16.8 M."""
+    frame, nw = wide
+    w, h = WIDE
+    dev = hip.contrast_pixels(frame, w, h, -1.0, 4, nw=nw)
+    assert dev.size == w * h
+    bad = np.flatnonzero(dev != np.arange(w * h, dtype=np.uint64))
+    assert bad.size == 0, "%d entries are not their own index, the first at %d" % (bad.size, int(bad[0]))
+    # and a small frame afterwards, in the grown buffers
+    small = random_frame(13, 7, 5)
+    assert np.array_equal(hip.contrast_pixels(small, 13, 7, 0.3, 8, nw=nw), hip.contrast_pixels(small, 13, 7, 0.3, 8))

@@ -15,7 +15,7 @@ from raytracer_challenge_amd.backend import Backend, RtwError, SamplingC, Shutte
 from raytracer_challenge_amd.image import Image
 from raytracer_challenge_amd.scene import Camera, Matrix, Sampling, Shutter
 from test_area_lights_cpu import jitter as draw_of
-from test_sampled_camera_cpu import sample_hash
+from test_sampled_camera_cpu import sample_hash, splitmix64_np
 from test_shim_layout import c_struct, rust_struct
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -50,6 +50,22 @@ def poses_of(sp: Sampling, hashed: bool, K: int, pixels) -> np.ndarray:
     if hashed:
         return np.array([draw_pose(u, K) for u in time_draws(sp, pixels)], dtype=np.int64)
     return np.array([(k * K) // N for _ in pixels for k in range(N)], dtype=np.int64)
+
+
+def poses_np(sp: Sampling, hashed: bool, K: int, pixels) -> np.ndarray:
+    """poses_of on numpy uint64 arrays (products wrap modulo 2^64 as the C ones do), for millions of samples; restated from include/rtc.h
+    like the scalar one:  sequential s = (k * K) / N;  hashed h = m(m(m(seed) ^ i) ^ k), u = (m(h ^ 4) >> 11) * 2^-53 (rtc_area_jitter(h, 4):
+    53 bits, exact in a double), t = u * (double)K, s = (uint32_t)t held to K - 1."""
+    pixels = np.ascontiguousarray(pixels, dtype=np.uint64).reshape(-1)
+    N = sp.samples
+    k = np.arange(N, dtype=np.uint64)
+    if not hashed:
+        return np.tile(((k * np.uint64(K)) // np.uint64(N)).astype(np.int64), pixels.size)
+    seed = splitmix64_np(np.array([sp.seed & 0xFFFFFFFFFFFFFFFF], dtype=np.uint64))
+    h = splitmix64_np(splitmix64_np(seed ^ pixels)[:, None] ^ k[None, :])
+    u = (splitmix64_np(h ^ np.uint64(4)) >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+    s = (u * float(K)).astype(np.int64)         # t >= 0: the conversion truncates, as the cast does
+    return np.minimum(s, K - 1).reshape(-1)
 
 
 def deal(poses: np.ndarray, K: int):
@@ -106,6 +122,62 @@ def test_host_dealing_is_the_restatement(host, side, hashed):
     a = host.shutter_deal(FRAME[0], 5, sp, Shutter(hashed), first=40, n=50)
     b = host.shutter_deal(FRAME[0], 5, sp, Shutter(hashed), pixel_indices=np.arange(40, 90, dtype=np.uint64))
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+
+
+@pytest.mark.parametrize("hashed", [False, True])
+def test_the_vectorised_restatement_is_the_scalar_one(hashed):
+    """poses_np against the Python-int poses_of: the whole 37x19 frame and LIST7, K in {1, 3, 5, 64}."""
+    frame_pixels = list(range(FRAME[0] * FRAME[1]))
+    for sp in (Sampling(side=3, seed=0), Sampling(side=4, seed=0x9E3779B97F4A7C15), Sampling(side=16, seed=1234), Sampling(side=1, seed=7)):
+        for K in (1, 3, 5, 64):
+            for pixels in (frame_pixels, [int(i) for i in LIST7]):
+                want = poses_of(sp, hashed, K, pixels)
+                got = poses_np(sp, hashed, K, pixels)
+                assert got.dtype == np.int64 and got.shape == want.shape and np.array_equal(got, want), (sp, hashed, K, len(pixels))
+                if hashed and K > 1 and len(pixels) > 7:
+                    assert got.min() == 0 and got.max() == K - 1
+    # indices past 2^32 hash as 64-bit words
+    far = [(1 << 33) + 5, (1 << 38) - 1]
+    assert np.array_equal(poses_np(Sampling(side=3, seed=5), True, 7, far), poses_of(Sampling(side=3, seed=5), True, 7, far))
+
+
+# 2^22 samples are one default chunk of a real frame (16 384 blocks of 256); the device's count table has K entries per block
+BIG_DEALS = [  # (hsize, vsize, side, K, hashed)
+    (512, 512, 4, 5, True),        # 81 920 entries: three scan levels on the device
+    (128, 129, 4, 64, True),       # 264 192 samples, 1 032 blocks: 66 048 entries -> 258 -> 2
+    (512, 512, 4, 16, False),      # 262 144 entries; every wave of 64 samples holds each pose four times
+]
+
+
+def big_deal_case(hsize, vsize, side, K, hashed, pixels=None):
+    """(sampling, shutter, the restated dealing) of a large case; the seed follows the shape."""
+    sp, sh = Sampling(side=side, seed=1000 * K + hsize + vsize), Shutter(hashed)
+    px = np.arange(hsize * vsize, dtype=np.uint64) if pixels is None else pixels
+    poses = poses_np(sp, hashed, K, px)
+    return sp, sh, poses, deal(poses, K)
+
+
+def check_dealing_properties(order, offsets, poses, K):
+    """What holds without any reference dealing: a permutation, ascending inside every run, offsets = prefix sums of the poses' counts."""
+    m = poses.size
+    seen = np.zeros(m, dtype=bool)
+    assert order.shape == (m,) and int(order.max()) < m
+    seen[order] = True
+    assert seen.all()
+    assert np.array_equal(offsets, np.concatenate(([0], np.cumsum(np.bincount(poses, minlength=K)))).astype(np.uint64))
+    rising = np.diff(order.astype(np.int64)) > 0
+    rising[offsets[1:K].astype(np.int64)[(offsets[1:K] > 0) & (offsets[1:K] < m)] - 1] = True    # (a run's first id may be below the last of the run before)
+    assert rising.all()
+    assert np.array_equal(poses[order], np.repeat(np.arange(K), np.diff(offsets.astype(np.int64))))
+
+
+@pytest.mark.parametrize("hsize,vsize,side,K,hashed", BIG_DEALS)
+def test_host_dealing_of_a_production_chunk_is_the_restatement(host, hsize, vsize, side, K, hashed):
+    sp, sh, poses, (want_order, want_offsets) = big_deal_case(hsize, vsize, side, K, hashed)
+    order, offsets = host.shutter_deal(hsize, K, sp, sh, n=hsize * vsize)
+    assert np.array_equal(offsets, want_offsets), (offsets, want_offsets)
+    assert np.array_equal(order, want_order)
+    check_dealing_properties(order, offsets, poses, K)
 
 
 def test_hashed_poses_depend_on_the_seed_and_not_on_jitter(host):

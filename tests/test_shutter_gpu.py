@@ -16,7 +16,7 @@ from raytracer_challenge_amd.device import RtcStatsC
 from raytracer_challenge_amd.image import Image
 from raytracer_challenge_amd.scene import Camera, Color, Element, Material, Matrix, Pattern, PointLight, Sampling, ShapeArgs, Shutter, Vector, World
 from test_sampled_camera_cpu import samples_mean
-from test_shutter_cpu import FRAME, LIST7, bind as bind_shutter, poses_of
+from test_shutter_cpu import BIG_DEALS, FRAME, LIST7, big_deal_case, bind as bind_shutter, check_dealing_properties, poses_np, poses_of
 
 pytestmark = pytest.mark.gpu
 PATHS = ["1", "4"]
@@ -51,13 +51,20 @@ def expected_frame(hip, lib, nws, cams, sp, shutter, fuel, pixels, shadow=None):
     """The definition, outside the library's shutter code: host sample rays per pose camera, the restated pose picks each sample's row,
     rtc_trace_rays on that pose's scene, the k-ordered sum / N in numpy.  shadow: a list that receives each pose's rays_shadow."""
     K, N = len(nws), sp.samples
-    pose = poses_of(sp, shutter.hashed, K, [int(i) for i in pixels]).reshape(len(pixels), N)
+    if len(pixels) * N > 100000:   # (the Python-int restatement is for small frames; test_shutter_cpu.py holds the two to one answer)
+        pose = poses_np(sp, shutter.hashed, K, pixels).reshape(len(pixels), N)
+    else:
+        pose = poses_of(sp, shutter.hashed, K, [int(i) for i in pixels]).reshape(len(pixels), N)
     colours = np.full((len(pixels), N, 3), np.nan)
+    host_rays = []   # (camera, its rays): evaluated once per distinct camera object, not once per pose
     for p in range(K):
         sel = pose == p
         if not sel.any():
             continue
-        rays = hip.camera_rays(cams[p], sp, pixel_indices=np.asarray(pixels, dtype=np.uint64))    # host evaluation: no world
+        rays = next((r for c, r in host_rays if c is cams[p]), None)
+        if rays is None:
+            rays = hip.camera_rays(cams[p], sp, pixel_indices=np.asarray(pixels, dtype=np.uint64))    # host evaluation: no world
+            host_rays.append((cams[p], rays))
         st = RtcStatsC()
         colours[sel] = trace(lib, nws[p], rays[sel], fuel, stats=st)
         if shadow is not None:
@@ -91,6 +98,40 @@ def test_device_dealing_is_the_host_dealing(hip, K, hashed, side, pixels):
     # a smaller dealing after a larger one reuses the buffers; a range that is not whole rows is a list launch
     dev2, host2 = hip.shutter_deal(FRAME[0], K, sp, sh, nw=nw, first=5, n=40), hip.shutter_deal(FRAME[0], K, sp, sh, first=5, n=40)
     assert np.array_equal(dev2[0], host2[0]) and np.array_equal(dev2[1], host2[1])
+
+
+# ---- 1b. the dealing of a production chunk: count tables of two full scan levels, and of three ------------------------------------------------
+BIG_DEVICE_DEALS = [d + (False,) for d in BIG_DEALS] + [  # (hsize, vsize, side, K, hashed, as a pixel list)
+    (512, 512, 4, 4, True, False),       # 65 536 entries: exactly two full levels
+    (512, 512, 4, 64, True, False),      # 2^20 entries
+    (128, 129, 4, 64, True, True),       # the frame as a list: a permutation with a few indices repeated
+]
+
+
+def listed_frame(hsize, vsize):
+    px = np.random.default_rng(hsize * vsize).permutation(hsize * vsize).astype(np.uint64)
+    px[[5, 300, 9000, px.size - 1]] = px[[4, 299, 17, 0]]   # four pixels twice (and four not at all)
+    return px
+
+
+@pytest.mark.parametrize("hsize,vsize,side,K,hashed,listed", BIG_DEVICE_DEALS)
+def test_device_dealing_of_a_production_chunk(hip, hsize, vsize, side, K, hashed, listed):
+    _, world = scenes.chapter11_glass_air_bubble(*FRAME)
+    nw = hip.build_world(world)
+    pixels = listed_frame(hsize, vsize) if listed else None
+    sp, sh, poses, (want_order, want_offsets) = big_deal_case(hsize, vsize, side, K, hashed, pixels)
+    kw = dict(pixel_indices=pixels) if listed else dict(n=hsize * vsize)
+    dev, host = hip.shutter_deal(hsize, K, sp, sh, nw=nw, **kw), hip.shutter_deal(hsize, K, sp, sh, **kw)
+    assert np.array_equal(dev[1], want_offsets) and np.array_equal(host[1], want_offsets), (dev[1], host[1], want_offsets)
+    bad = np.flatnonzero(dev[0] != want_order)
+    assert bad.size == 0, "%d of %d positions differ from the restated dealing, the first at %d" % (bad.size, want_order.size, int(bad[0]))
+    assert np.array_equal(host[0], want_order)
+    check_dealing_properties(dev[0], dev[1], poses, K)
+    # the small dealings of test_device_dealing_is_the_host_dealing on the same scene: the grown buffers are reused
+    sp2, sh2 = Sampling(side=3, seed=1237), Shutter()
+    for kw2 in (dict(n=FRAME[0] * FRAME[1]), dict(first=5, n=40)):
+        dev2, host2 = hip.shutter_deal(FRAME[0], 3, sp2, sh2, nw=nw, **kw2), hip.shutter_deal(FRAME[0], 3, sp2, sh2, **kw2)
+        assert np.array_equal(dev2[0], host2[0]) and np.array_equal(dev2[1], host2[1])
 
 
 # ---- 2. identities with rtc_render_sampled -------------------------------------------------------------------------------------------
@@ -145,6 +186,44 @@ def test_a_frame_is_the_mean_of_its_samples_each_in_its_pose(hip, path, monkeypa
     # sequential mode over the same poses
     seq = Shutter(hashed=False)
     assert np.array_equal(bits(hip.render_shutter(nws, cams, sp, seq, 5, pixel_indices=LIST7)), bits(expected_frame(hip, lib, nws, cams, sp, seq, 5, LIST7)))
+
+
+# ---- 3b. a frame across a dealing of three scan levels ----------------------------------------------------------------------------------------
+_wide = {}
+
+
+@pytest.mark.parametrize("path", PATHS)
+def test_a_frame_across_a_three_level_dealing(hip, path, monkeypatch):
+    """128x129 at 4x4 jittered samples over K = 64 hashed poses, one default chunk: 264 192 samples in 1 032 blocks, a count table of
+    66 048 entries -> 258 -> 2: two entries past a tile at the second level, so the table from entry 65 536 on -- pose 63's blocks
+    520 .. 1 031 -- gets its base from the third level, which no offset shows."""
+    monkeypatch.setenv("RTC_KERNEL", path)
+    monkeypatch.delenv("RTC_SAMPLED_MAX_RAYS", raising=False)
+    lib = bind(hip.lib)
+    W, H, K = 128, 129, 64
+    cam, world = scenes.chapter11_glass_air_bubble(W, H)
+    nw, twin = hip.build_world(world), hip.build_world(scenes.chapter11_glass_air_bubble(W, H)[1])
+    sp, sh = Sampling(side=4, jitter=True, seed=41), Shutter()
+    # identity: one camera 64 times over two equal scenes
+    still = hip.render_sampled(nw, cam, sp, 5)
+    assert np.isfinite(still).all() and still.max() > 0.0
+    assert np.array_equal(bits(hip.render_shutter([nw, twin] * 32, [cam] * K, sp, sh, 5)), bits(still))
+    # definition: two cameras alternate over the poses
+    cam2 = Camera.new(W, H, math.pi / 3.0, Camera.transform(Vector.point(0.4, 2.5, 0.2), Vector.point(0.0, 0.0, 0.0), Vector.vector(0.0, 0.0, 1.0)))
+    nws, cams = [nw, twin] * 32, [cam, cam2] * 32
+    if "want" not in _wide:   # (computed under the first path, shared: the other path must give these bits too)
+        _wide["want"] = expected_frame(hip, lib, nws, cams, sp, sh, 5, np.arange(W * H, dtype=np.uint64))
+    want = _wide["want"]
+    assert np.isfinite(want).all() and want.max() > 0.0
+    st = RtcStatsC()
+    got = hip.render_shutter(nws, cams, sp, sh, 5, stats=st)
+    assert np.array_equal(bits(got), bits(want))
+    assert not np.array_equal(bits(got), bits(still))
+    assert np.array_equal(bits(hip.render_shutter(nws, cams, sp, sh, 5)), bits(want))     # without counters: the plain kernel builds
+    T = 2 * 5 + 4 if path == "4" else 1    # trace launches of one run
+    assert st.pixels == W * H and st.rays_primary == 16512 * 16
+    # one chunk: count, three scan levels up and two down, place; per pose (none is empty) a generator and the traces; the resolve
+    assert st.n_launches == 2 + (2 * 3 - 1) + K * (1 + T) + 1, st.n_launches
 
 
 # ---- 4. chunks change no bit; 5. the quantised frame; 6. the counters ----------------------------------------------------------------
