@@ -255,6 +255,55 @@ typedef struct rtc_background {
   int32_t projection;  /* RTC_BG_* */
 } rtc_background;
 
+/* Normal perturbation (the book's "next steps"; not in the reference, whose surfaces are as smooth as their geometry): bump records for
+ * rtc_scene_create_ext4 / rtc_multi_create_ext4.  A record belongs to a material; at most one record per material.  A hit on a
+ * primitive whose material has a record is shaded with a perturbed normal ns in place of the geometric normal.  The inputs are
+ *   X, the hit point ray.position(t);  n, the unit world normal of Shape::normal BEFORE the inside flip;  m, the primitive's
+ *   material_inv;  a = amplitude, f = frequency.
+ * Every step is one f64 operation in the order written (csrc/bump_normal.h, one function for device and host, -ffp-contract=off).
+ *   1. q = rows 0..2 of m applied to (X, 1.0), each row as m[0]*x + m[1]*y + m[2]*z + m[3]*1.0 left to right (as for a pattern's
+ *      point); s = q * f componentwise.
+ *   2. d by kind:
+ *        RTC_BUMP_SIMPLEX: d = (simplex(sx,sy,sz), simplex(sx,sy,sz+1.0), simplex(sx,sy,sz+2.0)): the offsets of a point jitter.
+ *        RTC_BUMP_FRACTAL: the same with fractal(.., octaves).
+ *        RTC_BUMP_RIPPLE:  rings about the material-space y axis with a triangle wave as the slope (no libm function enters):
+ *          r = sqrt(sx*sx + sz*sz);  r == 0.0: d = (0, 0, 0);  otherwise g = 2.0 * (r - floor(r)),
+ *          w = (g < 1.0) ? 1.0 - 2.0*g : 2.0*g - 3.0,  d = ((sx / r) * w, 0.0, (sz / r) * w).
+ *   3. To world space the way a gradient transforms, by the transpose of the 3x3:
+ *        gx = (m[0]*dx + m[4]*dy) + m[8]*dz;  gy = (m[1]*dx + m[5]*dy) + m[9]*dz;  gz = (m[2]*dx + m[6]*dy) + m[10]*dz.
+ *   4. v = n + a * g componentwise.  vx == nx && vy == ny && vz == nz: ns = n, with its bits and no renormalisation (amplitude 0 is
+ *      exactly the scene without the record).  Otherwise mag = sqrt(vx*vx + vy*vy + vz*vz), ns = v / mag.
+ *   5. Where prepare_state flips the geometric normal (n . eye < 0), ns is negated too: the bumps are one field on the surface, seen
+ *      from either side.
+ *   6. over_point and under_point keep using the flipped GEOMETRIC normal: their bits, the shadow rays' origins and the pattern colour
+ *      do not move.
+ *   7. The state's normal is ns, and reflect = direction - ns * (2 * direction.dot(ns)) by the usual expression.  Everything that reads
+ *      the state's normal reads ns: the Phong terms, the light-behind-the-surface test, schlick, the blend of a glass mirror, and the
+ *      reflected and refracted rays.  Both device paths give the same bits.
+ * A scene without a record is exactly today's scene: the same kernels, the same builds, the same kernel arguments.
+ * Which kernels: on the one-kernel path a bumped scene takes the NP build of the general kernel that reads the program from memory
+ * (feature level 3) with the scene's own area / uv / spot / background flags, a row of RTC_NP_BUILDS (csrc/rtc_device.hpp); there is no
+ * LEAN, 3-wave or kernel-argument build for it.  On the wavefront path wf_shade's NP build (COUNT x UV) shades every level; wf_ts,
+ * wf_gather and wf_background run as they do without.  rtc_scene_kernel_info describes the scene as it would run without its records;
+ * rtc_scene_bump_info says what they replace.
+ * Limits: RTC_ERR_INVALID for a material index out of range, two records on one material, an unknown kind, an amplitude that is not
+ * finite, a frequency that is not finite or <= 0, FRACTAL with octaves == 0 or above RTC_BUMP_MAX_OCTAVES, and n_bumps > 0 with NULL
+ * bumps; checked before anything else, a device included.  (A pattern node's octaves have no limit beyond their 32 bits; a record's are
+ * capped because every hit pays three noise evaluations per octave, and octave 54 and later add less than one ulp of the sum.)
+ * Not covered: a shading normal that faces away from the eye or below the geometric surface is not clamped, so a reflected ray may
+ * re-enter its own surface; height maps taken from patterns or images (they need filtered texture lookups first); a transform of the
+ * record's own; distance-dependent amplitude. */
+enum { RTC_BUMP_SIMPLEX = 0, RTC_BUMP_FRACTAL = 1, RTC_BUMP_RIPPLE = 2 };
+#define RTC_BUMP_MAX_OCTAVES 64
+typedef struct rtc_bump {
+  uint32_t material;   /* index into desc->materials; at most one record per material */
+  int32_t  kind;       /* RTC_BUMP_* */
+  uint32_t octaves;    /* FRACTAL only */
+  uint32_t _pad;
+  double amplitude;    /* a */
+  double frequency;    /* f */
+} rtc_bump;
+
 /* The sampled camera (not in the reference, whose Camera::ray_at_pixel sends one ray through each pixel centre from a pinhole): n x n
  * samples per pixel (anti-aliasing, box filter) and an optional thin lens (depth of field), for the rtc_render_sampled* entry points
  * and rtc_camera_rays.  Pixel i has x = i % hsize, y = i / hsize; sample k of its N = n * n has sx = k % n, sy = k / n.  Every step is
@@ -482,6 +531,30 @@ typedef struct rtc_background_info {
   int32_t _pad;
 } rtc_background_info;
 int rtc_scene_background_info(const rtc_scene*, rtc_background_info* out);
+/* Same, with n_bumps bump records (rtc_bump above).  n_bumps == 0 is exactly rtc_scene_create_ext3 (same kernels, same bits).  The
+ * records' own numbers are checked before anything else, a device included.  Every render entry point takes the result. */
+int rtc_scene_create_ext4(const rtc_scene_desc* desc, const rtc_scene_ext* ext, const rtc_light_cone* cones, uint32_t n_cones, const rtc_background* bg,
+                          const rtc_bump* bumps, uint32_t n_bumps, int device, rtc_scene** out);
+/* Steps 1-4 of the rule alone: out = the shading normal of a hit at `point` whose unit normal is `normal`, on a primitive whose
+ * material_inv is the row-major 4x4 `material_inv`; bump->material is not read.  Host-only: no device needed (like rtc_spot_factor).
+ * RTC_ERR_INVALID for NULL arguments and for a record rtc_scene_create_ext4 would refuse. */
+int rtc_bump_normal(const rtc_bump* bump, const double material_inv[16], const double point[3], const double normal[3], double out[3]);
+/* The same steps on the device for n items (prims: n primitive indices; points, normals, out: n x {x, y, z}; all host): the record and
+ * the matrix come from the scene's tables by primitive index, and a primitive whose material has no record gets its normal back -- to
+ * a bump what rtc_background_colors is to the background.  RTC_ERR_INVALID for a primitive index out of range. */
+int rtc_bump_normals(rtc_scene*, const int32_t* prims, const double* points, const double* normals, uint64_t n, double* out);
+/* Test hook, read-only: what a launch of this scene takes for its bump records.  has_bump == 0: the builds are -1.  trace_build: path 1,
+ * the row of RTC_NP_BUILDS (csrc/rtc_device.hpp) whose NP instantiation of rtc_trace_kernel replaces the build rtc_scene_kernel_info
+ * (or rtc_scene_background_info) reports, with that row's flags; wf_shade_build: path 4, RTC_WF_NP_*, for every level. */
+enum { RTC_WF_NP_PLAIN = 0, RTC_WF_NP_UV = 1 };
+typedef struct rtc_bump_info {
+  int32_t has_bump;
+  uint32_t n_bumps;
+  int32_t trace_build;          /* path 1: row of RTC_NP_BUILDS (feature level 3, program read from memory) */
+  int32_t trace_area, trace_uv, trace_spot, trace_bg;  /* ... and its flags */
+  int32_t wf_shade_build;       /* path 4: RTC_WF_NP_PLAIN or RTC_WF_NP_UV (scenes with a UV node); each has its counting form */
+} rtc_bump_info;
+int rtc_scene_bump_info(const rtc_scene*, rtc_bump_info* out);
 /* The cone factor f alone, for a light (or sample) at light_pos and a shading point `point`; `cone->light` is not read.  Host-only: no
  * device needed (like rtc_ppm).  RTC_ERR_INVALID for NULL arguments and for a cone rtc_scene_create_ext2 would refuse. */
 int rtc_spot_factor(const rtc_light_cone* cone, const double light_pos[3], const double point[3], double* f);
@@ -546,6 +619,8 @@ int rtc_multi_create_ext(const rtc_scene_desc* desc, const rtc_scene_ext* ext, c
 int rtc_multi_create_ext2(const rtc_scene_desc* desc, const rtc_scene_ext* ext, const rtc_light_cone* cones, uint32_t n_cones, const int* devices, int n_devices,
                           rtc_multi** out);
 /* Same with the background of rtc_scene_create_ext3. */
+int rtc_multi_create_ext4(const rtc_scene_desc* desc, const rtc_scene_ext* ext, const rtc_light_cone* cones, uint32_t n_cones, const rtc_background* bg,
+                          const rtc_bump* bumps, uint32_t n_bumps, const int* devices, int n_devices, rtc_multi** out);  /* with the bump records of rtc_scene_create_ext4 */
 int rtc_multi_create_ext3(const rtc_scene_desc* desc, const rtc_scene_ext* ext, const rtc_light_cone* cones, uint32_t n_cones, const rtc_background* bg, const int* devices,
                           int n_devices, rtc_multi** out);
 void rtc_multi_destroy(rtc_multi*);

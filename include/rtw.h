@@ -91,6 +91,12 @@ rtw_element* rtw_composite(const double transform[16], const rtw_material* mater
 /* ObjParser::new(path).parse_obj(transform, material) (src/obj.rs:186-258).  n_ignored may be NULL. */
 rtw_element* rtw_parse_obj(const char* path, const double transform[16], const rtw_material* material,
                            uint64_t* n_ignored, uint64_t* n_triangles);
+/* Normal perturbation (include/rtc.h rtc_bump; not in the reference): every primitive of the element, a shape or a whole group, gets
+ * the bump record {kind (RTC_BUMP_*), octaves (fractal only), amplitude, frequency} on its material; a second call replaces the first.
+ * A group built with a material afterwards replaces its children's materials, bumps included, as ever.  Two shapes that share a
+ * material but not the bump flatten to two material rows.  Fails for numbers rtc_scene_create_ext4 would refuse.  Product library only;
+ * rendering such a world needs rtc_scene_create_ext4. */
+int rtw_element_set_bump(rtw_element*, int32_t kind, uint32_t octaves, double amplitude, double frequency);
 void rtw_element_release(rtw_element*);
 
 rtw_world* rtw_world_create(void);

@@ -13,7 +13,7 @@ from typing import Dict, Optional, Sequence
 
 import numpy as np
 
-from .scene import (BACKGROUND_PROJECTIONS, FUEL, GEOMETRY, GROUP_KINDS, JITTER_KINDS, MIXTURE_KINDS, Adaptive, AreaLight, Camera, Cone, Element, FILTER_KINDS, Filter, Material, Pattern, SHUTTER_MAX_POSES, Sampling, Shutter, World)
+from .scene import (BACKGROUND_PROJECTIONS, BUMP_KINDS, FUEL, GEOMETRY, GROUP_KINDS, JITTER_KINDS, MIXTURE_KINDS, Adaptive, AreaLight, Camera, Cone, Element, FILTER_KINDS, Filter, Material, Pattern, SHUTTER_MAX_POSES, Sampling, Shutter, World)
 from .texture import UV_KINDS, UV_MAPS, Texture
 
 HIT_DTYPE = np.dtype([("t", "<f8"), ("prim", "<i4"), ("push_idx", "<i4")])
@@ -149,6 +149,11 @@ class Backend:
         if self.has_background:
             lib.rtw_world_set_background.restype = i
             lib.rtw_world_set_background.argtypes = [vp, vp, C.c_int32]
+        # bumps (normal perturbation): the same
+        self.has_bump = hasattr(lib, "rtw_element_set_bump")
+        if self.has_bump:
+            lib.rtw_element_set_bump.restype = i
+            lib.rtw_element_set_bump.argtypes = [vp, C.c_int32, C.c_uint32, d, d]
         # texture-mapped patterns: the same (the oracle has none)
         self.has_texture_map = hasattr(lib, "rtw_pattern_uv")
         if self.has_texture_map:
@@ -218,24 +223,38 @@ class Backend:
         return _MaterialC(m.ambient, m.diffuse, m.specular, m.shininess, m.reflective, m.transparency, m.refractive_index,
                           self._pattern(m.pattern, cache, owned))
 
+    def _bump(self, h: int, m: Optional[Material]) -> int:
+        """The material's bump, if it has one, on every primitive of element `h` (include/rtw.h rtw_element_set_bump)."""
+        b = getattr(m, "bump", None)
+        if b is None:
+            return h
+        if not self.has_bump:
+            self.lib.rtw_element_release(h)
+            raise RtwError("a bump needs librtc_amd.so (backend %r has no rtw_element_set_bump)" % self.name)
+        if self.lib.rtw_element_set_bump(h, BUMP_KINDS.index(b.kind), int(b.octaves), float(b.amplitude), float(b.frequency)) != 0:
+            msg = self._err()
+            self.lib.rtw_element_release(h)
+            raise RtwError("set_bump failed: %s" % msg)
+        return h
+
     def _element(self, e: Element, cache, owned) -> int:
         lib = self.lib
         if e.tag == "shape":
             mat = self._material(e.args.material, cache, owned)
             params = (C.c_double * max(1, len(e.params)))(*e.params)
             h = lib.rtw_shape(GEOMETRY[e.geometry], _d16(e.args.transform), C.byref(mat), 1 if e.args.casts_shadow else 0, params, len(e.params))
-            return self._check_ptr(h, "shape")
+            return self._bump(self._check_ptr(h, "shape"), e.args.material)
         if e.tag == "composite":
             kids = [self._element(c, cache, owned) for c in e.children]
             arr = (C.c_void_p * max(1, len(kids)))(*kids)
             mat = self._material(e.material, cache, owned) if e.material is not None else None
             h = lib.rtw_composite(_d16(e.transform), C.byref(mat) if mat is not None else None, GROUP_KINDS[e.kind], arr, len(kids))
-            return self._check_ptr(h, "composite")
+            return self._bump(self._check_ptr(h, "composite"), e.material)
         if e.tag == "obj":
             mat = self._material(e.material, cache, owned)
             ign, tris = C.c_uint64(0), C.c_uint64(0)
             h = lib.rtw_parse_obj(e.path.encode(), _d16(e.transform), C.byref(mat), C.byref(ign), C.byref(tris))
-            return self._check_ptr(h, "parse_obj(%s)" % e.path)
+            return self._bump(self._check_ptr(h, "parse_obj(%s)" % e.path), e.material)
         raise RtwError("unknown element tag %r" % (e.tag,))
 
     def build_world(self, world: World) -> NativeWorld:

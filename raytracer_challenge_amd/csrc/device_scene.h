@@ -224,6 +224,22 @@ struct DSceneBg : DScene {
   DBackground bg;
 };
 
+// Normal perturbation (include/rtc.h rtc_bump): a per-material index into the records, -1 for a material without one.  It travels the
+// way the background does: only the NP builds of rtc_trace_kernel and wf_shade take a DSceneNp (its `bg` is read by the builds that are
+// BG too, and is {0, 0} otherwise); no other kernel's arguments move.
+struct DBump {  // 24 bytes
+  int32_t kind;      // RTC_BUMP_*
+  uint32_t octaves;  // RTC_BUMP_FRACTAL
+  double amplitude, frequency;
+};
+struct DBumpTable {
+  const int32_t* mat_bump;  // x n_materials
+  const DBump* recs;
+};
+struct DSceneNp : DSceneBg {
+  DBumpTable bump;
+};
+
 // Which pixels a launch covers.
 struct DPixelMap {
   uint64_t n;                 // pixels in this launch

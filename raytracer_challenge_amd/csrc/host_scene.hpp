@@ -184,6 +184,15 @@ struct Pat {  // src/material.rs:60-65
 struct Mat {  // src/material.rs:19-43
   PatRef pattern;
   double ambient = 0.1, diffuse = 0.9, specular = 0.9, shininess = 200.0, reflective = 0.0, transparency = 0.0, refractive_index = 1.0;
+  // normal perturbation (include/rtc.h rtc_bump; not in the reference): part of the material, so a group's material replaces it too
+  int32_t bump_kind = -1;  // RTC_BUMP_*; -1: none
+  uint32_t bump_octaves = 0;
+  double bump_amplitude = 0.0, bump_frequency = 0.0;
+  bool same_bump(const Mat& o) const {
+    if (bump_kind != o.bump_kind) return false;
+    return bump_kind < 0 || (bump_octaves == o.bump_octaves && std::memcmp(&bump_amplitude, &o.bump_amplitude, sizeof(double)) == 0 &&
+                             std::memcmp(&bump_frequency, &o.bump_frequency, sizeof(double)) == 0);
+  }
 };
 
 struct Geo {  // src/shape.rs:466-498
@@ -283,6 +292,19 @@ struct Elem {
     e->kids = std::move(kids);
     e->push_down(transform, ginv, ginv.transposed(), m);
     return e;
+  }
+  // rtw_element_set_bump: every primitive below gets the record on its material
+  void set_bump(int32_t kind, uint32_t octaves, double amplitude, double frequency) {
+    if (group_kind != RTC_NODE_PRIM) {
+      for (auto& k : kids) k->set_bump(kind, octaves, amplitude, frequency);
+      return;
+    }
+    material.bump_kind = kind; material.bump_octaves = octaves; material.bump_amplitude = amplitude; material.bump_frequency = frequency;
+  }
+  bool has_bump() const {
+    if (group_kind == RTC_NODE_PRIM) return material.bump_kind >= 0;
+    for (auto& k : kids) if (k->has_bump()) return true;
+    return false;
   }
   uint64_t count_prims() const {
     if (group_kind == RTC_NODE_PRIM) return 1;
@@ -479,6 +501,7 @@ struct Flat {
   std::vector<rtc_light> lights;
   std::vector<rtc_uv_pattern> uv_pats;  // texture-mapped patterns: rtc_scene_create_ext's records and textures (rgb: the Tex's own)
   std::vector<rtc_texture> textures;
+  std::vector<rtc_bump> bumps;  // bump records: rtc_scene_create_ext4's, one per material row that has one
   std::string error;
 
   rtc_scene_desc desc() const {
@@ -545,7 +568,8 @@ class Flattener {
     f_.textures.push_back(r);
     return tex_ids_[t.get()] = (int32_t)f_.textures.size() - 1;
   }
-  // materials are de-duplicated on (pattern node, 7 scalars): a whole OBJ group shares one
+  // materials are de-duplicated on (pattern node, 7 scalars, bump): a whole OBJ group shares one; two shapes that share a material
+  // but not the bump get two rows, each with its own record
   std::map<std::vector<uint64_t>, int32_t> mat_ids_;
 
   int32_t pattern(const PatRef& p) {
@@ -578,6 +602,7 @@ class Flattener {
   const Pat* last_mat_pat_ = nullptr;
   double last_mat_s_[7] = {0, 0, 0, 0, 0, 0, 0};
   int32_t last_mat_id_ = -1;
+  Mat last_mat_bump_;  // (its bump fields alone)
   static const PatRef& white_pat() {
     static const PatRef white = [] { auto p = std::make_shared<Pat>(); return PatRef(p); }();
     return white;
@@ -586,9 +611,10 @@ class Flattener {
     const PatRef& white = white_pat();
     const double s[7] = {m.ambient, m.diffuse, m.specular, m.shininess, m.reflective, m.transparency, m.refractive_index};
     const Pat* pp = (m.pattern ? m.pattern : white).get();
-    if (last_mat_id_ >= 0 && pp == last_mat_pat_ && std::memcmp(s, last_mat_s_, sizeof(s)) == 0) return last_mat_id_;
+    if (last_mat_id_ >= 0 && pp == last_mat_pat_ && std::memcmp(s, last_mat_s_, sizeof(s)) == 0 && m.same_bump(last_mat_bump_)) return last_mat_id_;
     const int32_t id = material_slow(m, s);
     last_mat_pat_ = pp; std::memcpy(last_mat_s_, s, sizeof(s)); last_mat_id_ = id;
+    last_mat_bump_.bump_kind = m.bump_kind; last_mat_bump_.bump_octaves = m.bump_octaves; last_mat_bump_.bump_amplitude = m.bump_amplitude; last_mat_bump_.bump_frequency = m.bump_frequency;
     return id;
   }
   int32_t material_slow(const Mat& m, const double s[7]) {
@@ -597,10 +623,21 @@ class Flattener {
     std::vector<uint64_t> key(8);
     key[0] = (uint64_t)pid;
     std::memcpy(&key[1], s, 7 * sizeof(double));
+    if (m.bump_kind >= 0) {  // (a material without a bump keeps the key it always had)
+      key.resize(11);
+      key[8] = ((uint64_t)(uint32_t)m.bump_kind << 32) | m.bump_octaves;
+      std::memcpy(&key[9], &m.bump_amplitude, sizeof(double));
+      std::memcpy(&key[10], &m.bump_frequency, sizeof(double));
+    }
     auto it = mat_ids_.find(key);
     if (it != mat_ids_.end()) return it->second;
     rtc_material r{s[0], s[1], s[2], s[3], s[4], s[5], s[6], pid, 0};
     f_.materials.push_back(r);
+    if (m.bump_kind >= 0) {
+      rtc_bump b{};
+      b.material = (uint32_t)f_.materials.size() - 1; b.kind = m.bump_kind; b.octaves = m.bump_octaves; b.amplitude = m.bump_amplitude; b.frequency = m.bump_frequency;
+      f_.bumps.push_back(b);
+    }
     return mat_ids_[key] = (int32_t)f_.materials.size() - 1;
   }
   int32_t xform(const Elem& e) {
@@ -665,7 +702,7 @@ class Flattener {
   static bool same_prim_frame(const Elem& a, const Elem& b) {
     const double sa[7] = {a.material.ambient, a.material.diffuse, a.material.specular, a.material.shininess, a.material.reflective, a.material.transparency, a.material.refractive_index};
     const double sb[7] = {b.material.ambient, b.material.diffuse, b.material.specular, b.material.shininess, b.material.reflective, b.material.transparency, b.material.refractive_index};
-    return a.material.pattern.get() == b.material.pattern.get() && std::memcmp(sa, sb, sizeof(sa)) == 0 && std::memcmp(a.inv.a, b.inv.a, sizeof(a.inv.a)) == 0 &&
+    return a.material.pattern.get() == b.material.pattern.get() && a.material.same_bump(b.material) && std::memcmp(sa, sb, sizeof(sa)) == 0 && std::memcmp(a.inv.a, b.inv.a, sizeof(a.inv.a)) == 0 &&
            std::memcmp(a.mat_inv.a, b.mat_inv.a, sizeof(a.mat_inv.a)) == 0 && std::memcmp(a.inv_tsp.a, b.inv_tsp.a, sizeof(a.inv_tsp.a)) == 0;
   }
   static bool uniform_triangles(const Elem& g) {

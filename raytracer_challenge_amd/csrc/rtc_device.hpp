@@ -1007,98 +1007,10 @@ __device__ TRAVERSE_INLINE void traverse(const DScene& S, const Ray& r, Trav& T,
   }
 }
 
-// ---- noise (src/noise.rs) ------------------------------------------------------------------------------
-__device__ const unsigned char PERM[256] = {
-    151, 160, 137, 91,  90,  15,  131, 13,  201, 95,  96,  53,  194, 233, 7,   225, 140, 36,  103, 30,  69,  142, 8,   99,  37,  240,
-    21,  10,  23,  190, 6,   148, 247, 120, 234, 75,  0,   26,  197, 62,  94,  252, 219, 203, 117, 35,  11,  32,  57,  177, 33,  88,
-    237, 149, 56,  87,  174, 20,  125, 136, 171, 168, 68,  175, 74,  165, 71,  134, 139, 48,  27,  166, 77,  146, 158, 231, 83,  111,
-    229, 122, 60,  211, 133, 230, 220, 105, 92,  41,  55,  46,  245, 40,  244, 102, 143, 54,  65,  25,  63,  161, 1,   216, 80,  73,
-    209, 76,  132, 187, 208, 89,  18,  169, 200, 196, 135, 130, 116, 188, 159, 86,  164, 100, 109, 198, 173, 186, 3,   64,  52,  217,
-    226, 250, 124, 123, 5,   202, 38,  147, 118, 126, 255, 82,  85,  212, 207, 206, 59,  227, 47,  16,  58,  17,  182, 189, 28,  42,
-    223, 183, 170, 213, 119, 248, 152, 2,   44,  154, 163, 70,  221, 153, 101, 155, 167, 43,  172, 9,   129, 22,  39,  253, 19,  98,
-    108, 110, 79,  113, 224, 232, 178, 185, 112, 104, 218, 246, 97,  228, 251, 34,  242, 193, 238, 210, 144, 12,  191, 179, 162, 241,
-    81,  51,  145, 235, 249, 14,  239, 107, 49,  192, 214, 31,  181, 199, 106, 157, 184, 84,  204, 176, 115, 121, 50,  45,  127, 4,
-    150, 254, 138, 236, 205, 93,  222, 114, 67,  29,  24,  72,  243, 141, 128, 195, 78,  66,  215, 61,  156, 180};
-
-__device__ __forceinline__ unsigned nhash(unsigned i) { return PERM[i & 255u]; }  // :90-92, table period 256
-
-__device__ __forceinline__ int as_i32(double x) {  // Rust `as i32`: saturating, NaN -> 0
-  if (x != x) return 0;
-  if (x >= 2147483647.0) return 2147483647;
-  if (x <= -2147483648.0) return (int)0x80000000;
-  return (int)x;
-}
-__device__ __forceinline__ int wadd(int a, int b) { return (int)((unsigned)a + (unsigned)b); }
-__device__ __forceinline__ int fast_floor(double x) { return x > 0.0 ? as_i32(x) : (int)((unsigned)as_i32(x) - 1u); }  // :116-122
-__device__ __forceinline__ unsigned modulus256(int x) { int a = x % 256; return a < 0 ? (unsigned)(a + 256) : (unsigned)a; }  // :124-131
-
-__device__ __forceinline__ double ngrad(unsigned h, double x, double y, double z) {  // :94-114
-  switch (h & 0xF) {
-    case 0x0: return x + y;
-    case 0x1: return -x + y;
-    case 0x2: return x - y;
-    case 0x3: return -x - y;
-    case 0x4: return x + z;
-    case 0x5: return -x + z;
-    case 0x6: return x - z;
-    case 0x7: return -x - z;
-    case 0x8: return y + z;
-    case 0x9: return -y + z;
-    case 0xA: return y - z;
-    case 0xB: return -y - z;
-    case 0xC: return y + x;
-    case 0xD: return -y + z;
-    case 0xE: return y - x;
-    default: return -y - z;
-  }
-}
-
-__device__ __noinline__ double simplex3(double x, double y, double z) {  // :134-219
-  const double F3 = 1.0 / 3.0, G3 = 1.0 / 6.0;
-  double s = (x + y + z) * F3;
-  int i = fast_floor(x + s), j = fast_floor(y + s), k = fast_floor(z + s);
-  double t = (double)wadd(wadd(i, j), k) * G3;
-  double x0 = x - ((double)i - t), y0 = y - ((double)j - t), z0 = z - ((double)k - t);
-  int i1, j1, k1, i2, j2, k2;
-  if (x0 >= y0) {
-    if (y0 >= z0) { i1 = 1; j1 = 0; k1 = 0; i2 = 1; j2 = 1; k2 = 0; }
-    else if (x0 >= z0) { i1 = 1; j1 = 0; k1 = 0; i2 = 1; j2 = 0; k2 = 1; }
-    else { i1 = 0; j1 = 0; k1 = 1; i2 = 1; j2 = 0; k2 = 1; }
-  } else {
-    if (y0 < z0) { i1 = 0; j1 = 0; k1 = 1; i2 = 0; j2 = 1; k2 = 1; }
-    else if (x0 < z0) { i1 = 0; j1 = 1; k1 = 0; i2 = 0; j2 = 1; k2 = 1; }
-    else { i1 = 0; j1 = 1; k1 = 0; i2 = 1; j2 = 1; k2 = 0; }
-  }
-  double x1 = x0 - (double)i1 + G3, y1 = y0 - (double)j1 + G3, z1 = z0 - (double)k1 + G3;
-  double x2 = x0 - (double)i2 + 2.0 * G3, y2 = y0 - (double)j2 + 2.0 * G3, z2 = z0 - (double)k2 + 2.0 * G3;
-  double x3 = x0 - 1.0 + 3.0 * G3, y3 = y0 - 1.0 + 3.0 * G3, z3 = z0 - 1.0 + 3.0 * G3;
-  unsigned ii = modulus256(i), jj = modulus256(j), kk = modulus256(k);
-  unsigned gi0 = nhash(ii + nhash(jj + nhash(kk)));
-  unsigned gi1 = nhash(ii + i1 + nhash(jj + j1 + nhash(kk + k1)));
-  unsigned gi2 = nhash(ii + i2 + nhash(jj + j2 + nhash(kk + k2)));
-  unsigned gi3 = nhash(ii + 1 + nhash(jj + 1 + nhash(kk + 1)));
-  double n0, n1, n2, n3;
-  double t0 = 0.6 - x0 * x0 - y0 * y0 - z0 * z0;
-  if (t0 < 0.0) n0 = 0.0; else { t0 *= t0; n0 = t0 * t0 * ngrad(gi0, x0, y0, z0); }
-  double t1 = 0.6 - x1 * x1 - y1 * y1 - z1 * z1;
-  if (t1 < 0.0) n1 = 0.0; else { t1 *= t1; n1 = t1 * t1 * ngrad(gi1, x1, y1, z1); }
-  double t2 = 0.6 - x2 * x2 - y2 * y2 - z2 * z2;
-  if (t2 < 0.0) n2 = 0.0; else { t2 *= t2; n2 = t2 * t2 * ngrad(gi2, x2, y2, z2); }
-  double t3 = 0.6 - x3 * x3 - y3 * y3 - z3 * z3;
-  if (t3 < 0.0) n3 = 0.0; else { t3 *= t3; n3 = t3 * t3 * ngrad(gi3, x3, y3, z3); }
-  return 32.0 * (n0 + n1 + n2 + n3);
-}
-
-__device__ __forceinline__ double fractal3(double x, double y, double z, unsigned octaves) {  // :221-237
-  double output = 0.0, denom = 0.0, frequency = 1.0, amplitude = 1.0;
-  for (unsigned o = 0; o < octaves; o++) {
-    output += amplitude * simplex3(x * frequency, y * frequency, z * frequency);
-    denom += amplitude;
-    frequency *= 2.0;
-    amplitude *= 0.5;
-  }
-  return output / denom;
-}
+// ---- noise (src/noise.rs): simplex3 / fractal3 live in noise3.h, one copy for the device and the host, and the bump rule that
+// uses them in bump_normal.h.  Included HERE, inside this file's unnamed namespace, where the noise always stood: the device
+// functions keep their linkage names (the headers they include themselves are all included above).
+#include "bump_normal.h"
 
 __device__ __forceinline__ void jitter_3d(const DPat& p, double x, double y, double z, double& ox, double& oy, double& oz) {  // :31-52
   double nx, ny, nz;
@@ -1322,7 +1234,10 @@ __device__ __forceinline__ void local_normal(const DScene& S, const DPrim& P, do
   }
 }
 
-__device__ __forceinline__ void prepare_state(const DScene& S, const DPrim& P, const Ray& r, double t, double u, double v, State& st) {
+// NP: the scene has bump records (include/rtc.h rtc_bump; `bt` is its table): State.n and the reflect vector are made from the shading
+// normal of bump_normal.h, over_point and under_point from the geometric normal as ever.  Only the NP builds compile any of it.
+template <bool NP = false>
+__device__ __forceinline__ void prepare_state(const DScene& S, const DPrim& P, const Ray& r, double t, double u, double v, State& st, const DBumpTable* bt = nullptr) {
   // point = ray.position(t); eye = -direction
   double qx = r.ox + r.dx * t, qy = r.oy + r.dy * t, qz = r.oz + r.dz * t;
   st.ex = -r.dx; st.ey = -r.dy; st.ez = -r.dz;
@@ -1348,10 +1263,27 @@ __device__ __forceinline__ void prepare_state(const DScene& S, const DPrim& P, c
     double mag = sqrt(wx * wx + wy * wy + wz * wz);
     nx = wx / mag; ny = wy / mag; nz = wz / mag;
   }
-  if (nx * st.ex + ny * st.ey + nz * st.ez < 0.0) { nx = -nx; ny = -ny; nz = -nz; }
+  double bn[3] = {0.0, 0.0, 0.0};  // (NP) the shading normal, before the flip
+  bool bumped = false;
+  if constexpr (NP) {
+    const int32_t b = bt->mat_bump[P.mat];
+    if (b >= 0) {
+      const DBump B = bt->recs[b];
+      const double gn[3] = {nx, ny, nz};
+      rtc_bump_normal_at(B.kind, B.octaves, B.amplitude, B.frequency, S.xf_matinv + 16 * P.xform, qx, qy, qz, gn, bn);
+      bumped = true;
+    }
+  }
+  if (nx * st.ex + ny * st.ey + nz * st.ez < 0.0) {
+    nx = -nx; ny = -ny; nz = -nz;
+    if constexpr (NP) { bn[0] = -bn[0]; bn[1] = -bn[1]; bn[2] = -bn[2]; }
+  }
   st.nx = nx; st.ny = ny; st.nz = nz;
   st.px = qx + nx * EPS; st.py = qy + ny * EPS; st.pz = qz + nz * EPS;
   st.ux = qx - nx * EPS; st.uy = qy - ny * EPS; st.uz = qz - nz * EPS;
+  if constexpr (NP) {
+    if (bumped) { nx = bn[0]; ny = bn[1]; nz = bn[2]; st.nx = nx; st.ny = ny; st.nz = nz; }
+  }
   // reflect = direction - normal * (2 * direction.dot(normal))
   double dn = 2.0 * (r.dx * nx + r.dy * ny + r.dz * nz);
   st.rx = r.dx - nx * dn; st.ry = r.dy - ny * dn; st.rz = r.dz - nz * dn;
@@ -1742,8 +1674,10 @@ __device__ __forceinline__ void shade_lights_area(const DScene& S, double px, do
 // BG: scenes with a background (include/rtc.h rtc_background): a ray that hits nothing adds weight * the background's colour where a
 // hit's surface colour would have been added.  Only these builds take a DSceneBg; they are instantiated by rtc_background.hip, not by
 // a row of RTC_VARIANTS.  Scenes without a background never run them.
-template <bool COUNT, int FEAT, bool KOPS, int WAVES = 0, bool LEAN = false, bool AREA = false, bool UV = false, bool SPOT = false, bool BG = false>
-__global__ void __launch_bounds__(RTC_BLOCK, WAVES ? WAVES : ((FEAT >= 2 && RTC_WAVES_PER_SIMD < 2) ? 2 : RTC_WAVES_PER_SIMD)) rtc_trace_kernel(std::conditional_t<BG, DSceneBg, DScene> S, DCamera cam, DPixelMap pm, int fuel0, double* __restrict__ rgb, double* __restrict__ hit_t,
+// NP: scenes with a bump record (include/rtc.h rtc_bump): prepare_state's NP build.  Only these builds take a DSceneNp; they are
+// instantiated by rtc_bump.hip, one object per row of RTC_NP_BUILDS.  Scenes without a bump record never run them.
+template <bool COUNT, int FEAT, bool KOPS, int WAVES = 0, bool LEAN = false, bool AREA = false, bool UV = false, bool SPOT = false, bool BG = false, bool NP = false>
+__global__ void __launch_bounds__(RTC_BLOCK, WAVES ? WAVES : ((FEAT >= 2 && RTC_WAVES_PER_SIMD < 2) ? 2 : RTC_WAVES_PER_SIMD)) rtc_trace_kernel(std::conditional_t<NP, DSceneNp, std::conditional_t<BG, DSceneBg, DScene>> S, DCamera cam, DPixelMap pm, int fuel0, double* __restrict__ rgb, double* __restrict__ hit_t,
                                                         int* __restrict__ hit_prim, int* __restrict__ hit_k, DStats* __restrict__ stats) {
   RTC_LDS_STACK(lds_stack);
   int* stack = lds_stack + threadIdx.x;
@@ -1796,7 +1730,8 @@ __global__ void __launch_bounds__(RTC_BLOCK, WAVES ? WAVES : ((FEAT >= 2 && RTC_
         State st;
         double hu, hv;
         hit_uv(S, P, ray, hu, hv);
-        prepare_state(S, P, ray, T.best_t, hu, hv, st);
+        if constexpr (NP) prepare_state<true>(S, P, ray, T.best_t, hu, hv, st, &S.bump);
+        else prepare_state(S, P, ray, T.best_t, hu, hv, st);
 
         // n1 / n2 / reflectance are only consumed when the surface is transparent (src/world.rs:70-78, :110)
         double n1 = 1.0, n2 = 1.0;
@@ -2265,6 +2200,11 @@ constexpr RtcWfShadeBuild rtc_pick_wf_shade_build(bool count, bool has_uv, bool 
   if (all_plain) return level0 ? RTC_SH_PIPE_LV0 : RTC_SH_PIPE;
   return RTC_SH_PAT;
 }
+// ... of a scene with a bump record (wf_shade's NP builds: PAT = true, no PIPE)
+enum RtcWfShadeNpBuild { RTC_SH_NP = 0, RTC_SH_NP_COUNT = 1, RTC_SH_NP_UV = 2, RTC_SH_NP_COUNT_UV = 3 };
+constexpr RtcWfShadeNpBuild rtc_pick_wf_shade_np_build(bool count, bool has_uv) {
+  return has_uv ? (count ? RTC_SH_NP_COUNT_UV : RTC_SH_NP_UV) : (count ? RTC_SH_NP_COUNT : RTC_SH_NP);
+}
 
 // Launch arguments (host side): what every ray kernel of a frame receives, and what one level of the wavefront path adds.
 struct RtcFrame {
@@ -2312,3 +2252,27 @@ constexpr int RTC_N_BG_BUILDS = (int)(sizeof(RTC_BG_BUILDS) / sizeof(RTC_BG_BUIL
 constexpr int rtc_pick_bg_build(bool area, bool uv, bool spot) { return spot ? (uv ? 5 : 4) : ((uv ? 2 : 0) + (area ? 1 : 0)); }
 template <int B>
 void rtc_launch_trace_bg_build(const RtcFrame& F, const DBackground& bg, unsigned grid, int fuel, double* rgb);  // defined by the object of build B
+
+// Scenes with a bump record (include/rtc.h rtc_bump) on the one-kernel path: rtc_trace_kernel's NP build of the general memory-program
+// kernel (feature level 3, KOPS = false), with the scene's own area / uv / spot flags as in RTC_BG_BUILDS -- rows 0..5 for scenes
+// without a background, rows 6..11 the same with BG.  rtc_bump.hip instantiates them, one object per row (-DRTC_NP_BUILD=<b>), each
+// with its counting form.  No LEAN, 3-wave or kernel-argument build serves a bumped scene.
+constexpr RtcVariant RTC_NP_BUILDS[] = {
+    {3, false, false, false, false},  // 0
+    {3, false, true, false, false},   // 1: an area light
+    {3, false, false, true, false},   // 2: a UV pattern
+    {3, false, true, true, false},    // 3: both
+    {3, false, true, false, true},    // 4: a light cone (always with the `area` code path)
+    {3, false, true, true, true},     // 5: a light cone and a UV pattern
+    {3, false, false, false, false},  // 6: row 0 with a background
+    {3, false, true, false, false},   // 7: row 1 with a background
+    {3, false, false, true, false},   // 8: row 2 with a background
+    {3, false, true, true, false},    // 9: row 3 with a background
+    {3, false, true, false, true},    // 10: row 4 with a background
+    {3, false, true, true, true},     // 11: row 5 with a background
+};
+constexpr int RTC_N_NP_BUILDS = (int)(sizeof(RTC_NP_BUILDS) / sizeof(RTC_NP_BUILDS[0]));
+constexpr bool rtc_np_build_bg(int b) { return b >= RTC_N_NP_BUILDS / 2; }
+constexpr int rtc_pick_np_build(bool area, bool uv, bool spot, bool bg) { return rtc_pick_bg_build(area, uv, spot) + (bg ? RTC_N_NP_BUILDS / 2 : 0); }
+template <int B>
+void rtc_launch_trace_np_build(const RtcFrame& F, const DSceneNp& S, unsigned grid, int fuel, double* rgb);  // defined by the object of build B

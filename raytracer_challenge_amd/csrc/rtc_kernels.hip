@@ -69,8 +69,10 @@ __device__ __forceinline__ unsigned wf_row_scan16(unsigned v) {
 // counters with one lane each, where thread 0 of the other builds walks them.  25 more VGPRs (97 -> 122): the PAT builds, at 127
 // with 672 B of scratch (UV: 896 B), keep the plain loop -- the wave scan alone cost them 16 B more scratch per lane.
 // LV0 (PIPE builds): the launch is level 0's, a compile-time fact there so that no branch surrounds the prefetch.
-template <bool COUNT, bool PAT = true, bool UV = false, bool PIPE = false, bool LV0 = false>
-__global__ void __launch_bounds__(RTC_WF_SHADE_BLOCK, RTC_WF_SHADE_WAVES) wf_shade(DScene S, DCamera cam, DPixelMap pm, DWave W, int level, unsigned n0, int fuel0, DStats* __restrict__ stats) {
+// NP: scenes with a bump record (include/rtc.h rtc_bump): prepare_state's NP build, so rows 3..5 of the shade record and the child rays
+// carry the shading normal.  Four builds (COUNT x UV, PAT = true, no PIPE); only they take a DSceneNp.
+template <bool COUNT, bool PAT = true, bool UV = false, bool PIPE = false, bool LV0 = false, bool NP = false>
+__global__ void __launch_bounds__(RTC_WF_SHADE_BLOCK, RTC_WF_SHADE_WAVES) wf_shade(std::conditional_t<NP, DSceneNp, DScene> S, DCamera cam, DPixelMap pm, DWave W, int level, unsigned n0, int fuel0, DStats* __restrict__ stats) {
   // per class and wave: its count, then its base index in the queue (double-buffered by iteration parity: no barrier needed before
   // the next iteration writes).  Classes keep like with like inside a block's span of the queues, so that most 64-item chunks of the
   // next traversal launch hold one kind of ray: shade records on planes / on other primitives [0..15]; reflected rays off planes
@@ -131,7 +133,8 @@ __global__ void __launch_bounds__(RTC_WF_SHADE_BLOCK, RTC_WF_SHADE_WAVES) wf_sha
       if (PIPE) shading_row = (int)M[7];  // (the other builds read it where they store it: they have no register to spare)
       double hu, hv;
       hit_uv(S, P, ray, hu, hv);
-      prepare_state(S, P, ray, PIPE ? in.t : W.h_t[i], hu, hv, st);
+      if constexpr (NP) prepare_state<true>(S, P, ray, W.h_t[i], hu, hv, st, &S.bump);
+      else prepare_state(S, P, ray, PIPE ? in.t : W.h_t[i], hu, hv, st);
       if (transparency != 0.0 && fuel > 0) { n1 = W.h_n12[i]; n2 = W.h_n12[cap + i]; }  // stored under the same condition
       if constexpr (PAT) {
         if (S.pats[S.mat_pattern[P.mat]].tag != 1) {
@@ -328,12 +331,13 @@ uint64_t rtc_wavefront_work(const DCamera& cam, const DPixelMap& pm) {
 // arrays for W.cap >= the work ids of the launch and fuel + 1 levels; `blocks` / `shade_blocks` = grid sizes of the traversal /
 // shading kernels; `lds` = the scene's rtc_wavefront_lds_bytes (0, the default: tables in memory -- all a caller without LDSC builds can ask for).
 // `bg` (optional): the scene's background: wf_background (rtc_background.hip) runs once per level, behind that level's trace role.
+// `bump` (optional): the scene's bump table: every level is shaded by wf_shade's NP build (COUNT x UV), whatever build the scene takes without.
 #ifndef RTC_EMU
 void rtc_launch_wf_background(const DScene& S, const DCamera& cam, const DPixelMap& pm, const DWave& W, int level, unsigned n0, const DBackground& bg, unsigned blocks,
                               hipStream_t stream);
 #endif
 void rtc_launch_wavefront(const DScene& S, const DCamera& cam, const DPixelMap& pm, int fuel, const DWave& W, double* rgb, double* hit_t, int* hit_prim, int* hit_k,
-                          DStats* stats, bool count, hipStream_t stream, unsigned blocks, unsigned shade_blocks, unsigned lds = 0u, const DBackground* bg = nullptr) {
+                          DStats* stats, bool count, hipStream_t stream, unsigned blocks, unsigned shade_blocks, unsigned lds = 0u, const DBackground* bg = nullptr, const DBumpTable* bump = nullptr) {
   if (pm.n == 0) return;
   const RtcVariantOps& ops = rtc_ops(rtc_variant(S, true));
   const RtcFrame F = {S, cam, pm, hit_t, hit_prim, hit_k, stats, stream, count};
@@ -352,6 +356,20 @@ void rtc_launch_wavefront(const DScene& S, const DCamera& cam, const DPixelMap& 
     ops.launch_wf_ts(F, RtcLevel{W, tl, sl, n0, level, fuel - level, blocks, 0u});
 #ifndef RTC_EMU
     if (bg && level <= fuel) rtc_launch_wf_background(S, cam, pm, W, level, n0, *bg, 4u * std::max(1u, shade_blocks), stream);
+#endif
+#ifndef RTC_EMU
+    if (bump && level <= fuel) {
+      DSceneNp N;
+      static_cast<DScene&>(N) = S;
+      N.bg = DBackground{0, 0};
+      N.bump = *bump;
+      switch (rtc_pick_wf_shade_np_build(count, S.has_uv != 0)) {
+        case RTC_SH_NP_COUNT_UV: hipLaunchKernelGGL((wf_shade<true, true, true, false, false, true>), sgrid, sblock, 0, stream, N, cam, pm, W, level, n0, fuel, stats); break;
+        case RTC_SH_NP_UV: hipLaunchKernelGGL((wf_shade<false, true, true, false, false, true>), sgrid, sblock, 0, stream, N, cam, pm, W, level, n0, fuel, stats); break;
+        case RTC_SH_NP_COUNT: hipLaunchKernelGGL((wf_shade<true, true, false, false, false, true>), sgrid, sblock, 0, stream, N, cam, pm, W, level, n0, fuel, stats); break;
+        case RTC_SH_NP: hipLaunchKernelGGL((wf_shade<false, true, false, false, false, true>), sgrid, sblock, 0, stream, N, cam, pm, W, level, n0, fuel, stats); break;
+      }
+    } else
 #endif
     if (level <= fuel) {
       switch (rtc_scene_shade_build(S, count, level == 0)) {

@@ -22,6 +22,7 @@
 #include "../../include/rtc.h"
 #include "adaptive_contrast.h"
 #include "background_point.h"
+#include "bump_normal.h"
 #include "camera_sampling.h"
 #include "device_scene.h"
 #include "filter_weights.h"
@@ -36,7 +37,12 @@ void rtc_launch_pack_hits(const double* t, const int* prim, const int* k, DHit* 
 void rtc_launch_deinterleave(const double* slab, double* image, unsigned rowlen, unsigned vsize, unsigned n, unsigned max_rows, unsigned band, hipStream_t stream);
 void rtc_launch_deinterleave8(const unsigned char* slab, unsigned char* image, unsigned rowlen, unsigned vsize, unsigned n, unsigned max_rows, unsigned band, hipStream_t stream);
 void rtc_launch_wavefront(const DScene& S, const DCamera& cam, const DPixelMap& pm, int fuel, const DWave& W, double* rgb, double* hit_t, int* hit_prim, int* hit_k,
-                          DStats* stats, bool count, hipStream_t stream, unsigned blocks, unsigned shade_blocks, unsigned lds, const DBackground* bg);
+                          DStats* stats, bool count, hipStream_t stream, unsigned blocks, unsigned shade_blocks, unsigned lds, const DBackground* bg, const DBumpTable* bump);
+void rtc_launch_trace_np(const DScene& S, const DBumpTable& bt, const DBackground* bg, const DCamera& cam, const DPixelMap& pm, int fuel, double* rgb, double* hit_t,
+                         int* hit_prim, int* hit_k, DStats* stats, bool count, hipStream_t stream);
+void rtc_launch_bump_normals(const DScene& S, const DBumpTable& bt, const int32_t* prims, const double* points, const double* normals, unsigned long long n, double* out,
+                             hipStream_t stream);
+int rtc_bump_trace_build(const DScene& S, bool has_bg);
 void rtc_launch_trace_bg(const DScene& S, const DBackground& bg, const DCamera& cam, const DPixelMap& pm, int fuel, double* rgb, double* hit_t, int* hit_prim, int* hit_k,
                          DStats* stats, bool count, hipStream_t stream);
 void rtc_launch_background_colors(const DScene& S, const DBackground& bg, const double* dirs, unsigned long long n, double* rgb, hipStream_t stream);
@@ -93,6 +99,9 @@ struct rtc_scene {
   bool has_bg = false;  // the scene has a background (rtc_scene_create_ext3): its launches take the BG builds (rtc_background.hip)
   DBackground bg{0, 0};
   bool bg_plain = false;  // its root is a Plain colour: no pattern walk
+  bool has_bump = false;  // the scene has bump records (rtc_scene_create_ext4): its launches take the NP builds (rtc_bump.hip, wf_shade's)
+  uint32_t n_bumps = 0;
+  DBumpTable bump{nullptr, nullptr};
   DStats* d_stats = nullptr;
   // scratch output buffers (grown on demand)
   double* d_rgb = nullptr;
@@ -379,7 +388,9 @@ int run(rtc_scene* s, const DCamera& cam, DPixelMap pm, int fuel, double* d_rgb,
     HIP_OK(hipMemsetAsync(s->wave.counts, 0, RTC_WF_COUNTS * sizeof(uint32_t), s->stream));
     HIP_OK(hipEventRecord(s->ev0, s->stream));
     rtc_launch_wavefront(s->d, cam, pm, fuel, s->wave, d_rgb, want_hits ? s->d_hit_t : nullptr, s->d_hit_prim, s->d_hit_k, s->d_stats, count, s->stream, s->wave_blocks, s->shade_blocks, s->lds_bytes,
-                         s->has_bg ? &s->bg : nullptr);
+                         s->has_bg ? &s->bg : nullptr, s->has_bump ? &s->bump : nullptr);
+  } else if (s->has_bump) {
+    rtc_launch_trace_np(s->d, s->bump, s->has_bg ? &s->bg : nullptr, cam, pm, fuel, d_rgb, want_hits ? s->d_hit_t : nullptr, s->d_hit_prim, s->d_hit_k, s->d_stats, count, s->stream);
   } else if (s->has_bg) {
     rtc_launch_trace_bg(s->d, s->bg, cam, pm, fuel, d_rgb, want_hits ? s->d_hit_t : nullptr, s->d_hit_prim, s->d_hit_k, s->d_stats, count, s->stream);
   } else {
@@ -1033,21 +1044,25 @@ int rtc_device_count(void) {
 namespace {
 // rtc_scene_create (ex == false) and rtc_scene_create_ex (ex == true: the lights are `lx`, desc->lights must be empty); `uv`: the UV
 // pattern records and textures of rtc_scene_create_ext; `cones`: the light cones of rtc_scene_create_ext2 (with ex == true only)
-// `bg`: the background of rtc_scene_create_ext3 (NULL: none)
+// `bg`: the background of rtc_scene_create_ext3 (NULL: none); `bumps`: the bump records of rtc_scene_create_ext4
 int scene_create(const rtc_scene_desc* desc, bool ex, const rtc_light_ex* lx, uint32_t n_lx, int device, rtc_scene** out, const rtb::UvInput& uv = rtb::UvInput{},
-                 const rtb::ConeInput& cones = rtb::ConeInput{}, const rtc_background* bg = nullptr) {
+                 const rtb::ConeInput& cones = rtb::ConeInput{}, const rtc_background* bg = nullptr, const rtb::BumpInput& bumps = rtb::BumpInput{}) {
   if (!desc || !out) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
   *out = nullptr;
   if (bg) {  // (its own limits first: they need no device)
     std::string why;
     if (const int rc = rtb::validate_background(*bg, desc->n_pattern_nodes, &why)) return rtc_fail(rc, why);
   }
+  if (bumps.n) {
+    std::string why;
+    if (const int rc = rtb::validate_bumps(bumps, desc->n_materials, &why)) return rtc_fail(rc, why);
+  }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return rtc_fail(RTC_ERR_DEVICE, "no HIP device available (this library has no CPU path)");
   if (device < 0 || device >= ndev) return rtc_fail(RTC_ERR_DEVICE, "device index out of range");
   HIP_OK(hipSetDevice(device));
   rtb::HostArrays H;
-  H.has_bg = bg ? 1 : 0;
+  H.has_bg = (bg || bumps.n) ? 1 : 0;  // (bump records too: the NP builds read the program from memory, like the BG builds)
   std::string err;
   // Mesh accelerators of at least 100 000 triangles are built on the device (LBVH over extent-aware bisection keys, bvh_device.hip)
   // instead of by the host's binned SAH: same pixels (the accelerator is results-neutral), a quarter of the build time, frames
@@ -1089,6 +1104,19 @@ int scene_create(const rtc_scene_desc* desc, bool ex, const rtc_light_ex* lx, ui
   UP(qgrids); UP(qcell); UP(bvh_frame); UP(csg); UP(prims); UP(pisect); UP(xf_inv); UP(xf_matinv); UP(limits);
   UP(tri_geo); UP(tri_nrm); UP(mat); UP(mat_pattern); UP(pats); UP(lights);
 #undef UP
+  if (bumps.n) {  // the bump table: a record index per material, -1 without one
+    std::vector<int32_t> mat_bump(desc->n_materials, -1);
+    std::vector<DBump> recs(bumps.n);
+    for (uint32_t k = 0; k < bumps.n; k++) {
+      const rtc_bump& b = bumps.bumps[k];
+      mat_bump[b.material] = (int32_t)k;
+      recs[k] = DBump{b.kind, b.octaves, b.amplitude, b.frequency};
+    }
+    if (const int rc_ = s->upload(mat_bump, &s->bump.mat_bump)) return rc_;
+    if (const int rc_ = s->upload(recs, &s->bump.recs)) return rc_;
+    s->has_bump = true;
+    s->n_bumps = bumps.n;
+  }
   d.n_ops = (int32_t)H.ops.size();
   d.n_prims = (int32_t)H.prims.size();
   d.n_recs = H.recs_bg_only ? 0 : (int32_t)H.pisect.size();
@@ -1248,6 +1276,79 @@ int rtc_scene_create_ext3(const rtc_scene_desc* desc, const rtc_scene_ext* ext, 
   if (!ext) return scene_create(desc, false, nullptr, 0, device, out, rtb::UvInput{}, rtb::ConeInput{}, bg);
   const rtb::UvInput uv{ext->uv_patterns, ext->n_uv_patterns, ext->textures, ext->n_textures};
   return scene_create(desc, ext->n_lights > 0, ext->lights, ext->n_lights, device, out, uv, rtb::ConeInput{}, bg);
+}
+
+int rtc_scene_create_ext4(const rtc_scene_desc* desc, const rtc_scene_ext* ext, const rtc_light_cone* cones, uint32_t n_cones, const rtc_background* bg,
+                          const rtc_bump* bumps, uint32_t n_bumps, int device, rtc_scene** out) {
+  if (n_bumps == 0) return rtc_scene_create_ext3(desc, ext, cones, n_cones, bg, device, out);
+  if (out) *out = nullptr;
+  if (!desc) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  const rtb::BumpInput bi{bumps, n_bumps};
+  std::string why;
+  if (const int rc = rtb::validate_bumps(bi, desc->n_materials, &why)) return rtc_fail(rc, why);
+  if (bg) {
+    if (const int rc = rtb::validate_background(*bg, desc->n_pattern_nodes, &why)) return rtc_fail(rc, why);
+  }
+  if (n_cones > 0) {
+    SpotArgs a;
+    if (const int rc = spot_args(desc, ext, cones, n_cones, &a)) return rc;
+    return scene_create(&a.desc, true, a.lx, a.n_lx, device, out, a.uv, a.cones, bg, bi);
+  }
+  if (!ext) return scene_create(desc, false, nullptr, 0, device, out, rtb::UvInput{}, rtb::ConeInput{}, bg, bi);
+  const rtb::UvInput uv{ext->uv_patterns, ext->n_uv_patterns, ext->textures, ext->n_textures};
+  return scene_create(desc, ext->n_lights > 0, ext->lights, ext->n_lights, device, out, uv, rtb::ConeInput{}, bg, bi);
+}
+
+int rtc_bump_normal(const rtc_bump* bump, const double material_inv[16], const double point[3], const double normal[3], double out[3]) {
+  if (!bump || !material_inv || !point || !normal || !out) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  if (const char* why = rtb::bump_invalid(*bump)) return rtc_fail(RTC_ERR_INVALID, std::string("bump: ") + why);
+  rtc_bump_normal_at(bump->kind, bump->octaves, bump->amplitude, bump->frequency, material_inv, point[0], point[1], point[2], normal, out);
+  return RTC_OK;
+}
+
+int rtc_bump_normals(rtc_scene* s, const int32_t* prims, const double* points, const double* normals, uint64_t n, double* out) {
+  if (!s || (n && (!prims || !points || !normals || !out))) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  if (n == 0) return RTC_OK;
+  for (uint64_t i = 0; i < n; i++)
+    if (prims[i] < 0 || prims[i] >= s->d.n_prims) return rtc_fail(RTC_ERR_INVALID, "bump_normals: primitive index out of range");
+  if (!s->has_bump) {  // no record anywhere: every primitive gets its normal back
+    std::memcpy(out, normals, n * 3 * sizeof(double));
+    return RTC_OK;
+  }
+  HIP_OK(hipSetDevice(s->device));
+  int rc = ensure_px(s, n, true);  // d_rgb: 3 rows of n doubles; d_hit_prim: n ints
+  if (rc != RTC_OK) return rc;
+  if (n > s->cap_rays) {  // d_rays: 6 rows of n doubles (the points' rows, then the normals')
+    if (s->d_rays) (void)hipFree(s->d_rays);
+    s->d_rays = nullptr; s->cap_rays = 0;
+    HIP_OK(hipMalloc((void**)&s->d_rays, n * 6 * sizeof(double)));
+    s->cap_rays = n;
+  }
+  std::vector<double> soa(6 * n);  // the kernel reads rows: a wave's loads are whole lines
+  for (uint64_t i = 0; i < n; i++)
+    for (int c = 0; c < 3; c++) { soa[c * n + i] = points[3 * i + c]; soa[(3 + c) * n + i] = normals[3 * i + c]; }
+  HIP_OK(hipMemcpyAsync(s->d_rays, soa.data(), 6 * n * sizeof(double), hipMemcpyHostToDevice, s->stream));
+  HIP_OK(hipMemcpyAsync(s->d_hit_prim, prims, n * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
+  rtc_launch_bump_normals(s->d, s->bump, s->d_hit_prim, s->d_rays, s->d_rays + 3 * n, n, s->d_rgb, s->stream);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(soa.data(), s->d_rgb, 3 * n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  HIP_OK(hipStreamSynchronize(s->stream));
+  for (uint64_t i = 0; i < n; i++)
+    for (int c = 0; c < 3; c++) out[3 * i + c] = soa[c * n + i];
+  return RTC_OK;
+}
+
+int rtc_scene_bump_info(const rtc_scene* s, rtc_bump_info* out) {
+  if (!s || !out) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  std::memset(out, 0, sizeof(*out));
+  out->trace_build = out->wf_shade_build = -1;
+  if (!s->has_bump) return RTC_OK;
+  out->has_bump = 1;
+  out->n_bumps = s->n_bumps;
+  out->trace_build = rtc_bump_trace_build(s->d, s->has_bg);
+  out->trace_area = s->d.has_area || s->d.has_spot; out->trace_uv = s->d.has_uv; out->trace_spot = s->d.has_spot; out->trace_bg = s->has_bg ? 1 : 0;
+  out->wf_shade_build = s->d.has_uv ? RTC_WF_NP_UV : RTC_WF_NP_PLAIN;
+  return RTC_OK;
 }
 
 int rtc_background_point(int32_t projection, const double dir[3], double point[3]) {
@@ -2059,13 +2160,14 @@ int render_multi(rtc_multi* m, const rtc_camera* cam, int32_t fuel, double* rgb_
 
 namespace {
 int multi_create(const rtc_scene_desc* desc, bool ex, const rtc_light_ex* lx, uint32_t n_lx, const int* devices, int n_devices, rtc_multi** out,
-                 const rtb::UvInput& uv = rtb::UvInput{}, const rtb::ConeInput& cones = rtb::ConeInput{}, const rtc_background* bg = nullptr) {
+                 const rtb::UvInput& uv = rtb::UvInput{}, const rtb::ConeInput& cones = rtb::ConeInput{}, const rtc_background* bg = nullptr,
+                 const rtb::BumpInput& bumps = rtb::BumpInput{}) {
   if (!desc || !devices || !out || n_devices <= 0) return rtc_fail(RTC_ERR_INVALID, "NULL argument / no devices");
   *out = nullptr;
   std::unique_ptr<rtc_multi> m(new rtc_multi());
   for (int k = 0; k < n_devices; k++) {
     rtc_scene* s = nullptr;
-    int rc = scene_create(desc, ex, lx, n_lx, devices[k], &s, uv, cones, bg);
+    int rc = scene_create(desc, ex, lx, n_lx, devices[k], &s, uv, cones, bg, bumps);
     if (rc != RTC_OK) { rtc_multi_destroy(m.release()); return rc; }
     m->scenes.push_back(s);
     m->tiles.push_back(nullptr);
@@ -2133,6 +2235,27 @@ int rtc_multi_create_ext3(const rtc_scene_desc* desc, const rtc_scene_ext* ext, 
   if (!ext) return multi_create(desc, false, nullptr, 0, devices, n_devices, out, rtb::UvInput{}, rtb::ConeInput{}, bg);
   const rtb::UvInput uv{ext->uv_patterns, ext->n_uv_patterns, ext->textures, ext->n_textures};
   return multi_create(desc, ext->n_lights > 0, ext->lights, ext->n_lights, devices, n_devices, out, uv, rtb::ConeInput{}, bg);
+}
+
+int rtc_multi_create_ext4(const rtc_scene_desc* desc, const rtc_scene_ext* ext, const rtc_light_cone* cones, uint32_t n_cones, const rtc_background* bg,
+                          const rtc_bump* bumps, uint32_t n_bumps, const int* devices, int n_devices, rtc_multi** out) {
+  if (n_bumps == 0) return rtc_multi_create_ext3(desc, ext, cones, n_cones, bg, devices, n_devices, out);
+  if (out) *out = nullptr;
+  if (!desc) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  const rtb::BumpInput bi{bumps, n_bumps};
+  std::string why;
+  if (const int rc = rtb::validate_bumps(bi, desc->n_materials, &why)) return rtc_fail(rc, why);
+  if (bg) {
+    if (const int rc = rtb::validate_background(*bg, desc->n_pattern_nodes, &why)) return rtc_fail(rc, why);
+  }
+  if (n_cones > 0) {
+    SpotArgs a;
+    if (const int rc = spot_args(desc, ext, cones, n_cones, &a)) return rc;
+    return multi_create(&a.desc, true, a.lx, a.n_lx, devices, n_devices, out, a.uv, a.cones, bg, bi);
+  }
+  if (!ext) return multi_create(desc, false, nullptr, 0, devices, n_devices, out, rtb::UvInput{}, rtb::ConeInput{}, bg, bi);
+  const rtb::UvInput uv{ext->uv_patterns, ext->n_uv_patterns, ext->textures, ext->n_textures};
+  return multi_create(desc, ext->n_lights > 0, ext->lights, ext->n_lights, devices, n_devices, out, uv, rtb::ConeInput{}, bg, bi);
 }
 
 void rtc_multi_destroy(rtc_multi* m) {

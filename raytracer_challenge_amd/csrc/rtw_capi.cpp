@@ -27,6 +27,10 @@ extern "C" int rtc_scene_create_ext2(const rtc_scene_desc*, const rtc_scene_ext*
 // (and for a background)
 extern "C" int rtc_scene_create_ext3(const rtc_scene_desc*, const rtc_scene_ext*, const rtc_light_cone*, uint32_t, const rtc_background*, int, rtc_scene**) __attribute__((weak));
 
+// (and for bump records)
+extern "C" int rtc_scene_create_ext4(const rtc_scene_desc*, const rtc_scene_ext*, const rtc_light_cone*, uint32_t, const rtc_background*, const rtc_bump*, uint32_t, int,
+                                     rtc_scene**) __attribute__((weak));
+
 struct rtw_pattern { PatRef p; };
 struct rtw_texture { TexRef t; };
 struct rtw_element { std::unique_ptr<Elem> e; };
@@ -68,7 +72,17 @@ static int ensure_scene(rtw_world* w) {
     rtc_scene_desc d = f.desc();
     if (timing) std::fprintf(stderr, "[rtc-timing] %-28s %.3f s\n", "flatten (host mirror -> desc)", since(t0));
     const auto t1 = std::chrono::steady_clock::now();
-    if (w->background) {  // a background: its pattern tree joins the node array; everything else the world has goes along
+    if (!f.bumps.empty()) {  // bump records: everything else the world has goes along
+      if (!rtc_scene_create_ext4) return fail("a bump (rtw_element_set_bump) needs rtc_scene_create_ext4 (librtc_amd.so)");
+      rtc_background bg{0, w->background_projection};
+      if (w->background) { bg.pattern = fl.root_pattern(w->background); d = f.desc(); }  // (the node array grew)
+      rtc_scene_ext x{};
+      if (!w->lights_ex.empty()) { d.n_lights = 0; d.lights = nullptr; x.n_lights = (uint32_t)w->lights_ex.size(); x.lights = w->lights_ex.data(); }
+      x.n_uv_patterns = (uint32_t)f.uv_pats.size(); x.uv_patterns = f.uv_pats.data();
+      x.n_textures = (uint32_t)f.textures.size(); x.textures = f.textures.data();
+      rc = rtc_scene_create_ext4(&d, &x, w->cones.empty() ? nullptr : w->cones.data(), (uint32_t)w->cones.size(), w->background ? &bg : nullptr, f.bumps.data(),
+                                 (uint32_t)f.bumps.size(), w->device, &w->scene);
+    } else if (w->background) {  // a background: its pattern tree joins the node array; everything else the world has goes along
       if (!rtc_scene_create_ext3) return fail("a background needs rtc_scene_create_ext3 (librtc_amd.so)");
       rtc_background bg{fl.root_pattern(w->background), w->background_projection};
       d = f.desc();  // (the node array grew)
@@ -239,6 +253,17 @@ rtw_element* rtw_parse_obj(const char* path, const double t[16], const rtw_mater
   if (n_triangles) *n_triangles = o.triangles;
   return new rtw_element{std::move(o.root)};
 }
+int rtw_element_set_bump(rtw_element* e, int32_t kind, uint32_t octaves, double amplitude, double frequency) {
+  if (!e || !e->e) return fail("set_bump: NULL/consumed element");
+  rtc_bump b{};
+  b.kind = kind; b.octaves = octaves; b.amplitude = amplitude; b.frequency = frequency;
+  if (kind != RTC_BUMP_SIMPLEX && kind != RTC_BUMP_FRACTAL && kind != RTC_BUMP_RIPPLE) return fail("set_bump: unknown kind of bump");
+  if (!std::isfinite(amplitude)) return fail("set_bump: the bump's amplitude is not finite");
+  if (!(std::isfinite(frequency) && frequency > 0.0)) return fail("set_bump: the bump's frequency must be finite and > 0");
+  if (kind == RTC_BUMP_FRACTAL && (octaves == 0 || octaves > RTC_BUMP_MAX_OCTAVES)) return fail("set_bump: a fractal bump takes 1 .. RTC_BUMP_MAX_OCTAVES (64) octaves");
+  e->e->set_bump(kind, kind == RTC_BUMP_FRACTAL ? octaves : 0u, amplitude, frequency);
+  return 0;
+}
 void rtw_element_release(rtw_element* e) { delete e; }
 
 rtw_world* rtw_world_create(void) { return new rtw_world(); }
@@ -359,12 +384,18 @@ static int refuse_cones(const rtw_world* w) {
 static int refuse_background(const rtw_world* w) {
   return !w->background ? 0 : fail("flatten: the world has a background; it goes to rtc_scene_create_ext3, not into a descriptor");
 }
+// ... a world with a bump on some shape, whose records only rtc_scene_create_ext4 takes ...
+static int refuse_bumps(const rtw_world* w) {
+  for (auto& e : w->w.elements)
+    if (e->has_bump()) return fail("flatten: the world has a bump on a shape; bump records go to rtc_scene_create_ext4, not into a descriptor");
+  return 0;
+}
 // ... and a world with a texture-mapped pattern, whose records and textures only rtc_scene_create_ext takes.
 static int refuse_uv(const Flat& f) {
   return f.uv_pats.empty() ? 0 : fail("flatten: the world has texture-mapped patterns; their records and textures go to rtc_scene_create_ext, not into a descriptor");
 }
 int rtw_world_flatten_counts(rtw_world* w, uint32_t counts[8]) {
-  if (refuse_area(w) || refuse_cones(w) || refuse_background(w)) return 1;
+  if (refuse_area(w) || refuse_cones(w) || refuse_background(w) || refuse_bumps(w)) return 1;
   Flat f;
   Flattener fl(f);
   if (!fl.run(w->w)) return fail("flatten: " + f.error);
@@ -378,7 +409,7 @@ int rtw_world_flatten_counts(rtw_world* w, uint32_t counts[8]) {
 // Flatten only (no device): the descriptor a Rust shim would hand to rtc_scene_create; its arrays live in the world handle until
 // the next call / the world's release.  Works without a GPU (tests compare it with a foreign flattener's output).
 int rtw_world_flatten_desc(rtw_world* w, rtc_scene_desc* out) {
-  if (refuse_area(w) || refuse_cones(w) || refuse_background(w)) return 1;
+  if (refuse_area(w) || refuse_cones(w) || refuse_background(w) || refuse_bumps(w)) return 1;
   w->flat.reset(new Flat());
   Flattener fl(*w->flat);
   if (!fl.run(w->w)) return fail("flatten: " + w->flat->error);

@@ -947,7 +947,7 @@ struct HostArrays {
   int32_t has_area = 0;    // lights holds RTC_ALIGHT doubles per light (build_arrays_ex)
   int32_t has_uv = 0;      // some pattern node is an RTC_PAT_UV node
   int32_t has_spot = 0;    // some light has a cone: lights holds RTC_SLIGHT doubles per light (build_arrays_ex)
-  int32_t has_bg = 0;      // the scene has a background (rtc_scene_create_ext3; set before build_arrays): its one-kernel launches read the
+  int32_t has_bg = 0;      // the scene has a background or bump records (rtc_scene_create_ext3 / _ext4; set before build_arrays): its one-kernel launches read the
                            // program from memory, whatever the program's own variant, so the intersection records are built
   int32_t recs_bg_only = 0;  // ... and nothing else reads them: DScene.n_recs stays 0, as without the background (rtc_kernel_info reports it)
   int32_t area_bounded = 1;  // every area light's sample positions lie below 1e30 in magnitude (the back-face scan's condition)
@@ -1258,6 +1258,32 @@ struct ConeInput {
 inline int validate_background(const rtc_background& b, uint32_t n_pattern_nodes, std::string* err) {
   if (b.projection != RTC_BG_DIRECTION && b.projection != RTC_BG_CUBE) { *err = "background: unknown projection"; return RTC_ERR_INVALID; }
   if (b.pattern < 0 || (uint32_t)b.pattern >= n_pattern_nodes) { *err = "background: pattern index out of range"; return RTC_ERR_INVALID; }
+  return RTC_OK;
+}
+// Bump records (include/rtc.h rtc_bump) and their own limits; needs no descriptor beyond the material count.
+struct BumpInput {
+  const rtc_bump* bumps = nullptr;
+  uint32_t n = 0;
+};
+// what is wrong with one record's numbers (`material` aside), or NULL
+inline const char* bump_invalid(const rtc_bump& b) {
+  if (b.kind != RTC_BUMP_SIMPLEX && b.kind != RTC_BUMP_FRACTAL && b.kind != RTC_BUMP_RIPPLE) return "unknown kind";
+  if (!std::isfinite(b.amplitude)) return "amplitude is not finite";
+  if (!(std::isfinite(b.frequency) && b.frequency > 0.0)) return "frequency must be finite and > 0";
+  if (b.kind == RTC_BUMP_FRACTAL && b.octaves == 0) return "a fractal bump needs at least one octave";
+  if (b.kind == RTC_BUMP_FRACTAL && b.octaves > RTC_BUMP_MAX_OCTAVES) return "a fractal bump takes at most RTC_BUMP_MAX_OCTAVES (64) octaves";
+  return nullptr;
+}
+inline int validate_bumps(const BumpInput& B, uint32_t n_materials, std::string* err) {
+  if (B.n > 0 && !B.bumps) { *err = "bumps is NULL"; return RTC_ERR_INVALID; }
+  std::vector<char> seen(n_materials, 0);
+  for (uint32_t k = 0; k < B.n; k++) {
+    const rtc_bump& b = B.bumps[k];
+    if (b.material >= n_materials) { *err = "bump " + std::to_string(k) + ": material index out of range"; return RTC_ERR_INVALID; }
+    if (seen[b.material]) { *err = "bump " + std::to_string(k) + ": material " + std::to_string(b.material) + " already has a bump record"; return RTC_ERR_INVALID; }
+    seen[b.material] = 1;
+    if (const char* why = bump_invalid(b)) { *err = "bump " + std::to_string(k) + ": " + why; return RTC_ERR_INVALID; }
+  }
   return RTC_OK;
 }
 // The cones' own limits; needs no descriptor beyond the light count.

@@ -211,6 +211,44 @@ class Pattern:  # src/material.rs:60-65, constructors :110-162
         return Pattern("uv", kind="cube", transform=transform, faces=faces)
 
 
+BUMP_KINDS = ("simplex", "fractal", "ripple")  # include/rtc.h RTC_BUMP_*, in enum order
+BUMP_MAX_OCTAVES = 64                          # include/rtc.h RTC_BUMP_MAX_OCTAVES
+
+
+@dataclass(frozen=True)
+class Bump:
+    """Normal perturbation (include/rtc.h rtc_bump; not in the reference): the shading normal of a hit is the geometric one plus
+    ``amplitude`` times a slope field looked up at ``frequency`` times the point in the material's space -- simplex or fractal noise,
+    or rings about the material-space y axis (ripple)."""
+    kind: str
+    amplitude: float
+    frequency: float
+    octaves: int = 0  # fractal only
+
+    def __post_init__(self):
+        if self.kind not in BUMP_KINDS:
+            raise ValueError("Bump.kind must be one of %r" % (BUMP_KINDS,))
+        for name in ("amplitude", "frequency"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise TypeError("Bump.%s must be a number" % name)
+        if not math.isfinite(self.amplitude):
+            raise ValueError("Bump.amplitude must be finite")
+        if not (math.isfinite(self.frequency) and self.frequency > 0.0):
+            raise ValueError("Bump.frequency must be finite and > 0")
+        if isinstance(self.octaves, bool) or not isinstance(self.octaves, int):
+            raise TypeError("Bump.octaves must be an integer")
+        if self.kind == "fractal" and not 1 <= self.octaves <= BUMP_MAX_OCTAVES:
+            raise ValueError("Bump.fractal: octaves must be 1 .. %d" % BUMP_MAX_OCTAVES)
+
+    @staticmethod
+    def simplex(amplitude: float, frequency: float) -> "Bump": return Bump("simplex", amplitude, frequency)
+    @staticmethod
+    def fractal(octaves: int, amplitude: float, frequency: float) -> "Bump": return Bump("fractal", amplitude, frequency, octaves)
+    @staticmethod
+    def ripple(amplitude: float, frequency: float) -> "Bump": return Bump("ripple", amplitude, frequency)
+
+
 @dataclass(frozen=True)
 class Material:  # src/material.rs:19-43 (defaults :30-43)
     pattern: Pattern = field(default_factory=lambda: Pattern.plain(Color.white()))
@@ -221,6 +259,11 @@ class Material:  # src/material.rs:19-43 (defaults :30-43)
     reflective: float = 0.0
     transparency: float = 0.0
     refractive_index: float = 1.0
+    bump: Optional[Bump] = None  # not in the reference: see Bump
+
+    def __post_init__(self):
+        if self.bump is not None and not isinstance(self.bump, Bump):
+            raise TypeError("Material.bump must be a Bump or None")
 
 
 # src/material.rs:8-16

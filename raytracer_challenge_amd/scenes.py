@@ -470,6 +470,24 @@ def sky_showcase(hsize=None, vsize=None, skybox: bool = False) -> Tuple[Camera, 
     return _cam(1920, 1080, PI / 3.0, (0.0, 1.8, -7.0), (0.0, 1.0, 0.5), (0.0, 1.0, 0.0), hsize, vsize), World(lights, [floor, mirror, glass, matte], background)
 
 
+def bump_showcase(hsize=None, vsize=None) -> Tuple[Camera, World]:
+    """Normal perturbation: a rippled floor mirror, a fractal-bumped glass ball and a simplex-bumped teapot (smooth triangles) under
+    sky_showcase's gradient sky and one jittered area light.  No geometry was added for any of the three surfaces."""
+    from .scene import AreaLight, Background, Bump
+    c = Color.new
+    floor = Element.plane(ShapeArgs(material=Material(
+        pattern=Pattern.plain(c(0.1, 0.15, 0.2)), diffuse=0.3, specular=0.6, shininess=200.0, reflective=0.7, bump=Bump.ripple(0.08, 0.8))))
+    glass = Element.sphere(ShapeArgs(transform=Matrix.translation(-1.8, 1.0, 0.5), material=Material(
+        pattern=Pattern.plain(Color.black()), diffuse=0.1, shininess=300.0, reflective=0.9, transparency=0.9, refractive_index=1.5,
+        bump=Bump.fractal(3, 0.15, 3.0))))
+    teapot = Element.obj(os.path.join(ASSETS, "obj", "teapot_low.obj"),Matrix.translation(1.6, 0.0, 0.0) * Matrix.rotation_y(-0.6) * Matrix.scaling(0.12, 0.12, 0.12) * Matrix.rotation_x(-PI / 2.0),
+                         Material(pattern=Pattern.plain(c(0.9, 0.55, 0.2)), diffuse=0.7, specular=0.6, shininess=80.0, bump=Bump.simplex(0.25, 1.5)))
+    up = Matrix.translation(0.0, -1.0, 0.0) * Matrix.scaling(2.0001, 2.0001, 2.0001) * Matrix.rotation_z(PI / 2.0)
+    background = Background(Pattern.gradient(up, Pattern.plain(c(0.95, 0.9, 0.8)), Pattern.plain(c(0.2, 0.45, 0.9))), "direction")
+    lights = [AreaLight(c(0.9, 0.9, 0.85), Vector.point(-6.0, 9.0, -8.0), Vector.vector(1.5, 0.0, 0.0), 3, Vector.vector(0.0, 1.5, 0.0), 3, jitter=True)]
+    return _cam(1920, 1080, PI / 3.0, (0.0, 2.2, -7.0), (0.0, 1.0, 0.5), (0.0, 1.0, 0.0), hsize, vsize), World(lights, [floor, glass, teapot], background)
+
+
 def motion_showcase(hsize=None, vsize=None, poses: int = 8) -> List[Tuple[Camera, World]]:
     """The shutter's showcase (not in the reference): `poses` (camera, world) pairs over the shutter's opening for
     Image.par_render_shutter.  A checkered floor, a glass and a matte sphere that move linearly across the poses, a mirror that stands

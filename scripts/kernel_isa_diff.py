@@ -4,7 +4,7 @@
     scripts/kernel_isa_diff.py OLD_TREE NEW_TREE [--rename 'REGEX=>REPLACEMENT']... [--jobs N] [--keep DIR [--reuse]]
 
 For each tree: rtc_feat.hip for every variant id of its csrc/Makefile, rtc_kernels.hip and, where the tree has them,
-rtc_camera.hip, rtc_adaptive.hip, rtc_filter.hip, rtc_shutter.hip and rtc_background.hip (once plain, once per BG build id) are compiled to device-only assembly with that Makefile's FLAGS.  The assembly is split per function; comments, directives and label definitions
+rtc_camera.hip, rtc_adaptive.hip, rtc_filter.hip, rtc_shutter.hip, rtc_background.hip (once plain, once per BG build id) and rtc_bump.hip (once plain, once per NP build id) are compiled to device-only assembly with that Makefile's FLAGS.  The assembly is split per function; comments, directives and label definitions
 are dropped, local label references (.LBB<fn>_<n> ...) lose their function number, the function's own symbol becomes
 <self>; what remains is counted and hashed.  Printed per function of NEW_TREE: unit, demangled name, instruction
 count, hash, next_free_vgpr, next_free_sgpr, private segment size (device functions that are not kernels: the
@@ -45,6 +45,9 @@ def units(tree):
     if os.path.exists(os.path.join(tree, CSRC, "rtc_background.hip")):   # the background's kernels, and one unit per BG build of the one-kernel path
         out.append(("background", "rtc_background.hip", flags))
         out += [("background%s" % b, "rtc_background.hip", flags + ["-DRTC_BG_BUILD=%s" % b]) for b in make_var(mk, "BG_BUILD_IDS")]
+    if os.path.exists(os.path.join(tree, CSRC, "rtc_bump.hip")):   # the bump records' kernel, and one unit per NP build of the one-kernel path
+        out.append(("bump", "rtc_bump.hip", flags))
+        out += [("bump%s" % b, "rtc_bump.hip", flags + ["-DRTC_NP_BUILD=%s" % b]) for b in make_var(mk, "NP_BUILD_IDS")]
     return out
 
 

@@ -148,6 +148,39 @@ pub struct RtcBackground {
     pub pattern: i32,    // index of a root RtcPatternNode
     pub projection: i32, // RTC_BG_*
 }
+// include/rtc.h rtc_bump: normal perturbation (not in the reference), one record per material, for rtc_scene_create_ext4 /
+// rtc_multi_create_ext4
+#[allow(dead_code)]
+pub const RTC_BUMP_SIMPLEX: i32 = 0;
+#[allow(dead_code)]
+pub const RTC_BUMP_FRACTAL: i32 = 1;
+#[allow(dead_code)]
+pub const RTC_BUMP_RIPPLE: i32 = 2;
+#[allow(dead_code)]
+pub const RTC_BUMP_MAX_OCTAVES: u32 = 64;
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtcBump {
+    pub material: u32, // index into desc.materials; at most one record per material
+    pub kind: i32,     // RTC_BUMP_*
+    pub octaves: u32,  // FRACTAL only
+    pub _pad: u32,
+    pub amplitude: f64,
+    pub frequency: f64,
+}
+// include/rtc.h rtc_bump_info: which builds a launch of a bumped scene takes (test hook)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtcBumpInfo {
+    pub has_bump: i32,
+    pub n_bumps: u32,
+    pub trace_build: i32,
+    pub trace_area: i32,
+    pub trace_uv: i32,
+    pub trace_spot: i32,
+    pub trace_bg: i32,
+    pub wf_shade_build: i32,
+}
 // include/rtc.h rtc_background_info: which builds a launch of a background scene takes (test hook)
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -337,6 +370,18 @@ extern "C" {
     fn rtc_background_colors(scene: *mut RtcScene, dirs: *const f64, n: u64, rgb: *mut f64) -> c_int;
     #[allow(dead_code)]
     fn rtc_scene_background_info(scene: *const RtcScene, out: *mut RtcBackgroundInfo) -> c_int;
+    #[allow(dead_code)]
+    fn rtc_scene_create_ext4(desc: *const RtcSceneDesc, ext: *const RtcSceneExt, cones: *const RtcLightCone, n_cones: u32, bg: *const RtcBackground,
+                             bumps: *const RtcBump, n_bumps: u32, device: c_int, out: *mut *mut RtcScene) -> c_int;
+    #[allow(dead_code)]
+    fn rtc_multi_create_ext4(desc: *const RtcSceneDesc, ext: *const RtcSceneExt, cones: *const RtcLightCone, n_cones: u32, bg: *const RtcBackground,
+                             bumps: *const RtcBump, n_bumps: u32, devices: *const c_int, n_devices: c_int, out: *mut *mut RtcMulti) -> c_int;
+    #[allow(dead_code)] // host-only: steps 1-4 of the bump rule for one hit
+    fn rtc_bump_normal(bump: *const RtcBump, material_inv: *const f64, point: *const f64, normal: *const f64, out: *mut f64) -> c_int;
+    #[allow(dead_code)] // the same steps for n hits, evaluated on the device from the scene's own tables
+    fn rtc_bump_normals(scene: *mut RtcScene, prims: *const i32, points: *const f64, normals: *const f64, n: u64, out: *mut f64) -> c_int;
+    #[allow(dead_code)]
+    fn rtc_scene_bump_info(scene: *const RtcScene, out: *mut RtcBumpInfo) -> c_int;
     fn rtc_multi_destroy(multi: *mut RtcMulti);
     fn rtc_render_multi(multi: *mut RtcMulti, camera: *const RtcCamera, fuel: i32, rgb: *mut f64, stats: *mut RtcStats) -> c_int;
     #[allow(dead_code)] // Color::clamp'ed pixels (what Image::ppm writes): 3 bytes per pixel cross xGMI instead of 24

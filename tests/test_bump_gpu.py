@@ -1,0 +1,378 @@
+"""Normal perturbation (include/rtc.h rtc_bump) on an MI355X, both device paths: amplitude 0 moves nothing, the rule on the device against
+the host entry, the normal through a render (a perfect mirror under a Debug background shows its own reflect vector, exactly), the
+lighting against a numpy Phong over the restated normal, path against path on one scene per row of RTC_NP_BUILDS, the frame shapes that
+can go wrong, and every render entry point."""
+import ctypes as C
+import dataclasses
+import math
+
+import numpy as np
+import pytest
+
+import build_matrix as bm
+import foreign_flattener as ff
+from parity import RGB_TOL
+from raytracer_challenge_amd import scenes
+from raytracer_challenge_amd.image import Image
+from raytracer_challenge_amd.scene import (EPSILON, Adaptive, Background, Bump, Camera, Color, Element, Filter, Material, Matrix, Pattern, PointLight, Sampling, ShapeArgs,
+                                           Shutter, Vector, World)
+from test_background_gpu import bind as bind_bg, open_world, quantised, real_backgrounds, render_scene, same_frames
+from test_bump_cpu import FRACTAL, RIPPLE, SIMPLEX, RtcBump, RtcBumpInfo, bind_bump, lib_normal, same_bits
+
+pytestmark = pytest.mark.gpu
+PATHS = ["1", "4"]
+vp = C.c_void_p
+FUEL = 5
+KINDS = {"simplex": SIMPLEX, "fractal": FRACTAL, "ripple": RIPPLE}
+
+
+def bind(lib):
+    bind_bg(lib)
+    bind_bump(lib)
+    return lib
+
+
+def bumped(world, pick):
+    """The world with pick(k) as the bump of the k-th material met (shapes, groups' materials and OBJ files, depth first)."""
+    k = [0]
+
+    def mat(m):
+        if m is None:
+            return None
+        k[0] += 1
+        return dataclasses.replace(m, bump=pick(k[0] - 1))
+
+    def el(e):
+        if e.tag == "shape":
+            return dataclasses.replace(e, args=dataclasses.replace(e.args, material=mat(e.args.material)))
+        if e.tag == "composite":
+            return dataclasses.replace(e, material=mat(e.material), children=tuple(el(c) for c in e.children))
+        return dataclasses.replace(e, material=mat(e.material))
+    return World(world.lights, [el(e) for e in world.elements], world.background)
+
+
+MIXED = (Bump.simplex(0.08, 2.0), Bump.fractal(3, 0.15, 1.5), Bump.ripple(0.1, 1.3), None)
+
+
+def mixed(k):
+    return MIXED[k % len(MIXED)]
+
+
+def render_world(hip, world, cam, fuel=FUEL):
+    lib = bind(hip.lib)
+    nw = hip.build_world(world)
+    out = render_scene(lib, bm.scene_of(hip, nw), cam, fuel)
+    nw.close()
+    return out
+
+
+def bump_info(hip, nw):
+    lib = bind(hip.lib)
+    info = RtcBumpInfo()
+    assert lib.rtc_scene_bump_info(bm.scene_of(hip, nw), C.byref(info)) == 0, lib.rtc_last_error()
+    return info
+
+
+# ---- 1. amplitude 0 moves nothing ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["planes6", "ops12_gated", "uv"])
+def test_amplitude_zero_is_the_world_without_records(hip, name, tmp_path, monkeypatch):
+    """Every material gets an amplitude-0 record of each kind in turn: the NP builds run (rtc_scene_bump_info says so) and give the frame,
+    hit records, digests and ray counters of the scene's own builds, bit for bit; rtc_scene_kernel_info does not see the records."""
+    cam, world = bm.BY_NAME[name].make(tmp_path)
+    lib = bind(hip.lib)
+    for path in PATHS:
+        monkeypatch.setenv("RTC_KERNEL", path)
+        nw = hip.build_world(world)
+        ia = bump_info(hip, nw)
+        assert ia.has_bump == 0 and ia.n_bumps == 0 and ia.trace_build == -1 and ia.wf_shade_build == -1
+        fa = render_scene(lib, bm.scene_of(hip, nw), cam, FUEL)
+        assert fa[3].rays_shadow > 0 and fa[0].max() > 0.0
+        for zero in (Bump.simplex(0.0, 2.0), Bump.fractal(3, 0.0, 2.0), Bump.ripple(0.0, 2.0)):
+            nb = hip.build_world(bumped(world, lambda k: zero))
+            for count in (False, True):
+                a, b = bm.kernel_info(hip, nw, 4, count), bm.kernel_info(hip, nb, 4, count)
+                assert bytes(a) == bytes(b), "%s: rtc_scene_kernel_info differs on path 4: %s" % (name, [(f, getattr(a, f), getattr(b, f)) for f, _ in a._fields_ if getattr(a, f) != getattr(b, f)])
+            ib = bump_info(hip, nb)
+            assert ib.has_bump == 1 and ib.n_bumps >= 2 and ib.trace_bg == 0
+            assert ib.trace_build == (2 if name == "uv" else 0) and ib.trace_uv == (1 if name == "uv" else 0) and ib.wf_shade_build == (1 if name == "uv" else 0)
+            same_frames(render_scene(lib, bm.scene_of(hip, nb), cam, FUEL), fa, "%s with %s records of amplitude 0, path %s" % (name, zero.kind, path))
+            nb.close()
+
+
+# ---- 2. the rule on the device --------------------------------------------------------------------------------------------------------------
+def test_rule_on_the_device_is_the_host_entry_bit_for_bit(hip):
+    lib = bind(hip.lib)
+    shear = Matrix.translation(0.5, 1.0, -2.0) * Matrix.rotation_y(0.7) * Matrix.shearing(0.3, 0.0, -0.2, 0.0, 0.1, 0.4) * Matrix.scaling(2.0, 0.5, 1.25)
+    specs = [(Matrix.id(), Bump.simplex(0.05, 2.0)), (Matrix.scaling(3.0, 0.25, 1.5), Bump.fractal(3, 0.3, 0.7)), (shear, Bump.ripple(1.0, 4.0)),
+             (shear, Bump.fractal(8, 10.0, 1.0)), (Matrix.translation(7.0, 0.0, 0.0), None), (Matrix.rotation_x(0.3) * Matrix.scaling(0.1, 0.1, 0.1), Bump.simplex(0.0, 9.0))]
+    els = [Element.sphere(ShapeArgs(transform=t, material=bm.plain(0.1 + 0.1 * k, 0.5, 0.5, bump=b))) for k, (t, b) in enumerate(specs)]
+    nw = hip.build_world(World([PointLight(Color.white(), Vector.point(0, 9, -9))], els))
+    n = 2000
+    rng = np.random.default_rng(11)
+    prims = rng.integers(0, len(specs), n).astype(np.int32)
+    points = rng.normal(size=(n, 3)) * rng.choice([1e-3, 1.0, 40.0, 1e3], (n, 1))
+    normals = rng.normal(size=(n, 3))
+    normals /= np.sqrt((normals * normals).sum(axis=1))[:, None]
+    out = np.full((n, 3), np.nan)
+    assert lib.rtc_bump_normals(bm.scene_of(hip, nw), prims.ctypes.data, points.ctypes.data, normals.ctypes.data, n, out.ctypes.data) == 0, lib.rtc_last_error()
+    moved = 0
+    for i in range(n):
+        t, b = specs[prims[i]]
+        if b is None:
+            want = normals[i]
+        else:
+            want = lib_normal(lib, KINDS[b.kind], b.octaves, b.amplitude, b.frequency, ff.inverse(t).flat(), points[i], normals[i])
+            moved += int(not same_bits(want, normals[i]))
+        assert same_bits(out[i], want), (i, int(prims[i]), out[i], want)
+    assert moved > n // 2
+    bad = np.array([0, len(specs)], dtype=np.int32)
+    assert lib.rtc_bump_normals(bm.scene_of(hip, nw), bad.ctypes.data, points.ctypes.data, normals.ctypes.data, 2, out.ctypes.data) == 1
+    plain = hip.build_world(World([], [Element.sphere()]))                          # a scene without records hands the normals back
+    out2 = np.full((4, 3), np.nan)
+    assert lib.rtc_bump_normals(bm.scene_of(hip, plain), np.zeros(4, dtype=np.int32).ctypes.data, points.ctypes.data, normals.ctypes.data, 4, out2.ctypes.data) == 0
+    assert same_bits(out2, normals[:4])
+
+
+# ---- 3. the normal through a render -----------------------------------------------------------------------------------------------------
+def dot3(a, b):
+    return (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]
+
+
+def sphere_normals(t, X):
+    """Shape::normal for a sphere (csrc/rtc_device.hpp prepare_state), numpy float64, one operation at a time: the unit world normal
+    before the inside flip."""
+    m = np.array(ff.inverse(t).flat()).reshape(4, 4)
+    o = [((m[r, 0] * X[:, 0] + m[r, 1] * X[:, 1]) + m[r, 2] * X[:, 2]) + m[r, 3] * 1.0 for r in range(3)]
+    w = np.stack([((m[0, c] * o[0] + m[1, c] * o[1]) + m[2, c] * o[2]) + 0.0 for c in range(3)], axis=1)
+    return w / np.sqrt(dot3(w, w))[:, None]
+
+
+def restated_states(hip, cam, hits, normal_of, mat_inv, bump):
+    """Per hit pixel: the ray direction d, the hit point X, the flipped geometric normal ng, the flipped shading normal ns (rtc_bump_normal
+    on the host) and the reflect vector of step 7."""
+    lib = bind(hip.lib)
+    rays = hip.camera_rays(cam, Sampling()).reshape(-1, 6)
+    hit = hits["prim"] >= 0
+    o, d, t = rays[hit, :3], rays[hit, 3:], hits["t"][hit]
+    X = o + d * t[:, None]
+    n = normal_of(X)
+    ns = np.array([lib_normal(lib, KINDS[bump.kind], bump.octaves, bump.amplitude, bump.frequency, mat_inv, X[i], n[i]) for i in range(len(X))])
+    flip = dot3(n, -d) < 0.0
+    ng = np.where(flip[:, None], -n, n)
+    ns = np.where(flip[:, None], -ns, ns)
+    dn = 2.0 * dot3(d, ns)
+    r = d - ns * dn[:, None]
+    return hit, d, X, ng, ns, r
+
+
+@pytest.mark.parametrize("path", PATHS)
+def test_a_perfect_mirror_shows_its_reflect_vector(hip, path, monkeypatch):
+    """ambient = diffuse = specular = 0 and reflective = 1 under one light and a Debug background looked up by direction: a pixel whose
+    reflected ray leaves the scene is 0.0 + 1.0 * r, r = step 7's reflect vector restated in numpy.  Exact.
+    Left out: the pixels whose reflected ray re-enters the sphere (r . n_geometric <= 0 in the restatement), at most 10 % of the hits; the
+    geometry predicts about 3 % (a tilt below ~5 degrees matters only within the outer 1.5 % of the disc's radius).  Counted on an MI355X:
+    0 of the sphere's 214 hit pixels on either path (at 48x32 the outer 1.5 % of the disc's radius is a fraction of a pixel); the rippled
+    plane, hit by all 1536 camera rays, leaves none out."""
+    monkeypatch.setenv("RTC_KERNEL", path)
+    mirror = dict(pattern=Pattern.plain(Color(0.3, 0.6, 0.9)), ambient=0.0, diffuse=0.0, specular=0.0, reflective=1.0)
+    light = [PointLight(Color.white(), Vector.point(-4.0, 6.0, -5.0))]
+    sky = Background(Pattern.debug(), "direction")
+    cam = bm.camera()
+    # a scaled, rotated sphere with a simplex bump
+    t = Matrix.translation(0.1, 0.7, 0.2) * Matrix.rotation_z(0.4) * Matrix.rotation_y(0.3) * Matrix.scaling(1.6, 0.9, 1.2)
+    bump = Bump.simplex(0.05, 2.0)
+    rgb, hits, _, _ = render_world(hip, World(light, [Element.sphere(ShapeArgs(transform=t, material=Material(**mirror, bump=bump)))], sky), cam)
+    hit, d, X, ng, ns, r = restated_states(hip, cam, hits, lambda X: sphere_normals(t, X), ff.inverse(t).flat(), bump)
+    leaves = dot3(r, ng) > 0.0
+    n_hit, n_out = int(hit.sum()), int((~leaves).sum())
+    print("mirror sphere, path %s: %d hit pixels, %d left out (reflected ray re-enters)" % (path, n_hit, n_out))
+    assert n_hit > 150 and n_out <= 0.10 * n_hit
+    assert same_bits(rgb[hit][leaves], 0.0 + 1.0 * r[leaves])
+    smooth, _, _, _ = render_world(hip, World(light, [Element.sphere(ShapeArgs(transform=t, material=Material(**mirror)))], sky), cam)
+    assert (smooth[hit] != rgb[hit]).any(axis=1).mean() > 0.9                      # the bump does move the reflections
+    # a rippled mirror plane, tilted, seen from high above: the frame's corner rays still meet it at about 35 degrees, and the ripples turn
+    # the normal by under 4 (amplitude 0.05 times a slope of at most 1 / 0.75) and a reflected ray by twice that, so every one leaves: no
+    # pixel is left out
+    tp = Matrix.rotation_x(0.1) * Matrix.scaling(1.5, 1.0, 0.75)
+    ripple = Bump.ripple(0.05, 1.7)
+    cam = bm.camera(frm=(0.0, 6.0, -2.0), to=(0.0, 0.0, 0.0))
+    rgb, hits, _, _ = render_world(hip, World(light, [Element.plane(ShapeArgs(transform=tp, material=Material(**mirror, bump=ripple)))], sky), cam)
+    m = np.array(ff.inverse(tp).flat()).reshape(4, 4)
+    w = np.array([((m[0, c] * 0.0 + m[1, c] * 1.0) + m[2, c] * 0.0) + 0.0 for c in range(3)])
+    pn = w / np.sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2])
+    hit, d, X, ng, ns, r = restated_states(hip, cam, hits, lambda X: np.tile(pn, (len(X), 1)), ff.inverse(tp).flat(), ripple)
+    print("mirror plane, path %s: %d hit pixels, %d with r . n <= 0" % (path, int(hit.sum()), int((dot3(r, ng) <= 0.0).sum())))
+    assert hit.all() and (dot3(r, ng) > 0.0).all()
+    assert same_bits(rgb[hit], 0.0 + 1.0 * r)
+    assert len(np.unique(ns, axis=0)) > 100                                          # (and the ripples are there)
+
+
+# ---- 4. lighting ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("path", PATHS)
+def test_lighting_follows_the_shading_normal(hip, path, monkeypatch):
+    """One bumped sphere of each kind, a Plain colour, one point light, fuel 0, against Shape::lighting (src/shape.rs:429-462) in numpy over
+    the restated shading normal, within RGB_TOL.  The sphere is convex and alone: a point is shadowed exactly where the light is behind the
+    GEOMETRIC surface.  Left out: |light . n_geometric| < 1e-3 (the self-shadow terminator), at most 2 % of the hit pixels.
+    Measured on an MI355X: max |dRGB| 1.1e-16 for each kind on either path, 0 of 225 hit pixels left out."""
+    monkeypatch.setenv("RTC_KERNEL", path)
+    lp = np.array([-4.0, 6.0, -5.0])
+    li = np.array([0.9, 0.8, 1.0])
+    col = np.array([0.8, 0.5, 0.3])
+    amb, dif, spe, shi = 0.1, 0.7, 0.6, 40.0
+    t = Matrix.translation(0.1, 0.7, 0.2) * Matrix.rotation_y(0.3) * Matrix.scaling(1.5, 1.0, 1.2)
+    cam = bm.camera()
+    for bump in (Bump.simplex(0.2, 2.0), Bump.fractal(3, 0.3, 1.5), Bump.ripple(0.25, 3.0)):
+        mat = Material(pattern=Pattern.plain(Color(*col)), ambient=amb, diffuse=dif, specular=spe, shininess=shi, bump=bump)
+        world = World([PointLight(Color(*li), Vector.point(*lp))], [Element.sphere(ShapeArgs(transform=t, material=mat))])
+        rgb, hits, _, _ = render_world(hip, world, cam, 0)
+        hit, d, X, ng, ns, _ = restated_states(hip, cam, hits, lambda X: sphere_normals(t, X), ff.inverse(t).flat(), bump)
+        over = X + ng * EPSILON
+        v = lp - over
+        l = v / np.sqrt(dot3(v, v))[:, None]
+        lng = dot3(l, ng)
+        keep = np.abs(lng) >= 1e-3
+        eff = col * li
+        ldn = dot3(l, ns)
+        lit = (lng > 0.0) & (ldn >= 0.0)
+        diffuse = np.where(lit[:, None], eff * dif * ldn[:, None], 0.0)
+        rf = -l - ns * (2.0 * dot3(-l, ns))[:, None]
+        rde = dot3(rf, -d)
+        with np.errstate(invalid="ignore"):
+            spec = np.where((lit & (rde > 0.0))[:, None], li * spe * np.power(np.where(rde > 0.0, rde, 0.0), shi)[:, None], 0.0)
+        want = (eff * amb + diffuse) + spec
+        err = float(np.abs(rgb[hit][keep] - want[keep]).max())
+        print("lighting, %s, path %s: %d hit pixels, %d left out, max |dRGB| = %.3e" % (bump.kind, path, int(hit.sum()), int((~keep).sum()), err))
+        assert hit.sum() > 150 and (~keep).sum() <= 0.02 * hit.sum()
+        assert err <= RGB_TOL
+        smooth, _, _, _ = render_world(hip, World(world.lights, [Element.sphere(ShapeArgs(transform=t, material=dataclasses.replace(mat, bump=None)))]), cam, 0)
+        assert float(np.abs(smooth - rgb).max()) > 0.05                            # far outside the tolerance: the bump is in the frame
+
+
+# ---- 5. path against path, one scene per row of RTC_NP_BUILDS ---------------------------------------------------------------------------------
+ROWS = {  # row -> (scene of tests/build_matrix.py or the open world with the teapot, with a background?)
+    0: ("csg", False), 1: ("area_csg_real", False), 2: ("uv_real", False), 3: ("uv_area_real", False), 4: ("spot_real", False), 5: ("uv_spot_real", False),
+    6: ("open", True), 7: ("area_kops_real", True), 8: ("uv_real", True), 9: ("uv_area_real", True), 10: ("spot_real", True), 11: ("uv_spot_real", True),
+}
+
+
+def row_world(row, tmp_path):
+    name, bg = ROWS[row]
+    sky = real_backgrounds()[0][1]
+    if name == "open":                                                               # a glass-and-mirror ball, a CSG solid and the low teapot
+        return bm.camera(), open_world(sky)
+    cam, world = bm.BY_NAME[name].make(tmp_path)
+    if bg:
+        world = World(world.lights, world.elements[:1] + world.elements[2:], sky)   # without the back wall: the sky is in frame
+    return cam, world
+
+
+@pytest.mark.parametrize("row", sorted(ROWS))
+def test_path_against_path_on_every_np_build(hip, row, tmp_path, monkeypatch):
+    cam, twin = row_world(row, tmp_path)
+    world = bumped(twin, mixed)
+    frames = []
+    for path in PATHS:
+        monkeypatch.setenv("RTC_KERNEL", path)
+        nw = hip.build_world(world)
+        info = bump_info(hip, nw)
+        assert info.has_bump == 1 and info.trace_build == row and info.trace_bg == (1 if row >= 6 else 0), (row, info.trace_build)
+        assert (info.trace_area, info.trace_uv, info.trace_spot) == {0: (0, 0, 0), 1: (1, 0, 0), 2: (0, 1, 0), 3: (1, 1, 0), 4: (1, 0, 1), 5: (1, 1, 1)}[row % 6]
+        assert info.wf_shade_build == info.trace_uv
+        frames.append(render_scene(bind(hip.lib), bm.scene_of(hip, nw), cam, FUEL))
+        frames[-1] += (hip.color_at(nw, bm.rays_for(World(bm.LIGHTS, twin.elements), 512), FUEL),)   # (rays towards point lights' places)
+        nw.close()
+    same_frames(frames[0], frames[1], "row %d, both paths" % row)
+    assert same_bits(frames[0][4][0], frames[1][4][0]) and frames[0][4][1].tobytes() == frames[1][4][1].tobytes(), "row %d: explicit rays" % row
+    smooth = render_world(hip, twin, cam)
+    assert smooth[1].tobytes() == frames[1][1].tobytes()                             # the same primary hits as its twin ...
+    assert (smooth[0] != frames[1][0]).any(axis=1).mean() > 0.3                      # ... under other pixels
+    assert frames[0][3].rays_reflect > 0 and frames[0][3].rays_refract > 0
+
+
+# ---- 6. shapes of the launch ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("path", PATHS)
+def test_frame_shapes_and_pixel_lists(hip, path, monkeypatch):
+    monkeypatch.setenv("RTC_KERNEL", path)
+    world = bumped(open_world(real_backgrounds()[0][1]), mixed)
+    nw = hip.build_world(world)
+    lib = bind(hip.lib)
+    monkeypatch.setenv("RTC_KERNEL", "1" if path == "4" else "4")
+    other = hip.build_world(world)
+    for h, v in ((37, 19), (1, 1)):                                                  # tile padding on the wavefront path
+        cam = bm.camera(h=h, v=v)
+        same_frames(render_scene(lib, bm.scene_of(hip, nw), cam, FUEL), render_scene(lib, bm.scene_of(hip, other), cam, FUEL), "%dx%d, both paths" % (h, v))
+    cam = bm.camera(h=37, v=19)
+    full, full_hits = hip.render(nw, cam, FUEL)
+    idx = np.random.default_rng(9).integers(0, 37 * 19, 300).astype(np.uint64)       # unordered, with repeats
+    assert len(np.unique(idx)) < len(idx)
+    rgb, hits = hip.render(nw, cam, FUEL, idx)
+    assert same_bits(rgb, full[idx]) and hits.tobytes() == full_hits[idx].tobytes()
+
+
+# ---- 7. every entry point carries it ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("path", PATHS)
+def test_every_entry_point_carries_the_bumps(hip, path, monkeypatch):
+    monkeypatch.setenv("RTC_KERNEL", path)
+    lib = bind(hip.lib)
+    cam = bm.camera()
+    world = bumped(open_world(real_backgrounds()[0][1]), mixed)
+    nw = hip.build_world(world)
+    frame, _ = hip.render(nw, cam, FUEL)
+    smooth, _ = hip.render(hip.build_world(open_world(real_backgrounds()[0][1])), cam, FUEL)
+    assert (frame != smooth).any(axis=1).mean() > 0.3
+    assert same_bits(hip.render_sampled(nw, cam, Sampling(1), FUEL), frame)
+    sp = Sampling(2)
+    sampled = hip.render_sampled(nw, cam, sp, FUEL)
+    assert same_bits(hip.render_adaptive(nw, cam, Adaptive(sp, Sampling(3), math.inf), FUEL), sampled)
+    assert same_bits(hip.render_filtered(nw, cam, sp, Filter.box(0.5), FUEL), sampled)
+    assert same_bits(hip.render_shutter([nw], [cam], sp, Shutter(), FUEL), sampled)
+    rgb8 = np.zeros((48 * 32, 3), dtype=np.uint8)
+    rc = ff.make_camera(cam)
+    assert lib.rtc_render_rgb8(bm.scene_of(hip, nw), C.byref(rc), FUEL, rgb8.ctypes.data, None) == 0, lib.rtc_last_error()
+    assert np.array_equal(rgb8, quantised(frame))
+    # rtc_scene_create_ext4 / rtc_multi_create_ext4 on a descriptor of the foreign flattener's, one record on every material; device 0 alone
+    plain_world = open_world(pot=False)                                              # (the foreign flattener has no OBJ loader)
+    desc = ff.flatten(plain_world).desc()
+    one = Bump.fractal(2, 0.2, 1.1)
+    recs = (RtcBump * desc.n_materials)(*[RtcBump(k, FRACTAL, 2, 0, 0.2, 1.1) for k in range(desc.n_materials)])
+    s = vp()
+    assert lib.rtc_scene_create_ext4(C.byref(desc), None, None, 0, None, recs, desc.n_materials, 0, C.byref(s)) == 0, lib.rtc_last_error()
+    single = render_scene(lib, s, cam, FUEL)
+    info = RtcBumpInfo()
+    assert lib.rtc_scene_bump_info(s, C.byref(info)) == 0 and info.has_bump == 1 and info.n_bumps == desc.n_materials and info.trace_build == 0
+    lib.rtc_scene_destroy(s)
+    same_frames(single, render_world(hip, bumped(plain_world, lambda k: one), cam), "ext4 on a descriptor against the Python layer, path %s" % path)
+    m, devs = vp(), (C.c_int * 1)(0)
+    assert lib.rtc_multi_create_ext4(C.byref(desc), None, None, 0, None, recs, desc.n_materials, devs, 1, C.byref(m)) == 0, lib.rtc_last_error()
+    mrgb = np.full((48 * 32, 3), np.nan)
+    assert lib.rtc_render_multi(m, C.byref(rc), FUEL, mrgb.ctypes.data, None) == 0, lib.rtc_last_error()
+    lib.rtc_multi_destroy(m)
+    assert same_bits(mrgb, single[0])
+    # n_bumps == 0 is rtc_scene_create_ext3
+    assert lib.rtc_scene_create_ext4(C.byref(desc), None, None, 0, None, recs, 0, 0, C.byref(s)) == 0, lib.rtc_last_error()
+    a = render_scene(lib, s, cam, FUEL)
+    assert lib.rtc_scene_bump_info(s, C.byref(info)) == 0 and info.has_bump == 0
+    lib.rtc_scene_destroy(s)
+    assert lib.rtc_scene_create_ext3(C.byref(desc), None, None, 0, None, 0, C.byref(s)) == 0, lib.rtc_last_error()
+    b = render_scene(lib, s, cam, FUEL)
+    lib.rtc_scene_destroy(s)
+    same_frames(a, b, "n_bumps == 0 against _ext3, path %s" % path)
+
+
+def test_par_render_of_bump_showcase(hip, monkeypatch):
+    cam, world = scenes.bump_showcase(96, 54)
+    img = Image.par_render(cam, world)
+    px = np.asarray(img.pixels).reshape(-1, 3)
+    assert px.shape == (96 * 54, 3) and np.isfinite(px).all()
+    frames = []
+    for path in PATHS:
+        monkeypatch.setenv("RTC_KERNEL", path)
+        frames.append(render_world(hip, world, cam))
+    monkeypatch.delenv("RTC_KERNEL")
+    same_frames(frames[0], frames[1], "bump_showcase, both paths")
+    assert np.array_equal(frames[0][0], px)
+    info_world = hip.build_world(world)
+    info = bump_info(hip, info_world)
+    assert info.has_bump == 1 and info.n_bumps == 3 and info.trace_build == 7        # an area light and a background
+    smooth = render_world(hip, World(world.lights, bumped(world, lambda k: None).elements, world.background), cam)
+    assert (smooth[0] != px).any(axis=1).mean() > 0.3
