@@ -13,6 +13,7 @@
 #include <cstring>
 #include <deque>
 #include <functional>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -176,24 +177,32 @@ struct rtc_scene {
 
 namespace {
 
-int ensure_px(rtc_scene* s, uint64_t n, bool hits) {
-  if (n > s->cap_px) {
-    (void)hipFree(s->d_rgb); (void)hipFree(s->d_hit_t); (void)hipFree(s->d_hit_prim); (void)hipFree(s->d_hit_k);  // hipFree(nullptr) is a no-op
-    s->d_rgb = nullptr; s->d_hit_t = nullptr; s->d_hit_prim = nullptr; s->d_hit_k = nullptr; s->cap_px = 0;
-    HIP_OK(hipMalloc((void**)&s->d_rgb, n * 3 * sizeof(double)));
-    HIP_OK(hipMalloc((void**)&s->d_hit_t, n * sizeof(double)));
-    HIP_OK(hipMalloc((void**)&s->d_hit_prim, n * sizeof(int)));
-    HIP_OK(hipMalloc((void**)&s->d_hit_k, n * sizeof(int)));
-    s->cap_px = n;
-  }
-  if (hits && n > s->cap_hits) {
-    (void)hipFree(s->d_hits);
-    s->d_hits = nullptr; s->cap_hits = 0;
-    HIP_OK(hipMalloc((void**)&s->d_hits, n * sizeof(DHit)));
-    s->cap_hits = n;
-  }
+// Grows the device scratch buffers that share the capacity `*cap` to `need` elements; nothing happens (no wait either) when the
+// capacity suffices.  Otherwise every buffer is freed and nulled and the capacity zeroed before the first hipMalloc, so that a failed
+// allocation leaves a consistent scene.  `wait`: a stream whose queued work may still use the buffers, waited for before they are
+// freed (the buffers a chunked launch reuses on the stream, the wavefront digests, the CSG slab).  The others pass none: they are
+// written and read within one synchronous call, and hipFree (hipFree(nullptr) is a no-op) waits for the device anyway.
+struct GrowBuf { void** p; uint64_t bytes; };
+int grow(uint64_t* cap, uint64_t need, std::initializer_list<GrowBuf> bufs, hipStream_t wait = nullptr) {
+  if (need <= *cap) return RTC_OK;
+  if (wait) HIP_OK(hipStreamSynchronize(wait));
+  for (const GrowBuf& b : bufs) { (void)hipFree(*b.p); *b.p = nullptr; }
+  *cap = 0;
+  for (const GrowBuf& b : bufs) HIP_OK(hipMalloc(b.p, b.bytes));
+  *cap = need;
   return RTC_OK;
 }
+
+int ensure_px(rtc_scene* s, uint64_t n, bool hits) {
+  int rc = grow(&s->cap_px, n, {{(void**)&s->d_rgb, n * 3 * sizeof(double)}, {(void**)&s->d_hit_t, n * sizeof(double)},
+                                {(void**)&s->d_hit_prim, n * sizeof(int)}, {(void**)&s->d_hit_k, n * sizeof(int)}});
+  if (rc == RTC_OK && hits) rc = grow(&s->cap_hits, n, {{(void**)&s->d_hits, n * sizeof(DHit)}});
+  return rc;
+}
+// the quantised pixels of a launch whose caller wants bytes (render_to_host): n x 3
+int ensure_rgb8(rtc_scene* s, uint64_t n) { return grow(&s->cap_rgb8, 3 * n, {{(void**)&s->d_rgb8, 3 * n}}); }
+// d_rays for n explicit rays (or as many doubles of another kind): n x 6
+int ensure_rays(rtc_scene* s, uint64_t n) { return grow(&s->cap_rays, n, {{(void**)&s->d_rays, n * 6 * sizeof(double)}}); }
 
 // ---- device -> host for the caller's output buffers (Image::par_render returns host pixels, src/image.rs:76-80) ----------------
 // Measured on the GPU box (scripts/d2h_probe.hip, profiles/r3_d2h_probe.txt): a pageable hipMemcpy runs at PCIe speed (52-56 GB/s,
@@ -225,7 +234,7 @@ void join_all(std::vector<std::thread>* pool) {
 // n_work rays (1.125 x to start with: a level larger than the frame's work ids needs most hits to spawn two rays).  A level that
 // needs more sets the overflow flag; a synchronous launch then doubles the factor and renders again while the arrays stay
 // under RTC_WF_MAX_BYTES (default 24 GiB), else falls back to the one-kernel path.
-uint64_t wave_cap(const rtc_scene* s, uint64_t n_work, unsigned eighths) { (void)s; return std::max<uint64_t>((n_work * eighths + 7) / 8, 4096); }
+uint64_t wave_cap(uint64_t n_work, unsigned eighths) { return std::max<uint64_t>((n_work * eighths + 7) / 8, 4096); }
 uint64_t wave_bytes(uint64_t cap, int lv) { return dwave_bytes(cap, lv); }
 uint64_t wave_budget() {
   const char* e = std::getenv("RTC_WF_MAX_BYTES");
@@ -233,7 +242,7 @@ uint64_t wave_budget() {
 }
 int ensure_wave(rtc_scene* s, uint64_t n_work, int fuel) {
   const int levels = fuel + 1;
-  uint64_t cap = wave_cap(s, n_work, s->wave_eighths);
+  uint64_t cap = wave_cap(n_work, s->wave_eighths);
   if (cap > 0x7fffff00ull || wave_bytes(cap, levels) > wave_budget()) return rtc_fail(RTC_ERR_UNSUPPORTED, "launch too large for the wavefront path");
   if (cap <= s->wave_cap && levels <= s->wave_levels) return RTC_OK;
   cap = std::max(cap, s->wave_cap);
@@ -303,6 +312,15 @@ int pick_path(rtc_scene* s, uint64_t sig, uint64_t n_work, int fuel, bool will_s
   const int ng = s->tune_n[guess == 4 ? 1 : 0], no = s->tune_n[other == 4 ? 1 : 0];
   return ng <= no ? guess : other;
 }
+// The wavefront path is no candidate for the current signature any more (its queues were refused or overflowed): the choice is made.
+void drop_wavefront(rtc_scene* s) { s->tune_ms[1] = 1e30; s->tune_n[1] = 2; s->tune_choice = 1; }
+// One sample of pick_path's measurement: `ms` of a launch of the current signature on the one-kernel or the wavefront path.
+void record_sample(rtc_scene* s, bool wavefront, double ms) {
+  const int k = wavefront ? 1 : 0;
+  s->tune_ms[k] = s->tune_n[k] ? std::min(s->tune_ms[k], ms) : ms;
+  s->tune_n[k]++;
+  if (s->tune_n[0] >= 2 && s->tune_n[1] >= 2) s->tune_choice = s->tune_ms[1] < s->tune_ms[0] ? 4 : 1;
+}
 
 // Sticky error state of the scene (DStats tail): read and cleared together.
 int read_clear_sticky(rtc_scene* s, DStats* h) {
@@ -356,11 +374,8 @@ int run(rtc_scene* s, const DCamera& cam, DPixelMap pm, int fuel, double* d_rgb,
       const char* e = std::getenv("RTC_CSG_MAX_BYTES");
       if (bytes > (e ? std::strtoull(e, nullptr, 10) : (16ull << 30)))
         return rtc_fail(RTC_ERR_UNSUPPORTED, "the CSG intersection slab of this launch exceeds RTC_CSG_MAX_BYTES: render fewer pixels per call");
-      HIP_OK(hipStreamSynchronize(s->stream));
-      (void)hipFree(s->csg_slab);
-      s->csg_slab = nullptr; s->csg_slab_threads = 0;
-      HIP_OK(hipMalloc((void**)&s->csg_slab, bytes));
-      s->csg_slab_threads = threads;
+      const int rc = grow(&s->csg_slab_threads, threads, {{(void**)&s->csg_slab, bytes}}, s->stream);
+      if (rc != RTC_OK) return rc;
     }
     s->d.csg_slab = s->csg_slab;
   }
@@ -368,7 +383,7 @@ int run(rtc_scene* s, const DCamera& cam, DPixelMap pm, int fuel, double* d_rgb,
     int rc = ensure_wave(s, rtc_wavefront_work(cam, pm), fuel);
     if (rc == RTC_ERR_UNSUPPORTED && force == 0) {
       // does not fit the memory budget / the device's free memory: this launch shape stays on the one-kernel path (same bits)
-      if (tuned) { s->tune_ms[1] = 1e30; s->tune_n[1] = 2; s->tune_choice = 1; }
+      if (tuned) drop_wavefront(s);
       else s->wave_alloc_failed = true;
       return run(s, cam, pm, fuel, d_rgb, want_hits, stats, count, sync, 1, after);
     }
@@ -376,13 +391,8 @@ int run(rtc_scene* s, const DCamera& cam, DPixelMap pm, int fuel, double* d_rgb,
     s->wave.dig = nullptr;
     if (pm.digest && count) {  // parity launch: (levels) x cap hit hashes beside the queues
       const uint64_t need = (uint64_t)s->wave_cap * (uint64_t)(fuel + 1);
-      if (need > s->cap_wave_dig) {
-        HIP_OK(hipStreamSynchronize(s->stream));
-        (void)hipFree(s->d_wave_dig);
-        s->d_wave_dig = nullptr; s->cap_wave_dig = 0;
-        HIP_OK(hipMalloc((void**)&s->d_wave_dig, need * sizeof(unsigned long long)));
-        s->cap_wave_dig = need;
-      }
+      rc = grow(&s->cap_wave_dig, need, {{(void**)&s->d_wave_dig, need * sizeof(unsigned long long)}}, s->stream);
+      if (rc != RTC_OK) return rc;
       s->wave.dig = s->d_wave_dig;
     }
     HIP_OK(hipMemsetAsync(s->wave.counts, 0, RTC_WF_COUNTS * sizeof(uint32_t), s->stream));
@@ -418,22 +428,19 @@ int run(rtc_scene* s, const DCamera& cam, DPixelMap pm, int fuel, double* d_rgb,
     HIP_OK(hipMemcpy(&overflow, s->wave.counts + RTC_WF_OVERFLOW, sizeof(overflow), hipMemcpyDeviceToHost));
     if (overflow) {  // a level outgrew its queue: larger queues if they fit the budget, else the one-kernel path (always fits)
       const uint64_t n_work = rtc_wavefront_work(cam, pm);
-      if (s->wave_eighths < 512 && wave_bytes(wave_cap(s, n_work, 2 * s->wave_eighths), fuel + 1) <= wave_budget() && wave_cap(s, n_work, 2 * s->wave_eighths) <= 0x7fffff00ull) {
+      if (s->wave_eighths < 512 && wave_bytes(wave_cap(n_work, 2 * s->wave_eighths), fuel + 1) <= wave_budget() && wave_cap(n_work, 2 * s->wave_eighths) <= 0x7fffff00ull) {
         s->wave_eighths *= 2;
         const int rc2 = run(s, cam, pm, fuel, d_rgb, want_hits, stats, count, true, 4, after);
         if (rc2 != RTC_ERR_UNSUPPORTED) return rc2;  // (the larger queues were refused by the device: fall through)
       }
-      if (tuned) { s->tune_ms[1] = 1e30; s->tune_n[1] = 2; s->tune_choice = 1; }
+      if (tuned) drop_wavefront(s);
       return run(s, cam, pm, fuel, d_rgb, want_hits, stats, count, true, 1, after);
     }
   }
   if (tuned && !count && pm.mode == 2 && !s->tune_choice) {
     float ms = 0.f;
     HIP_OK(hipEventElapsedTime(&ms, s->ev0, s->ev1));
-    const int k = wavefront ? 1 : 0;
-    s->tune_ms[k] = s->tune_n[k] ? std::min(s->tune_ms[k], (double)ms) : (double)ms;
-    s->tune_n[k]++;
-    if (s->tune_n[0] >= 2 && s->tune_n[1] >= 2) s->tune_choice = s->tune_ms[1] < s->tune_ms[0] ? 4 : 1;
+    record_sample(s, wavefront, ms);
   }
   if (stats) {
     int rcf = fill_stats(s, h, pm.n, stats);
@@ -468,12 +475,8 @@ int make_pixel_map(rtc_scene* s, uint64_t hsize, uint64_t total, const uint64_t*
   if (pixel_indices) {
     for (uint64_t i = 0; i < n; i++)
       if (pixel_indices[i] >= total) return rtc_fail(RTC_ERR_INVALID, "pixel index exceeds the image");
-    if (n > s->cap_idx) {
-      if (s->d_idx) (void)hipFree(s->d_idx);
-      s->d_idx = nullptr; s->cap_idx = 0;
-      HIP_OK(hipMalloc((void**)&s->d_idx, n * sizeof(uint64_t)));
-      s->cap_idx = n;
-    }
+    const int rc = grow(&s->cap_idx, n, {{(void**)&s->d_idx, n * sizeof(uint64_t)}});
+    if (rc != RTC_OK) return rc;
     HIP_OK(hipMemcpy(s->d_idx, pixel_indices, n * sizeof(uint64_t), hipMemcpyHostToDevice));
     pm->mode = 1; pm->indices = s->d_idx;
   }
@@ -481,6 +484,12 @@ int make_pixel_map(rtc_scene* s, uint64_t hsize, uint64_t total, const uint64_t*
 }
 int make_pixel_map(rtc_scene* s, const rtc_camera* cam, const uint64_t* pixel_indices, uint64_t first, uint64_t n, DPixelMap* pm, std::vector<uint64_t>* range_idx) {
   return make_pixel_map(s, cam->hsize, cam->hsize * cam->vsize, pixel_indices, first, n, pm, range_idx);
+}
+// The pixel map of the n pixels of whole rows from row_first on.
+DPixelMap rows_map(uint64_t n, uint32_t row_first = 0) {
+  DPixelMap pm{};
+  pm.n = n; pm.mode = 2; pm.row_first = row_first; pm.row_step = 1;
+  return pm;
 }
 
 // ---- the sampled camera (include/rtc.h rtc_sampling; kernels in rtc_camera.hip) ---------------------------------------------------
@@ -504,20 +513,16 @@ uint64_t sampled_max_rays() {
 }
 
 int ensure_sampled(rtc_scene* s, uint64_t n_rays, bool colours) {
-  if (n_rays > s->cap_srays) {
-    HIP_OK(hipStreamSynchronize(s->stream));
-    (void)hipFree(s->d_srays);
-    s->d_srays = nullptr; s->cap_srays = 0;
-    HIP_OK(hipMalloc((void**)&s->d_srays, n_rays * 6 * sizeof(double)));
-    s->cap_srays = n_rays;
-  }
-  if (colours && n_rays > s->cap_srgb) {
-    HIP_OK(hipStreamSynchronize(s->stream));
-    (void)hipFree(s->d_srgb);
-    s->d_srgb = nullptr; s->cap_srgb = 0;
-    HIP_OK(hipMalloc((void**)&s->d_srgb, n_rays * 3 * sizeof(double)));
-    s->cap_srgb = n_rays;
-  }
+  int rc = grow(&s->cap_srays, n_rays, {{(void**)&s->d_srays, n_rays * 6 * sizeof(double)}}, s->stream);
+  if (rc == RTC_OK && colours) rc = grow(&s->cap_srgb, n_rays, {{(void**)&s->d_srgb, n_rays * 3 * sizeof(double)}}, s->stream);
+  return rc;
+}
+
+// Pixels per chunk of a sampled launch over n pixels with N rays each: as many as RTC_SAMPLED_MAX_RAYS allows, in whole `unit`s (a row
+// of the frame, or one pixel of a list), never fewer than one unit.
+int sampled_chunk_px(uint64_t n, uint64_t unit, uint64_t N, uint64_t* chunk_px) {
+  *chunk_px = std::min<uint64_t>(n / unit, std::max<uint64_t>(1, sampled_max_rays() / (unit * N))) * unit;
+  if (*chunk_px * N > 0x7fffff00ull) return rtc_fail(RTC_ERR_UNSUPPORTED, "one row of this sampled launch exceeds 2^31 rays");
   return RTC_OK;
 }
 
@@ -530,14 +535,106 @@ uint64_t sampled_signature(const DCamera& cam, const DPixelMap& pm, const rtc_sa
   return h ? h : 1;
 }
 
+void add_stats(rtc_stats* a, const rtc_stats& b) {
+  a->rays_primary += b.rays_primary; a->rays_shadow += b.rays_shadow; a->rays_reflect += b.rays_reflect; a->rays_refract += b.rays_refract;
+  a->rays_container += b.rays_container; a->accel_nodes += b.accel_nodes; a->group_tests += b.group_tests; a->tri_tests += b.tri_tests;
+  a->analytic_tests += b.analytic_tests; a->nan_ts += b.nan_ts; a->n_launches += b.n_launches;
+  a->accel_nodes_kernarg += b.accel_nodes_kernarg; a->analytic_tests_kernarg += b.analytic_tests_kernarg;
+  a->light_grid_cells += b.light_grid_cells; a->group_tests_uniform += b.group_tests_uniform;
+  a->kernel_ms += b.kernel_ms;
+}
+
+// What the chunked launches (run_sampled, run_filtered) do alike.  All on the scene's stream, so the ray buffer d_srays and the per-ray
+// colours d_srgb are reused chunk after chunk; a synchronous launch reads every chunk's state back (a chunk whose wavefront queues
+// overflowed is rendered again by run() before its rays are overwritten; the resolves only write).
+//   begin(): the path of the call.  A tuned call goes through pick_path ONCE -- the signature is the whole launch's, the guess counts
+//     the rays of a chunk, the measurement is the sum of the chunks' trace times -- and every chunk takes that path; an untuned call
+//     leaves force at 0 (run() decides: the scene's pinned path, the one-kernel path for lists) unless the caller sets it.
+//   chunk(): `generate` fills d_srays with the chunk's n_rays rays, run() traces them as explicit rays into d_srgb, `resolve` queues the
+//     caller's kernel behind them as run()'s hook (again behind every attempt run() makes); `after` follows the last chunk's resolve.
+//     Queues that the device refuses and a fallback of run()'s own after an overflow move the rest of the call to the one-kernel path
+//     (same bits) and drop the wavefront candidate.  With stats: the chunk's counters, its launches + 2, the span evs0 .. evs1.
+//   end(): one sample of pick_path's measurement, as run() takes it, when the call kept its path; the pixel count of the stats.
+struct ChunkDriver {
+  rtc_scene* s;
+  int fuel;
+  rtc_stats* stats;
+  bool count, sync;
+  const AfterLaunch* after;
+  const char* resolve_name;  // of the caller's resolve kernel, for an error's text
+  bool tuned = false;
+  int force = 0, first_path = 0;
+  double trace_ms = 0.0;
+
+  bool will_sync() const { return sync || stats != nullptr; }
+  void begin(bool tune, uint64_t signature, uint64_t chunk_rays) {
+    tuned = tune;
+    if (tuned) {
+      force = pick_path(s, signature, chunk_rays, fuel, will_sync(), false);
+      if (force == 4 && s->wave_alloc_failed) force = 1;
+    }
+    first_path = force;
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+  }
+  int chunk(uint64_t n_rays, bool last, const std::function<void()>& generate, const std::function<void()>& resolve) {
+    if (stats) HIP_OK(hipEventRecord(s->evs0, s->stream));
+    generate();
+    HIP_OK(hipGetLastError());
+    DCamera ray_cam{};
+    ray_cam.hsize = 1; ray_cam.vsize = 1;
+    DPixelMap rm{};
+    rm.n = n_rays; rm.mode = 3; rm.rays = s->d_srays;
+    const AfterLaunch hook = [&]() -> int {
+      resolve();
+      hipError_t e = hipGetLastError();
+      if (e == hipSuccess && stats) e = hipEventRecord(s->evs1, s->stream);
+      if (e != hipSuccess) return rtc_fail(RTC_ERR_DEVICE, std::string(resolve_name) + ": " + hipGetErrorString(e));
+      return (last && after) ? (*after)() : RTC_OK;
+    };
+    rtc_stats st;
+    int rc = run(s, ray_cam, rm, fuel, s->d_srgb, false, stats ? &st : nullptr, count, sync, force, &hook);
+    if (rc == RTC_ERR_UNSUPPORTED && force == 4) {  // the queues were refused: this shape stays on the one-kernel path (same bits)
+      if (tuned) drop_wavefront(s);
+      force = 1;
+      rc = run(s, ray_cam, rm, fuel, s->d_srgb, false, stats ? &st : nullptr, count, sync, force, &hook);
+    }
+    if (rc != RTC_OK) return rc;
+    if (force == 4 && will_sync() && !s->last_wavefront) {  // run() rendered the chunk again on the one-kernel path after an overflow
+      if (tuned) drop_wavefront(s);
+      force = 1;
+    }
+    if (will_sync()) {
+      float ms = 0.f;
+      HIP_OK(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+      trace_ms += ms;
+    }
+    if (stats) {
+      float ms = 0.f;
+      HIP_OK(hipEventElapsedTime(&ms, s->evs0, s->evs1));
+      st.n_launches += 2u;
+      st.kernel_ms = ms;
+      add_stats(stats, st);
+    }
+    return RTC_OK;
+  }
+  void end(uint64_t pixels) {
+    if (tuned && will_sync() && !count && !s->tune_choice && force == first_path) record_sample(s, force == 4, trace_ms);
+    if (stats) stats->pixels = pixels;
+  }
+};
+// debug aid (RTC_SAMPLED_TIMING): the three parts of the chunk that chunk() just ran with stats, by the events around them
+int chunk_parts_ms(rtc_scene* s, float* generator, float* traces, float* resolve) {
+  HIP_OK(hipEventElapsedTime(generator, s->evs0, s->ev0));
+  HIP_OK(hipEventElapsedTime(traces, s->ev0, s->ev1));
+  HIP_OK(hipEventElapsedTime(resolve, s->ev1, s->evs1));
+  return RTC_OK;
+}
+
 // run() for a sampled camera: the pixel set `pm` (mode 1 or 2) is cut into chunks of whole rows (mode 2) or slices of the list (mode 1)
-// of at most RTC_SAMPLED_MAX_RAYS rays, never fewer than one row / pixel; per chunk rtc_gen_rays fills the scene's ray buffer, run()
-// traces it as explicit rays into the per-ray colours, rtc_resolve_samples writes the pixels' means to their slots of d_rgb.  All on
-// the scene's stream, so the two buffers are reused chunk after chunk.  A synchronous launch reads every chunk's state back (a chunk
-// whose wavefront queues overflowed is rendered again by run() before its rays are overwritten; the resolve only writes).
-// Path: whole-row launches go through pick_path ONCE per call -- the shape is the whole launch's (camera, sampling, rows, fuel), the
-// guess counts the rays of a chunk, the measurement is the sum of the chunks' trace times -- and every chunk takes that path; lists
-// are left to run(), which keeps them on the one-kernel path.  `after`: behind the last chunk's resolve (see run()).
+// of at most RTC_SAMPLED_MAX_RAYS rays, never fewer than one row / pixel; per chunk (ChunkDriver) rtc_gen_rays fills the scene's ray
+// buffer, run() traces it, rtc_resolve_samples writes the pixels' means to their slots of d_rgb.
+// Path: whole-row launches are tuned -- the shape is the whole launch's (camera, sampling, rows, fuel) --; lists are left to run(),
+// which keeps them on the one-kernel path.  `after`: behind the last chunk's resolve (see run()).
 // `scatter` (run_adaptive's refine pass; pm is a device-resident list): d_rgb is the whole FRAME and a slot's mean goes to its pixel
 // of it (rtc_resolve_samples_scatter); such a list may be millions of rays, 64 consecutive of which belong to four neighbouring
 // pixels, so its chunks take the scene's first guess over a chunk's rays (nothing is measured: the list changes with every frame).
@@ -547,83 +644,28 @@ int run_sampled(rtc_scene* s, const DCamera& cam, const DPixelMap& pm, const rtc
   HIP_OK(hipSetDevice(s->device));
   const uint64_t N = (uint64_t)sp.side * sp.side;
   const bool rows = pm.mode == 2;
-  const uint64_t unit = rows ? cam.hsize : 1;  // pixels a chunk grows by
-  const uint64_t chunk_px = std::min<uint64_t>(pm.n / unit, std::max<uint64_t>(1, sampled_max_rays() / (unit * N))) * unit;
-  if (chunk_px * N > 0x7fffff00ull) return rtc_fail(RTC_ERR_UNSUPPORTED, "one row of this sampled launch exceeds 2^31 rays");
-  int rc = ensure_sampled(s, chunk_px * N, true);
+  uint64_t chunk_px = 0;
+  int rc = sampled_chunk_px(pm.n, rows ? cam.hsize : 1, N, &chunk_px);
+  if (rc == RTC_OK) rc = ensure_sampled(s, chunk_px * N, true);
   if (rc != RTC_OK) return rc;
-  const bool will_sync = sync || stats != nullptr;
-  const bool tuned = rows && s->kernel_version == 0;
-  int force = 0;
-  if (tuned) {
-    force = pick_path(s, sampled_signature(cam, pm, sp, s->d.n_lights == 0 ? 0 : fuel), chunk_px * N, fuel, will_sync, false);
-    if (force == 4 && s->wave_alloc_failed) force = 1;
-  } else if (scatter && s->kernel_version == 0) {
-    force = s->wave_alloc_failed ? 1 : first_guess(s, chunk_px * N, fuel);
-  }
-  const int first_path = force;
-  if (stats) std::memset(stats, 0, sizeof(*stats));
-  double trace_ms = 0.0;
-  DCamera ray_cam{};
-  ray_cam.hsize = 1; ray_cam.vsize = 1;
+  ChunkDriver drv{s, fuel, stats, count, sync, after, "rtc_resolve_samples"};
+  drv.begin(rows && s->kernel_version == 0, sampled_signature(cam, pm, sp, s->d.n_lights == 0 ? 0 : fuel), chunk_px * N);
+  if (!drv.tuned && scatter && s->kernel_version == 0) drv.force = s->wave_alloc_failed ? 1 : first_guess(s, chunk_px * N, fuel);
   for (uint64_t p0 = 0; p0 < pm.n; p0 += chunk_px) {
     const uint64_t np = std::min(chunk_px, pm.n - p0);
-    const bool last = p0 + np == pm.n;
-    if (stats) HIP_OK(hipEventRecord(s->evs0, s->stream));
-    rtc_launch_gen_rays(cam, pm, sp, p0, np, s->d_srays, s->stream);
-    HIP_OK(hipGetLastError());
-    DPixelMap rm{};
-    rm.n = np * N; rm.mode = 3; rm.rays = s->d_srays;
-    const AfterLaunch resolve = [&]() -> int {
+    rc = drv.chunk(np * N, p0 + np == pm.n, [&] { rtc_launch_gen_rays(cam, pm, sp, p0, np, s->d_srays, s->stream); }, [&] {
       if (scatter) rtc_launch_resolve_samples_scatter(s->d_srgb, (unsigned)N, np, (const unsigned long long*)pm.indices + p0, d_rgb, s->stream);
       else rtc_launch_resolve_samples(s->d_srgb, (unsigned)N, np, d_rgb + 3 * p0, s->stream);
-      hipError_t e = hipGetLastError();
-      if (e == hipSuccess && stats) e = hipEventRecord(s->evs1, s->stream);
-      if (e != hipSuccess) return rtc_fail(RTC_ERR_DEVICE, std::string("rtc_resolve_samples: ") + hipGetErrorString(e));
-      return (last && after) ? (*after)() : RTC_OK;
-    };
-    rtc_stats st;
-    rc = run(s, ray_cam, rm, fuel, s->d_srgb, false, stats ? &st : nullptr, count, sync, force, &resolve);
-    if (rc == RTC_ERR_UNSUPPORTED && force == 4) {  // the queues were refused: this shape stays on the one-kernel path (same bits)
-      if (tuned) { s->tune_ms[1] = 1e30; s->tune_n[1] = 2; s->tune_choice = 1; }
-      force = 1;
-      rc = run(s, ray_cam, rm, fuel, s->d_srgb, false, stats ? &st : nullptr, count, sync, force, &resolve);
-    }
+    });
     if (rc != RTC_OK) return rc;
-    if (force == 4 && will_sync && !s->last_wavefront) {  // run() rendered the chunk again on the one-kernel path after an overflow
-      if (tuned) { s->tune_ms[1] = 1e30; s->tune_n[1] = 2; s->tune_choice = 1; }
-      force = 1;
-    }
-    if (will_sync) {
-      float ms = 0.f;
-      HIP_OK(hipEventElapsedTime(&ms, s->ev0, s->ev1));
-      trace_ms += ms;
-    }
-    if (stats) {
-      float ms = 0.f;
-      HIP_OK(hipEventElapsedTime(&ms, s->evs0, s->evs1));
-      if (std::getenv("RTC_SAMPLED_TIMING")) {  // debug aid (scripts/sampled_camera_probe.py): the chunk's three parts by the events around them
-        float g = 0.f, t = 0.f, r = 0.f;
-        HIP_OK(hipEventElapsedTime(&g, s->evs0, s->ev0));
-        HIP_OK(hipEventElapsedTime(&t, s->ev0, s->ev1));
-        HIP_OK(hipEventElapsedTime(&r, s->ev1, s->evs1));
-        std::fprintf(stderr, "[rtc-sampled] chunk of %llu rays: generator %.3f ms, traces %.3f ms, resolve %.3f ms\n", (unsigned long long)rm.n, g, t, r);
-      }
-      stats->rays_primary += st.rays_primary; stats->rays_shadow += st.rays_shadow; stats->rays_reflect += st.rays_reflect; stats->rays_refract += st.rays_refract;
-      stats->rays_container += st.rays_container; stats->accel_nodes += st.accel_nodes; stats->group_tests += st.group_tests; stats->tri_tests += st.tri_tests;
-      stats->analytic_tests += st.analytic_tests; stats->nan_ts += st.nan_ts; stats->n_launches += st.n_launches + 2u;
-      stats->accel_nodes_kernarg += st.accel_nodes_kernarg; stats->analytic_tests_kernarg += st.analytic_tests_kernarg;
-      stats->light_grid_cells += st.light_grid_cells; stats->group_tests_uniform += st.group_tests_uniform;
-      stats->kernel_ms += ms;
+    if (stats && std::getenv("RTC_SAMPLED_TIMING")) {  // debug aid (scripts/sampled_camera_probe.py)
+      float g = 0.f, t = 0.f, r = 0.f;
+      rc = chunk_parts_ms(s, &g, &t, &r);
+      if (rc != RTC_OK) return rc;
+      std::fprintf(stderr, "[rtc-sampled] chunk of %llu rays: generator %.3f ms, traces %.3f ms, resolve %.3f ms\n", (unsigned long long)(np * N), g, t, r);
     }
   }
-  if (tuned && will_sync && !count && !s->tune_choice && force == first_path) {  // one sample of pick_path's measurement, as run() takes it
-    const int k = force == 4 ? 1 : 0;
-    s->tune_ms[k] = s->tune_n[k] ? std::min(s->tune_ms[k], trace_ms) : trace_ms;
-    s->tune_n[k]++;
-    if (s->tune_n[0] >= 2 && s->tune_n[1] >= 2) s->tune_choice = s->tune_ms[1] < s->tune_ms[0] ? 4 : 1;
-  }
-  if (stats) stats->pixels = pm.n;
+  drv.end(pm.n);
   return RTC_OK;
 }
 
@@ -646,15 +688,8 @@ int check_contrast_frame(uint64_t hsize, uint64_t vsize) {
 // The compaction's buffers for a frame of n pixels, grown like d_srays.
 int ensure_adaptive(rtc_scene* s, uint64_t n) {
   if (!s->d_acount) HIP_OK(hipMalloc((void**)&s->d_acount, sizeof(unsigned long long)));
-  if (n > s->cap_alist) {
-    HIP_OK(hipStreamSynchronize(s->stream));
-    (void)hipFree(s->d_alist); (void)hipFree(s->d_awork);
-    s->d_alist = nullptr; s->d_awork = nullptr; s->cap_alist = 0;
-    HIP_OK(hipMalloc((void**)&s->d_alist, n * sizeof(unsigned long long)));
-    HIP_OK(hipMalloc((void**)&s->d_awork, rtc_contrast_work_words(n) * sizeof(unsigned long long)));  // (monotonic in n)
-    s->cap_alist = n;
-  }
-  return RTC_OK;
+  return grow(&s->cap_alist, n, {{(void**)&s->d_alist, n * sizeof(unsigned long long)},
+                                 {(void**)&s->d_awork, rtc_contrast_work_words(n) * sizeof(unsigned long long)}}, s->stream);  // (monotonic in n)
 }
 
 // Detect and compact over the frame in d_frame (hsize x vsize), on the stream; then the ONE read-back the host needs: the list's length.
@@ -674,23 +709,13 @@ int contrast_compact(rtc_scene* s, const double* d_frame, uint64_t hsize, uint64
   return RTC_OK;
 }
 
-void add_stats(rtc_stats* a, const rtc_stats& b) {
-  a->rays_primary += b.rays_primary; a->rays_shadow += b.rays_shadow; a->rays_reflect += b.rays_reflect; a->rays_refract += b.rays_refract;
-  a->rays_container += b.rays_container; a->accel_nodes += b.accel_nodes; a->group_tests += b.group_tests; a->tri_tests += b.tri_tests;
-  a->analytic_tests += b.analytic_tests; a->nan_ts += b.nan_ts; a->n_launches += b.n_launches;
-  a->accel_nodes_kernarg += b.accel_nodes_kernarg; a->analytic_tests_kernarg += b.analytic_tests_kernarg;
-  a->light_grid_cells += b.light_grid_cells; a->group_tests_uniform += b.group_tests_uniform;
-  a->kernel_ms += b.kernel_ms;
-}
-
 // The whole frame of `cam` into s->d_rgb (ensure_px'ed by the caller) under the rule `ad`: base pass, detect and compact, count
 // read-back, refine pass over the device-resident list with the scatter resolve.  `mask` / `n_refined`: optional host outputs.
 // `after`: queued behind the last kernel that writes the frame (see run()).
 int run_adaptive(rtc_scene* s, const DCamera& cam, const rtc_adaptive& ad, int fuel, rtc_stats* stats, uint8_t* mask, uint64_t* n_refined, const AfterLaunch* after) {
   const uint64_t n = cam.hsize * cam.vsize;
   const bool count = stats != nullptr;
-  DPixelMap rows{};
-  rows.n = n; rows.mode = 2; rows.row_first = 0; rows.row_step = 1;
+  const DPixelMap rows = rows_map(n);
   rtc_stats st_base, st_fine;
   std::memset(&st_fine, 0, sizeof(st_fine));
   // 1. base: one centre sample per pixel IS rtc_render's frame (include/rtc.h rtc_sampling), so it takes rtc_render's launch
@@ -764,16 +789,8 @@ int check_poses(rtc_scene* const* scenes, const rtc_camera* cameras, uint32_t n_
 
 // The dealing's buffers for a chunk of m samples, grown like d_srays.
 int ensure_shutter(rtc_scene* s, uint64_t m) {
-  if (m > s->cap_shutter) {
-    HIP_OK(hipStreamSynchronize(s->stream));
-    (void)hipFree(s->d_shorder); (void)hipFree(s->d_shwhere); (void)hipFree(s->d_shwork);
-    s->d_shorder = nullptr; s->d_shwhere = nullptr; s->d_shwork = nullptr; s->cap_shutter = 0;
-    HIP_OK(hipMalloc((void**)&s->d_shorder, m * sizeof(unsigned)));
-    HIP_OK(hipMalloc((void**)&s->d_shwhere, m * sizeof(unsigned)));
-    HIP_OK(hipMalloc((void**)&s->d_shwork, rtc_shutter_work_words(m) * sizeof(unsigned long long)));
-    s->cap_shutter = m;
-  }
-  return RTC_OK;
+  return grow(&s->cap_shutter, m, {{(void**)&s->d_shorder, m * sizeof(unsigned)}, {(void**)&s->d_shwhere, m * sizeof(unsigned)},
+                                   {(void**)&s->d_shwork, rtc_shutter_work_words(m) * sizeof(unsigned long long)}}, s->stream);
 }
 
 // Deal the m samples of the output slots slot_first .. of `pm` on s's stream (ensure_shutter'ed for m), then the ONE read-back the host
@@ -805,10 +822,9 @@ int run_shutter(rtc_scene* const* scenes, const DCamera* cams, uint32_t K, const
   if (fuel < 0) fuel = 0;
   HIP_OK(hipSetDevice(s->device));
   const uint64_t N = (uint64_t)sp.side * sp.side;
-  const uint64_t unit = pm.mode == 2 ? cams[0].hsize : 1;  // pixels a chunk grows by
-  const uint64_t chunk_px = std::min<uint64_t>(pm.n / unit, std::max<uint64_t>(1, sampled_max_rays() / (unit * N))) * unit;
-  if (chunk_px * N > 0x7fffff00ull) return rtc_fail(RTC_ERR_UNSUPPORTED, "one row of this sampled launch exceeds 2^31 rays");
-  int rc = ensure_sampled(s, chunk_px * N, true);
+  uint64_t chunk_px = 0;
+  int rc = sampled_chunk_px(pm.n, pm.mode == 2 ? cams[0].hsize : 1, N, &chunk_px);
+  if (rc == RTC_OK) rc = ensure_sampled(s, chunk_px * N, true);
   if (rc == RTC_OK) rc = ensure_shutter(s, chunk_px * N);
   if (rc != RTC_OK) return rc;
   const bool count = stats != nullptr;
@@ -896,11 +912,12 @@ uint64_t filtered_signature(const DCamera& cam, const DPixelMap& pm, const rtc_s
 
 // run_sampled for whole rows with a reconstruction filter: pm (mode 2, row_step 1, no bands) names the OUTPUT rows [a, b); they are cut
 // into chunks of whole rows, a chunk [a', b') traces the image rows [max(0, a' - W), min(vsize, b' + W)) -- rtc_gen_rays, run() over
-// explicit rays -- and rtc_resolve_filtered, the hook behind run()'s kernels, writes the chunk's own rows of d_rgb and nothing else, so a
-// chunk that run() renders again resolves to the same bits.  RTC_SAMPLED_MAX_RAYS bounds a chunk's TRACED rays, halo included, never
-// below one output row and its halo.  The halo rows are traced again by the neighbouring chunk: the two buffers stay reusable.
-// Path: pick_path once per call as run_sampled does; the shape also holds the filter (and pm the row range), the guess counts a chunk's
-// traced rays.  `after`: behind the last chunk's filter kernel (see run()).
+// explicit rays (ChunkDriver) -- and rtc_resolve_filtered, the hook behind run()'s kernels, writes the chunk's own rows of d_rgb and
+// nothing else, so a chunk that run() renders again resolves to the same bits.  RTC_SAMPLED_MAX_RAYS bounds a chunk's TRACED rays, halo
+// included, never below one output row and its halo.  The halo rows are traced again by the neighbouring chunk: the two buffers stay
+// reusable.
+// Path: always tuned (unless the scene's path is pinned); the shape also holds the filter (and pm the row range), the guess counts a
+// chunk's traced rays.  `after`: behind the last chunk's filter kernel (see run()).
 int run_filtered(rtc_scene* s, const DCamera& cam, const DPixelMap& pm, const rtc_sampling& sp, const rtc_filter& f, int fuel, double* d_rgb, rtc_stats* stats,
                  bool count, bool sync, const AfterLaunch* after = nullptr) {
   if (fuel < 0) fuel = 0;
@@ -913,92 +930,36 @@ int run_filtered(rtc_scene* s, const DCamera& cam, const DPixelMap& pm, const rt
   if (traced_rows * row_rays > 0x7fffff00ull) return rtc_fail(RTC_ERR_UNSUPPORTED, "one row of this filtered launch and its halo exceed 2^31 rays");
   int rc = ensure_sampled(s, traced_rows * row_rays, true);
   if (rc != RTC_OK) return rc;
-  const bool will_sync = sync || stats != nullptr;
-  const bool tuned = s->kernel_version == 0;
-  int force = 0;
-  if (tuned) {
-    force = pick_path(s, filtered_signature(cam, pm, sp, f, s->d.n_lights == 0 ? 0 : fuel), traced_rows * row_rays, fuel, will_sync, false);
-    if (force == 4 && s->wave_alloc_failed) force = 1;
-  }
-  const int first_path = force;
-  if (stats) std::memset(stats, 0, sizeof(*stats));
-  double trace_ms = 0.0;
-  DCamera ray_cam{};
-  ray_cam.hsize = 1; ray_cam.vsize = 1;
+  ChunkDriver drv{s, fuel, stats, count, sync, after, "rtc_resolve_filtered"};
+  drv.begin(s->kernel_version == 0, filtered_signature(cam, pm, sp, f, s->d.n_lights == 0 ? 0 : fuel), traced_rows * row_rays);
   for (uint64_t c0 = a; c0 < b; c0 += chunk_rows) {
     const uint64_t c1 = std::min(c0 + chunk_rows, b);
     const uint64_t t0 = c0 > W ? c0 - W : 0, t1 = std::min<uint64_t>(c1 + W, cam.vsize);
-    const bool last = c1 == b;
-    if (stats) HIP_OK(hipEventRecord(s->evs0, s->stream));
-    DPixelMap tm{};
-    tm.n = (t1 - t0) * cam.hsize; tm.mode = 2; tm.row_first = (uint32_t)t0; tm.row_step = 1;
-    rtc_launch_gen_rays(cam, tm, sp, 0, tm.n, s->d_srays, s->stream);
-    HIP_OK(hipGetLastError());
-    DPixelMap rm{};
-    rm.n = tm.n * N; rm.mode = 3; rm.rays = s->d_srays;
+    const DPixelMap tm = rows_map((t1 - t0) * cam.hsize, (uint32_t)t0);
     unsigned lds = 0, tile = 0;
-    const AfterLaunch resolve = [&]() -> int {
+    rc = drv.chunk(tm.n * N, c1 == b, [&] { rtc_launch_gen_rays(cam, tm, sp, 0, tm.n, s->d_srays, s->stream); }, [&] {
       lds = rtc_launch_resolve_filtered(f, sp, cam.hsize, t0, t1, c0, c1, s->d_srgb, d_rgb + 3 * (c0 - a) * cam.hsize, s->stream, &tile);
-      hipError_t e = hipGetLastError();
-      if (e == hipSuccess && stats) e = hipEventRecord(s->evs1, s->stream);
-      if (e != hipSuccess) return rtc_fail(RTC_ERR_DEVICE, std::string("rtc_resolve_filtered: ") + hipGetErrorString(e));
-      return (last && after) ? (*after)() : RTC_OK;
-    };
-    rtc_stats st;
-    rc = run(s, ray_cam, rm, fuel, s->d_srgb, false, stats ? &st : nullptr, count, sync, force, &resolve);
-    if (rc == RTC_ERR_UNSUPPORTED && force == 4) {  // the queues were refused: this shape stays on the one-kernel path (same bits)
-      if (tuned) { s->tune_ms[1] = 1e30; s->tune_n[1] = 2; s->tune_choice = 1; }
-      force = 1;
-      rc = run(s, ray_cam, rm, fuel, s->d_srgb, false, stats ? &st : nullptr, count, sync, force, &resolve);
-    }
+    });
     if (rc != RTC_OK) return rc;
-    if (force == 4 && will_sync && !s->last_wavefront) {  // run() rendered the chunk again on the one-kernel path after an overflow
-      if (tuned) { s->tune_ms[1] = 1e30; s->tune_n[1] = 2; s->tune_choice = 1; }
-      force = 1;
-    }
-    if (will_sync) {
-      float ms = 0.f;
-      HIP_OK(hipEventElapsedTime(&ms, s->ev0, s->ev1));
-      trace_ms += ms;
-    }
-    if (stats) {
-      float ms = 0.f;
-      HIP_OK(hipEventElapsedTime(&ms, s->evs0, s->evs1));
-      if (std::getenv("RTC_SAMPLED_TIMING")) {  // debug aid (scripts/filter_probe.py): the chunk's three parts by the events around them
-        float g = 0.f, t = 0.f, r = 0.f;
-        HIP_OK(hipEventElapsedTime(&g, s->evs0, s->ev0));
-        HIP_OK(hipEventElapsedTime(&t, s->ev0, s->ev1));
-        HIP_OK(hipEventElapsedTime(&r, s->ev1, s->evs1));
-        std::fprintf(stderr, "[rtc-filtered] chunk of %llu rays for %llu rows: generator %.3f ms, traces %.3f ms, filter %.3f ms (%s, tile %ux%u, %u B of LDS)\n",
-                     (unsigned long long)rm.n, (unsigned long long)(c1 - c0), g, t, r, lds ? "LDS" : "memory", tile >> 16, tile & 0xffffu, lds);
-      }
-      st.n_launches += 2u;
-      st.kernel_ms = ms;
-      add_stats(stats, st);
+    if (stats && std::getenv("RTC_SAMPLED_TIMING")) {  // debug aid (scripts/filter_probe.py)
+      float g = 0.f, t = 0.f, r = 0.f;
+      rc = chunk_parts_ms(s, &g, &t, &r);
+      if (rc != RTC_OK) return rc;
+      std::fprintf(stderr, "[rtc-filtered] chunk of %llu rays for %llu rows: generator %.3f ms, traces %.3f ms, filter %.3f ms (%s, tile %ux%u, %u B of LDS)\n",
+                   (unsigned long long)(tm.n * N), (unsigned long long)(c1 - c0), g, t, r, lds ? "LDS" : "memory", tile >> 16, tile & 0xffffu, lds);
     }
   }
-  if (tuned && will_sync && !count && !s->tune_choice && force == first_path) {  // one sample of pick_path's measurement, as run() takes it
-    const int k = force == 4 ? 1 : 0;
-    s->tune_ms[k] = s->tune_n[k] ? std::min(s->tune_ms[k], trace_ms) : trace_ms;
-    s->tune_n[k]++;
-    if (s->tune_n[0] >= 2 && s->tune_n[1] >= 2) s->tune_choice = s->tune_ms[1] < s->tune_ms[0] ? 4 : 1;
-  }
-  if (stats) stats->pixels = pm.n;
+  drv.end(pm.n);
   return RTC_OK;
 }
 
 // One launch whose results go to the caller's host buffers: rgb (n x 3 doubles) or rgb8 (n x 3 bytes, Color::clamp on the device),
-// and optionally the primary-hit records.  The destination's pages are touched by host threads while the device renders, the
-// copies are queued behind the kernels (see pretouch_pages above).
-// `sp`: the launch goes through run_sampled (no hit records).  `ad`: the whole frame through run_adaptive (pm covers it).
-// `sp` and `fl`: whole rows through run_filtered.
-// `sp` and `shu`: run_shutter over the poses (s = scenes[0], dc = its camera).
-struct AdaptiveOut { const rtc_adaptive* rule; uint8_t* mask; uint64_t* n_refined; };
-struct ShutterIn { rtc_scene* const* scenes; const DCamera* cams; uint32_t n_poses; const rtc_shutter* rule; };
-int render_to_host(rtc_scene* s, const DCamera& dc, const DPixelMap& pm, int fuel, double* rgb, uint8_t* rgb8, rtc_hit* hits, rtc_stats* stats,
-                   const rtc_sampling* sp = nullptr, const AdaptiveOut* ad = nullptr, const rtc_filter* fl = nullptr, const ShutterIn* shu = nullptr) {
+// and optionally the primary-hit records, all of the n pixels the launch leaves in the scene's buffers (ensure_px, ensure_rgb8).  The
+// destination's pages are touched by host threads while the device renders, the copies are queued behind the kernels (see
+// pretouch_pages above).  `body`: the launch itself -- run(), run_sampled(), run_adaptive(), run_filtered() or run_shutter() into
+// s->d_rgb, synchronous, with the hook it is handed as their `after`.
+int render_to_host(rtc_scene* s, uint64_t n, double* rgb, uint8_t* rgb8, rtc_hit* hits, const std::function<int(const AfterLaunch*)>& body) {
   static_assert(sizeof(DHit) == sizeof(rtc_hit) && offsetof(DHit, prim) == offsetof(rtc_hit, prim) && offsetof(DHit, k) == offsetof(rtc_hit, push_idx), "hit layout");
-  const uint64_t n = pm.n;
   std::vector<std::thread> pool;
   bool touched = false;
   const AfterLaunch after = [&]() -> int {
@@ -1018,14 +979,26 @@ int render_to_host(rtc_scene* s, const DCamera& dc, const DPixelMap& pm, int fue
     if (e != hipSuccess) return rtc_fail(RTC_ERR_DEVICE, std::string("copy to the host: ") + hipGetErrorString(e));
     return RTC_OK;
   };
-  const int rc = ad ? run_adaptive(s, dc, *ad->rule, fuel, stats, ad->mask, ad->n_refined, &after)
-                 : shu ? run_shutter(shu->scenes, shu->cams, shu->n_poses, *shu->rule, pm, *sp, fuel, s->d_rgb, stats, &after)
-                 : fl ? run_filtered(s, dc, pm, *sp, *fl, fuel, s->d_rgb, stats, stats != nullptr, true, &after)
-                 : sp ? run_sampled(s, dc, pm, *sp, fuel, s->d_rgb, stats, stats != nullptr, true, &after)
-                    : run(s, dc, pm, fuel, s->d_rgb, hits != nullptr, stats, stats != nullptr, true, 0, &after);
+  const int rc = body(&after);
   join_all(&pool);  // (an error before the hook ran its join)
   return rc;
 }
+
+// What the entry points with host pixels need on the device before their launch: the scene's device current, its pixel buffers for n
+// pixels (`hits`: the packed hit records too; `rgb8`: the quantised pixels too).
+int prepare_output(rtc_scene* s, uint64_t n, bool hits, bool rgb8) {
+  HIP_OK(hipSetDevice(s->device));
+  int rc = ensure_px(s, n, hits);
+  if (rc == RTC_OK && rgb8) rc = ensure_rgb8(s, n);
+  return rc;
+}
+// "empty camera" and, for a range (no index list), "pixel range exceeds the image"
+int check_pixel_range(const rtc_camera* cam, const uint64_t* pixel_indices, uint64_t first, uint64_t n) {
+  if (cam->hsize == 0 || cam->vsize == 0) return rtc_fail(RTC_ERR_INVALID, "empty camera");
+  if (!pixel_indices && first + n > cam->hsize * cam->vsize) return rtc_fail(RTC_ERR_INVALID, "pixel range exceeds the image");
+  return RTC_OK;
+}
+
 
 }  // namespace
 
@@ -1042,21 +1015,78 @@ int rtc_device_count(void) {
 }  // extern "C"
 
 namespace {
-// rtc_scene_create (ex == false) and rtc_scene_create_ex (ex == true: the lights are `lx`, desc->lights must be empty); `uv`: the UV
-// pattern records and textures of rtc_scene_create_ext; `cones`: the light cones of rtc_scene_create_ext2 (with ex == true only)
-// `bg`: the background of rtc_scene_create_ext3 (NULL: none); `bumps`: the bump records of rtc_scene_create_ext4
-int scene_create(const rtc_scene_desc* desc, bool ex, const rtc_light_ex* lx, uint32_t n_lx, int device, rtc_scene** out, const rtb::UvInput& uv = rtb::UvInput{},
-                 const rtb::ConeInput& cones = rtb::ConeInput{}, const rtc_background* bg = nullptr, const rtb::BumpInput& bumps = rtb::BumpInput{}) {
-  if (!desc || !out) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
-  *out = nullptr;
-  if (bg) {  // (its own limits first: they need no device)
-    std::string why;
+// What a creation call was given, in the one form scene_create takes (scene_inputs fills it for all twelve rtc_*_create* entry points).
+struct SceneInputs {
+  rtc_scene_desc desc{};             // the caller's descriptor; without its lights once they were converted into `lights`
+  bool ex = false;                   // the lights are lx[0 .. n_lx) for build_arrays_ex (desc.lights must be empty); else desc.lights
+  const rtc_light_ex* lx = nullptr;
+  uint32_t n_lx = 0;
+  std::vector<rtc_light_ex> lights;  // desc->lights as point lights of an rtc_light_ex list: cones sit on lights of that form
+  rtb::UvInput uv;                   // rtc_scene_create_ext: the UV pattern records and textures
+  rtb::ConeInput cones;              // rtc_scene_create_ext2: the light cones (with ex == true only)
+  bool has_bg = false;               // rtc_scene_create_ext3: the background
+  rtc_background bg{};
+  rtb::BumpInput bumps;              // rtc_scene_create_ext4: the bump records
+};
+
+// Fills `in` from a creation call's arguments and makes every check that needs no device, in this order: the descriptor, the bump
+// records, the background, the cones.  `*out` (the caller's handle) is cleared first, so every failure leaves it NULL.
+// Lights: `ext` with a light list, or `always_ex` (rtc_scene_create_ex: even an empty list), takes build_arrays_ex; cones on
+// desc->lights convert those into such a list; everything else stays with desc->lights and build_arrays.
+template <class Handle>
+int scene_inputs(const rtc_scene_desc* desc, const rtc_scene_ext* ext, bool always_ex, const rtc_light_cone* cones, uint32_t n_cones, const rtc_background* bg,
+                 const rtc_bump* bumps, uint32_t n_bumps, Handle** out, SceneInputs* in) {
+  if (out) *out = nullptr;
+  if (!desc) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  in->desc = *desc;
+  std::string why;
+  if (n_bumps > 0) {
+    in->bumps = rtb::BumpInput{bumps, n_bumps};
+    if (const int rc = rtb::validate_bumps(in->bumps, desc->n_materials, &why)) return rtc_fail(rc, why);
+  }
+  if (bg) {
     if (const int rc = rtb::validate_background(*bg, desc->n_pattern_nodes, &why)) return rtc_fail(rc, why);
+    in->has_bg = true;
+    in->bg = *bg;
   }
-  if (bumps.n) {
-    std::string why;
-    if (const int rc = rtb::validate_bumps(bumps, desc->n_materials, &why)) return rtc_fail(rc, why);
+  if (ext) in->uv = rtb::UvInput{ext->uv_patterns, ext->n_uv_patterns, ext->textures, ext->n_textures};
+  const bool ext_lights = ext && ext->n_lights > 0;
+  in->ex = ext_lights || always_ex;
+  if (in->ex) { in->lx = ext->lights; in->n_lx = ext->n_lights; }
+  if (n_cones == 0) return RTC_OK;
+  in->cones = rtb::ConeInput{cones, n_cones};
+  if (const int rc = rtb::validate_cones(in->cones, ext_lights ? ext->n_lights : desc->n_lights, &why)) return rtc_fail(rc, why);
+  if (ext_lights) return RTC_OK;
+  if (desc->n_lights > 0 && !desc->lights) return rtc_fail(RTC_ERR_INVALID, "lights is NULL");
+  in->lights.resize(desc->n_lights);
+  for (uint32_t i = 0; i < desc->n_lights; i++) {
+    rtc_light_ex x{};
+    x.kind = RTC_LIGHT_POINT;
+    std::memcpy(x.intensity, desc->lights[i].intensity, sizeof(x.intensity));
+    std::memcpy(x.corner, desc->lights[i].origin, sizeof(x.corner));
+    in->lights[i] = x;
   }
+  in->desc.n_lights = 0; in->desc.lights = nullptr;
+  in->ex = true; in->lx = in->lights.data(); in->n_lx = desc->n_lights;
+  return RTC_OK;
+}
+
+// rtc_scene_create_ex / rtc_multi_create_ex: the light list alone, as an ext that holds nothing else
+template <class Handle>
+int scene_inputs_ex(const rtc_scene_desc* desc, const rtc_light_ex* lights, uint32_t n_lights, Handle** out, SceneInputs* in) {
+  rtc_scene_ext ext{};
+  ext.lights = lights; ext.n_lights = n_lights;
+  return scene_inputs(desc, &ext, true, nullptr, 0, nullptr, nullptr, 0, out, in);
+}
+
+// One scene on one device from normalised inputs: its own checks (the handle, the device), then the host build (build_arrays or
+// build_arrays_ex, which validate the descriptor and the lights), the upload and the per-scene launch parameters.
+int scene_create(const SceneInputs& in, int device, rtc_scene** out) {
+  if (!out) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  *out = nullptr;
+  const rtc_scene_desc* desc = &in.desc;
+  const rtb::BumpInput& bumps = in.bumps;
+  const rtc_background* bg = in.has_bg ? &in.bg : nullptr;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return rtc_fail(RTC_ERR_DEVICE, "no HIP device available (this library has no CPU path)");
   if (device < 0 || device >= ndev) return rtc_fail(RTC_ERR_DEVICE, "device index out of range");
@@ -1071,8 +1101,8 @@ int scene_create(const rtc_scene_desc* desc, bool ex, const rtc_light_ex* lx, ui
   const char* dbe = std::getenv("RTC_DEVICE_BVH");
   const bool device_bvh = !(dbe && dbe[0] == '0');
   const size_t device_min = (dbe && dbe[0] == '1') ? 4096 : 100000;
-  int rc = ex ? rtb::build_arrays_ex(*desc, lx, n_lx, &H, &err, device_bvh ? rtc_bvh_build_device : nullptr, device_min, uv, cones)
-              : rtb::build_arrays(*desc, &H, &err, device_bvh ? rtc_bvh_build_device : nullptr, device_min, uv);
+  int rc = in.ex ? rtb::build_arrays_ex(*desc, in.lx, in.n_lx, &H, &err, device_bvh ? rtc_bvh_build_device : nullptr, device_min, in.uv, in.cones)
+                 : rtb::build_arrays(*desc, &H, &err, device_bvh ? rtc_bvh_build_device : nullptr, device_min, in.uv);
   if (rc != RTC_OK) return rtc_fail(rc, err);
   const bool timing = std::getenv("RTC_TIMING") != nullptr;
   const auto t_up0 = std::chrono::steady_clock::now();
@@ -1204,99 +1234,38 @@ int scene_create(const rtc_scene_desc* desc, bool ex, const rtc_light_ex* lx, ui
 
 extern "C" {
 
-int rtc_scene_create(const rtc_scene_desc* desc, int device, rtc_scene** out) { return scene_create(desc, false, nullptr, 0, device, out); }
+// The six entry points differ in what they can be given; what they are not given is empty (include/rtc.h).
+int rtc_scene_create(const rtc_scene_desc* desc, int device, rtc_scene** out) {
+  SceneInputs in;
+  if (const int rc = scene_inputs(desc, nullptr, false, nullptr, 0, nullptr, nullptr, 0, out, &in)) return rc;
+  return scene_create(in, device, out);
+}
 int rtc_scene_create_ex(const rtc_scene_desc* desc, const rtc_light_ex* lights, uint32_t n_lights, int device, rtc_scene** out) {
-  return scene_create(desc, true, lights, n_lights, device, out);
+  SceneInputs in;
+  if (const int rc = scene_inputs_ex(desc, lights, n_lights, out, &in)) return rc;
+  return scene_create(in, device, out);
 }
 int rtc_scene_create_ext(const rtc_scene_desc* desc, const rtc_scene_ext* ext, int device, rtc_scene** out) {
-  if (!ext) return scene_create(desc, false, nullptr, 0, device, out);
-  const rtb::UvInput uv{ext->uv_patterns, ext->n_uv_patterns, ext->textures, ext->n_textures};
-  return scene_create(desc, ext->n_lights > 0, ext->lights, ext->n_lights, device, out, uv);
+  SceneInputs in;
+  if (const int rc = scene_inputs(desc, ext, false, nullptr, 0, nullptr, nullptr, 0, out, &in)) return rc;
+  return scene_create(in, device, out);
 }
-
-}  // extern "C"
-
-namespace {
-// What rtc_scene_create_ext2 / rtc_multi_create_ext2 hand on: the cones' own limits are checked first (no device needed); a scene whose
-// cones sit on desc->lights gets those lights as an rtc_light_ex list, the form build_arrays_ex takes.
-struct SpotArgs {
-  rtc_scene_desc desc;
-  std::vector<rtc_light_ex> lights;
-  const rtc_light_ex* lx = nullptr;
-  uint32_t n_lx = 0;
-  rtb::UvInput uv;
-  rtb::ConeInput cones;
-};
-int spot_args(const rtc_scene_desc* desc, const rtc_scene_ext* ext, const rtc_light_cone* cones, uint32_t n_cones, SpotArgs* a) {
-  if (!desc) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
-  a->desc = *desc;
-  a->cones = rtb::ConeInput{cones, n_cones};
-  if (ext) a->uv = rtb::UvInput{ext->uv_patterns, ext->n_uv_patterns, ext->textures, ext->n_textures};
-  const bool ext_lights = ext && ext->n_lights > 0;
-  std::string err;
-  if (const int rc = rtb::validate_cones(a->cones, ext_lights ? ext->n_lights : desc->n_lights, &err)) return rtc_fail(rc, err);
-  if (ext_lights) { a->lx = ext->lights; a->n_lx = ext->n_lights; return RTC_OK; }
-  if (desc->n_lights > 0 && !desc->lights) return rtc_fail(RTC_ERR_INVALID, "lights is NULL");
-  a->lights.resize(desc->n_lights);
-  for (uint32_t i = 0; i < desc->n_lights; i++) {
-    rtc_light_ex x{};
-    x.kind = RTC_LIGHT_POINT;
-    std::memcpy(x.intensity, desc->lights[i].intensity, sizeof(x.intensity));
-    std::memcpy(x.corner, desc->lights[i].origin, sizeof(x.corner));
-    a->lights[i] = x;
-  }
-  a->desc.n_lights = 0; a->desc.lights = nullptr;
-  a->lx = a->lights.data(); a->n_lx = desc->n_lights;
-  return RTC_OK;
-}
-}  // namespace
-
-extern "C" {
-
 int rtc_scene_create_ext2(const rtc_scene_desc* desc, const rtc_scene_ext* ext, const rtc_light_cone* cones, uint32_t n_cones, int device, rtc_scene** out) {
-  if (n_cones == 0) return rtc_scene_create_ext(desc, ext, device, out);
-  if (out) *out = nullptr;
-  SpotArgs a;
-  if (const int rc = spot_args(desc, ext, cones, n_cones, &a)) return rc;
-  return scene_create(&a.desc, true, a.lx, a.n_lx, device, out, a.uv, a.cones);
+  SceneInputs in;
+  if (const int rc = scene_inputs(desc, ext, false, cones, n_cones, nullptr, nullptr, 0, out, &in)) return rc;
+  return scene_create(in, device, out);
 }
-
 int rtc_scene_create_ext3(const rtc_scene_desc* desc, const rtc_scene_ext* ext, const rtc_light_cone* cones, uint32_t n_cones, const rtc_background* bg, int device,
                           rtc_scene** out) {
-  if (!bg) return rtc_scene_create_ext2(desc, ext, cones, n_cones, device, out);
-  if (out) *out = nullptr;
-  if (!desc) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
-  std::string why;
-  if (const int rc = rtb::validate_background(*bg, desc->n_pattern_nodes, &why)) return rtc_fail(rc, why);
-  if (n_cones > 0) {
-    SpotArgs a;
-    if (const int rc = spot_args(desc, ext, cones, n_cones, &a)) return rc;
-    return scene_create(&a.desc, true, a.lx, a.n_lx, device, out, a.uv, a.cones, bg);
-  }
-  if (!ext) return scene_create(desc, false, nullptr, 0, device, out, rtb::UvInput{}, rtb::ConeInput{}, bg);
-  const rtb::UvInput uv{ext->uv_patterns, ext->n_uv_patterns, ext->textures, ext->n_textures};
-  return scene_create(desc, ext->n_lights > 0, ext->lights, ext->n_lights, device, out, uv, rtb::ConeInput{}, bg);
+  SceneInputs in;
+  if (const int rc = scene_inputs(desc, ext, false, cones, n_cones, bg, nullptr, 0, out, &in)) return rc;
+  return scene_create(in, device, out);
 }
-
 int rtc_scene_create_ext4(const rtc_scene_desc* desc, const rtc_scene_ext* ext, const rtc_light_cone* cones, uint32_t n_cones, const rtc_background* bg,
                           const rtc_bump* bumps, uint32_t n_bumps, int device, rtc_scene** out) {
-  if (n_bumps == 0) return rtc_scene_create_ext3(desc, ext, cones, n_cones, bg, device, out);
-  if (out) *out = nullptr;
-  if (!desc) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
-  const rtb::BumpInput bi{bumps, n_bumps};
-  std::string why;
-  if (const int rc = rtb::validate_bumps(bi, desc->n_materials, &why)) return rtc_fail(rc, why);
-  if (bg) {
-    if (const int rc = rtb::validate_background(*bg, desc->n_pattern_nodes, &why)) return rtc_fail(rc, why);
-  }
-  if (n_cones > 0) {
-    SpotArgs a;
-    if (const int rc = spot_args(desc, ext, cones, n_cones, &a)) return rc;
-    return scene_create(&a.desc, true, a.lx, a.n_lx, device, out, a.uv, a.cones, bg, bi);
-  }
-  if (!ext) return scene_create(desc, false, nullptr, 0, device, out, rtb::UvInput{}, rtb::ConeInput{}, bg, bi);
-  const rtb::UvInput uv{ext->uv_patterns, ext->n_uv_patterns, ext->textures, ext->n_textures};
-  return scene_create(desc, ext->n_lights > 0, ext->lights, ext->n_lights, device, out, uv, rtb::ConeInput{}, bg, bi);
+  SceneInputs in;
+  if (const int rc = scene_inputs(desc, ext, false, cones, n_cones, bg, bumps, n_bumps, out, &in)) return rc;
+  return scene_create(in, device, out);
 }
 
 int rtc_bump_normal(const rtc_bump* bump, const double material_inv[16], const double point[3], const double normal[3], double out[3]) {
@@ -1317,13 +1286,8 @@ int rtc_bump_normals(rtc_scene* s, const int32_t* prims, const double* points, c
   }
   HIP_OK(hipSetDevice(s->device));
   int rc = ensure_px(s, n, true);  // d_rgb: 3 rows of n doubles; d_hit_prim: n ints
+  if (rc == RTC_OK) rc = ensure_rays(s, n);  // d_rays: 6 rows of n doubles (the points' rows, then the normals')
   if (rc != RTC_OK) return rc;
-  if (n > s->cap_rays) {  // d_rays: 6 rows of n doubles (the points' rows, then the normals')
-    if (s->d_rays) (void)hipFree(s->d_rays);
-    s->d_rays = nullptr; s->cap_rays = 0;
-    HIP_OK(hipMalloc((void**)&s->d_rays, n * 6 * sizeof(double)));
-    s->cap_rays = n;
-  }
   std::vector<double> soa(6 * n);  // the kernel reads rows: a wave's loads are whole lines
   for (uint64_t i = 0; i < n; i++)
     for (int c = 0; c < 3; c++) { soa[c * n + i] = points[3 * i + c]; soa[(3 + c) * n + i] = normals[3 * i + c]; }
@@ -1364,13 +1328,8 @@ int rtc_background_colors(rtc_scene* s, const double* dirs, uint64_t n, double* 
   if (n == 0) return RTC_OK;
   HIP_OK(hipSetDevice(s->device));
   int rc = ensure_px(s, n, false);  // d_rgb: n x 3 doubles
+  if (rc == RTC_OK) rc = ensure_rays(s, (n + 1) / 2);  // d_rays holds 6 doubles per ray: n directions need half as many
   if (rc != RTC_OK) return rc;
-  if ((n + 1) / 2 > s->cap_rays) {  // d_rays holds 6 doubles per ray: n directions need half as many
-    if (s->d_rays) (void)hipFree(s->d_rays);
-    s->d_rays = nullptr; s->cap_rays = 0;
-    HIP_OK(hipMalloc((void**)&s->d_rays, ((n + 1) / 2) * 6 * sizeof(double)));
-    s->cap_rays = (n + 1) / 2;
-  }
   HIP_OK(hipMemcpyAsync(s->d_rays, dirs, n * 3 * sizeof(double), hipMemcpyHostToDevice, s->stream));
   rtc_launch_background_colors(s->d, s->bg, s->d_rays, n, s->d_rgb, s->stream);
   HIP_OK(hipGetLastError());
@@ -1432,12 +1391,10 @@ uint64_t rtc_scene_device_bytes(const rtc_scene* s) { return s ? s->bytes : 0; }
 int rtc_render(rtc_scene* s, const rtc_camera* cam, int32_t fuel, const uint64_t* pixel_indices, uint64_t first, uint64_t n, double* rgb, rtc_hit* hits,
                rtc_stats* stats) {
   if (!s || !cam || (!rgb && n)) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
-  if (cam->hsize == 0 || cam->vsize == 0) return rtc_fail(RTC_ERR_INVALID, "empty camera");
-  const uint64_t total = cam->hsize * cam->vsize;
-  if (!pixel_indices && first + n > total) return rtc_fail(RTC_ERR_INVALID, "pixel range exceeds the image");
+  int rc = check_pixel_range(cam, pixel_indices, first, n);
+  if (rc != RTC_OK) return rc;
   if (n == 0) { if (stats) std::memset(stats, 0, sizeof(*stats)); return RTC_OK; }
-  HIP_OK(hipSetDevice(s->device));
-  int rc = ensure_px(s, n, hits != nullptr);
+  rc = prepare_output(s, n, hits != nullptr, false);
   if (rc != RTC_OK) return rc;
   DPixelMap pm{};
   std::vector<uint64_t> range_idx;
@@ -1445,26 +1402,18 @@ int rtc_render(rtc_scene* s, const rtc_camera* cam, int32_t fuel, const uint64_t
   if (rc != RTC_OK) return rc;
   DCamera dc;
   to_dcam(*cam, &dc);
-  return render_to_host(s, dc, pm, fuel, rgb, nullptr, hits, stats);
+  return render_to_host(s, n, rgb, nullptr, hits, [&](const AfterLaunch* after) { return run(s, dc, pm, fuel, s->d_rgb, hits != nullptr, stats, stats != nullptr, true, 0, after); });
 }
 
 int rtc_render_hit_digest(rtc_scene* s, const rtc_camera* cam, int32_t fuel, const uint64_t* pixel_indices, uint64_t first, uint64_t n, uint64_t* digest) {
   if (!s || !cam || (!digest && n)) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
-  if (cam->hsize == 0 || cam->vsize == 0) return rtc_fail(RTC_ERR_INVALID, "empty camera");
-  const uint64_t total = cam->hsize * cam->vsize;
-  if (!pixel_indices && first + n > total) return rtc_fail(RTC_ERR_INVALID, "pixel range exceeds the image");
-  if (n == 0) return RTC_OK;
-  HIP_OK(hipSetDevice(s->device));
-  int rc = ensure_px(s, n, false);
+  int rc = check_pixel_range(cam, pixel_indices, first, n);
   if (rc != RTC_OK) return rc;
-  if (n > s->cap_digest) {
-    (void)hipFree(s->d_digest);
-    s->d_digest = nullptr; s->cap_digest = 0;
-    HIP_OK(hipMalloc((void**)&s->d_digest, n * sizeof(unsigned long long)));
-    s->cap_digest = n;
-  }
+  if (n == 0) return RTC_OK;
+  rc = prepare_output(s, n, false, false);
+  if (rc == RTC_OK) rc = grow(&s->cap_digest, n, {{(void**)&s->d_digest, n * sizeof(unsigned long long)}});
+  if (rc != RTC_OK) return rc;
   DPixelMap pm{};
-  pm.n = n;
   std::vector<uint64_t> range_idx;
   rc = make_pixel_map(s, cam, pixel_indices, first, n, &pm, &range_idx);
   if (rc != RTC_OK) return rc;
@@ -1481,21 +1430,13 @@ int rtc_render_hit_digest(rtc_scene* s, const rtc_camera* cam, int32_t fuel, con
 int rtc_render_rgb8(rtc_scene* s, const rtc_camera* cam, int32_t fuel, uint8_t* rgb8, rtc_stats* stats) {
   if (!s || !cam || !rgb8) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
   if (cam->hsize == 0 || cam->vsize == 0) return rtc_fail(RTC_ERR_INVALID, "empty camera");
-  HIP_OK(hipSetDevice(s->device));
   const uint64_t n = cam->hsize * cam->vsize;
-  int rc = ensure_px(s, n, false);
+  const int rc = prepare_output(s, n, false, true);
   if (rc != RTC_OK) return rc;
-  if (3 * n > s->cap_rgb8) {
-    (void)hipFree(s->d_rgb8);
-    s->d_rgb8 = nullptr; s->cap_rgb8 = 0;
-    HIP_OK(hipMalloc((void**)&s->d_rgb8, 3 * n));
-    s->cap_rgb8 = 3 * n;
-  }
-  DPixelMap pm{};
-  pm.n = n; pm.mode = 2; pm.row_first = 0; pm.row_step = 1;
+  const DPixelMap pm = rows_map(n);
   DCamera dc;
   to_dcam(*cam, &dc);
-  return render_to_host(s, dc, pm, fuel, nullptr, rgb8, nullptr, stats);
+  return render_to_host(s, n, nullptr, rgb8, nullptr, [&](const AfterLaunch* after) { return run(s, dc, pm, fuel, s->d_rgb, false, stats, stats != nullptr, true, 0, after); });
 }
 
 // Rows of the image owned by part `first` of `step` when bands of `band` rows are dealt out round-robin (the last band of the image
@@ -1541,21 +1482,15 @@ uint64_t rtc_band_rows_owned(uint64_t vsize, uint32_t band_rows, uint32_t band_f
 int rtc_trace_rays(rtc_scene* s, const double* rays, uint64_t n, int32_t fuel, double* rgb, rtc_hit* hits, rtc_stats* stats) {
   if (!s || (!rays && n) || (!rgb && n)) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
   if (n == 0) return RTC_OK;
-  HIP_OK(hipSetDevice(s->device));
-  int rc = ensure_px(s, n, hits != nullptr);
+  int rc = prepare_output(s, n, hits != nullptr, false);
+  if (rc == RTC_OK) rc = ensure_rays(s, n);
   if (rc != RTC_OK) return rc;
-  if (n > s->cap_rays) {
-    if (s->d_rays) (void)hipFree(s->d_rays);
-    s->d_rays = nullptr; s->cap_rays = 0;
-    HIP_OK(hipMalloc((void**)&s->d_rays, n * 6 * sizeof(double)));
-    s->cap_rays = n;
-  }
   HIP_OK(hipMemcpyAsync(s->d_rays, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice, s->stream));
   DPixelMap pm{};
   pm.n = n; pm.mode = 3; pm.rays = s->d_rays;
   DCamera dc{};
   dc.hsize = 1; dc.vsize = 1;
-  return render_to_host(s, dc, pm, fuel, rgb, nullptr, hits, stats);
+  return render_to_host(s, n, rgb, nullptr, hits, [&](const AfterLaunch* after) { return run(s, dc, pm, fuel, s->d_rgb, hits != nullptr, stats, stats != nullptr, true, 0, after); });
 }
 
 // ---- the sampled camera's entry points (include/rtc.h) ---------------------------------------------------------------------------
@@ -1563,13 +1498,10 @@ int rtc_render_sampled(rtc_scene* s, const rtc_camera* cam, const rtc_sampling* 
                        double* rgb, rtc_stats* stats) {
   if (!s || !cam || !sp || (!rgb && n)) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
   int rc = check_sampling(sp);
+  if (rc == RTC_OK) rc = check_pixel_range(cam, pixel_indices, first, n);
   if (rc != RTC_OK) return rc;
-  if (cam->hsize == 0 || cam->vsize == 0) return rtc_fail(RTC_ERR_INVALID, "empty camera");
-  const uint64_t total = cam->hsize * cam->vsize;
-  if (!pixel_indices && first + n > total) return rtc_fail(RTC_ERR_INVALID, "pixel range exceeds the image");
   if (n == 0) { if (stats) std::memset(stats, 0, sizeof(*stats)); return RTC_OK; }
-  HIP_OK(hipSetDevice(s->device));
-  rc = ensure_px(s, n, false);
+  rc = prepare_output(s, n, false, false);
   if (rc != RTC_OK) return rc;
   DPixelMap pm{};
   std::vector<uint64_t> range_idx;
@@ -1577,7 +1509,7 @@ int rtc_render_sampled(rtc_scene* s, const rtc_camera* cam, const rtc_sampling* 
   if (rc != RTC_OK) return rc;
   DCamera dc;
   to_dcam(*cam, &dc);
-  return render_to_host(s, dc, pm, fuel, rgb, nullptr, nullptr, stats, sp);
+  return render_to_host(s, n, rgb, nullptr, nullptr, [&](const AfterLaunch* after) { return run_sampled(s, dc, pm, *sp, fuel, s->d_rgb, stats, stats != nullptr, true, after); });
 }
 
 int rtc_render_sampled_rgb8(rtc_scene* s, const rtc_camera* cam, const rtc_sampling* sp, int32_t fuel, uint8_t* rgb8, rtc_stats* stats) {
@@ -1585,22 +1517,15 @@ int rtc_render_sampled_rgb8(rtc_scene* s, const rtc_camera* cam, const rtc_sampl
   int rc = check_sampling(sp);
   if (rc != RTC_OK) return rc;
   if (cam->hsize == 0 || cam->vsize == 0) return rtc_fail(RTC_ERR_INVALID, "empty camera");
-  HIP_OK(hipSetDevice(s->device));
   const uint64_t n = cam->hsize * cam->vsize;
-  rc = ensure_px(s, n, false);
+  rc = prepare_output(s, n, false, true);
   if (rc != RTC_OK) return rc;
-  if (3 * n > s->cap_rgb8) {
-    (void)hipFree(s->d_rgb8);
-    s->d_rgb8 = nullptr; s->cap_rgb8 = 0;
-    HIP_OK(hipMalloc((void**)&s->d_rgb8, 3 * n));
-    s->cap_rgb8 = 3 * n;
-  }
-  DPixelMap pm{};
-  pm.n = n; pm.mode = 2; pm.row_first = 0; pm.row_step = 1;
+  const DPixelMap pm = rows_map(n);
   DCamera dc;
   to_dcam(*cam, &dc);
-  return render_to_host(s, dc, pm, fuel, nullptr, rgb8, nullptr, stats, sp);
+  return render_to_host(s, n, nullptr, rgb8, nullptr, [&](const AfterLaunch* after) { return run_sampled(s, dc, pm, *sp, fuel, s->d_rgb, stats, stats != nullptr, true, after); });
 }
+
 
 int rtc_render_sampled_bands_device(rtc_scene* s, const rtc_camera* cam, const rtc_sampling* sp, int32_t fuel, uint32_t band_rows, uint32_t band_first,
                                     uint32_t band_step, uint32_t n_rows, double* rgb_dev, rtc_stats* stats, int count_stats, int sync) {
@@ -1664,23 +1589,14 @@ static int render_adaptive(rtc_scene* s, const rtc_camera* cam, const rtc_adapti
   if (cam->hsize == 0 || cam->vsize == 0) return rtc_fail(RTC_ERR_INVALID, "empty camera");
   rc = check_contrast_frame(cam->hsize, cam->vsize);
   if (rc != RTC_OK) return rc;
-  HIP_OK(hipSetDevice(s->device));
   const uint64_t n = cam->hsize * cam->vsize;
-  rc = ensure_px(s, n, false);
+  rc = prepare_output(s, n, false, rgb8 != nullptr);
   if (rc != RTC_OK) return rc;
-  if (rgb8 && 3 * n > s->cap_rgb8) {
-    (void)hipFree(s->d_rgb8);
-    s->d_rgb8 = nullptr; s->cap_rgb8 = 0;
-    HIP_OK(hipMalloc((void**)&s->d_rgb8, 3 * n));
-    s->cap_rgb8 = 3 * n;
-  }
-  DPixelMap pm{};
-  pm.n = n; pm.mode = 2; pm.row_first = 0; pm.row_step = 1;
   DCamera dc;
   to_dcam(*cam, &dc);
-  const AdaptiveOut out{ad, mask, n_refined};
-  return render_to_host(s, dc, pm, fuel, rgb, rgb8, nullptr, stats, nullptr, &out);
+  return render_to_host(s, n, rgb, rgb8, nullptr, [&](const AfterLaunch* after) { return run_adaptive(s, dc, *ad, fuel, stats, mask, n_refined, after); });
 }
+
 
 int rtc_render_adaptive(rtc_scene* s, const rtc_camera* cam, const rtc_adaptive* ad, int32_t fuel, double* rgb, uint8_t* mask, uint64_t* n_refined, rtc_stats* stats) {
   return render_adaptive(s, cam, ad, fuel, rgb, nullptr, mask, n_refined, stats);
@@ -1730,24 +1646,17 @@ static int render_shutter(rtc_scene* const* scenes, const rtc_camera* cameras, u
   if (!pixel_indices && (first > total || n > total - first)) return rtc_fail(RTC_ERR_INVALID, "pixel range exceeds the image");
   if (n == 0) { if (stats) std::memset(stats, 0, sizeof(*stats)); return RTC_OK; }
   rtc_scene* s = scenes[0];
-  HIP_OK(hipSetDevice(s->device));
-  rc = ensure_px(s, n, false);
+  rc = prepare_output(s, n, false, rgb8 != nullptr);
   if (rc != RTC_OK) return rc;
-  if (rgb8 && 3 * n > s->cap_rgb8) {
-    (void)hipFree(s->d_rgb8);
-    s->d_rgb8 = nullptr; s->cap_rgb8 = 0;
-    HIP_OK(hipMalloc((void**)&s->d_rgb8, 3 * n));
-    s->cap_rgb8 = 3 * n;
-  }
   DPixelMap pm{};
   std::vector<uint64_t> range_idx;
   rc = make_pixel_map(s, &cameras[0], pixel_indices, first, n, &pm, &range_idx);
   if (rc != RTC_OK) return rc;
   std::vector<DCamera> cams(n_poses);
   for (uint32_t p = 0; p < n_poses; p++) to_dcam(cameras[p], &cams[p]);
-  const ShutterIn in{scenes, cams.data(), n_poses, sh};
-  return render_to_host(s, cams[0], pm, fuel, rgb, rgb8, nullptr, stats, sp, nullptr, nullptr, &in);
+  return render_to_host(s, n, rgb, rgb8, nullptr, [&](const AfterLaunch* after) { return run_shutter(scenes, cams.data(), n_poses, *sh, pm, *sp, fuel, s->d_rgb, stats, after); });
 }
+
 
 int rtc_render_shutter(rtc_scene* const* scenes, const rtc_camera* cameras, uint32_t n_poses, const rtc_shutter* sh, const rtc_sampling* sp, int32_t fuel,
                        const uint64_t* pixel_indices, uint64_t first, uint64_t n, double* rgb, rtc_stats* stats) {
@@ -1812,22 +1721,15 @@ static int render_filtered(rtc_scene* s, const rtc_camera* cam, const rtc_sampli
   if (cam->hsize == 0 || cam->vsize == 0) return rtc_fail(RTC_ERR_INVALID, "empty camera");
   if (n_rows == 0 || row_first >= cam->vsize || n_rows > cam->vsize - row_first) return rtc_fail(RTC_ERR_INVALID, "filtered: the row range is empty or leaves the image");
   if (cam->vsize > 0xffffffffull) return rtc_fail(RTC_ERR_UNSUPPORTED, "filtered: frames of 2^32 rows or more");
-  HIP_OK(hipSetDevice(s->device));
   const uint64_t n = n_rows * cam->hsize;
-  rc = ensure_px(s, n, false);
+  rc = prepare_output(s, n, false, rgb8 != nullptr);
   if (rc != RTC_OK) return rc;
-  if (rgb8 && 3 * n > s->cap_rgb8) {
-    (void)hipFree(s->d_rgb8);
-    s->d_rgb8 = nullptr; s->cap_rgb8 = 0;
-    HIP_OK(hipMalloc((void**)&s->d_rgb8, 3 * n));
-    s->cap_rgb8 = 3 * n;
-  }
-  DPixelMap pm{};
-  pm.n = n; pm.mode = 2; pm.row_first = (uint32_t)row_first; pm.row_step = 1;
+  const DPixelMap pm = rows_map(n, (uint32_t)row_first);
   DCamera dc;
   to_dcam(*cam, &dc);
-  return render_to_host(s, dc, pm, fuel, rgb, rgb8, nullptr, stats, sp, nullptr, f);
+  return render_to_host(s, n, rgb, rgb8, nullptr, [&](const AfterLaunch* after) { return run_filtered(s, dc, pm, *sp, *f, fuel, s->d_rgb, stats, stats != nullptr, true, after); });
 }
+
 
 int rtc_render_filtered(rtc_scene* s, const rtc_camera* cam, const rtc_sampling* sp, const rtc_filter* f, int32_t fuel, uint32_t row_first, uint32_t n_rows, double* rgb,
                         rtc_stats* stats) {
@@ -2002,7 +1904,6 @@ struct rtc_multi {
 };
 
 namespace {
-int multi_fail(rtc_multi* m, int rc) { (void)m; return rc; }
 
 // `sp`: every replica renders its tile through run_sampled (with stats: synchronously, one replica after the other -- a sampled
 // launch's counters are summed over its chunks by the host).
@@ -2156,18 +2057,15 @@ int render_multi(rtc_multi* m, const rtc_camera* cam, int32_t fuel, double* rgb_
   }
   return RTC_OK;
 }
-}  // namespace
 
-namespace {
-int multi_create(const rtc_scene_desc* desc, bool ex, const rtc_light_ex* lx, uint32_t n_lx, const int* devices, int n_devices, rtc_multi** out,
-                 const rtb::UvInput& uv = rtb::UvInput{}, const rtb::ConeInput& cones = rtb::ConeInput{}, const rtc_background* bg = nullptr,
-                 const rtb::BumpInput& bumps = rtb::BumpInput{}) {
-  if (!desc || !devices || !out || n_devices <= 0) return rtc_fail(RTC_ERR_INVALID, "NULL argument / no devices");
+// One replica of the scene per listed device, each created from the same normalised inputs.
+int multi_create(const SceneInputs& in, const int* devices, int n_devices, rtc_multi** out) {
+  if (!devices || !out || n_devices <= 0) return rtc_fail(RTC_ERR_INVALID, "NULL argument / no devices");
   *out = nullptr;
   std::unique_ptr<rtc_multi> m(new rtc_multi());
   for (int k = 0; k < n_devices; k++) {
     rtc_scene* s = nullptr;
-    int rc = scene_create(desc, ex, lx, n_lx, devices[k], &s, uv, cones, bg, bumps);
+    int rc = scene_create(in, devices[k], &s);
     if (rc != RTC_OK) { rtc_multi_destroy(m.release()); return rc; }
     m->scenes.push_back(s);
     m->tiles.push_back(nullptr);
@@ -2201,61 +2099,39 @@ int multi_create(const rtc_scene_desc* desc, bool ex, const rtc_light_ex* lx, ui
 }
 }  // namespace
 
-int rtc_multi_create(const rtc_scene_desc* desc, const int* devices, int n_devices, rtc_multi** out) { return multi_create(desc, false, nullptr, 0, devices, n_devices, out); }
+// (as the six rtc_scene_create* above)
+int rtc_multi_create(const rtc_scene_desc* desc, const int* devices, int n_devices, rtc_multi** out) {
+  SceneInputs in;
+  if (const int rc = scene_inputs(desc, nullptr, false, nullptr, 0, nullptr, nullptr, 0, out, &in)) return rc;
+  return multi_create(in, devices, n_devices, out);
+}
 int rtc_multi_create_ex(const rtc_scene_desc* desc, const rtc_light_ex* lights, uint32_t n_lights, const int* devices, int n_devices, rtc_multi** out) {
-  return multi_create(desc, true, lights, n_lights, devices, n_devices, out);
+  SceneInputs in;
+  if (const int rc = scene_inputs_ex(desc, lights, n_lights, out, &in)) return rc;
+  return multi_create(in, devices, n_devices, out);
 }
 int rtc_multi_create_ext(const rtc_scene_desc* desc, const rtc_scene_ext* ext, const int* devices, int n_devices, rtc_multi** out) {
-  if (!ext) return multi_create(desc, false, nullptr, 0, devices, n_devices, out);
-  const rtb::UvInput uv{ext->uv_patterns, ext->n_uv_patterns, ext->textures, ext->n_textures};
-  return multi_create(desc, ext->n_lights > 0, ext->lights, ext->n_lights, devices, n_devices, out, uv);
+  SceneInputs in;
+  if (const int rc = scene_inputs(desc, ext, false, nullptr, 0, nullptr, nullptr, 0, out, &in)) return rc;
+  return multi_create(in, devices, n_devices, out);
 }
-
 int rtc_multi_create_ext2(const rtc_scene_desc* desc, const rtc_scene_ext* ext, const rtc_light_cone* cones, uint32_t n_cones, const int* devices, int n_devices,
                           rtc_multi** out) {
-  if (n_cones == 0) return rtc_multi_create_ext(desc, ext, devices, n_devices, out);
-  if (out) *out = nullptr;
-  SpotArgs a;
-  if (const int rc = spot_args(desc, ext, cones, n_cones, &a)) return rc;
-  return multi_create(&a.desc, true, a.lx, a.n_lx, devices, n_devices, out, a.uv, a.cones);
+  SceneInputs in;
+  if (const int rc = scene_inputs(desc, ext, false, cones, n_cones, nullptr, nullptr, 0, out, &in)) return rc;
+  return multi_create(in, devices, n_devices, out);
 }
-
 int rtc_multi_create_ext3(const rtc_scene_desc* desc, const rtc_scene_ext* ext, const rtc_light_cone* cones, uint32_t n_cones, const rtc_background* bg, const int* devices,
                           int n_devices, rtc_multi** out) {
-  if (!bg) return rtc_multi_create_ext2(desc, ext, cones, n_cones, devices, n_devices, out);
-  if (out) *out = nullptr;
-  if (!desc) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
-  std::string why;
-  if (const int rc = rtb::validate_background(*bg, desc->n_pattern_nodes, &why)) return rtc_fail(rc, why);
-  if (n_cones > 0) {
-    SpotArgs a;
-    if (const int rc = spot_args(desc, ext, cones, n_cones, &a)) return rc;
-    return multi_create(&a.desc, true, a.lx, a.n_lx, devices, n_devices, out, a.uv, a.cones, bg);
-  }
-  if (!ext) return multi_create(desc, false, nullptr, 0, devices, n_devices, out, rtb::UvInput{}, rtb::ConeInput{}, bg);
-  const rtb::UvInput uv{ext->uv_patterns, ext->n_uv_patterns, ext->textures, ext->n_textures};
-  return multi_create(desc, ext->n_lights > 0, ext->lights, ext->n_lights, devices, n_devices, out, uv, rtb::ConeInput{}, bg);
+  SceneInputs in;
+  if (const int rc = scene_inputs(desc, ext, false, cones, n_cones, bg, nullptr, 0, out, &in)) return rc;
+  return multi_create(in, devices, n_devices, out);
 }
-
 int rtc_multi_create_ext4(const rtc_scene_desc* desc, const rtc_scene_ext* ext, const rtc_light_cone* cones, uint32_t n_cones, const rtc_background* bg,
                           const rtc_bump* bumps, uint32_t n_bumps, const int* devices, int n_devices, rtc_multi** out) {
-  if (n_bumps == 0) return rtc_multi_create_ext3(desc, ext, cones, n_cones, bg, devices, n_devices, out);
-  if (out) *out = nullptr;
-  if (!desc) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
-  const rtb::BumpInput bi{bumps, n_bumps};
-  std::string why;
-  if (const int rc = rtb::validate_bumps(bi, desc->n_materials, &why)) return rtc_fail(rc, why);
-  if (bg) {
-    if (const int rc = rtb::validate_background(*bg, desc->n_pattern_nodes, &why)) return rtc_fail(rc, why);
-  }
-  if (n_cones > 0) {
-    SpotArgs a;
-    if (const int rc = spot_args(desc, ext, cones, n_cones, &a)) return rc;
-    return multi_create(&a.desc, true, a.lx, a.n_lx, devices, n_devices, out, a.uv, a.cones, bg, bi);
-  }
-  if (!ext) return multi_create(desc, false, nullptr, 0, devices, n_devices, out, rtb::UvInput{}, rtb::ConeInput{}, bg, bi);
-  const rtb::UvInput uv{ext->uv_patterns, ext->n_uv_patterns, ext->textures, ext->n_textures};
-  return multi_create(desc, ext->n_lights > 0, ext->lights, ext->n_lights, devices, n_devices, out, uv, rtb::ConeInput{}, bg, bi);
+  SceneInputs in;
+  if (const int rc = scene_inputs(desc, ext, false, cones, n_cones, bg, bumps, n_bumps, out, &in)) return rc;
+  return multi_create(in, devices, n_devices, out);
 }
 
 void rtc_multi_destroy(rtc_multi* m) {

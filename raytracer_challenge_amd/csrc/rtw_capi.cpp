@@ -72,46 +72,33 @@ static int ensure_scene(rtw_world* w) {
     rtc_scene_desc d = f.desc();
     if (timing) std::fprintf(stderr, "[rtc-timing] %-28s %.3f s\n", "flatten (host mirror -> desc)", since(t0));
     const auto t1 = std::chrono::steady_clock::now();
-    if (!f.bumps.empty()) {  // bump records: everything else the world has goes along
-      if (!rtc_scene_create_ext4) return fail("a bump (rtw_element_set_bump) needs rtc_scene_create_ext4 (librtc_amd.so)");
-      rtc_background bg{0, w->background_projection};
-      if (w->background) { bg.pattern = fl.root_pattern(w->background); d = f.desc(); }  // (the node array grew)
-      rtc_scene_ext x{};
-      if (!w->lights_ex.empty()) { d.n_lights = 0; d.lights = nullptr; x.n_lights = (uint32_t)w->lights_ex.size(); x.lights = w->lights_ex.data(); }
-      x.n_uv_patterns = (uint32_t)f.uv_pats.size(); x.uv_patterns = f.uv_pats.data();
-      x.n_textures = (uint32_t)f.textures.size(); x.textures = f.textures.data();
-      rc = rtc_scene_create_ext4(&d, &x, w->cones.empty() ? nullptr : w->cones.data(), (uint32_t)w->cones.size(), w->background ? &bg : nullptr, f.bumps.data(),
-                                 (uint32_t)f.bumps.size(), w->device, &w->scene);
-    } else if (w->background) {  // a background: its pattern tree joins the node array; everything else the world has goes along
-      if (!rtc_scene_create_ext3) return fail("a background needs rtc_scene_create_ext3 (librtc_amd.so)");
-      rtc_background bg{fl.root_pattern(w->background), w->background_projection};
-      d = f.desc();  // (the node array grew)
-      rtc_scene_ext x{};
-      if (!w->lights_ex.empty()) { d.n_lights = 0; d.lights = nullptr; x.n_lights = (uint32_t)w->lights_ex.size(); x.lights = w->lights_ex.data(); }
-      x.n_uv_patterns = (uint32_t)f.uv_pats.size(); x.uv_patterns = f.uv_pats.data();
-      x.n_textures = (uint32_t)f.textures.size(); x.textures = f.textures.data();
-      rc = rtc_scene_create_ext3(&d, &x, w->cones.empty() ? nullptr : w->cones.data(), (uint32_t)w->cones.size(), &bg, w->device, &w->scene);
-    } else if (!w->cones.empty()) {  // light cones: everything else the world has goes along in the ext
-      if (!rtc_scene_create_ext2) return fail("light cones need rtc_scene_create_ext2 (librtc_amd.so)");
-      rtc_scene_ext x{};
-      if (!w->lights_ex.empty()) { d.n_lights = 0; d.lights = nullptr; x.n_lights = (uint32_t)w->lights_ex.size(); x.lights = w->lights_ex.data(); }
-      x.n_uv_patterns = (uint32_t)f.uv_pats.size(); x.uv_patterns = f.uv_pats.data();
-      x.n_textures = (uint32_t)f.textures.size(); x.textures = f.textures.data();
-      rc = rtc_scene_create_ext2(&d, &x, w->cones.data(), (uint32_t)w->cones.size(), w->device, &w->scene);
-    } else if (!f.uv_pats.empty()) {  // texture-mapped patterns: records and textures (and an area light's list) through the ext
-      if (!rtc_scene_create_ext) return fail("texture-mapped patterns need rtc_scene_create_ext (librtc_amd.so)");
-      rtc_scene_ext x{};
-      if (!w->lights_ex.empty()) { d.n_lights = 0; d.lights = nullptr; x.n_lights = (uint32_t)w->lights_ex.size(); x.lights = w->lights_ex.data(); }
-      x.n_uv_patterns = (uint32_t)f.uv_pats.size(); x.uv_patterns = f.uv_pats.data();
-      x.n_textures = (uint32_t)f.textures.size(); x.textures = f.textures.data();
-      rc = rtc_scene_create_ext(&d, &x, w->device, &w->scene);
-    } else if (!w->lights_ex.empty()) {  // area lights: the light list replaces the descriptor's point lights
-      if (!rtc_scene_create_ex) return fail("area lights need rtc_scene_create_ex (librtc_amd.so)");
+    // The lowest entry point that takes everything the world has (the emulator library exports rtc_scene_create alone): bump records
+    // need _ext4, a background _ext3, light cones _ext2, texture-mapped patterns _ext, an area light's list _ex; whatever else the
+    // world has goes along.
+    const int level = !f.bumps.empty() ? 4 : w->background ? 3 : !w->cones.empty() ? 2 : !f.uv_pats.empty() ? 1 : 0;
+    const bool light_list = !w->lights_ex.empty();
+    if (level == 4 && !rtc_scene_create_ext4) return fail("a bump (rtw_element_set_bump) needs rtc_scene_create_ext4 (librtc_amd.so)");
+    if (level == 3 && !rtc_scene_create_ext3) return fail("a background needs rtc_scene_create_ext3 (librtc_amd.so)");
+    if (level == 2 && !rtc_scene_create_ext2) return fail("light cones need rtc_scene_create_ext2 (librtc_amd.so)");
+    if (level == 1 && !rtc_scene_create_ext) return fail("texture-mapped patterns need rtc_scene_create_ext (librtc_amd.so)");
+    if (level == 0 && light_list && !rtc_scene_create_ex) return fail("area lights need rtc_scene_create_ex (librtc_amd.so)");
+    rtc_background bg{0, w->background_projection};
+    if (w->background) { bg.pattern = fl.root_pattern(w->background); d = f.desc(); }  // (its pattern tree joins the node array, which grew)
+    rtc_scene_ext x{};
+    if (light_list) {  // the light list replaces the descriptor's point lights
       d.n_lights = 0; d.lights = nullptr;
-      rc = rtc_scene_create_ex(&d, w->lights_ex.data(), (uint32_t)w->lights_ex.size(), w->device, &w->scene);
-    } else {
-      rc = rtc_scene_create(&d, w->device, &w->scene);
+      x.n_lights = (uint32_t)w->lights_ex.size(); x.lights = w->lights_ex.data();
     }
+    x.n_uv_patterns = (uint32_t)f.uv_pats.size(); x.uv_patterns = f.uv_pats.data();
+    x.n_textures = (uint32_t)f.textures.size(); x.textures = f.textures.data();
+    const rtc_light_cone* cones = w->cones.empty() ? nullptr : w->cones.data();
+    const uint32_t n_cones = (uint32_t)w->cones.size();
+    if (level == 4) rc = rtc_scene_create_ext4(&d, &x, cones, n_cones, w->background ? &bg : nullptr, f.bumps.data(), (uint32_t)f.bumps.size(), w->device, &w->scene);
+    else if (level == 3) rc = rtc_scene_create_ext3(&d, &x, cones, n_cones, &bg, w->device, &w->scene);
+    else if (level == 2) rc = rtc_scene_create_ext2(&d, &x, cones, n_cones, w->device, &w->scene);
+    else if (level == 1) rc = rtc_scene_create_ext(&d, &x, w->device, &w->scene);
+    else if (light_list) rc = rtc_scene_create_ex(&d, x.lights, x.n_lights, w->device, &w->scene);
+    else rc = rtc_scene_create(&d, w->device, &w->scene);
     if (timing) std::fprintf(stderr, "[rtc-timing] %-28s %.3f s\n", "rtc_scene_create (all of it)", since(t1));
   }
   if (timing) std::fprintf(stderr, "[rtc-timing] %-28s %.3f s\n", "flatten + create + frees", since(t0));

@@ -211,6 +211,37 @@ def test_hip_wavefront_allocation_failure_falls_back(hip, orc, monkeypatch):
     assert np.array_equal(ref[0], got[0])
 
 
+def test_hip_wavefront_allocation_failure_inside_a_chunked_launch(hip, monkeypatch):
+    """The same refusal met by the first chunk of a sampled and of a filtered launch whose first guess is the wavefront path: the chunk
+    is traced again by the one-kernel path and so is every later one (3 launches per chunk: generator, trace, resolve), same bits, and
+    the wavefront candidate of that launch shape is dropped."""
+    import ctypes as C
+    from raytracer_challenge_amd.device import RtcStatsC
+    from raytracer_challenge_amd.scene import Filter, Sampling
+    from test_filter_gpu import bind as bind_filtered, filtered
+    from test_sampled_camera_gpu import bind as bind_sampled, bits, sampled
+    lib = bind_filtered(bind_sampled(hip.lib))
+    cam, world = scenes.chapter11_glass_air_bubble(16, 16)
+    sp, box = Sampling(side=2), Filter.box(0.5)
+    monkeypatch.setenv("RTC_SAMPLED_MAX_RAYS", "256")    # a row is 16 pixels x 4 rays: 4 rows per chunk, 4 chunks (the box has no halo)
+    monkeypatch.setenv("RTC_KERNEL", "1")
+    nw1 = hip.build_world(world)
+    one = lib.rtw_world_scene(nw1.handle, 0)
+    ref_sampled, ref_filtered = sampled(lib, one, cam, sp, 2), filtered(lib, one, cam, sp, box, 2)
+    monkeypatch.delenv("RTC_KERNEL")
+    monkeypatch.setenv("RTC_FIRST_GUESS", "4")
+    monkeypatch.setenv("RTC_WF_FAIL_ALLOC", "1")
+    nw = hip.build_world(world)
+    scene = lib.rtw_world_scene(nw.handle, 0)
+    for render, ref in ((lambda st: sampled(lib, scene, cam, sp, 2, stats=st), ref_sampled), (lambda st: filtered(lib, scene, cam, sp, box, 2, stats=st), ref_filtered)):
+        st = RtcStatsC()
+        assert np.array_equal(bits(render(st)), bits(ref))
+        assert st.pixels == 16 * 16 and st.n_launches == 4 * 3
+        ch, t1, t4 = C.c_int32(0), C.c_double(-1.0), C.c_double(-1.0)
+        lib.rtc_scene_path_info(scene, C.byref(ch), C.byref(t1), C.byref(t4))
+        assert ch.value == 1
+
+
 @pytest.mark.parametrize("path", ["1", "4"])
 def test_hip_csg_subtrees_beyond_the_per_lane_buffer(hip, orc, path, monkeypatch):
     """CSG subtrees that can produce more than 32 intersections run through a slab in device memory (include/rtc.h): 20 overlapping
