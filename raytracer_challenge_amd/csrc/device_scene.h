@@ -332,12 +332,20 @@ static inline RTC_HD double rtc_area_jitter(unsigned long long h, unsigned j) {
 #define RTC_WF_OVERFLOW 63     // counts[RTC_WF_OVERFLOW] != 0: a queue overflowed, the frame must be rendered by the one-kernel path
 #define RTC_WF_CHUNK_NEXT 64   // counts[RTC_WF_CHUNK_NEXT + 32 * (8 * launch + xcd)]: next chunk of traversal launch `launch` for blocks of
                                // that XCD; one 128-byte line per cursor (same-line device atomics serialise)
-#define RTC_WF_COUNTS (64 + 32 * 8 * (RTC_MAX_FUEL + 2))
+#define RTC_WF_TOP_COUNT (64 + 32 * 8 * (RTC_MAX_FUEL + 2))  // counts[RTC_WF_TOP_COUNT + level] = rays of the level at the far end of its queue
+#define RTC_WF_SHADE_TOP_COUNT (RTC_WF_TOP_COUNT + 32)       // counts[RTC_WF_SHADE_TOP_COUNT + level] = shade records of the level at the far end
+#define RTC_WF_COUNTS (RTC_WF_TOP_COUNT + 64)
 #ifndef RTC_WF_CHUNK
 #define RTC_WF_CHUNK 64u       // work items per chunk: one wave pass (larger chunks leave waves idle at the small, deep levels: 256 -> +25 %)
 #endif
 #define RTC_SR_PLAIN 0x40000000  // DWave.sr_mat: the record's colour is its material's constant (DScene.mat, shading rows)
 #define RTC_WF_MISS (-2)        // child row 0 of a ray that hit nothing: no contribution was written for it, it has no children
+// The queues are two-ended, so that a level's 64-item traversal chunks hold one class of work each.  A level's rays:
+// rays reflected off planes from index 0 up (counts[level]); rays reflected off other primitives, then refracted rays, from cap - 1 down
+// (counts[RTC_WF_TOP_COUNT + level]; a block's m of them take [cap - old - m, cap - old), ascending).  Its shade records: records on planes from 0 up (counts[RTC_WF_SHADE_COUNT + level]),
+// all others from cap - 1 down (counts[RTC_WF_SHADE_TOP_COUNT + level]).  Level 0 has no far end.  The two ends of a queue meeting
+// (bottom + top > cap) is the overflow.  Whatever loops over a level maps its linear work ids through wf_index (rtc_device.hpp): the
+// far end first.  The per-ray arrays (h_*, child, contrib, dig) are indexed like the ray queue.
 struct DWave {
   double* rq[2];        // ray queues (level parity): 7 rows ox oy oz dx dy dz weight
   double* h_t;          // per ray of the level: closest hit t
@@ -350,7 +358,8 @@ struct DWave {
   int32_t* sr_node;     //   ray index within the level
   double* contrib;      // (levels) x 3 rows: colour contribution of each ray that hit something (written by the shadow pass)
   int32_t* child;       // (levels) x 2 rows: index of the reflected / refracted child ray in the next level (-1 none); row 0 = RTC_WF_MISS: no hit
-  uint32_t* counts;     // RTC_WF_COUNTS counters: [level] rays of the level, [32 + level] shade records, [63] overflow flag, [64..] chunk cursors
+  uint32_t* counts;     // RTC_WF_COUNTS counters: [level] rays of the level from 0 up, [32 + level] shade records from 0 up, [63] overflow flag,
+                        //   [64..] chunk cursors, [RTC_WF_TOP_COUNT + level] / [RTC_WF_SHADE_TOP_COUNT + level] rays / records from cap - 1 down
   uint32_t cap;
   uint32_t pad;
   unsigned long long* dig;  // hit-tree digest launches only (else NULL; its own allocation): (levels) x cap rtc_hit_hash_base of each ray's closest hit

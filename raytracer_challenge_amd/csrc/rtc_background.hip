@@ -38,12 +38,14 @@ uint64_t rtc_wavefront_work(const DCamera& cam, const DPixelMap& pm);  // rtc_ke
 template <bool UV>
 __global__ void __launch_bounds__(256) wf_background(DScene S, DCamera cam, DPixelMap pm, DWave W, int level, unsigned n0, DBackground bg) {
   const WorkMap wm = make_workmap(pm, cam);
-  const unsigned count = wf_count(W, level, n0);
+  const WfParts parts = wf_count(W, level, n0);
+  const unsigned count = parts.top + parts.bottom;
   const size_t cap = W.cap;
   int32_t* ch = W.child + (size_t)level * 2 * cap;
   double* cb = W.contrib + (size_t)level * 3 * cap;
   const double* rq = W.rq[level & 1];
-  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (unsigned long long)gridDim.x * blockDim.x) {
+  for (unsigned long long w = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; w < count; w += (unsigned long long)gridDim.x * blockDim.x) {
+    const unsigned i = wf_index(parts, W.cap, (unsigned)w);
     double dx, dy, dz, weight = 1.0;
     if (level == 0) {
       uint64_t q = 0;

@@ -1846,11 +1846,28 @@ __global__ void __launch_bounds__(RTC_BLOCK, WAVES ? WAVES : ((FEAT >= 2 && RTC_
 // =================================================================================================================
 namespace {
 
-__device__ __forceinline__ unsigned wf_count(const DWave& W, int level, unsigned n0) {
-  if (level == 0) return n0;
-  unsigned c = W.counts[level];
-  return c < W.cap ? c : W.cap;
+// The two parts of a two-ended queue (DWave): `top` items at [cap - top, cap), `bottom` items at [0, bottom).  Of queues whose ends met
+// (an overflow: the frame is rendered again) only what lies in range and apart is kept.
+struct WfParts {
+  unsigned top, bottom;
+};
+__device__ __forceinline__ WfParts wf_parts(const DWave& W, unsigned top, unsigned bottom) {
+  WfParts p;
+  p.top = top < W.cap ? top : W.cap;
+  p.bottom = bottom < W.cap - p.top ? bottom : W.cap - p.top;
+  return p;
 }
+// rays of a level (level 0: the launch's n0 work ids, all at the near end)
+__device__ __forceinline__ WfParts wf_count(const DWave& W, int level, unsigned n0) {
+  if (level == 0) return {0u, n0};
+  return wf_parts(W, W.counts[RTC_WF_TOP_COUNT + level], W.counts[level]);
+}
+// shade records of a level
+__device__ __forceinline__ WfParts wf_rec_count(const DWave& W, int level) {
+  return wf_parts(W, W.counts[RTC_WF_SHADE_TOP_COUNT + level], W.counts[RTC_WF_SHADE_COUNT + level]);
+}
+// Queue index of a level's linear work id w in [0, top + bottom): the far end's items first, both parts in ascending order.
+__device__ __forceinline__ unsigned wf_index(const WfParts& p, unsigned cap, unsigned w) { return w < p.top ? cap - p.top + w : w - p.top; }
 __device__ __forceinline__ Ray wf_load_ray(const DWave& W, int level, unsigned i, double& weight) {
   const double* q = W.rq[level & 1];
   const size_t cap = W.cap;
@@ -2037,7 +2054,8 @@ __device__ __forceinline__ void wf_shadow_rec_area(const DScene& S, const DCamer
 // Traversal kernel of the wavefront path: the closest-hit pass of level `tl` and the shadow + lighting pass of level `sl`
 // (either may be -1) as ONE launch, so the two independent passes fill the chip together.  Work is handed out in chunks of
 // RTC_WF_CHUNK items from per-XCD counters (block b belongs to XCD b % 8 and takes chunks b % 8, b % 8 + 8, ...): trace
-// chunks first (the next shading kernel waits for them), then shadow chunks; a wave that finishes early simply takes more.
+// chunks first (the next shading kernel waits for them), then shadow chunks, of each the far end of the two-ended queue first (DWave);
+// a wave that finishes early simply takes more.
 #ifndef RTC_WF_TS_WAVES
 #define RTC_WF_TS_WAVES 3  // waves per SIMD the traversal kernel is compiled for: 168 VGPRs, no scratch.  At 4 (128 VGPRs) the ray and the
                            // leaf record spill around every leaf test: same frame time, +1.7 GB of HBM traffic per frame (profiles/r2_*)
@@ -2071,10 +2089,12 @@ __global__ void __launch_bounds__(LDSC ? RTC_LDS_BLOCK : RTC_BLOCK, (KOPS || FEA
   __syncthreads();
 #endif
   const WorkMap wm = make_workmap(pm, cam);
-  const unsigned nt = tl >= 0 ? wf_count(W, tl, n0) : 0u;
-  unsigned ns = sl >= 0 ? W.counts[RTC_WF_SHADE_COUNT + sl] : 0u;
-  if (ns > W.cap) ns = W.cap;
-  const unsigned ct = (nt + RTC_WF_CHUNK - 1) / RTC_WF_CHUNK, cs = (ns + RTC_WF_CHUNK - 1) / RTC_WF_CHUNK;
+  const WfParts pt = tl >= 0 ? wf_count(W, tl, n0) : WfParts{0u, 0u};
+  const WfParts ps = sl >= 0 ? wf_rec_count(W, sl) : WfParts{0u, 0u};
+  // Hardest first: the trace chunks of the far end (rays that left a curved primitive -- incoherent, and the refracted ones start inside
+  // glass and nearly always need a container pass), the other trace chunks, the shadow chunks of the far end (records off planes), the
+  // other shadow chunks.  Every part is cut into its own chunks: none holds items of two parts.
+  const unsigned n_a = pt.top, n_b = pt.bottom, n_c = ps.top, n_d = ps.bottom;
   const unsigned nx = gridDim.x < 8u ? gridDim.x : 8u;  // chunk residues in use (a grid smaller than 8 blocks has fewer)
   const unsigned x = blockIdx.x % nx;
   unsigned* next = &W.counts[RTC_WF_CHUNK_NEXT + 32 * (8 * slot + (int)x)];
@@ -2084,22 +2104,31 @@ __global__ void __launch_bounds__(LDSC ? RTC_LDS_BLOCK : RTC_BLOCK, (KOPS || FEA
     if (lane == 0) kx = atomicAdd(next, 1u);
     kx = __shfl(kx, 0);
     const unsigned long long chunk = (unsigned long long)kx * nx + x;
-    if (chunk >= (unsigned long long)ct + cs) break;
-    if (chunk < ct) {
-      const unsigned base = (unsigned)chunk * RTC_WF_CHUNK;
+    // the chunk's part (wave-uniform; the four sizes are all that stays live across the work items): its size, whether it lies at the
+    // far end, the chunk's number within it
+    if (chunk >= 0x80000000ull) break;
+    unsigned c = (unsigned)chunk, part_n = n_a;
+    int part = 0;
+    for (; part < 3 && c >= (part_n + RTC_WF_CHUNK - 1) / RTC_WF_CHUNK; part++) {
+      c -= (part_n + RTC_WF_CHUNK - 1) / RTC_WF_CHUNK;
+      part_n = part == 0 ? n_b : part == 1 ? n_c : n_d;
+    }
+    if (c >= (part_n + RTC_WF_CHUNK - 1) / RTC_WF_CHUNK) break;
+    const unsigned origin = (part & 1) == 0 ? W.cap - part_n : 0u;
+    const unsigned base = c * RTC_WF_CHUNK;
+    if (part < 2) {
       for (unsigned o = 0; o < RTC_WF_CHUNK; o += RTC_WF_LANES) {
-        const unsigned i = base + o + (unsigned)lane;
-        if (i < nt) {
+        const unsigned i = origin + base + o + (unsigned)lane;
+        if (base + o + (unsigned)lane < part_n) {
           DIAG_SPAN_BEGIN();
           wf_trace_ray<FEAT, KOPS, LDSC>(S, cam, pm, W, wm, tl, i, hit_t, hit_prim, hit_k, stack, stride, C, n_rays, n_container, fuel_left, L, COUNT && W.dig != nullptr);
           DIAG_SPAN_END(7);
         }
       }
     } else {
-      const unsigned base = (unsigned)(chunk - ct) * RTC_WF_CHUNK;
       for (unsigned o = 0; o < RTC_WF_CHUNK; o += RTC_WF_LANES) {
-        const unsigned s = base + o + (unsigned)lane;
-        if (s < ns) {
+        const unsigned s = origin + base + o + (unsigned)lane;
+        if (base + o + (unsigned)lane < part_n) {
           DIAG_SPAN_BEGIN();
           if constexpr (AREA) wf_shadow_rec_area<FEAT, KOPS, LDSC, SPOT>(S, cam, pm, W, wm, sl, s, stack, stride, C, n_shadow, L);
           else wf_shadow_rec<FEAT, KOPS, LDSC, KOPS && !COUNT && FEAT <= RTC_WF_TS_WAVES_MAXFEAT>(S, cam, pm, W, wm, sl, s, stack, stride, C, n_shadow, L);
@@ -2107,6 +2136,13 @@ __global__ void __launch_bounds__(LDSC ? RTC_LDS_BLOCK : RTC_BLOCK, (KOPS || FEA
         }
       }
     }
+  }
+  // The two ends of a queue met (bottom + top > cap): decided here, where both of its counts are final -- wf_shade's blocks each see
+  // their own reservations only.  (Behind the loop: in front of it the branch made the compiler keep W.cap, and every row address
+  // derived from it, in vector registers.)
+  if ((tl > 0 && (unsigned long long)W.counts[RTC_WF_TOP_COUNT + tl] + W.counts[tl] > W.cap) ||
+      (sl >= 0 && (unsigned long long)W.counts[RTC_WF_SHADE_TOP_COUNT + sl] + W.counts[RTC_WF_SHADE_COUNT + sl] > W.cap)) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) { W.counts[RTC_WF_OVERFLOW] = 1u; stats->wf_overflow = 1ull; }
   }
   if (C.nan_ts) atomicAdd(&stats->nan_ts, (unsigned long long)C.nan_ts);
 #ifdef RTC_DIAG

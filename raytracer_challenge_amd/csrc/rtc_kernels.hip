@@ -37,15 +37,19 @@ struct WfShadeIn {
   Ray ray;
   double weight, t;
 };
-__device__ __forceinline__ int wf_shade_fetch_prim(const DWave& W, unsigned long long i, unsigned count) { return i < count ? W.h_prim[i] : -1; }
+// (w: a linear work id of the level, top + bottom = count of them; wf_index gives its place in the two-ended queue)
+__device__ __forceinline__ int wf_shade_fetch_prim(const DWave& W, const WfParts& parts, unsigned long long w, unsigned count) {
+  return w < count ? W.h_prim[wf_index(parts, W.cap, (unsigned)w)] : -1;
+}
 // Every lane loads, without a branch: values that arrive under a branch are merged with the other path's by register copies, for which
 // the compiler waits right there -- in front of the barrier the loads are meant to cross.  A lane without a hit reads the element of
 // its wave's first lane instead of its own (or element 0 past the level's end): one address for all of them, in a line the wave's hits
-// fetch anyway, so a miss's ray still costs no bandwidth (71 % of level 3 on the headline scene are misses).
+// fetch anyway, so a miss's ray still costs no bandwidth (71 % of level 3 on the headline scene are misses).  (A wave whose work ids
+// span the queue's two parts has its first lane's element at the far end: one more line for that one wave of the level.)
 template <bool LV0>
-__device__ __forceinline__ WfShadeIn wf_shade_prefetch(const DWave& W, int level, unsigned long long i, int lane, unsigned count, int prim) {
-  const unsigned long long first = i - (unsigned)lane;
-  const unsigned j = prim >= 0 ? (unsigned)i : (first < count ? (unsigned)first : 0u);
+__device__ __forceinline__ WfShadeIn wf_shade_prefetch(const DWave& W, const WfParts& parts, int level, unsigned long long w, int lane, unsigned count, int prim) {
+  const unsigned long long first = w - (unsigned)lane;
+  const unsigned j = prim >= 0 ? wf_index(parts, W.cap, (unsigned)w) : (first < count ? wf_index(parts, W.cap, (unsigned)first) : 0u);
   WfShadeIn in = {prim, {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, 1.0, 0.0};
   if (!LV0) in.ray = wf_load_ray(W, level, j, in.weight);  // (level 0: the camera's ray, computed where it is used)
   in.t = W.h_t[j];
@@ -77,12 +81,18 @@ __global__ void __launch_bounds__(RTC_WF_SHADE_BLOCK, RTC_WF_SHADE_WAVES) wf_sha
   // the next iteration writes).  Classes keep like with like inside a block's span of the queues, so that most 64-item chunks of the
   // next traversal launch hold one kind of ray: shade records on planes / on other primitives [0..15]; reflected rays off planes
   // (mirror images of their coherent parents) / off other primitives / refracted rays [16..39].  Entry = 8 * class + wave.
+  // A block iteration makes four reservations, one per end of the two queues (DWave): records on planes at the near end, the other
+  // records at the far end; rays reflected off planes at the near end, rays reflected off other primitives and then the refracted rays
+  // at the far end.  end_of[class]: its reservation.
+  constexpr int end_of[5] = {0, 1, 2, 3, 3};
   constexpr int n_waves = RTC_WF_SHADE_BLOCK >= 64 ? RTC_WF_SHADE_BLOCK / 64 : 1;
   static_assert(n_waves <= 8, "wf_shade: eight counters per class");
   __shared__ unsigned s_cnt2[2][40];
   unsigned parity = 0;
   const WorkMap wm = make_workmap(pm, cam);
-  const unsigned count = wf_count(W, level, n0);
+  const bool level0 = PIPE ? LV0 : level == 0;
+  const WfParts parts = level0 ? WfParts{0u, n0} : wf_count(W, level, n0);
+  const unsigned count = parts.top + parts.bottom;
   const size_t cap = W.cap;
   const double L = (double)S.n_lights;
   const int fuel = fuel0 - level;
@@ -94,16 +104,15 @@ __global__ void __launch_bounds__(RTC_WF_SHADE_BLOCK, RTC_WF_SHADE_WAVES) wf_sha
   const unsigned long long step = (unsigned long long)gridDim.x * RTC_WF_SHADE_BLOCK;
   WfShadeIn nx = {-1, {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, 1.0, 0.0};
   int nx_prim = -1;
-  const bool level0 = PIPE ? LV0 : level == 0;
   if (PIPE) {
-    const unsigned long long i0 = (unsigned long long)blockIdx.x * RTC_WF_SHADE_BLOCK + threadIdx.x;
-    nx = wf_shade_prefetch<LV0>(W, level, i0, lane, count, wf_shade_fetch_prim(W, i0, count));
+    const unsigned long long w0 = (unsigned long long)blockIdx.x * RTC_WF_SHADE_BLOCK + threadIdx.x;
+    nx = wf_shade_prefetch<LV0>(W, parts, level, w0, lane, count, wf_shade_fetch_prim(W, parts, w0, count));
   }
   for (unsigned long long base = (unsigned long long)blockIdx.x * RTC_WF_SHADE_BLOCK; base < count; base += step) {  // block-uniform bound: barriers inside
-    const unsigned i = (unsigned)base + threadIdx.x;
+    const unsigned i = wf_index(parts, W.cap, (unsigned)base + threadIdx.x);  // (the ray's place in the queue; only a hit uses it)
     const WfShadeIn in = nx;
-    const int prim = PIPE ? in.prim : wf_shade_fetch_prim(W, i, count);
-    if (PIPE) nx_prim = wf_shade_fetch_prim(W, base + step + threadIdx.x, count);
+    const int prim = PIPE ? in.prim : wf_shade_fetch_prim(W, parts, base + threadIdx.x, count);
+    if (PIPE) nx_prim = wf_shade_fetch_prim(W, parts, base + step + threadIdx.x, count);
     const bool hit = prim >= 0;
     State st;
     double cr = 0.0, cg = 0.0, cbl = 0.0, weight = 1.0, n1 = 1.0, n2 = 1.0;
@@ -164,37 +173,49 @@ __global__ void __launch_bounds__(RTC_WF_SHADE_BLOCK, RTC_WF_SHADE_WAVES) wf_sha
       s_cnt[wave] = (unsigned)__popcll(m_rec0); s_cnt[8 + wave] = (unsigned)__popcll(m_rec1);
       s_cnt[16 + wave] = (unsigned)__popcll(m_c0); s_cnt[24 + wave] = (unsigned)__popcll(m_c1); s_cnt[32 + wave] = (unsigned)__popcll(m_c2);
     }
-    if (PIPE) nx = wf_shade_prefetch<LV0>(W, level, base + step + threadIdx.x, lane, count, nx_prim);  // in flight across the reservation and the stores
+    if (PIPE) nx = wf_shade_prefetch<LV0>(W, parts, level, base + step + threadIdx.x, lane, count, nx_prim);  // in flight across the reservation and the stores
     __syncthreads();
 #ifndef RTC_EMU
     if (PIPE && n_waves == 8 && wave == 0) {
-      // one lane per counter: lanes 0..15 the record classes (one DPP row), 16..39 the child classes (a row and a half); both totals
-      // in one atomic instruction (lanes 0 and 1), so the block waits for one round trip
+      // one lane per counter: lanes 0..15 the record classes (one DPP row), 16..39 the child classes (a row and a half); the totals of
+      // the four reservations in one atomic instruction (lanes 0..3), so the block waits for one round trip
       const unsigned c = lane < 40 ? s_cnt[lane] : 0u;
       const unsigned in_row = wf_row_scan16(c);
-      const unsigned tr = (unsigned)__builtin_amdgcn_readlane((int)in_row, 15), t1 = (unsigned)__builtin_amdgcn_readlane((int)in_row, 31);
-      const unsigned tc = t1 + (unsigned)__builtin_amdgcn_readlane((int)in_row, 39);
-      const unsigned total = lane == 0 ? tr : tc;
-      unsigned old = 0u;
-      if (lane < 2 && total) {
-        old = atomicAdd(&W.counts[lane == 0 ? RTC_WF_SHADE_COUNT + level : level + 1], total);
-        if ((unsigned long long)old + total > W.cap) { W.counts[RTC_WF_OVERFLOW] = 1u; stats->wf_overflow = 1ull; }
+      const unsigned r0 = (unsigned)__builtin_amdgcn_readlane((int)in_row, 7), r01 = (unsigned)__builtin_amdgcn_readlane((int)in_row, 15);
+      const unsigned k0 = (unsigned)__builtin_amdgcn_readlane((int)in_row, 23), k01 = (unsigned)__builtin_amdgcn_readlane((int)in_row, 31);
+      const unsigned k2 = (unsigned)__builtin_amdgcn_readlane((int)in_row, 39);
+      const unsigned t_rn = r0, t_rf = r01 - r0, t_cn = k0, t_cf = k01 - k0 + k2;
+      const unsigned total = lane == 0 ? t_rn : lane == 1 ? t_rf : lane == 2 ? t_cn : t_cf;
+      unsigned first = 0u;
+      if (lane < 4 && total) {
+        const int row = lane == 0 ? RTC_WF_SHADE_COUNT + level : lane == 1 ? RTC_WF_SHADE_TOP_COUNT + level : lane == 2 ? level + 1 : RTC_WF_TOP_COUNT + level + 1;
+        const unsigned old = atomicAdd(&W.counts[row], total);
+        const bool fits = (unsigned long long)old + total <= W.cap;
+        if (!fits) { W.counts[RTC_WF_OVERFLOW] = 1u; stats->wf_overflow = 1ull; }
+        first = (lane & 1) ? (fits ? W.cap - old - total : W.cap) : old;
       }
-      const unsigned br = (unsigned)__builtin_amdgcn_readlane((int)old, 0), bc = (unsigned)__builtin_amdgcn_readlane((int)old, 1);
-      if (lane < 40) s_cnt[lane] = (lane < 16 ? br : bc + (lane >= 32 ? t1 : 0u)) + in_row - c;
+      const unsigned b_rn = (unsigned)__builtin_amdgcn_readlane((int)first, 0), b_rf = (unsigned)__builtin_amdgcn_readlane((int)first, 1);
+      const unsigned b_cn = (unsigned)__builtin_amdgcn_readlane((int)first, 2), b_cf = (unsigned)__builtin_amdgcn_readlane((int)first, 3);
+      if (lane < 40) {
+        const unsigned ex = in_row - c;  // the counters in front of this one in its row
+        s_cnt[lane] = lane < 8 ? b_rn + ex : lane < 16 ? b_rf + ex - r0 : lane < 24 ? b_cn + ex : lane < 32 ? b_cf + ex - k0 : b_cf + k01 - k0 + ex;
+      }
     }
     if (!PIPE || n_waves != 8)
 #endif
     if (threadIdx.x == 0) {
-      unsigned tr = 0, tc = 0;
-      for (int w = 0; w < n_waves; w++) { tr += s_cnt[w] + s_cnt[8 + w]; tc += s_cnt[16 + w] + s_cnt[24 + w] + s_cnt[32 + w]; }
-      unsigned br = tr ? atomicAdd(&W.counts[RTC_WF_SHADE_COUNT + level], tr) : 0u;
-      unsigned bc = tc ? atomicAdd(&W.counts[level + 1], tc) : 0u;
-      if ((unsigned long long)br + tr > W.cap || (unsigned long long)bc + tc > W.cap) { W.counts[RTC_WF_OVERFLOW] = 1u; stats->wf_overflow = 1ull; }
-      for (int k = 0; k < 2; k++)
-        for (int w = 0; w < n_waves; w++) { unsigned r = s_cnt[8 * k + w]; s_cnt[8 * k + w] = br; br += r; }
-      for (int k = 2; k < 5; k++)
-        for (int w = 0; w < n_waves; w++) { unsigned c = s_cnt[8 * k + w]; s_cnt[8 * k + w] = bc; bc += c; }
+      unsigned t[4] = {0u, 0u, 0u, 0u}, b[4];
+      for (int k = 0; k < 5; k++)
+        for (int w = 0; w < n_waves; w++) t[end_of[k]] += s_cnt[8 * k + w];
+      const int row[4] = {RTC_WF_SHADE_COUNT + level, RTC_WF_SHADE_TOP_COUNT + level, level + 1, RTC_WF_TOP_COUNT + level + 1};
+      for (int e = 0; e < 4; e++) {
+        const unsigned old = t[e] ? atomicAdd(&W.counts[row[e]], t[e]) : 0u;
+        const bool fits = (unsigned long long)old + t[e] <= W.cap;
+        if (!fits) { W.counts[RTC_WF_OVERFLOW] = 1u; stats->wf_overflow = 1ull; }
+        b[e] = (e & 1) ? (fits ? W.cap - old - t[e] : W.cap) : old;
+      }
+      for (int k = 0; k < 5; k++)
+        for (int w = 0; w < n_waves; w++) { const unsigned r = s_cnt[8 * k + w]; s_cnt[8 * k + w] = b[end_of[k]]; b[end_of[k]] += r; }
     }
     __syncthreads();
     const unsigned s = on_plane ? s_cnt[wave] + (unsigned)__popcll(m_rec0 & lt) : s_cnt[8 + wave] + (unsigned)__popcll(m_rec1 & lt);

@@ -418,10 +418,12 @@ int run(rtc_scene* s, const DCamera& cam, DPixelMap pm, int fuel, double* d_rgb,
   if (rcs != RTC_OK) return rcs;
   if (wavefront) {
     if (std::getenv("RTC_WF_DUMP_COUNTS")) {  // debug aid: rays and shade records per level of this frame
-      uint32_t c[64];
+      uint32_t c[64], top[64];  // (the near ends' counts; the far ends': rays, records)
       HIP_OK(hipMemcpy(c, s->wave.counts, sizeof(c), hipMemcpyDeviceToHost));
-      std::fprintf(stderr, "[rtc-wf] level: rays / shade records:");
-      for (int l = 0; l <= fuel; l++) std::fprintf(stderr, " %d: %u / %u;", l, l ? c[l] : (unsigned)rtc_wavefront_work(cam, pm), c[RTC_WF_SHADE_COUNT + l]);
+      HIP_OK(hipMemcpy(top, s->wave.counts + RTC_WF_TOP_COUNT, sizeof(top), hipMemcpyDeviceToHost));
+      std::fprintf(stderr, "[rtc-wf] level: rays far + near / shade records far + near:");
+      for (int l = 0; l <= fuel; l++)
+        std::fprintf(stderr, " %d: %u + %u / %u + %u;", l, top[l], l ? c[l] : (unsigned)rtc_wavefront_work(cam, pm), top[32 + l], c[RTC_WF_SHADE_COUNT + l]);
       std::fprintf(stderr, "\n");
     }
     uint32_t overflow = 0;
