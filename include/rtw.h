@@ -94,8 +94,8 @@ rtw_element* rtw_parse_obj(const char* path, const double transform[16], const r
 /* Normal perturbation (include/rtc.h rtc_bump; not in the reference): every primitive of the element, a shape or a whole group, gets
  * the bump record {kind (RTC_BUMP_*), octaves (fractal only), amplitude, frequency} on its material; a second call replaces the first.
  * A group built with a material afterwards replaces its children's materials, bumps included, as ever.  Two shapes that share a
- * material but not the bump flatten to two material rows.  Fails for numbers rtc_scene_create_ext4 would refuse.  Product library only;
- * rendering such a world needs rtc_scene_create_ext4. */
+ * material but not the bump flatten to two material rows.  Fails for numbers rtc_scene_create_ext4 would refuse.  Product library (rendering
+ * such a world needs rtc_scene_create_ext4) and the tests' extended oracle; the reference restatement liboracle.so has no such entry. */
 int rtw_element_set_bump(rtw_element*, int32_t kind, uint32_t octaves, double amplitude, double frequency);
 void rtw_element_release(rtw_element*);
 

@@ -106,6 +106,29 @@ int rtw_world_set_background(rtw_world* w, const rtw_pattern* pattern, int32_t p
   return 0;
 }
 
+// include/rtw.h: the record on the material of every primitive of the element (a shape, a whole group, an OBJ element); a second call
+// replaces the first; a group built with a material afterwards replaces its children's materials (Element::propagate_inverses), the
+// record with the rest.  The limits are rtc_scene_create_ext4's.
+static const char* bump_limits(int32_t kind, uint32_t octaves, double amplitude, double frequency) {
+  if (kind < RTC_BUMP_SIMPLEX || kind > RTC_BUMP_RIPPLE) return "bump: unknown kind (simplex, fractal, ripple)";
+  if (!std::isfinite(amplitude)) return "bump: the amplitude is not finite";
+  if (!std::isfinite(frequency) || !(frequency > 0.0)) return "bump: the frequency must be finite and > 0";
+  if (kind == RTC_BUMP_FRACTAL && (octaves == 0 || octaves > RTC_BUMP_MAX_OCTAVES)) return "bump: fractal octaves must be within 1..RTC_BUMP_MAX_OCTAVES (64)";
+  return nullptr;
+}
+static void put_bump(Element& e, const std::shared_ptr<const BumpRecord>& b) {
+  if (!e.is_group) { e.shape.material.bump = b; return; }
+  for (auto& c : e.children) put_bump(*c, b);
+}
+int rtw_element_set_bump(rtw_element* e, int32_t kind, uint32_t octaves, double amplitude, double frequency) {
+  if (!e || !e->e) return fail("set_bump: NULL/consumed element");
+  if (const char* why = bump_limits(kind, octaves, amplitude, frequency)) return fail(why);
+  auto b = std::make_shared<BumpRecord>();
+  b->kind = kind; b->octaves = octaves; b->amplitude = amplitude; b->frequency = frequency;
+  put_bump(*e->e, b);
+  return 0;
+}
+
 // ---- probes of the single rules ---------------------------------------------------------------------------------------------------
 // The usteps * vsteps sample positions (k order) of an area light that is number light_index of its list, for a shading point `over`.
 void orc_ext_sample_positions(const double corner[3], const double uvec[3], uint32_t usteps, const double vvec[3], uint32_t vsteps, int jitter,
@@ -132,6 +155,54 @@ void orc_ext_pattern_colors(const rtw_pattern* p, const double* points, uint64_t
     rgb[3 * q] = c.r; rgb[3 * q + 1] = c.g; rgb[3 * q + 2] = c.b;
     if (tie) tie[q] = g_tie ? 1 : 0;
   }
+}
+// Steps 1-4 of rtc_bump: the unit shading normal before the inside flip, for a record, a material_inv (16, row-major), a hit point and
+// the unit normal.
+int orc_ext_bump_normal(int32_t kind, uint32_t octaves, double amplitude, double frequency, const double material_inv[16], const double point[3],
+                        const double normal[3], double out[3]) {
+  if (!material_inv || !point || !normal || !out) return fail("bump_normal: NULL argument");
+  if (const char* why = bump_limits(kind, octaves, amplitude, frequency)) return fail(why);
+  BumpRecord b;
+  b.kind = kind; b.octaves = octaves; b.amplitude = amplitude; b.frequency = frequency;
+  bump_normal(b, Matrix::from16(material_inv), Vector::point(point[0], point[1], point[2]), Vector::vector(normal[0], normal[1], normal[2]), out);
+  return 0;
+}
+// rtc_bump_normals' counterpart: item q is a primitive (its place in the depth-first numbering), a point and a unit normal; out is steps
+// 1-4 with the record and the material_inv that primitive holds in THIS world, or the normal itself where its material has no record.
+int orc_ext_world_bump_normals(const rtw_world* w, const int32_t* prims, const double* points, const double* normals, uint64_t n, double* out) {
+  if (!w || !prims || !points || !normals || !out) return fail("world_bump_normals: NULL argument");
+  std::vector<const Shape*> order;
+  w->w.number_shapes(order);
+  for (uint64_t q = 0; q < n; q++) {
+    if (prims[q] < 0 || (size_t)prims[q] >= order.size()) return fail("world_bump_normals: primitive out of range");
+    const Shape& s = *order[(size_t)prims[q]];
+    const double *X = points + 3 * q, *nn = normals + 3 * q;
+    if (!s.material.bump) { out[3 * q] = nn[0]; out[3 * q + 1] = nn[1]; out[3 * q + 2] = nn[2]; continue; }
+    bump_normal(*s.material.bump, s.material_inv, Vector::point(X[0], X[1], X[2]), Vector::vector(nn[0], nn[1], nn[2]), out + 3 * q);
+  }
+  return 0;
+}
+// normal . eye of the state of each listed pixel's (idx == NULL: every pixel's) primary hit -- the shading normal after the flip against
+// the eye vector; NaN for a pixel that hits nothing.  Negative where a bump turns the shading normal away from the viewer.
+int orc_ext_pixel_normal_dot_eye(rtw_world* w, const rtw_camera* cam, const uint64_t* idx, uint64_t n, double* out) {
+  Matrix m = Matrix::from16(cam->transform), inv;
+  if (!m.inverse(&inv)) return fail("camera: singular transform");
+  Camera c = Camera::make((size_t)cam->hsize, (size_t)cam->vsize, cam->field_of_view, m);
+  World::Ctx ctx;
+  for (uint64_t q = 0; q < n; q++) {
+    uint64_t i = idx ? idx[q] : q;
+    Ray ray = c.ray_at_pixel((size_t)(i % c.hsize), (size_t)(i / c.hsize));
+    w->w.intersect(ray, ctx);
+    sort_intersections(ctx.xs, &ctx.nan_seen);
+    const Intersection* h = hit(ctx.xs);
+    out[q] = std::nan("");
+    if (h) {
+      Intersection self = *h;
+      State st = prepare_state(self, ray, ctx.xs);
+      out[q] = st.normal.dot(st.eye);
+    }
+  }
+  return 0;
 }
 // Where a ray of direction dir looks the background up.
 int orc_ext_background_point(int32_t projection, const double dir[3], double point[3]) {

@@ -34,6 +34,10 @@
 #include <utility>
 #include <vector>
 
+#if defined(ORC_EXT) && !defined(ORC_EXT_MUTANT)
+#define ORC_EXT_MUTANT 0
+#endif
+
 namespace orc {
 
 // src/config.rs:1-2
@@ -458,6 +462,9 @@ struct Material {  // material.rs:19-43
   PatternPtr pattern = Pattern::plain(Color::white());
   double ambient = 0.1, diffuse = 0.9, specular = 0.9, shininess = 200.0;
   double reflective = 0.0, transparency = 0.0, refractive_index = 1.0;
+#ifdef ORC_EXT
+  std::shared_ptr<const struct BumpRecord> bump;  // include/rtc.h rtc_bump (rt_oracle_ext.hpp); null: no record
+#endif
 };
 
 // ---------------------------------------------------------------- bounding_box.rs
@@ -900,7 +907,15 @@ struct State {  // :9-22
   Vector point, over_point, under_point, eye, normal, reflect;
   bool inside;
   double n1, n2, reflectance;
+#ifdef ORC_EXT
+  Vector geo_normal;  // the flipped geometric normal (`normal` is the shading normal ns where the material has a bump record)
+#endif
 };
+#ifdef ORC_EXT
+// include/rtc.h rtc_bump (rt_oracle_ext.hpp): steps 1-4, the unit shading normal before the flip; steps 5-7 on the state.
+inline Vector bump_shading_normal(const Shape& shape, const Vector& point, const Vector& n);
+inline void bump_state(State& st, Vector ns);
+#endif
 inline State prepare_state(const Intersection& self, const Ray& ray, const Intersections& xs) {  // :50-121
   State st;
   st.t = self.t;
@@ -908,6 +923,11 @@ inline State prepare_state(const Intersection& self, const Ray& ray, const Inter
   st.point = ray.position(self.t);
   st.eye = -ray.direction;
   st.normal = self.shape->normal(st.point, self.has_uv, self.u, self.v);
+#ifdef ORC_EXT
+  const bool bumped = self.shape->material.bump != nullptr;  // a material without a record takes every step as the reference does
+  Vector ns = st.normal;
+  if (bumped) ns = bump_shading_normal(*self.shape, st.point, st.normal);
+#endif
   st.inside = false;
   if (st.normal.dot(st.eye) < 0.0) {
     st.normal = -st.normal;
@@ -915,6 +935,10 @@ inline State prepare_state(const Intersection& self, const Ray& ray, const Inter
   }
   st.over_point = st.point + (st.normal * EPSILON);
   st.under_point = st.point - (st.normal * EPSILON);
+#ifdef ORC_EXT
+  st.geo_normal = st.normal;
+  if (bumped) bump_state(st, ns);  // the flip was decided on the geometric normal, over / under_point are made from it; normal = +-ns
+#endif
   st.reflect = ray.direction.reflect(st.normal);
 
   std::vector<const Shape*> shapes;  // the HashSet mirrors membership of this Vec
@@ -935,7 +959,11 @@ inline State prepare_state(const Intersection& self, const Ray& ray, const Inter
   }
   st.n1 = n1;
   st.n2 = n2;
+#if defined(ORC_EXT) && ORC_EXT_MUTANT == 11   // schlick (here) and the refracted direction (refracted_color) from the geometric normal
+  st.reflectance = schlick(st.eye, st.geo_normal, n1, n2);
+#else
   st.reflectance = schlick(st.eye, st.normal, n1, n2);
+#endif
   return st;
 }
 
@@ -1048,11 +1076,19 @@ struct World {  // :12-15
   Color refracted_color(const State& st, int fuel, Ctx& c) const {  // :104-132
     if (fuel <= 0 || st.shape->material.transparency == 0.0) return Color::black();
     double n_ratio = st.n1 / st.n2;
+#if defined(ORC_EXT) && ORC_EXT_MUTANT == 11
+    double cos_i = st.eye.dot(st.geo_normal);
+#else
     double cos_i = st.eye.dot(st.normal);
+#endif
     double sin2_t = (n_ratio * n_ratio) * (1.0 - cos_i * cos_i);
     if (sin2_t > 1.0) return Color::black();
     double cos_t = std::sqrt(1.0 - sin2_t);
+#if defined(ORC_EXT) && ORC_EXT_MUTANT == 11
+    Vector direction = st.geo_normal * (n_ratio * cos_i - cos_t) - st.eye * n_ratio;
+#else
     Vector direction = st.normal * (n_ratio * cos_i - cos_t) - st.eye * n_ratio;
+#endif
     Ray r{st.under_point, direction};
     c.next_kind = 2;
     return color_at(r, fuel - 1, c) * st.shape->material.transparency;

@@ -1,5 +1,5 @@
 """Test-only access to the extended CPU oracle (oracle/_build/liboracle_ext.so): the reference restatement plus area lights, texture
-maps, light cones and the scene background, restated from include/rtc.h (oracle/rt_oracle_ext.hpp).  Never imported by the product
+maps, light cones, the scene background and bump records, restated from include/rtc.h (oracle/rt_oracle_ext.hpp).  Never imported by the product
 package.  ``mutant(n)`` loads one of the deliberately wrong builds of the sensitivity test; nothing else does."""
 import ctypes as C
 import os
@@ -13,7 +13,8 @@ from oracle_lib import ORACLE_DIR, OracleBackend
 LIB_EXT = os.path.join(ORACLE_DIR, "_build", "liboracle_ext.so")
 MUTANTS = {1: "jv hashed with 2k", 2: "samples in u-outer order", 3: "secondary colour once per sample",
            5: "background without the L factors", 6: "cube faces tested y before x", 7: "texture row 0 at the bottom",
-           8: "UV children at the untransformed point"}
+           8: "UV children at the untransformed point", 9: "ns not negated on an inside hit", 10: "over_point / under_point from ns",
+           11: "schlick and the refracted direction from the geometric normal", 12: "step 3 by the 3x3 itself", 13: "the slope offsets applied to sx"}
 
 
 class OracleExtBackend(OracleBackend):
@@ -25,7 +26,7 @@ class OracleExtBackend(OracleBackend):
             oracle_lib.build_oracle()
         Backend.__init__(self, path)   # (OracleBackend's own constructor insists on the plain oracle's library and name)
         assert self.name == self.NAME, self.name
-        assert self.has_area_lights and self.has_light_cones and self.has_background and self.has_texture_map
+        assert self.has_area_lights and self.has_light_cones and self.has_background and self.has_texture_map and self.has_bump
         vp, d3 = C.c_void_p, C.POINTER(C.c_double)
         lib = self.lib
         lib.orc_render.restype = C.c_int
@@ -48,6 +49,12 @@ class OracleExtBackend(OracleBackend):
         lib.orc_ext_pixel_ties.argtypes = [vp, vp, C.c_int, vp, C.c_uint64, vp]
         lib.orc_ext_ray_ties.restype = C.c_int
         lib.orc_ext_ray_ties.argtypes = [vp, vp, C.c_uint64, C.c_int, vp]
+        lib.orc_ext_bump_normal.restype = C.c_int
+        lib.orc_ext_bump_normal.argtypes = [C.c_int32, C.c_uint32, C.c_double, C.c_double, C.POINTER(C.c_double), d3, d3, d3]
+        lib.orc_ext_world_bump_normals.restype = C.c_int
+        lib.orc_ext_world_bump_normals.argtypes = [vp, vp, vp, vp, C.c_uint64, vp]
+        lib.orc_ext_pixel_normal_dot_eye.restype = C.c_int
+        lib.orc_ext_pixel_normal_dot_eye.argtypes = [vp, vp, vp, C.c_uint64, vp]
 
     # ---- probes of the single rules
     @staticmethod
@@ -89,6 +96,29 @@ class OracleExtBackend(OracleBackend):
             out[k] = list(p)
         return out
 
+    def bump_normal(self, kind, octaves, amplitude, frequency, material_inv, point, normal):
+        """Steps 1-4 of include/rtc.h rtc_bump: kind 0 simplex, 1 fractal, 2 ripple; material_inv: 16 floats, row-major."""
+        out = (C.c_double * 3)()
+        self._check(self.lib.orc_ext_bump_normal(int(kind), int(octaves), float(amplitude), float(frequency), (C.c_double * 16)(*[float(x) for x in material_inv]),
+                                                 self._v3(point), self._v3(normal), out), "bump_normal")
+        return np.array(list(out))
+
+    def world_bump_normals(self, nw, prims, points, normals):
+        """rtc_bump_normals' counterpart: steps 1-4 with the record and material_inv each listed primitive holds in the built world."""
+        prims = np.ascontiguousarray(prims, dtype=np.int32)
+        points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        normals = np.ascontiguousarray(normals, dtype=np.float64).reshape(-1, 3)
+        out = np.full((len(prims), 3), np.nan)
+        self._check(self.lib.orc_ext_world_bump_normals(nw.handle, prims.ctypes.data, points.ctypes.data, normals.ctypes.data, len(prims), out.ctypes.data), "world_bump_normals")
+        return out
+
+    def pixel_normal_dot_eye(self, nw, camera):
+        """normal . eye of every pixel's primary-hit state (the shading normal after the flip); NaN where the pixel hits nothing."""
+        cam = self.camera_c(camera)
+        out = np.full(camera.hsize * camera.vsize, np.nan)
+        self._check(self.lib.orc_ext_pixel_normal_dot_eye(nw.handle, C.byref(cam), None, out.size, out.ctypes.data), "pixel_normal_dot_eye")
+        return out
+
     def pixel_ties(self, nw, camera, fuel, pixel_indices=None):
         """The tie flag of every pixel's ray tree (oracle/rt_oracle_ext.hpp: a (u, v) decision behind atan2 / acos within 1e-9 of its threshold)."""
         cam = self.camera_c(camera)
@@ -106,6 +136,19 @@ class OracleExtBackend(OracleBackend):
         tie = np.zeros(len(rays), dtype=np.uint8)
         self._check(self.lib.orc_ext_ray_ties(nw.handle, rays.ctypes.data, len(rays), int(fuel), tie.ctypes.data), "ray_ties")
         return tie.astype(bool)
+
+
+def world_with_two_set_bump_calls(backend, first, second, transform16):
+    """One sphere under `transform16` whose element took rtw_element_set_bump twice -- first, then second, each (kind, octaves, amplitude,
+    frequency) -- through the back end's own rtw entry points (the Python classes hold one record per material, so they cannot say this)."""
+    from raytracer_challenge_amd.backend import NativeWorld
+    lib = backend.lib
+    w = backend._check_ptr(lib.rtw_world_create(), "world_create")
+    e = backend._check_ptr(lib.rtw_shape(0, (C.c_double * 16)(*[float(x) for x in transform16]), None, 1, None, 0), "shape")
+    for kind, octaves, a, f in (first, second):
+        backend._check(lib.rtw_element_set_bump(e, int(kind), int(octaves), float(a), float(f)), "set_bump")
+    backend._check(lib.rtw_world_add_element(w, e), "add_element")
+    return NativeWorld(backend, w, 0)
 
 
 _ext = None

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import build_matrix as bm
+from bump_cases import ROWS, bumped, mixed, row_world
 import foreign_flattener as ff
 from parity import RGB_TOL
 from raytracer_challenge_amd import scenes
@@ -30,32 +31,6 @@ def bind(lib):
     bind_bg(lib)
     bind_bump(lib)
     return lib
-
-
-def bumped(world, pick):
-    """The world with pick(k) as the bump of the k-th material met (shapes, groups' materials and OBJ files, depth first)."""
-    k = [0]
-
-    def mat(m):
-        if m is None:
-            return None
-        k[0] += 1
-        return dataclasses.replace(m, bump=pick(k[0] - 1))
-
-    def el(e):
-        if e.tag == "shape":
-            return dataclasses.replace(e, args=dataclasses.replace(e.args, material=mat(e.args.material)))
-        if e.tag == "composite":
-            return dataclasses.replace(e, material=mat(e.material), children=tuple(el(c) for c in e.children))
-        return dataclasses.replace(e, material=mat(e.material))
-    return World(world.lights, [el(e) for e in world.elements], world.background)
-
-
-MIXED = (Bump.simplex(0.08, 2.0), Bump.fractal(3, 0.15, 1.5), Bump.ripple(0.1, 1.3), None)
-
-
-def mixed(k):
-    return MIXED[k % len(MIXED)]
 
 
 def render_world(hip, world, cam, fuel=FUEL):
@@ -249,23 +224,6 @@ def test_lighting_follows_the_shading_normal(hip, path, monkeypatch):
 
 
 # ---- 5. path against path, one scene per row of RTC_NP_BUILDS ---------------------------------------------------------------------------------
-ROWS = {  # row -> (scene of tests/build_matrix.py or the open world with the teapot, with a background?)
-    0: ("csg", False), 1: ("area_csg_real", False), 2: ("uv_real", False), 3: ("uv_area_real", False), 4: ("spot_real", False), 5: ("uv_spot_real", False),
-    6: ("open", True), 7: ("area_kops_real", True), 8: ("uv_real", True), 9: ("uv_area_real", True), 10: ("spot_real", True), 11: ("uv_spot_real", True),
-}
-
-
-def row_world(row, tmp_path):
-    name, bg = ROWS[row]
-    sky = real_backgrounds()[0][1]
-    if name == "open":                                                               # a glass-and-mirror ball, a CSG solid and the low teapot
-        return bm.camera(), open_world(sky)
-    cam, world = bm.BY_NAME[name].make(tmp_path)
-    if bg:
-        world = World(world.lights, world.elements[:1] + world.elements[2:], sky)   # without the back wall: the sky is in frame
-    return cam, world
-
-
 @pytest.mark.parametrize("row", sorted(ROWS))
 def test_path_against_path_on_every_np_build(hip, row, tmp_path, monkeypatch):
     cam, twin = row_world(row, tmp_path)
