@@ -805,6 +805,20 @@ int rtc_scan_raw(rtc_scene* scene, uint64_t* values, uint64_t n, uint64_t* total
  * stacks fit 160 KB); 0 = they are read from memory.  bench.py's byte accounting counts LDS-resident records as 0 bytes. */
 uint32_t rtc_scene_wavefront_lds_bytes(const rtc_scene*);
 
+/* Read-only: the grid (blocks) of the wavefront traversal kernel in a launch of this scene made now.  sync != 0: a launch the host
+ * waits for (rtc_render, any launch with a stats pointer or sync set); 0: an unsynchronised one (rtc_render_rows_device / _bands_device
+ * with sync = 0 and no stats).  A scene whose tables live in LDS (rtc_scene_wavefront_lds_bytes > 0) runs one persistent 768-thread
+ * block per CU, which fills the CU: *grid = the device's CU count.  Such a block leaves no room for the kernels of other streams, so an
+ * UNSYNCHRONISED launch of such a scene, while at least one other scene is alive on the same device, leaves *spare_cus CUs out:
+ * *grid = n_cu - spare_cus, and the shading and gather kernels of the other scenes' frames run there meanwhile ("Spare
+ * CUs").  Every grid renders the same bits.  The environment variable RTC_WF_SPARE_CUS=k, read when a scene is created and clamped
+ * to 0 .. n_cu - 1, replaces the built-in number for that scene; 0 turns the rule off.  A scene whose tables are read from memory
+ * (lds_bytes == 0) reports the grid of that build (one-wave blocks, as many as the device holds), which no switch changes.  (A device
+ * that refused the LDS size, rtc_kernel_info.lds_refused, runs that build too, whatever is reported here.)  *n_cu: CUs of the scene's
+ * device; *spare_cus: the scene's number, whether or not it applies now; *live: scenes alive on the device, this one included.  Any
+ * out pointer may be NULL.  RTC_ERR_INVALID for a NULL scene. */
+int rtc_scene_wavefront_ts_grid(const rtc_scene*, int32_t sync, uint32_t* grid, uint32_t* n_cu, uint32_t* spare_cus, uint32_t* live);
+
 /* Test hook: which build of each ray kernel a launch of this scene takes, read-only.  The ray kernels are compiled in several builds
  * (DESIGN.md "Kernel builds"); the launchers and this query call the same selection functions, so what is reported is what runs -- with one exception, decided
  * at launch time: a device that refuses the dynamic LDS size runs wf_ts's memory build (lds_refused below tells).

@@ -2229,6 +2229,21 @@ constexpr unsigned rtc_pick_lds_bytes(RtcVariant r, bool lds_enabled, unsigned l
   return need <= 158ull * 1024 ? (unsigned)need : 0u;
 }
 constexpr RtcWfTsBuild rtc_pick_wf_ts_build(bool count, bool lds) { return lds ? (count ? RTC_TS_LDS_COUNT : RTC_TS_LDS) : (count ? RTC_TS_MEM_COUNT : RTC_TS_MEM); }
+// wavefront traversal, LDSC build: its grid.  One persistent block fills a CU, so the grid is the CUs the launch takes: all n_cu of
+// them, or n_cu - spare when the launch leaves `spare` CUs to the shading and gather kernels of other scenes' streams (DESIGN.md 5,
+// "Spare CUs"; the kernel hands out its chunks from cursors, so every grid of 1 .. n_cu blocks renders the same bits)
+constexpr unsigned rtc_pick_wf_ts_lds_grid(int n_cu, int spare) {
+  return (unsigned)(n_cu < 1 ? 1 : (spare <= 0 ? n_cu : (spare >= n_cu ? 1 : n_cu - spare)));
+}
+static_assert(rtc_pick_wf_ts_lds_grid(256, 0) == 256u && rtc_pick_wf_ts_lds_grid(256, 24) == 232u && rtc_pick_wf_ts_lds_grid(256, 255) == 1u, "n_cu - spare");
+static_assert(rtc_pick_wf_ts_lds_grid(256, 256) == 1u && rtc_pick_wf_ts_lds_grid(256, 261) == 1u && rtc_pick_wf_ts_lds_grid(1, 1) == 1u, "spare >= n_cu: one block");
+static_assert(rtc_pick_wf_ts_lds_grid(256, -8) == 256u && rtc_pick_wf_ts_lds_grid(0, 0) == 1u, "a negative spare: n_cu; never an empty grid");
+// spare CUs of an unsynchronised LDSC launch of a scene that has company on its device, unless RTC_WF_SPARE_CUS says otherwise
+// (measured on 256 CUs, profiles/wf_spare_cus.txt: config 2 at three frames in flight -2.8 %; a multiple of 32 = the same number from
+// every shader engine of every XCD -- other values lose; beyond 128 nothing more is gained, and a stream whose company is idle pays
+// for every spare CU, so the smallest value on the plateau).  As a share of the device, 3 / 8, for a device or partition of another size.
+constexpr int rtc_wf_spare_cus_default(int n_cu) { return n_cu < 8 ? 0 : 3 * (n_cu / 8); }
+static_assert(rtc_wf_spare_cus_default(256) == 96 && rtc_wf_spare_cus_default(32) == 12 && rtc_wf_spare_cus_default(4) == 0, "3 / 8 of the CUs");
 // wavefront shading of one level (see wf_shade)
 constexpr RtcWfShadeBuild rtc_pick_wf_shade_build(bool count, bool has_uv, bool all_plain, bool level0) {
   if (has_uv) return count ? RTC_SH_COUNT_UV : RTC_SH_UV;

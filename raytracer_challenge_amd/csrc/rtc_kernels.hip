@@ -340,6 +340,9 @@ bool rtc_scene_is_big(unsigned long long scene_bytes) { return rtc_big_scene(sce
 unsigned rtc_wavefront_grid(const DScene& S, int n_cu) {
   return (unsigned)std::max(1, n_cu * rtc_ops(rtc_variant(S, true)).wf_ts_blocks_per_cu(rtc_stack_bytes(S)));
 }
+// ... and of its LDS-resident build: one block per CU, `spare` CUs left out (rtc_pick_wf_ts_lds_grid; spare 0: every CU)
+unsigned rtc_wavefront_lds_grid(int n_cu, int spare) { return rtc_pick_wf_ts_lds_grid(n_cu, spare); }
+int rtc_wavefront_spare_cus_default(int n_cu) { return rtc_wf_spare_cus_default(n_cu); }
 #endif
 
 // work ids of a launch (tile padding included): the minimum DWave.cap
@@ -350,29 +353,28 @@ uint64_t rtc_wavefront_work(const DCamera& cam, const DPixelMap& pm) {
 
 // One frame through the wavefront kernels.  The caller zeroed W.counts (RTC_WF_COUNTS entries) on the stream and sized the
 // arrays for W.cap >= the work ids of the launch and fuel + 1 levels; `blocks` / `shade_blocks` = grid sizes of the traversal /
-// shading kernels; `lds` = the scene's rtc_wavefront_lds_bytes (0, the default: tables in memory -- all a caller without LDSC builds can ask for).
-// `bg` (optional): the scene's background: wf_background (rtc_background.hip) runs once per level, behind that level's trace role.
-// `bump` (optional): the scene's bump table: every level is shaded by wf_shade's NP build (COUNT x UV), whatever build the scene takes without.
+// shading kernels; `lds` = the scene's rtc_wavefront_lds_bytes (0: tables in memory) and `lds_blocks` = the grid of the LDSC traversal build
+// (rtc_wavefront_lds_grid; read only when lds != 0), always given together.
+// `bg` (may be null): the scene's background: wf_background (rtc_background.hip) runs once per level, behind that level's trace role.
+// `bump` (may be null): the scene's bump table: every level is shaded by wf_shade's NP build (COUNT x UV), whatever build the scene takes without.
+// The overload without these four is all a caller without LDSC builds can ask for: tables in memory, no background, no bumps.
 #ifndef RTC_EMU
 void rtc_launch_wf_background(const DScene& S, const DCamera& cam, const DPixelMap& pm, const DWave& W, int level, unsigned n0, const DBackground& bg, unsigned blocks,
                               hipStream_t stream);
 #endif
 void rtc_launch_wavefront(const DScene& S, const DCamera& cam, const DPixelMap& pm, int fuel, const DWave& W, double* rgb, double* hit_t, int* hit_prim, int* hit_k,
-                          DStats* stats, bool count, hipStream_t stream, unsigned blocks, unsigned shade_blocks, unsigned lds = 0u, const DBackground* bg = nullptr, const DBumpTable* bump = nullptr) {
+                          DStats* stats, bool count, hipStream_t stream, unsigned blocks, unsigned shade_blocks, unsigned lds, unsigned lds_blocks, const DBackground* bg, const DBumpTable* bump) {
   if (pm.n == 0) return;
   const RtcVariantOps& ops = rtc_ops(rtc_variant(S, true));
   const RtcFrame F = {S, cam, pm, hit_t, hit_prim, hit_k, stats, stream, count};
   const unsigned n0 = (unsigned)rtc_wavefront_work(cam, pm);
-#ifndef RTC_EMU
-  const unsigned lds_blocks = std::max(1u, shade_blocks / 2u);  // one block per CU (the shading grid is two per CU)
-#endif
   const dim3 sgrid(std::max(1u, shade_blocks)), sblock(RTC_WF_SHADE_BLOCK);
   // trace_0; shade_0; [shadow_0 + trace_1]; shade_1; ... [shadow_{fuel-1} + trace_fuel]; shade_fuel; shadow_fuel; sums
   for (int level = 0; level <= fuel + 1; level++) {
     const int tl = level <= fuel ? level : -1, sl = level - 1;
 #ifndef RTC_EMU
     // (a device that refuses the LDS size — the opt-in is per device — runs the kernel that reads the tables from memory)
-    if (!lds || !ops.launch_wf_ts_lds(F, RtcLevel{W, tl, sl, n0, level, fuel - level, lds_blocks, lds}))
+    if (!lds || !ops.launch_wf_ts_lds(F, RtcLevel{W, tl, sl, n0, level, fuel - level, std::max(1u, lds_blocks), lds}))
 #endif
     ops.launch_wf_ts(F, RtcLevel{W, tl, sl, n0, level, fuel - level, blocks, 0u});
 #ifndef RTC_EMU
@@ -408,6 +410,10 @@ void rtc_launch_wavefront(const DScene& S, const DCamera& cam, const DPixelMap& 
     }
   }
   hipLaunchKernelGGL(wf_gather, dim3(std::max(1u, std::min(blocks, (n0 + 255u) / 256u))), dim3(256), 0, stream, cam, pm, W, n0, rgb);
+}
+void rtc_launch_wavefront(const DScene& S, const DCamera& cam, const DPixelMap& pm, int fuel, const DWave& W, double* rgb, double* hit_t, int* hit_prim, int* hit_k,
+                          DStats* stats, bool count, hipStream_t stream, unsigned blocks, unsigned shade_blocks) {
+  rtc_launch_wavefront(S, cam, pm, fuel, W, rgb, hit_t, hit_prim, hit_k, stats, count, stream, blocks, shade_blocks, 0u, 0u, nullptr, nullptr);
 }
 
 // ---- host-callable launcher (C++ linkage, used by rtc_scene.cpp) ------------------------------------------

@@ -38,7 +38,8 @@ void rtc_launch_pack_hits(const double* t, const int* prim, const int* k, DHit* 
 void rtc_launch_deinterleave(const double* slab, double* image, unsigned rowlen, unsigned vsize, unsigned n, unsigned max_rows, unsigned band, hipStream_t stream);
 void rtc_launch_deinterleave8(const unsigned char* slab, unsigned char* image, unsigned rowlen, unsigned vsize, unsigned n, unsigned max_rows, unsigned band, hipStream_t stream);
 void rtc_launch_wavefront(const DScene& S, const DCamera& cam, const DPixelMap& pm, int fuel, const DWave& W, double* rgb, double* hit_t, int* hit_prim, int* hit_k,
-                          DStats* stats, bool count, hipStream_t stream, unsigned blocks, unsigned shade_blocks, unsigned lds, const DBackground* bg, const DBumpTable* bump);
+                          DStats* stats, bool count, hipStream_t stream, unsigned blocks, unsigned shade_blocks, unsigned lds, unsigned lds_blocks, const DBackground* bg,
+                          const DBumpTable* bump);
 void rtc_launch_trace_np(const DScene& S, const DBumpTable& bt, const DBackground* bg, const DCamera& cam, const DPixelMap& pm, int fuel, double* rgb, double* hit_t,
                          int* hit_prim, int* hit_k, DStats* stats, bool count, hipStream_t stream);
 void rtc_launch_bump_normals(const DScene& S, const DBumpTable& bt, const int32_t* prims, const double* points, const double* normals, unsigned long long n, double* out,
@@ -52,6 +53,8 @@ void rtc_kernel_info_fill(const DScene& S, bool wavefront, bool count, bool big_
 bool rtc_scene_is_big(unsigned long long scene_bytes);
 uint64_t rtc_wavefront_work(const DCamera& cam, const DPixelMap& pm);
 unsigned rtc_wavefront_grid(const DScene& S, int n_cu);
+unsigned rtc_wavefront_lds_grid(int n_cu, int spare);
+int rtc_wavefront_spare_cus_default(int n_cu);
 unsigned rtc_wavefront_lds_bytes(const DScene& S, bool enabled);
 void rtc_launch_gen_rays(const DCamera& cam, const DPixelMap& pm, const rtc_sampling& sp, unsigned long long slot_first, unsigned long long n_slots, double* rays,
                          hipStream_t stream);
@@ -156,6 +159,9 @@ struct rtc_scene {
   int wave_levels = 0;
   unsigned wave_blocks = 0, shade_blocks = 0;
   unsigned lds_bytes = 0;     // dynamic LDS of the wavefront traversal kernel (0: tables in memory; RTC_WF_LDS=0 at creation pins that)
+  int n_cu = 1;               // CUs of the scene's device: the grid of the LDS-resident traversal build, less the spare ones (lds_grid below)
+  int spare_cus = 0;          // CUs an unsynchronised launch of that build leaves to other scenes' kernels (RTC_WF_SPARE_CUS at creation, else the default)
+  bool counted = false;       // the scene is in its device's count of live scenes (g_live_scenes)
   unsigned wave_eighths = 9;  // queue capacity per level, in eighths of the launch's level-0 work ids
   int bvh_depth = 0;
   int built_on_device = 0;  // mesh accelerators of this scene whose tree came from bvh_device.hip
@@ -322,6 +328,22 @@ void record_sample(rtc_scene* s, bool wavefront, double ms) {
   if (s->tune_n[0] >= 2 && s->tune_n[1] >= 2) s->tune_choice = s->tune_ms[1] < s->tune_ms[0] ? 4 : 1;
 }
 
+// Scenes alive per device (up at the end of scene_create, down in rtc_scene_destroy): a scene's stream can overlap another's kernels
+// only where another scene exists.  (A device index beyond the table is never counted: its scenes launch as lone ones do.)
+constexpr int RTC_LIVE_DEVICES = 64;
+std::atomic<int> g_live_scenes[RTC_LIVE_DEVICES];
+int live_scenes(int device) { return device >= 0 && device < RTC_LIVE_DEVICES ? g_live_scenes[device].load(std::memory_order_relaxed) : 0; }
+
+// Grid of the LDS-resident traversal build for a launch of scene s ("Spare CUs").  The persistent 768-thread blocks fill
+// their CUs, so while they run no block of another stream's wf_shade or wf_gather fits anywhere.  An UNSYNCHRONISED launch of a scene
+// that has company on its device therefore leaves spare_cus CUs out of its grid: pipelined frames of other scenes shade there.  Every
+// other launch takes all n_cu: a synchronous one (rtc_render, the tuning and counting launches) has the host waiting for this frame
+// alone, and a lone scene has no other stream that could use the room.
+unsigned lds_grid(const rtc_scene* s, bool will_sync) {
+  const bool spare = !will_sync && live_scenes(s->device) > 1;
+  return rtc_wavefront_lds_grid(s->n_cu, spare ? s->spare_cus : 0);
+}
+
 // Sticky error state of the scene (DStats tail): read and cleared together.
 int read_clear_sticky(rtc_scene* s, DStats* h) {
   HIP_OK(hipMemcpy(h, s->d_stats, sizeof(*h), hipMemcpyDeviceToHost));
@@ -398,7 +420,7 @@ int run(rtc_scene* s, const DCamera& cam, DPixelMap pm, int fuel, double* d_rgb,
     HIP_OK(hipMemsetAsync(s->wave.counts, 0, RTC_WF_COUNTS * sizeof(uint32_t), s->stream));
     HIP_OK(hipEventRecord(s->ev0, s->stream));
     rtc_launch_wavefront(s->d, cam, pm, fuel, s->wave, d_rgb, want_hits ? s->d_hit_t : nullptr, s->d_hit_prim, s->d_hit_k, s->d_stats, count, s->stream, s->wave_blocks, s->shade_blocks, s->lds_bytes,
-                         s->has_bg ? &s->bg : nullptr, s->has_bump ? &s->bump : nullptr);
+                         lds_grid(s, will_sync), s->has_bg ? &s->bg : nullptr, s->has_bump ? &s->bump : nullptr);
   } else if (s->has_bump) {
     rtc_launch_trace_np(s->d, s->bump, s->has_bg ? &s->bg : nullptr, cam, pm, fuel, d_rgb, want_hits ? s->d_hit_t : nullptr, s->d_hit_prim, s->d_hit_k, s->d_stats, count, s->stream);
   } else if (s->has_bg) {
@@ -1228,6 +1250,15 @@ int scene_create(const SceneInputs& in, int device, rtc_scene** out) {
     if (const char* w = std::getenv("RTC_WF_BLOCKS_PER_CU")) s->wave_blocks = (unsigned)std::max(1, n_cu * std::atoi(w));
     s->shade_blocks = (unsigned)std::max(1, n_cu * 2);
     if (const char* w = std::getenv("RTC_WF_SHADE_BLOCKS_PER_CU")) s->shade_blocks = (unsigned)std::max(1, n_cu * std::atoi(w));
+    // the LDS-resident traversal build: one block per CU, whatever the shading grid is; RTC_WF_SPARE_CUS=k: its unsynchronised launches
+    // leave k CUs out while another scene is alive on the device (lds_grid), pinned here as the switches above are
+    s->n_cu = std::max(1, n_cu);
+    const char* sp = std::getenv("RTC_WF_SPARE_CUS");
+    s->spare_cus = std::min(std::max(sp ? std::atoi(sp) : rtc_wavefront_spare_cus_default(s->n_cu), 0), s->n_cu - 1);
+  }
+  if (device >= 0 && device < RTC_LIVE_DEVICES) {
+    g_live_scenes[device].fetch_add(1, std::memory_order_relaxed);
+    s->counted = true;
   }
   *out = s.release();
   return RTC_OK;
@@ -1385,6 +1416,7 @@ void rtc_scene_destroy(rtc_scene* s) {
   if (s->ev0) (void)hipEventDestroy(s->ev0);
   if (s->ev1) (void)hipEventDestroy(s->ev1);
   if (s->stream) (void)hipStreamDestroy(s->stream);
+  if (s->counted) g_live_scenes[s->device].fetch_sub(1, std::memory_order_relaxed);
   delete s;
 }
 
@@ -2263,6 +2295,15 @@ int rtc_scan_raw(rtc_scene* s, uint64_t* values, uint64_t n, uint64_t* total) {
 }
 
 uint32_t rtc_scene_wavefront_lds_bytes(const rtc_scene* s) { return s ? s->lds_bytes : 0u; }
+
+int rtc_scene_wavefront_ts_grid(const rtc_scene* s, int32_t sync, uint32_t* grid, uint32_t* n_cu, uint32_t* spare_cus, uint32_t* live) {
+  if (!s) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  if (grid) *grid = s->lds_bytes ? lds_grid(s, sync != 0) : s->wave_blocks;  // (what run() hands rtc_launch_wavefront)
+  if (n_cu) *n_cu = (uint32_t)s->n_cu;
+  if (spare_cus) *spare_cus = (uint32_t)s->spare_cus;
+  if (live) *live = (uint32_t)live_scenes(s->device);
+  return RTC_OK;
+}
 
 int rtc_scene_kernel_info(const rtc_scene* s, int32_t path, int32_t count, rtc_kernel_info* out) {
   if (!s || !out) return rtc_fail(RTC_ERR_INVALID, "NULL argument");

@@ -193,6 +193,16 @@ class DeviceRenderer:
         return {"path": {0: "undecided", 1: "one kernel", 4: "wavefront"}.get(ch.value, str(ch.value)),
                 "one_kernel_ms": a.value, "wavefront_ms": b.value}
 
+    def wavefront_grid(self, sync: bool) -> dict:
+        """include/rtc.h rtc_scene_wavefront_ts_grid: the traversal kernel's grid in a synchronous / an unsynchronised launch made
+        now, the device's CUs, the scene's spare CUs (RTC_WF_SPARE_CUS when it was created) and the scenes alive on the device."""
+        lib = self.backend.lib
+        lib.rtc_scene_wavefront_ts_grid.restype = C.c_int
+        lib.rtc_scene_wavefront_ts_grid.argtypes = [C.c_void_p, C.c_int32] + [C.POINTER(C.c_uint32)] * 4
+        a = [C.c_uint32(0) for _ in range(4)]
+        self._rc(lib.rtc_scene_wavefront_ts_grid(self.scene, 1 if sync else 0, *[C.byref(x) for x in a]), "rtc_scene_wavefront_ts_grid")
+        return {"grid": a[0].value, "n_cu": a[1].value, "spare_cus": a[2].value, "live_scenes": a[3].value}
+
     def info(self) -> dict:
         a = [C.c_uint32(0) for _ in range(4)]
         self.backend.lib.rtc_scene_accel_info(self.scene, *[C.byref(x) for x in a])
