@@ -153,6 +153,23 @@ typedef struct rtc_light_ex {
  *   RTC_UV_IMAGE:       the texel of textures[texture] (w x h) at column xi = clamp(as_i32(round(u * (double)(w-1))), 0, w-1), row
  *                       yi = clamp(as_i32(round((1.0 - v) * (double)(h-1))), 0, h-1); row 0 is the top row.  No filtering; every
  *                       lookup stays in bounds (NaN and +-inf included).
+ *   RTC_UV_IMAGE_LINEAR, RTC_UV_IMAGE_LINEAR_WRAP_U, RTC_UV_IMAGE_LINEAR_WRAP: the bilinear blend of four texels of textures[texture]
+ *     (csrc/uv_image.h, one function for device and host).  They read `texture` exactly as RTC_UV_IMAGE does, have no children and
+ *     ignore width / height / child[].  _LINEAR clamps both axes (cube-map faces, decals), _LINEAR_WRAP_U takes u as periodic and
+ *     clamps v (spherical maps), _LINEAR_WRAP takes both as periodic (planar and cylindrical maps).
+ *     Per axis, with n = the texture's size along it and a = the coordinate (columns: a = u; rows: a = 1.0 - v, row 0 at the top):
+ *       clamped axis, texel centres where RTC_UV_IMAGE samples them (a = i / (n-1)):
+ *         x = a * (double)(n - 1), f = floor(x), t = x - f, i0 = clamp(as_i32(f), 0, n-1), i1 = clamp(as_i32(f + 1.0), 0, n-1);
+ *       periodic axis, n texels per period with centres at (i + 0.5) / n:
+ *         x = a * (double)n - 0.5, f = floor(x), t = x - f, i0 = emod(as_i32(f), n) with emod(k, n) = ((k % n) + n) % n in i32,
+ *         i1 = (i0 + 1 == n) ? 0 : i0 + 1;
+ *       either: a NaN t (a NaN or infinite a) becomes 0.0.  So t is in [0, 1], and every lookup stays in bounds, NaN and +-inf included.
+ *     Colour, per channel, with c[col][row] the four texels and tx, ty the two axes' t:
+ *       top = c[x0][y0] + (c[x1][y0] - c[x0][y0]) * tx, bot = c[x0][y1] + (c[x1][y1] - c[x0][y1]) * tx, out = top + (bot - top) * ty
+ *     -- the lerp of the Gradient mixture.  Four equal texels give that texel's bits whatever tx and ty are; a clamped axis at an
+ *     integer x gives RTC_UV_IMAGE's texel.
+ *     Not covered: mip-mapping and any minification filter, a per-record wrap choice beyond these three kinds, mirrored wrap,
+ *     filtering of RTC_UV_CHECKERS, height-map bumps (rtc_bump).
  * Textures are `height` rows of `width` f64 RGB triples, copied at scene creation; one texture may back any number of records and
  * is uploaded once per device.
  * Limits: RTC_ERR_INVALID for a UV node without records (always so in a plain rtc_scene_create descriptor), a cube map whose
@@ -162,11 +179,14 @@ typedef struct rtc_light_ex {
 enum { RTC_PAT_UV = 4 };
 enum { RTC_UVMAP_PLANAR = 0, RTC_UVMAP_SPHERICAL = 1, RTC_UVMAP_CYLINDRICAL = 2, RTC_UVMAP_CUBE = 3 };
 enum { RTC_UV_CHECKERS = 0, RTC_UV_ALIGN_CHECK = 1, RTC_UV_IMAGE = 2 };
+enum { RTC_UV_IMAGE_LINEAR = 3,         /* bilinear, both axes clamped            (cube-map faces, decals)        */
+       RTC_UV_IMAGE_LINEAR_WRAP_U = 4,  /* bilinear, u periodic, v clamped        (spherical maps)                */
+       RTC_UV_IMAGE_LINEAR_WRAP = 5 };  /* bilinear, both axes periodic           (planar, cylindrical maps)      */
 #define RTC_TEXTURE_MAX_SIDE 16384
 #define RTC_TEXTURE_MAX_TEXELS (1ull << 26)
 typedef struct rtc_uv_pattern {
   int32_t kind;          /* RTC_UV_* */
-  int32_t texture;       /* RTC_UV_IMAGE: index into the ext's textures */
+  int32_t texture;       /* RTC_UV_IMAGE*: index into the ext's textures */
   double width, height;  /* RTC_UV_CHECKERS: squares along u and v */
   int32_t child[5];      /* CHECKERS: the two colours; ALIGN_CHECK: main, ul, ur, bl, br */
   int32_t _pad;
@@ -248,7 +268,7 @@ typedef struct rtc_light_cone {
  * (rtc_background_point, rtc_background_colors, rtc_scene_background_info); checked before anything else, a device included.  The
  * pattern tree's own limits apply as they do for a material: RTC_MAX_PATTERN_DEPTH, UV records, textures.
  * Not covered: importance-sampled environment lighting; a background that only the camera sees; a per-channel or per-level tint;
- * filtered texture lookups. */
+ * mip-mapped (minified) texture lookups -- a skybox magnifies, and RTC_UV_IMAGE_LINEAR covers that. */
 enum { RTC_BG_DIRECTION = 0, RTC_BG_CUBE = 1 };
 typedef struct rtc_background {
   int32_t pattern;     /* index of a root rtc_pattern_node */
@@ -291,8 +311,8 @@ typedef struct rtc_background {
  * bumps; checked before anything else, a device included.  (A pattern node's octaves have no limit beyond their 32 bits; a record's are
  * capped because every hit pays three noise evaluations per octave, and octave 54 and later add less than one ulp of the sum.)
  * Not covered: a shading normal that faces away from the eye or below the geometric surface is not clamped, so a reflected ray may
- * re-enter its own surface; height maps taken from patterns or images (they need filtered texture lookups first); a transform of the
- * record's own; distance-dependent amplitude. */
+ * re-enter its own surface; height maps taken from patterns or images (the filtered lookups they need exist now,
+ * RTC_UV_IMAGE_LINEAR*; the bump kind that reads them does not); a transform of the record's own; distance-dependent amplitude. */
 enum { RTC_BUMP_SIMPLEX = 0, RTC_BUMP_FRACTAL = 1, RTC_BUMP_RIPPLE = 2 };
 #define RTC_BUMP_MAX_OCTAVES 64
 typedef struct rtc_bump {
@@ -558,6 +578,11 @@ int rtc_scene_bump_info(const rtc_scene*, rtc_bump_info* out);
 /* The cone factor f alone, for a light (or sample) at light_pos and a shading point `point`; `cone->light` is not read.  Host-only: no
  * device needed (like rtc_ppm).  RTC_ERR_INVALID for NULL arguments and for a cone rtc_scene_create_ext2 would refuse. */
 int rtc_spot_factor(const rtc_light_cone* cone, const double light_pos[3], const double point[3], double* f);
+/* One image record's colour at (u, v), on the host: rgb = the texel rule of `kind` (RTC_UV_IMAGE, or RTC_UV_IMAGE_LINEAR* through
+ * csrc/uv_image.h, the function the kernels compile) on `tex`.  Host-only: no device needed (like rtc_spot_factor).  RTC_ERR_INVALID for
+ * NULL arguments, a kind outside RTC_UV_IMAGE .. RTC_UV_IMAGE_LINEAR_WRAP, and a texture rtc_scene_create_ext would refuse (a side of 0
+ * or above RTC_TEXTURE_MAX_SIDE, NULL rgb). */
+int rtc_texture_sample(const rtc_texture* tex, int32_t kind, double u, double v, double rgb[3]);
 void rtc_scene_destroy(rtc_scene*);
 /* Size in bytes of the scene's device buffers (accelerator and texels included). */
 uint64_t rtc_scene_device_bytes(const rtc_scene*);

@@ -69,7 +69,8 @@ void rtw_pattern_release(rtw_pattern*);
  * rtw_texture_create copies h rows of w {r, g, b} (row 0 at the top); textures are immutable and ref-counted like patterns.
  * rtw_pattern_uv: map_kind = RTC_UVMAP_*, transform as rtw_pattern_mixture's; n_faces = 1, or 6 for a cube map (left, front, right,
  * back, up, down).  A face is one rtc_uv_pattern: kind RTC_UV_*, width / height (checkers), texture (image) and the children its
- * kind reads (checkers: child[0], child[1]; align check: main, ul, ur, bl, br), all borrowed. */
+ * kind reads (checkers: child[0], child[1]; align check: main, ul, ur, bl, br), all borrowed.  The bilinear image kinds
+ * RTC_UV_IMAGE_LINEAR, _LINEAR_WRAP_U and _LINEAR_WRAP take a texture as RTC_UV_IMAGE does and read no child. */
 typedef struct rtw_texture rtw_texture;
 typedef struct rtw_uv_pattern {
   int kind;

@@ -14,7 +14,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 
 from .scene import (BACKGROUND_PROJECTIONS, BUMP_KINDS, FUEL, GEOMETRY, GROUP_KINDS, JITTER_KINDS, MIXTURE_KINDS, Adaptive, AreaLight, Camera, Cone, Element, FILTER_KINDS, Filter, Material, Pattern, SHUTTER_MAX_POSES, Sampling, Shutter, World)
-from .texture import UV_KINDS, UV_MAPS, Texture
+from .texture import UV_MAPS, Texture
 
 HIT_DTYPE = np.dtype([("t", "<f8"), ("prim", "<i4"), ("push_idx", "<i4")])
 
@@ -198,7 +198,7 @@ class Backend:
                 raise RtwError("texture-mapped patterns need librtc_amd.so (backend %r has no rtw_pattern_uv)" % self.name)
             faces = (_UvFaceC * len(p.faces))()
             for k, f in enumerate(p.faces):
-                faces[k].kind, faces[k].width, faces[k].height = UV_KINDS[f.kind], f.width, f.height
+                faces[k].kind, faces[k].width, faces[k].height = f.kind_code(p.kind), f.width, f.height
                 faces[k].texture = self._texture(f.texture, cache, owned) if f.texture is not None else None
                 for c, child in enumerate(f.children):
                     faces[k].child[c] = self._pattern(child, cache, owned)

@@ -1011,6 +1011,8 @@ __device__ TRAVERSE_INLINE void traverse(const DScene& S, const Ray& r, Trav& T,
 // uses them in bump_normal.h.  Included HERE, inside this file's unnamed namespace, where the noise always stood: the device
 // functions keep their linkage names (the headers they include themselves are all included above).
 #include "bump_normal.h"
+// ---- the bilinear texture lookup (uv_image.h): one copy for the device and the host, included here for the same reason.
+#include "uv_image.h"
 
 __device__ __forceinline__ void jitter_3d(const DPat& p, double x, double y, double z, double& ox, double& oy, double& oz) {  // :31-52
   double nx, ny, nz;
@@ -1061,7 +1063,7 @@ __device__ __forceinline__ int uv_map(int kind, double x, double y, double z, do
   return 3;
 }
 // One UV record at (u, v): the child node it selects, or -1 with (r, g, b) = its texel (RTC_UV_IMAGE; the indices are clamped, so a
-// NaN or infinite u / v reads an edge texel).
+// NaN or infinite u / v reads an edge texel; kinds 3..5, the bilinear lookups, are uv_image.h's).
 __device__ __forceinline__ int uv_lookup(const DScene& S, const DUv& q, double u, double v, double& r, double& g, double& b) {
   if (q.kind == 0) return (wadd(as_i32(floor(u * q.width)), as_i32(floor(v * q.height))) % 2 == 0) ? q.child[0] : q.child[1];
   if (q.kind == 1) {  // main, ul, ur, bl, br
@@ -1073,6 +1075,12 @@ __device__ __forceinline__ int uv_lookup(const DScene& S, const DUv& q, double u
       if (u > 0.8) return q.child[4];
     }
     return q.child[0];
+  }
+  if (q.kind > 2) {  // RTC_UV_IMAGE_LINEAR, _LINEAR_WRAP_U, _LINEAR_WRAP
+    double c[3];
+    rtc_uv_image_linear((const double*)((const char*)S.pats + q.off), q.tw, q.th, q.kind, u, v, c);
+    r = c[0]; g = c[1]; b = c[2];
+    return -1;
   }
   int xi = as_i32(round(u * (double)(q.tw - 1))), yi = as_i32(round((1.0 - v) * (double)(q.th - 1)));
   xi = xi < 0 ? 0 : (xi > q.tw - 1 ? q.tw - 1 : xi);

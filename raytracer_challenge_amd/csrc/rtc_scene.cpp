@@ -30,6 +30,7 @@
 #include "scene_build.hpp"
 #include "shutter_pose.h"
 #include "spot_factor.h"
+#include "uv_image.h"
 
 void rtc_launch_trace(const DScene& S, const DCamera& cam, const DPixelMap& pm, int fuel, double* rgb, double* hit_t, int* hit_prim, int* hit_k,
                       DStats* stats, bool count, hipStream_t stream, bool big_scene);
@@ -1392,6 +1393,24 @@ int rtc_spot_factor(const rtc_light_cone* cone, const double light_pos[3], const
   double a[3];
   rtc_spot_axis(cone->axis, a);
   *f = rtc_spot_factor_at(a, cone->cos_inner, cone->cos_outer, light_pos, point);
+  return RTC_OK;
+}
+
+int rtc_texture_sample(const rtc_texture* tex, int32_t kind, double u, double v, double rgb[3]) {
+  if (!tex || !rgb) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  if (kind < RTC_UV_IMAGE || kind > RTC_UV_IMAGE_LINEAR_WRAP) return rtc_fail(RTC_ERR_INVALID, "kind is not an image kind (RTC_UV_IMAGE .. RTC_UV_IMAGE_LINEAR_WRAP)");
+  if (tex->width == 0 || tex->height == 0) return rtc_fail(RTC_ERR_INVALID, "texture of width or height 0");
+  if (tex->width > RTC_TEXTURE_MAX_SIDE || tex->height > RTC_TEXTURE_MAX_SIDE) return rtc_fail(RTC_ERR_INVALID, "a texture side above RTC_TEXTURE_MAX_SIDE");
+  if (!tex->rgb) return rtc_fail(RTC_ERR_INVALID, "texture rgb is NULL");
+  const int w = (int)tex->width, h = (int)tex->height;
+  if (kind == RTC_UV_IMAGE) {  // uv_lookup's nearest texel (rtc_device.hpp), restated
+    int xi = as_i32(round(u * (double)(w - 1))), yi = as_i32(round((1.0 - v) * (double)(h - 1)));
+    xi = xi < 0 ? 0 : (xi > w - 1 ? w - 1 : xi);
+    yi = yi < 0 ? 0 : (yi > h - 1 ? h - 1 : yi);
+    std::memcpy(rgb, tex->rgb + 3 * ((int64_t)yi * w + xi), 3 * sizeof(double));
+  } else {
+    rtc_uv_image_linear(tex->rgb, w, h, kind, u, v, rgb);
+  }
   return RTC_OK;
 }
 

@@ -163,13 +163,13 @@ rtw_pattern* rtw_pattern_uv(int map_kind, const double t[16], const rtw_uv_patte
     const rtw_uv_pattern& in = faces[k];
     UvFace f;
     f.kind = in.kind; f.width = in.width; f.height = in.height;
-    if (in.kind < RTC_UV_CHECKERS || in.kind > RTC_UV_IMAGE) { fail("uv: face kind out of range (checkers, align_check, image)"); return nullptr; }
+    if (in.kind < RTC_UV_CHECKERS || in.kind > RTC_UV_IMAGE_LINEAR_WRAP) { fail("uv: face kind out of range (checkers, align_check, image, image_linear, image_linear_wrap_u, image_linear_wrap)"); return nullptr; }
     if (in.kind == RTC_UV_CHECKERS && !(std::isfinite(in.width) && in.width > 0.0 && std::isfinite(in.height) && in.height > 0.0)) {
       fail("uv: checkers width and height must be finite and > 0");
       return nullptr;
     }
-    if (in.kind == RTC_UV_IMAGE) {
-      if (!in.texture) { fail("uv: image face without a texture"); return nullptr; }
+    if (in.kind >= RTC_UV_IMAGE) {  // nearest or bilinear
+      if (!in.texture) { fail(in.kind == RTC_UV_IMAGE ? "uv: image face without a texture" : "uv: face kind image_linear* without a texture"); return nullptr; }
       f.texture = in.texture->t;
     }
     for (int c = 0; c < f.n_children(); c++) {

@@ -816,7 +816,8 @@ struct UvInput {
   const rtc_texture* tex = nullptr;
   uint32_t n_tex = 0;
 };
-// children of a UV record that its kind reads (checkers: 2, align check: 5, image: none)
+// children of a UV record that its kind reads (checkers: 2, align check: 5, image, nearest or bilinear: none)
+inline bool uv_is_image(int32_t kind) { return kind >= RTC_UV_IMAGE && kind <= RTC_UV_IMAGE_LINEAR_WRAP; }
 inline int uv_children(const rtc_uv_pattern& q) { return q.kind == RTC_UV_CHECKERS ? 2 : (q.kind == RTC_UV_ALIGN_CHECK ? 5 : 0); }
 
 inline int validate(const rtc_scene_desc& D, std::string* err, const UvInput& uv = UvInput{}) {
@@ -854,12 +855,12 @@ inline int validate(const rtc_scene_desc& D, std::string* err, const UvInput& uv
   if ((uv.n_pats > 0 && !uv.pats) || (uv.n_tex > 0 && !uv.tex)) return bad("uv_patterns / textures is NULL");
   for (uint32_t k = 0; k < uv.n_pats; k++) {
     const rtc_uv_pattern& q = uv.pats[k];
-    if (q.kind < RTC_UV_CHECKERS || q.kind > RTC_UV_IMAGE) return bad("UV pattern kind out of range");
+    if (q.kind < RTC_UV_CHECKERS || q.kind > RTC_UV_IMAGE_LINEAR_WRAP) return bad("UV pattern kind out of range");
     for (int c = 0; c < uv_children(q); c++)
       if (q.child[c] < 0 || (uint32_t)q.child[c] >= D.n_pattern_nodes) return bad("UV pattern child out of range");
     if (q.kind == RTC_UV_CHECKERS && !(std::isfinite(q.width) && q.width > 0.0 && std::isfinite(q.height) && q.height > 0.0))
       return bad("UV checkers width and height must be finite and > 0");
-    if (q.kind == RTC_UV_IMAGE && (q.texture < 0 || (uint32_t)q.texture >= uv.n_tex)) return bad("UV pattern texture index out of range");
+    if (uv_is_image(q.kind) && (q.texture < 0 || (uint32_t)q.texture >= uv.n_tex)) return bad("UV pattern texture index out of range");
   }
   for (uint32_t t = 0; t < uv.n_tex; t++) {
     if (uv.tex[t].width == 0 || uv.tex[t].height == 0) return bad("texture of width or height 0");
@@ -1170,7 +1171,7 @@ inline int build_arrays(const rtc_scene_desc& D, HostArrays* H, std::string* err
       o.kind = q.kind;
       std::memcpy(o.child, q.child, sizeof(o.child));
       o.width = q.width; o.height = q.height;
-      if (q.kind == RTC_UV_IMAGE) { o.tw = (int32_t)uv.tex[q.texture].width; o.th = (int32_t)uv.tex[q.texture].height; o.off = (int64_t)toff[(size_t)q.texture]; }
+      if (uv_is_image(q.kind)) { o.tw = (int32_t)uv.tex[q.texture].width; o.th = (int32_t)uv.tex[q.texture].height; o.off = (int64_t)toff[(size_t)q.texture]; }
       std::memcpy(base + rec0 + (size_t)k * sizeof(DUv), &o, sizeof(o));
     }
     for (uint32_t t = 0; t < uv.n_tex; t++) std::memcpy(base + toff[t], uv.tex[t].rgb, (size_t)3 * uv.tex[t].width * uv.tex[t].height * sizeof(double));

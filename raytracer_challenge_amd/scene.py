@@ -199,7 +199,7 @@ class Pattern:  # src/material.rs:60-65, constructors :110-162
             raise ValueError("Pattern.texture_map: mapping must be 'planar', 'spherical' or 'cylindrical' (cube_map for cubes), got %r" % (mapping,))
         if not isinstance(uv, UvPattern):
             raise TypeError("Pattern.texture_map: a UvPattern expected, got %s" % type(uv).__name__)
-        return Pattern("uv", kind=mapping, transform=transform, faces=(uv,))
+        return Pattern("uv", kind=mapping, transform=transform, faces=(uv.resolved(mapping),))
 
     @staticmethod
     def cube_map(transform: Matrix, left, front, right, back, up, down) -> "Pattern":
@@ -208,7 +208,7 @@ class Pattern:  # src/material.rs:60-65, constructors :110-162
         for f in faces:
             if not isinstance(f, UvPattern):
                 raise TypeError("Pattern.cube_map: six UvPatterns expected, got %s" % type(f).__name__)
-        return Pattern("uv", kind="cube", transform=transform, faces=faces)
+        return Pattern("uv", kind="cube", transform=transform, faces=tuple(f.resolved("cube") for f in faces))
 
 
 BUMP_KINDS = ("simplex", "fractal", "ripple")  # include/rtc.h RTC_BUMP_*, in enum order

@@ -399,6 +399,17 @@ def procedural_texture(width: int = 64, height: int = 32, seed: int = 2024):
 def texture_showcase(hsize=None, vsize=None) -> Tuple[Camera, World]:
     """Texture mapping (the book's bonus chapter): a planar-checkered floor, spherical UV checkers (16 x 8) on a sphere,
     cylindrical checkers on a cylinder, an align-check cube map, a sphere with a seeded image texture and a glass sphere in front."""
+    return _texture_showcase("nearest", hsize, vsize)
+
+
+def texture_showcase_linear(hsize=None, vsize=None) -> Tuple[Camera, World]:
+    """:func:`texture_showcase` with its image texture looked up bilinearly (``UvPattern.image(..., filter="linear")``; the spherical
+    map makes u periodic, so the seam at u = 0 / 1 blends too).  The same geometry and rays, another scene: the nearest one's bits
+    do not move."""
+    return _texture_showcase("linear", hsize, vsize)
+
+
+def _texture_showcase(image_filter: str, hsize, vsize) -> Tuple[Camera, World]:
     from .texture import UvPattern
     c = Color.new
     plain = Pattern.plain
@@ -416,7 +427,7 @@ def texture_showcase(hsize=None, vsize=None) -> Tuple[Camera, World]:
     box = Element.cube(ShapeArgs(transform=Matrix.translation(0.0, 1.0, 4.0) * Matrix.rotation_y(0.7) * Matrix.rotation_x(0.5), material=Material(
         pattern=Pattern.cube_map(Matrix.id(), *faces), diffuse=0.8, specular=0.2)))
     earth = Element.sphere(ShapeArgs(transform=Matrix.translation(0.3, 0.8, -0.5) * Matrix.scaling(0.8, 0.8, 0.8), material=Material(
-        pattern=Pattern.texture_map(Matrix.id(), "spherical", UvPattern.image(procedural_texture())), diffuse=0.9, specular=0.1)))
+        pattern=Pattern.texture_map(Matrix.id(), "spherical", UvPattern.image(procedural_texture(), filter=image_filter)), diffuse=0.9, specular=0.1)))
     glass = Element.sphere(ShapeArgs(transform=Matrix.translation(-0.8, 0.6, -2.5) * Matrix.scaling(0.6, 0.6, 0.6), material=Material(
         pattern=plain(Color.black()), diffuse=0.1, shininess=300.0, reflective=0.9, transparency=0.9, refractive_index=1.5)))
     world = World([PointLight(Color.white(), Vector.point(-8.0, 10.0, -10.0))], [floor, globe, can, box, earth, glass])

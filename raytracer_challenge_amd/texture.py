@@ -9,13 +9,18 @@ from __future__ import annotations
 
 import math
 import os
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Tuple, Union
 
 import numpy as np
 
 UV_MAPS = {"planar": 0, "spherical": 1, "cylindrical": 2, "cube": 3}
 UV_KINDS = {"checkers": 0, "align_check": 1, "image": 2}
+# image lookups (include/rtc.h RTC_UV_IMAGE*): nearest texel, or bilinear with the edge rule of each axis
+UV_FILTERS = ("nearest", "linear")
+UV_WRAPS = ("auto", "clamp", "u", "uv")
+UV_LINEAR_KINDS = {"clamp": 3, "u": 4, "uv": 5}  # RTC_UV_IMAGE_LINEAR, _LINEAR_WRAP_U, _LINEAR_WRAP
+UV_MAP_WRAPS = {"planar": "uv", "cylindrical": "uv", "spherical": "u", "cube": "clamp"}  # what wrap="auto" becomes under each map
 MAX_SIDE = 16384  # include/rtc.h RTC_TEXTURE_MAX_SIDE
 
 
@@ -122,6 +127,8 @@ class UvPattern:
     height: float = 1.0
     texture: "Texture" = None
     children: Tuple = ()
+    filter: str = "nearest"  # image: "nearest" | "linear" (bilinear)
+    wrap: str = "auto"       # image, linear only: "clamp" | "u" | "uv" (the periodic axes), "auto" = what suits the map
 
     @staticmethod
     def checkers(width: float, height: float, a, b) -> "UvPattern":
@@ -135,10 +142,38 @@ class UvPattern:
         return UvPattern("align_check", children=_patterns("align_check", (main, ul, ur, bl, br)))
 
     @staticmethod
-    def image(texture: Texture) -> "UvPattern":
+    def image(texture: Texture, filter: str = "nearest", wrap: str = "auto") -> "UvPattern":
+        """An image lookup.  ``filter="linear"`` blends the four nearest texels; ``wrap`` says which axes are periodic there:
+        ``"clamp"`` none (cube-map faces, decals), ``"u"`` u only (spherical maps), ``"uv"`` both (planar and cylindrical maps),
+        ``"auto"`` the one that suits the map the pattern is put under.  ``filter="nearest"`` ignores ``wrap``."""
         if not isinstance(texture, Texture):
             raise TypeError("UvPattern.image: a Texture expected, got %s" % type(texture).__name__)
-        return UvPattern("image", texture=texture)
+        if filter not in UV_FILTERS:
+            raise ValueError("UvPattern.image: filter must be 'nearest' or 'linear', got %r" % (filter,))
+        if wrap not in UV_WRAPS:
+            raise ValueError("UvPattern.image: wrap must be 'auto', 'clamp', 'u' or 'uv', got %r" % (wrap,))
+        return UvPattern("image", texture=texture, filter=filter, wrap=wrap)
+
+    def resolved(self, mapping: str) -> "UvPattern":
+        """This record under the map ``mapping``: a linear image's ``wrap="auto"`` becomes the map's own; anything else is itself."""
+        if self.kind == "image" and self.filter == "linear" and self.wrap == "auto":
+            return replace(self, wrap=UV_MAP_WRAPS[mapping])
+        return self
+
+    def kind_code(self, mapping: str = None) -> int:
+        """The record's RTC_UV_* kind (include/rtc.h): 0..2, or 3..5 for a linear image."""
+        if self.kind != "image" or self.filter == "nearest":
+            return UV_KINDS[self.kind]
+        if self.filter not in UV_FILTERS:
+            raise ValueError("UvPattern: filter must be 'nearest' or 'linear', got %r" % (self.filter,))
+        wrap = self.wrap
+        if wrap == "auto":
+            if mapping is None:
+                raise ValueError("UvPattern: wrap='auto' is resolved by the map (Pattern.texture_map / Pattern.cube_map)")
+            wrap = UV_MAP_WRAPS[mapping]
+        if wrap not in UV_LINEAR_KINDS:
+            raise ValueError("UvPattern: wrap must be 'auto', 'clamp', 'u' or 'uv', got %r" % (wrap,))
+        return UV_LINEAR_KINDS[wrap]
 
 
 def _patterns(what, kids) -> Tuple:

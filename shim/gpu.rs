@@ -96,10 +96,19 @@ pub struct RtcLightEx {
 // rtc_multi_create_ext
 #[allow(dead_code)]
 pub const RTC_PAT_UV: i32 = 4;
+// image records: nearest texel, and the bilinear lookups (both axes clamped / u periodic / both periodic)
+#[allow(dead_code)]
+pub const RTC_UV_IMAGE: i32 = 2;
+#[allow(dead_code)]
+pub const RTC_UV_IMAGE_LINEAR: i32 = 3;
+#[allow(dead_code)]
+pub const RTC_UV_IMAGE_LINEAR_WRAP_U: i32 = 4;
+#[allow(dead_code)]
+pub const RTC_UV_IMAGE_LINEAR_WRAP: i32 = 5;
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct RtcUvPattern {
-    pub kind: i32,    // RTC_UV_CHECKERS / _ALIGN_CHECK / _IMAGE
+    pub kind: i32,    // RTC_UV_CHECKERS / _ALIGN_CHECK / _IMAGE / _IMAGE_LINEAR*
     pub texture: i32, // image: index into the ext's textures
     pub width: f64,
     pub height: f64,
@@ -358,6 +367,8 @@ extern "C" {
                              n_devices: c_int, out: *mut *mut RtcMulti) -> c_int;
     #[allow(dead_code)] // host-only: the cone factor of one light position and shading point
     fn rtc_spot_factor(cone: *const RtcLightCone, light_pos: *const f64, point: *const f64, f: *mut f64) -> c_int;
+    #[allow(dead_code)] // host-only: one image record's colour at (u, v), kinds RTC_UV_IMAGE .. RTC_UV_IMAGE_LINEAR_WRAP
+    fn rtc_texture_sample(tex: *const RtcTexture, kind: i32, u: f64, v: f64, rgb: *mut f64) -> c_int;
     #[allow(dead_code)]
     fn rtc_scene_create_ext3(desc: *const RtcSceneDesc, ext: *const RtcSceneExt, cones: *const RtcLightCone, n_cones: u32, bg: *const RtcBackground,
                              device: c_int, out: *mut *mut RtcScene) -> c_int;
