@@ -487,7 +487,9 @@ typedef struct rtc_hit {
 typedef struct rtc_stats {
   uint64_t pixels;
   uint64_t rays_primary, rays_shadow, rays_reflect, rays_refract; /* unique rays, SURVEY.md §8d */
-  uint64_t rays_container;   /* extra n1/n2 passes (device-internal, not counted as rays)                 */
+  uint64_t rays_container;   /* hits whose n1 / n2 (src/intersection.rs:70-103) reach a result: the material has
+                                transparency != 0.0, World::shade_hit gets fuel > 0 and the world has a light (src/world.rs:70-78,
+                                :110) -- one extra pass over the hit's ray each; not counted as rays                            */
   uint64_t accel_nodes;      /* accelerator BVH nodes visited (4-wide nodes, 128 B each)                  */
   uint64_t group_tests;      /* reference group boxes tested (BoundingBox::intersects; 48 B each)         */
   uint64_t tri_tests;        /* triangles tested (72 B each)                                              */

@@ -195,6 +195,45 @@ int rtw_color_at(rtw_world* w, const double* rays, uint64_t n, int fuel, double*
   return 0;
 }
 
+// ---- the ray counts of the de-duplicated tree (rt_oracle.hpp Counters::u_*) -------------------------------------------------------
+// out: ORC_COUNT_ROWS rows of orc_ray_count_depths() values, indexed by depth: primary, reflect, refract, shadow, container -- each ray
+// (each hit, for container) of the tree once -- and then the literal call counts color_at and shadow, with the reference's per-light
+// re-tracing.  No pixel is rendered twice and no result of another entry point changes: the counts ride on the pass orc_render makes.
+enum { ORC_COUNT_ROWS = 7 };
+static void put_counts(const Counters& k, uint64_t* out) {
+  const uint64_t* rows[ORC_COUNT_ROWS] = {k.u_primary, k.u_reflect, k.u_refract, k.u_shadow, k.u_container, k.color_at, k.shadow};
+  for (int r = 0; r < ORC_COUNT_ROWS; r++) std::memcpy(out + (size_t)r * Counters::MAXD, rows[r], sizeof(uint64_t) * Counters::MAXD);
+}
+uint32_t orc_ray_count_depths(void) { return (uint32_t)Counters::MAXD; }
+// Frames: the camera and a pixel list or range, as orc_render_ex takes them (a pixel listed twice is counted twice).
+int orc_ray_counts(rtw_world* w, const rtw_camera* cam, int fuel, const uint64_t* idx, uint64_t n, uint32_t threads, uint64_t* out) {
+  if (!w || !cam || !out) return fail("ray_counts: NULL argument");
+  Matrix m = Matrix::from16(cam->transform), inv;
+  if (!m.inverse(&inv)) return fail("camera: singular transform");
+  Camera c = Camera::make((size_t)cam->hsize, (size_t)cam->vsize, cam->field_of_view, m);
+  RenderResult rr = render_pixels(c, w->w, fuel, idx, (size_t)n, nullptr, nullptr, threads, nullptr);
+  put_counts(rr.counters, out);
+  if (rr.nan_seen) return fail("NaN intersection t reached Intersection::sort (reference panics, src/intersection.rs:124)");
+  return 0;
+}
+// Explicit rays: what rtw_color_at takes.
+int orc_ray_counts_rays(rtw_world* w, const double* rays, uint64_t n, int fuel, uint64_t* out) {
+  if (!w || (!rays && n) || !out) return fail("ray_counts_rays: NULL argument");
+  Counters k;
+  bool nan_any = false;
+  for (uint64_t q = 0; q < n; q++) {
+    const double* r = rays + 6 * q;
+    World::Ctx c;
+    c.fuel0 = fuel;
+    c.counters = &k;
+    w->w.color_at(Ray{Vector::point(r[0], r[1], r[2]), Vector::vector(r[3], r[4], r[5])}, fuel, c);
+    nan_any |= c.nan_seen;
+  }
+  put_counts(k, out);
+  if (nan_any) return fail("NaN intersection t reached Intersection::sort (reference panics, src/intersection.rs:124)");
+  return 0;
+}
+
 // Image::ppm (src/image.rs:93-112).  Returns bytes written (excluding NUL) or the size needed if cap is too small.
 uint64_t orc_ppm(uint64_t hsize, uint64_t vsize, const double* rgb, char* out, uint64_t cap) {
   std::string s = ppm((size_t)hsize, (size_t)vsize, rgb);

@@ -976,8 +976,17 @@ struct Counters {
   uint64_t color_at[MAXD] = {0};
   uint64_t shadow[MAXD] = {0};
   uint64_t prim_tests = 0;
+  // The de-duplicated ray tree (TEST CHANNEL, as the digest): every ray once, by class and depth -- the copies the reference re-traces
+  // for a light other than the first (Ctx::repeat > 0) are left out.  u_shadow[d]: the is_shadowed calls made for a hit at depth d;
+  // u_container[d]: the hits at depth d whose n1 / n2 reach a result (World::color_at).  For a plain world of L lights
+  // (u_primary + u_reflect + u_refract)[d] * L^d == color_at[d] and u_shadow[d] * L^d == shadow[d].
+  uint64_t u_primary[MAXD] = {0}, u_reflect[MAXD] = {0}, u_refract[MAXD] = {0}, u_shadow[MAXD] = {0}, u_container[MAXD] = {0};
   void add(const Counters& o) {
-    for (int i = 0; i < MAXD; i++) { color_at[i] += o.color_at[i]; shadow[i] += o.shadow[i]; }
+    for (int i = 0; i < MAXD; i++) {
+      color_at[i] += o.color_at[i]; shadow[i] += o.shadow[i];
+      u_primary[i] += o.u_primary[i]; u_reflect[i] += o.u_reflect[i]; u_refract[i] += o.u_refract[i];
+      u_shadow[i] += o.u_shadow[i]; u_container[i] += o.u_container[i];
+    }
     prim_tests += o.prim_tests;
   }
 };
@@ -1036,7 +1045,10 @@ struct World {  // :12-15
     for (auto& e : elements) e->intersect(ray, c.xs, &c.nan_seen);
   }
   bool is_shadowed(const PointLight& light, const Vector& point, Ctx& c, int depth = 0) const {  // :26-48
-    if (c.counters && depth < Counters::MAXD) c.counters->shadow[depth]++;
+    if (c.counters && depth < Counters::MAXD) {
+      c.counters->shadow[depth]++;
+      if (c.repeat == 0) c.counters->u_shadow[depth]++;
+    }
     Vector v = light.origin - point;
     double distance = v.magnitude();
     Ray ray{point, v.normalize()};
@@ -1096,7 +1108,11 @@ struct World {  // :12-15
   // :134-149.  `first` (optional) receives the nearest-hit record of THIS call.
   Color color_at(const Ray& ray, int fuel, Ctx& c, Intersection* first = nullptr, bool* did_hit = nullptr) const {
     int depth = c.fuel0 - fuel;
-    if (c.counters && depth >= 0 && depth < Counters::MAXD) c.counters->color_at[depth]++;
+    const bool counted = c.counters && depth >= 0 && depth < Counters::MAXD;
+    if (counted) {
+      c.counters->color_at[depth]++;
+      if (c.repeat == 0) (c.next_kind == 0 ? c.counters->u_primary : c.next_kind == 1 ? c.counters->u_reflect : c.counters->u_refract)[depth]++;
+    }
     intersect(ray, c);
     sort_intersections(c.xs, &c.nan_seen);
     const Intersection* h = hit(c.xs);
@@ -1116,6 +1132,9 @@ struct World {  // :12-15
       Intersection self = *h;
       if (first) *first = self;
       State st = prepare_state(self, ray, c.xs);
+      // n1 / n2 reach a result only through schlick's blend and refracted_color (:70-78, :110): a transparent material, fuel left, and
+      // a light to run shade_hit's loop for
+      if (counted && c.repeat == 0 && self.shape->material.transparency != 0.0 && fuel > 0 && !lights.empty()) c.counters->u_container[depth]++;
       return shade_hit(st, fuel, c);
     }
 #ifdef ORC_EXT

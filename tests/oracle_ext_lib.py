@@ -37,6 +37,7 @@ class OracleExtBackend(OracleBackend):
         lib.orc_quantize.argtypes = [vp, C.c_uint64, vp]
         lib.orc_ppm.restype = C.c_uint64
         lib.orc_ppm.argtypes = [C.c_uint64, C.c_uint64, vp, C.c_char_p, C.c_uint64]
+        oracle_lib.bind_ray_counts(lib)
         lib.orc_ext_sample_positions.restype = None
         lib.orc_ext_sample_positions.argtypes = [d3, d3, C.c_uint32, d3, C.c_uint32, C.c_int, C.c_uint64, d3, vp]
         lib.orc_ext_spot_factor.restype = C.c_double

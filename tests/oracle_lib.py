@@ -17,6 +17,26 @@ class OrcStats(C.Structure):
     _fields_ = [("seconds", C.c_double), ("threads", C.c_uint64), ("unique_rays", C.c_double), ("traced_rays", C.c_double), ("nan_seen", C.c_uint64)]
 
 
+COUNT_ROWS = ("primary", "reflect", "refract", "shadow", "container", "calls_color_at", "calls_shadow")
+
+
+class RayCounts(dict):
+    """The oracle's ray counts by depth (oracle_capi.cpp orc_ray_counts): "primary", "reflect", "refract", "shadow", "container" count the
+    de-duplicated tree, each ray (each hit, for container) once; "calls_color_at" and "calls_shadow" are the literal call counts, with
+    the reference's per-light re-tracing.  Every value is a uint64 array indexed by depth."""
+
+    def totals(self):
+        """What include/rtc.h's rtc_stats reports: rays_primary, rays_shadow, rays_reflect, rays_refract, rays_container."""
+        return {"rays_" + k: int(self[k].sum()) for k in ("primary", "shadow", "reflect", "refract", "container")}
+
+
+def bind_ray_counts(lib):
+    vp = C.c_void_p
+    lib.orc_ray_count_depths.restype, lib.orc_ray_count_depths.argtypes = C.c_uint32, []
+    lib.orc_ray_counts.restype, lib.orc_ray_counts.argtypes = C.c_int, [vp, vp, C.c_int, vp, C.c_uint64, C.c_uint32, vp]
+    lib.orc_ray_counts_rays.restype, lib.orc_ray_counts_rays.argtypes = C.c_int, [vp, vp, C.c_uint64, C.c_int, vp]
+
+
 def build_oracle():
     subprocess.run(["make", "-s", "-C", ORACLE_DIR], check=True)
 
@@ -40,6 +60,7 @@ class OracleBackend(Backend):
         self.lib.orc_simplex.argtypes = [C.c_double] * 3
         self.lib.orc_fractal.restype = C.c_double
         self.lib.orc_fractal.argtypes = [C.c_double] * 3 + [C.c_uint64]
+        bind_ray_counts(self.lib)
 
     def render_timed(self, nw, camera, fuel, pixel_indices=None, threads=0):
         cam = self.camera_c(camera)
@@ -67,6 +88,28 @@ class OracleBackend(Backend):
         dig = np.empty(n, dtype=np.uint64)
         self._check(self.lib.orc_render_ex(nw.handle, C.byref(cam), int(fuel), idx_p, n, rgb.ctypes.data, hits.ctypes.data, threads, None, dig.ctypes.data), "orc_render_ex")
         return rgb, hits, dig
+
+    def _counts(self, out):
+        return RayCounts(zip(COUNT_ROWS, out.copy()))
+
+    def ray_counts(self, nw, camera, fuel, pixel_indices=None, threads=0):
+        """RayCounts of the listed pixels (None: the whole frame; a pixel listed twice counts twice)."""
+        cam = self.camera_c(camera)
+        if pixel_indices is None:
+            n, idx_p = camera.hsize * camera.vsize, None
+        else:
+            pixel_indices = np.ascontiguousarray(pixel_indices, dtype=np.uint64)
+            n, idx_p = pixel_indices.size, pixel_indices.ctypes.data
+        out = np.zeros((len(COUNT_ROWS), int(self.lib.orc_ray_count_depths())), dtype=np.uint64)
+        self._check(self.lib.orc_ray_counts(nw.handle, C.byref(cam), int(fuel), idx_p, n, threads, out.ctypes.data), "orc_ray_counts")
+        return self._counts(out)
+
+    def ray_counts_rays(self, nw, rays, fuel):
+        """RayCounts of explicit rays (what color_at takes)."""
+        rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+        out = np.zeros((len(COUNT_ROWS), int(self.lib.orc_ray_count_depths())), dtype=np.uint64)
+        self._check(self.lib.orc_ray_counts_rays(nw.handle, rays.ctypes.data, len(rays), int(fuel), out.ctypes.data), "orc_ray_counts_rays")
+        return self._counts(out)
 
     def quantize(self, rgb):
         rgb = np.ascontiguousarray(rgb, dtype=np.float64)

@@ -1,0 +1,222 @@
+"""The ray counters of include/rtc.h's rtc_stats against the oracle's count of the de-duplicated ray tree (oracle_capi.cpp
+orc_ray_counts: every ray once, by class and depth), for test_ray_counts_cpu.py and test_ray_counts_gpu.py: the case lists, the calls
+that fill an rtc_stats through each entry point, and the comparison.  Every comparison is exact equality of integers: a decision that
+spawns or drops a ray is a comparison on operands both sides hold bit for bit (fuel, == 0.0, sin2_t > 1.0, f == 0.0)."""
+import ctypes as C
+
+import numpy as np
+
+import build_matrix as bm
+import cases
+import ext_cases as ec
+from raytracer_challenge_amd import scenes
+from raytracer_challenge_amd.backend import HIT_DTYPE, AdaptiveC, FilterC, SamplingC, ShutterC
+from raytracer_challenge_amd.device import RtcCameraC, RtcStatsC
+from raytracer_challenge_amd.scene import Camera, Color, Element, Material, Matrix, Pattern, PointLight, ShapeArgs, Vector, World
+
+COUNTERS = ("pixels", "rays_primary", "rays_shadow", "rays_reflect", "rays_refract", "rays_container")
+vp = C.c_void_p
+P, V = Vector.point, Vector.vector
+
+
+# ---- the cases -------------------------------------------------------------------------------------------------------------------------
+def resized(cam, w, h):
+    return Camera.new(w, h, cam.field_of_view, cam.transform_matrix)
+
+
+def _small(fn, w, h, *args):
+    def make():
+        cam, world = fn(*args)
+        return resized(cam, w, h), world, 5
+    return make
+
+
+# (camera, world, fuel); no frame above 64x36, no fuel above 5
+PLAIN_CASES = {
+    "cover": lambda: scenes.cover(48, 48) + (5,),
+    "glass_air_bubble": lambda: scenes.chapter11_glass_air_bubble(64, 32) + (5,),
+    "teapot_low": lambda: scenes.chapter15_teapot("teapot_low.obj", 48, 27) + (5,),     # the one-kernel path's light_is_behind: counted and answered
+    "nested_glass": _small(cases.nested_glass, 48, 30),
+    "glass_cluster": _small(cases.glass_cluster, 36, 24),
+}
+
+
+def _area_fixture(world_fn):
+    from test_area_lights_gpu import camera
+    return lambda: (camera(24, 16), world_fn(), 5)
+
+
+EXT_CASES = {
+    "penumbra_jittered": _area_fixture(ec._penumbra),
+    "mirror_area_3x3": _area_fixture(ec.mirror_area_world),
+    "spot_showcase": lambda: scenes.spot_showcase(48, 27) + (5,),
+    "sky_showcase": lambda: scenes.sky_showcase(48, 27, skybox=False) + (5,),
+    "everything_skybox_24x16": lambda: (ec.everything_camera(24, 16), ec.everything_world(True), 5),
+    "everything_gradient_13x7": lambda: (ec.everything_camera(13, 7), ec.everything_world(False), 5),
+    "bumped_everything_24x16": lambda: (ec.everything_camera(24, 16), ec.bumped_everything_world(True), 5),
+    "steep_bumps": lambda: (ec.steep_camera(), ec.steep_world(), 4),
+}
+
+FUZZ_SEEDS = {"first": (1000, 1001, 1002, 1003), "seventh": (80000, 80001, 80002, 80003), "eighth": (80000, 80001, 80002, 80003)}
+FUZZ_SIZES = dict(sizes=((48, 27), (64, 36)), counts=(17, 40, 96))
+
+
+def fuzz_case(wave, seed):
+    """(camera, world, fuel, which oracle) of one fuzz world: the first wave's generator at the emulator tests' sizes, the seventh and
+    eighth waves as test_oracle_ext_gpu.py runs them; fuel held to 5."""
+    if wave == "first":
+        from test_fuzz_parity import random_case
+        cam, world, fuel, _ = random_case(seed, **FUZZ_SIZES)
+        return cam, world, min(fuel, 5), "plain"
+    cam, world, fuel, _ = (ec.seventh_wave if wave == "seventh" else ec.eighth_wave)(seed)
+    return cam, world, min(fuel, 5), "ext"
+
+
+def two_light_glass_and_mirror():
+    """One glass-and-mirror sphere, one mirror sphere and a glass cube over a reflective floor, two lights: the scene of the per-depth
+    differences."""
+    glass = Material(pattern=Pattern.plain(Color.new(0.1, 0.1, 0.15)), diffuse=0.2, reflective=0.5, transparency=0.8, refractive_index=1.5)
+    mirror = Material(pattern=Pattern.plain(Color.new(0.2, 0.2, 0.2)), diffuse=0.3, reflective=0.9)
+    clear = Material(pattern=Pattern.plain(Color.new(0.1, 0.2, 0.1)), diffuse=0.2, transparency=0.9, refractive_index=1.3)
+    floor = Material(pattern=Pattern.checkers(Matrix.id(), Pattern.plain(Color.white()), Pattern.plain(Color.new(0.2, 0.2, 0.2))), reflective=0.3)
+    els = [Element.plane(ShapeArgs(material=floor)),
+           Element.sphere(ShapeArgs(transform=Matrix.translation(-0.8, 1.0, 0.0), material=glass)),
+           Element.sphere(ShapeArgs(transform=Matrix.translation(1.4, 0.7, 0.8) * Matrix.scaling(0.7, 0.7, 0.7), material=mirror)),
+           Element.cube(ShapeArgs(transform=Matrix.translation(0.6, 0.5, -1.6) * Matrix.rotation_y(0.5) * Matrix.scaling(0.5, 0.5, 0.5), material=clear))]
+    lights = [PointLight(Color.new(0.8, 0.8, 0.8), P(-6.0, 8.0, -6.0)), PointLight(Color.new(0.3, 0.3, 0.4), P(5.0, 4.0, -3.0))]
+    cam = Camera.new(37, 23, 1.0, Camera.transform(P(0.2, 2.2, -6.0), P(0.0, 0.8, 0.0), V(0.0, 1.0, 0.0)))
+    return cam, World(lights, els)
+
+
+# ---- what the oracle says an rtc_stats must hold --------------------------------------------------------------------------------------
+def expected(counts, pixels):
+    want = counts.totals()
+    want["pixels"] = int(pixels)
+    return want
+
+
+def add(*wants):
+    return {k: sum(w[k] for w in wants) for k in COUNTERS}
+
+
+def as_counts(st):
+    return {k: int(getattr(st, k)) for k in COUNTERS}
+
+
+def assert_counts(got, want, label):
+    """Every counter and `pixels`, exactly."""
+    got = as_counts(got) if isinstance(got, RtcStatsC) else {k: int(got[k]) for k in COUNTERS}
+    wrong = {k: (got[k], want[k]) for k in COUNTERS if got[k] != want[k]}
+    assert not wrong, "%s: (device, oracle) %s" % (label, wrong)
+
+
+# ---- the entry points that fill an rtc_stats ------------------------------------------------------------------------------------------
+def bind(backend):
+    lib = bm.bind(backend.lib)
+    lib.rtw_make_camera.restype, lib.rtw_make_camera.argtypes = C.c_int, [vp, vp]
+    cam = st = vp    # (plain pointers: other test modules hand these functions their own structure classes through the same library object)
+    sigs = {"rtc_render": [vp, cam, C.c_int32, vp, C.c_uint64, C.c_uint64, vp, vp, st],
+            "rtc_render_rgb8": [vp, cam, C.c_int32, vp, st],
+            "rtc_trace_rays": [vp, vp, C.c_uint64, C.c_int32, vp, vp, st],
+            "rtc_render_bands_device": [vp, cam, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, st, C.c_int, C.c_int],
+            "rtc_render_rows_device": [vp, cam, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, vp, st, C.c_int, C.c_int],
+            "rtc_render_sampled": [vp, cam, C.POINTER(SamplingC), C.c_int32, vp, C.c_uint64, C.c_uint64, vp, st],
+            "rtc_render_adaptive": [vp, cam, C.POINTER(AdaptiveC), C.c_int32, vp, vp, C.POINTER(C.c_uint64), st],
+            "rtc_render_filtered": [vp, cam, C.POINTER(SamplingC), C.POINTER(FilterC), C.c_int32, C.c_uint32, C.c_uint32, vp, st],
+            "rtc_render_shutter": [vp, vp, C.c_uint32, C.POINTER(ShutterC), C.POINTER(SamplingC), C.c_int32, vp, C.c_uint64, C.c_uint64, vp, st]}
+    for name, args in sigs.items():
+        if hasattr(lib, name):
+            getattr(lib, name).restype, getattr(lib, name).argtypes = C.c_int, args
+    return lib
+
+
+def rtc_camera(backend, cam):
+    cc, rc = backend.camera_c(cam), RtcCameraC()
+    assert bind(backend).rtw_make_camera(C.byref(cc), C.byref(rc)) == 0, backend._err()
+    return rc
+
+
+def _ok(lib, code, what):
+    assert code == 0, "%s: %s" % (what, (lib.rtc_last_error() or b"").decode())
+
+
+def render_stats(backend, nw, cam, fuel, pixel_indices=None, first=0, n=None):
+    """rtc_render over the whole frame, the range first .. first + n - 1, or a pixel list."""
+    lib, rc = bind(backend), rtc_camera(backend, cam)
+    idx_p = None
+    if pixel_indices is not None:
+        pixel_indices = np.ascontiguousarray(pixel_indices, dtype=np.uint64)
+        n, idx_p = pixel_indices.size, pixel_indices.ctypes.data
+    elif n is None:
+        n = cam.hsize * cam.vsize - first
+    rgb, hits, st = np.empty((n, 3)), np.empty(n, dtype=HIT_DTYPE), RtcStatsC()
+    _ok(lib, lib.rtc_render(bm.scene_of(backend, nw), C.byref(rc), int(fuel), idx_p, int(first), int(n), rgb.ctypes.data, hits.ctypes.data, C.byref(st)), "rtc_render")
+    return st
+
+
+def rgb8_stats(backend, nw, cam, fuel):
+    lib, rc = bind(backend), rtc_camera(backend, cam)
+    out, st = np.empty(cam.hsize * cam.vsize * 3, dtype=np.uint8), RtcStatsC()
+    _ok(lib, lib.rtc_render_rgb8(bm.scene_of(backend, nw), C.byref(rc), int(fuel), out.ctypes.data, C.byref(st)), "rtc_render_rgb8")
+    return st
+
+
+def trace_stats(backend, nw, rays, fuel):
+    lib = bind(backend)
+    rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+    rgb, hits, st = np.empty((len(rays), 3)), np.empty(len(rays), dtype=HIT_DTYPE), RtcStatsC()
+    _ok(lib, lib.rtc_trace_rays(bm.scene_of(backend, nw), rays.ctypes.data, len(rays), int(fuel), rgb.ctypes.data, hits.ctypes.data, C.byref(st)), "rtc_trace_rays")
+    return st
+
+
+def band_rows_of(vsize, band_rows, band_first, band_step):
+    """The image rows of part band_first of band_step, in the dense tile's order (include/rtc.h rtc_render_bands_device)."""
+    rows = []
+    for b in range(band_first, (vsize + band_rows - 1) // band_rows, band_step):
+        rows.extend(range(b * band_rows, min(vsize, (b + 1) * band_rows)))
+    return rows
+
+
+def bands_stats(backend, nw, cam, fuel, band_rows, band_first, band_step, n_rows, out_ptr):
+    """rtc_render_bands_device (band_rows = 1 through rtc_render_rows_device) into the caller's buffer (device memory on the GPU, host
+    memory in the emulator), counting and synchronous."""
+    lib, rc, st = bind(backend), rtc_camera(backend, cam), RtcStatsC()
+    scene = bm.scene_of(backend, nw)
+    if band_rows == 1:
+        _ok(lib, lib.rtc_render_rows_device(scene, C.byref(rc), int(fuel), band_first, band_step, n_rows, out_ptr, C.byref(st), 1, 1), "rtc_render_rows_device")
+    else:
+        _ok(lib, lib.rtc_render_bands_device(scene, C.byref(rc), int(fuel), band_rows, band_first, band_step, n_rows, out_ptr, C.byref(st), 1, 1), "rtc_render_bands_device")
+    return st
+
+
+def rows_pixels(cam, rows):
+    return np.concatenate([np.arange(y * cam.hsize, (y + 1) * cam.hsize, dtype=np.uint64) for y in rows]) if len(rows) else np.zeros(0, dtype=np.uint64)
+
+
+def sampled_stats(backend, nw, cam, sp, fuel, pixel_indices=None):
+    lib, rc, spc, st = bind(backend), rtc_camera(backend, cam), SamplingC.of(sp), RtcStatsC()
+    idx_p, n = None, cam.hsize * cam.vsize
+    if pixel_indices is not None:
+        pixel_indices = np.ascontiguousarray(pixel_indices, dtype=np.uint64)
+        n, idx_p = pixel_indices.size, pixel_indices.ctypes.data
+    rgb = np.empty((n, 3))
+    _ok(lib, lib.rtc_render_sampled(bm.scene_of(backend, nw), C.byref(rc), C.byref(spc), int(fuel), idx_p, 0, n, rgb.ctypes.data, C.byref(st)), "rtc_render_sampled")
+    return st
+
+
+def adaptive_stats(backend, nw, cam, adaptive, fuel):
+    """(rtc_stats, the refined pixels' mask) of rtc_render_adaptive."""
+    lib, rc, ad, st = bind(backend), rtc_camera(backend, cam), AdaptiveC.of(adaptive), RtcStatsC()
+    n = cam.hsize * cam.vsize
+    rgb, mask, n_ref = np.empty((n, 3)), np.zeros(n, dtype=np.uint8), C.c_uint64(0)
+    _ok(lib, lib.rtc_render_adaptive(bm.scene_of(backend, nw), C.byref(rc), C.byref(ad), int(fuel), rgb.ctypes.data, mask.ctypes.data, C.byref(n_ref), C.byref(st)), "rtc_render_adaptive")
+    assert int(mask.sum()) == n_ref.value
+    return st, mask.astype(bool)
+
+
+def filtered_stats(backend, nw, cam, sp, flt, fuel, row_first=0, n_rows=None):
+    lib, rc, spc, flc, st = bind(backend), rtc_camera(backend, cam), SamplingC.of(sp), FilterC.of(flt), RtcStatsC()
+    n_rows = cam.vsize - row_first if n_rows is None else n_rows
+    rgb = np.empty((n_rows * cam.hsize, 3))
+    _ok(lib, lib.rtc_render_filtered(bm.scene_of(backend, nw), C.byref(rc), C.byref(spc), C.byref(flc), int(fuel), row_first, n_rows, rgb.ctypes.data, C.byref(st)), "rtc_render_filtered")
+    return st
