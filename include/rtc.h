@@ -302,7 +302,7 @@ typedef struct rtc_background {
  *      reflected and refracted rays.  Both device paths give the same bits.
  * A scene without a record is exactly today's scene: the same kernels, the same builds, the same kernel arguments.
  * Which kernels: on the one-kernel path a bumped scene takes the NP build of the general kernel that reads the program from memory
- * (feature level 3) with the scene's own area / uv / spot / background flags, a row of RTC_NP_BUILDS (csrc/rtc_device.hpp); there is no
+ * (feature level 3) with the scene's own area / uv / spot / background flags (rtc_bump_info.trace_build numbers them); there is no
  * LEAN, 3-wave or kernel-argument build for it.  On the wavefront path wf_shade's NP build (COUNT x UV) shades every level; wf_ts,
  * wf_gather and wf_background run as they do without.  rtc_scene_kernel_info describes the scene as it would run without its records;
  * rtc_scene_bump_info says what they replace.
@@ -540,14 +540,16 @@ int rtc_background_point(int32_t projection, const double dir[3], double point[3
  * dirs[i] -- to a background what rtc_camera_rays is to the camera.  RTC_ERR_INVALID for a scene without a background. */
 int rtc_background_colors(rtc_scene*, const double* dirs, uint64_t n, double* rgb);
 /* Test hook, read-only: what a launch of this scene takes for its background.  has_background == 0: pattern, projection and the
- * builds are -1.  trace_build: path 1, the row of RTC_BG_BUILDS (csrc/rtc_device.hpp) whose BG instantiation of rtc_trace_kernel
- * replaces the build rtc_scene_kernel_info reports, with that row's flags; wf_background_build: path 4, RTC_WF_BG_*. */
+ * builds are -1.  trace_build: path 1, the general kernel (feature level 3, program read from memory) whose BG instantiation of
+ * rtc_trace_kernel replaces the build rtc_scene_kernel_info reports, numbered by the scene's flags -- 0 none, 1 area lights, 2 UV patterns,
+ * 3 area + UV, 4 light cones, 5 cones + UV (a cone always comes with the area code path) -- which trace_area / trace_uv / trace_spot
+ * repeat; wf_background_build: path 4, RTC_WF_BG_*. */
 enum { RTC_WF_BG_PLAIN = 0, RTC_WF_BG_UV = 1 };
 typedef struct rtc_background_info {
   int32_t has_background;
   int32_t pattern, projection;
   int32_t plain_root;           /* the root is a Plain colour: no pattern walk, no projection */
-  int32_t trace_build;          /* path 1: row of RTC_BG_BUILDS (feature level 3, program read from memory) */
+  int32_t trace_build;          /* path 1: 0..5 by the scene's flags, as above (feature level 3, program read from memory) */
   int32_t trace_area, trace_uv, trace_spot;  /* ... and its flags */
   int32_t wf_background_build;  /* path 4: RTC_WF_BG_PLAIN (pattern_color) or RTC_WF_BG_UV (pattern_color_uv, scenes with a UV node) */
   int32_t _pad;
@@ -566,13 +568,14 @@ int rtc_bump_normal(const rtc_bump* bump, const double material_inv[16], const d
  * a bump what rtc_background_colors is to the background.  RTC_ERR_INVALID for a primitive index out of range. */
 int rtc_bump_normals(rtc_scene*, const int32_t* prims, const double* points, const double* normals, uint64_t n, double* out);
 /* Test hook, read-only: what a launch of this scene takes for its bump records.  has_bump == 0: the builds are -1.  trace_build: path 1,
- * the row of RTC_NP_BUILDS (csrc/rtc_device.hpp) whose NP instantiation of rtc_trace_kernel replaces the build rtc_scene_kernel_info
- * (or rtc_scene_background_info) reports, with that row's flags; wf_shade_build: path 4, RTC_WF_NP_*, for every level. */
+ * the general kernel whose NP instantiation of rtc_trace_kernel replaces the build rtc_scene_kernel_info (or rtc_scene_background_info)
+ * reports: rtc_background_info.trace_build's 0..5 by the scene's area / uv / spot flags, and 6 more (6..11) for a scene that has a
+ * background too; trace_area / trace_uv / trace_spot / trace_bg repeat the flags; wf_shade_build: path 4, RTC_WF_NP_*, for every level. */
 enum { RTC_WF_NP_PLAIN = 0, RTC_WF_NP_UV = 1 };
 typedef struct rtc_bump_info {
   int32_t has_bump;
   uint32_t n_bumps;
-  int32_t trace_build;          /* path 1: row of RTC_NP_BUILDS (feature level 3, program read from memory) */
+  int32_t trace_build;          /* path 1: 0..5 by the scene's flags, + 6 with a background (feature level 3, program read from memory) */
   int32_t trace_area, trace_uv, trace_spot, trace_bg;  /* ... and its flags */
   int32_t wf_shade_build;       /* path 4: RTC_WF_NP_PLAIN or RTC_WF_NP_UV (scenes with a UV node); each has its counting form */
 } rtc_bump_info;

@@ -239,6 +239,19 @@ struct DBumpTable {
 struct DSceneNp : DSceneBg {
   DBumpTable bump;
 };
+// Host side: what a scene has beside its DScene (either may be null), and the scene argument of the kernels that take a wider one
+// (a kernel that takes a DSceneBg is handed the DSceneNp's base).
+struct RtcSceneExt {
+  const DBackground* bg;
+  const DBumpTable* bump;
+};
+static inline DSceneNp rtc_widen_scene(const DScene& S, const RtcSceneExt& X) {
+  DSceneNp N;
+  static_cast<DScene&>(N) = S;
+  N.bg = X.bg ? *X.bg : DBackground{0, 0};
+  N.bump = X.bump ? *X.bump : DBumpTable{nullptr, nullptr};
+  return N;
+}
 
 // Which pixels a launch covers.
 struct DPixelMap {

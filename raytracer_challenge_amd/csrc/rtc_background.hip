@@ -1,30 +1,8 @@
-// rtc_background.hip — everything a scene's background (include/rtc.h rtc_background) adds to the device: hand-written HIP for gfx950.
-//   without -DRTC_BG_BUILD: wf_background (the wavefront path's kernel for the rays of a level that hit nothing), the kernel behind
-//     rtc_background_colors, and the launchers rtc_kernels.hip and rtc_scene.cpp call;
-//   with -DRTC_BG_BUILD=<b>: the one-kernel path's BG instantiations of row b of RTC_BG_BUILDS (rtc_device.hpp), plain and counting --
-//     one object each, built in parallel like the rows of RTC_VARIANTS (each instantiation is tens of thousands of instructions).
+// rtc_background.hip — the small kernels a scene's background (include/rtc.h rtc_background) adds to the device, hand-written HIP for
+// gfx950: wf_background (the wavefront path's kernel for the rays of a level that hit nothing), the kernel behind rtc_background_colors,
+// and their launchers, which rtc_kernels.hip and rtc_scene.cpp call.  (The one-kernel path's BG builds: rtc_feat.hip, RtcExt.)
 // Scenes without a background launch nothing of this file.
 #include "rtc_device.hpp"
-
-#ifdef RTC_BG_BUILD
-
-template <>
-void rtc_launch_trace_bg_build<RTC_BG_BUILD>(const RtcFrame& F, const DBackground& bg, unsigned grid, int fuel, double* rgb) {
-  constexpr RtcVariant R = RTC_BG_BUILDS[RTC_BG_BUILD];
-  DSceneBg S;
-  static_cast<DScene&>(S) = F.S;
-  S.bg = bg;
-  if (F.count)
-    hipLaunchKernelGGL((rtc_trace_kernel<true, R.feat, R.kops, 0, false, R.area, R.uv, R.spot, true>), dim3(grid), dim3(RTC_BLOCK), rtc_stack_bytes(F.S), F.stream, S, F.cam, F.pm, fuel,
-                       rgb, F.hit_t, F.hit_prim, F.hit_k, F.stats);
-  else
-    hipLaunchKernelGGL((rtc_trace_kernel<false, R.feat, R.kops, 0, false, R.area, R.uv, R.spot, true>), dim3(grid), dim3(RTC_BLOCK), rtc_stack_bytes(F.S), F.stream, S, F.cam, F.pm, fuel,
-                       rgb, F.hit_t, F.hit_prim, F.hit_k, F.stats);
-}
-
-#else
-
-uint64_t rtc_wavefront_work(const DCamera& cam, const DPixelMap& pm);  // rtc_kernels.hip
 
 // Wavefront path: once per level of a background scene, after the trace role of wf_ts for that level and before the shading kernel
 // that overwrites the level's ray queue.  Ray i of the level whose link says RTC_WF_MISS gets contrib[level][*][i] = weight * B and
@@ -89,23 +67,3 @@ void rtc_launch_background_colors(const DScene& S, const DBackground& bg, const 
   if (S.has_uv) hipLaunchKernelGGL(rtc_background_colors_kernel<true>, grid, block, 0, stream, S, bg, dirs, n, rgb);
   else hipLaunchKernelGGL(rtc_background_colors_kernel<false>, grid, block, 0, stream, S, bg, dirs, n, rgb);
 }
-
-// One-kernel path of a background scene: one lane per work id (tile padding included), as rtc_launch_trace.
-void rtc_launch_trace_bg(const DScene& S, const DBackground& bg, const DCamera& cam, const DPixelMap& pm, int fuel, double* rgb, double* hit_t, int* hit_prim, int* hit_k,
-                         DStats* stats, bool count, hipStream_t stream) {
-  if (pm.n == 0) return;
-  const unsigned grid = (unsigned)((rtc_wavefront_work(cam, pm) + RTC_BLOCK - 1) / RTC_BLOCK);
-  const RtcFrame F = {S, cam, pm, hit_t, hit_prim, hit_k, stats, stream, count};
-  switch (rtc_pick_bg_build(S.has_area != 0, S.has_uv != 0, S.has_spot != 0)) {
-    case 0: return rtc_launch_trace_bg_build<0>(F, bg, grid, fuel, rgb);
-    case 1: return rtc_launch_trace_bg_build<1>(F, bg, grid, fuel, rgb);
-    case 2: return rtc_launch_trace_bg_build<2>(F, bg, grid, fuel, rgb);
-    case 3: return rtc_launch_trace_bg_build<3>(F, bg, grid, fuel, rgb);
-    case 4: return rtc_launch_trace_bg_build<4>(F, bg, grid, fuel, rgb);
-    case 5: return rtc_launch_trace_bg_build<5>(F, bg, grid, fuel, rgb);
-  }
-}
-// What a launch of a background scene takes (rtc.h rtc_scene_background_info): the same selection the launchers above make.
-int rtc_background_trace_build(const DScene& S) { return rtc_pick_bg_build(S.has_area != 0, S.has_uv != 0, S.has_spot != 0); }
-
-#endif

@@ -1680,10 +1680,9 @@ __device__ __forceinline__ void shade_lights_area(const DScene& S, double px, do
 // UV: scenes with a texture-mapped pattern (DScene.has_uv): the pattern walk with the RTC_PAT_UV branch.  Other scenes never run it.
 // SPOT (with AREA): scenes with a cone (DScene.has_spot): shade_lights_area's SPOT build.
 // BG: scenes with a background (include/rtc.h rtc_background): a ray that hits nothing adds weight * the background's colour where a
-// hit's surface colour would have been added.  Only these builds take a DSceneBg; they are instantiated by rtc_background.hip, not by
-// a row of RTC_VARIANTS.  Scenes without a background never run them.
-// NP: scenes with a bump record (include/rtc.h rtc_bump): prepare_state's NP build.  Only these builds take a DSceneNp; they are
-// instantiated by rtc_bump.hip, one object per row of RTC_NP_BUILDS.  Scenes without a bump record never run them.
+// hit's surface colour would have been added.  Only these builds take a DSceneBg.  Scenes without a background never run them.
+// NP: scenes with a bump record (include/rtc.h rtc_bump): prepare_state's NP build.  Only these builds take a DSceneNp.  Scenes without
+// a bump record never run them.  (BG and NP builds exist for the general rows of RTC_VARIANTS only: RtcExt.)
 template <bool COUNT, int FEAT, bool KOPS, int WAVES = 0, bool LEAN = false, bool AREA = false, bool UV = false, bool SPOT = false, bool BG = false, bool NP = false>
 __global__ void __launch_bounds__(RTC_BLOCK, WAVES ? WAVES : ((FEAT >= 2 && RTC_WAVES_PER_SIMD < 2) ? 2 : RTC_WAVES_PER_SIMD)) rtc_trace_kernel(std::conditional_t<NP, DSceneNp, std::conditional_t<BG, DSceneBg, DScene>> S, DCamera cam, DPixelMap pm, int fuel0, double* __restrict__ rgb, double* __restrict__ hit_t,
                                                         int* __restrict__ hit_prim, int* __restrict__ hit_k, DStats* __restrict__ stats) {
@@ -2265,6 +2264,22 @@ constexpr RtcWfShadeNpBuild rtc_pick_wf_shade_np_build(bool count, bool has_uv) 
   return has_uv ? (count ? RTC_SH_NP_COUNT_UV : RTC_SH_NP_UV) : (count ? RTC_SH_NP_COUNT : RTC_SH_NP);
 }
 
+// Extensions of the one-kernel path: features that travel as a wider scene argument (DSceneBg, DSceneNp) on the GENERAL rows of the
+// table -- feature level 3, program read from memory (DScene.ops is always in memory, as variant 10 relies on) -- with the scene's own
+// area / uv / spot flags.  rtc_feat.hip is compiled once more per general row and extension (-DRTC_VARIANT=<row> -DRTC_EXT=<e>), one
+// object each, plain and counting form.  No LEAN, 3-wave or kernel-argument build serves an extended scene.
+enum RtcExt {
+  RTC_EXT_NONE = 0,
+  RTC_EXT_BG = 1,     // a background (include/rtc.h rtc_background): rtc_trace_kernel's BG build, a DSceneBg
+  RTC_EXT_NP = 2,     // a bump record (include/rtc.h rtc_bump): the NP build, a DSceneNp whose bg is {0, 0}
+  RTC_EXT_NP_BG = 3,  // both: the NP and BG build, a DSceneNp
+};
+constexpr int RTC_N_EXT = 4;
+constexpr bool rtc_ext_bg(int e) { return (e & RTC_EXT_BG) != 0; }
+constexpr bool rtc_ext_np(int e) { return (e & RTC_EXT_NP) != 0; }
+// the extension a scene's background and bump table (device_scene.h RtcSceneExt) make
+static inline RtcExt rtc_ext_of(const RtcSceneExt& X) { return (RtcExt)((X.bg ? RTC_EXT_BG : 0) | (X.bump ? RTC_EXT_NP : 0)); }
+
 // Launch arguments (host side): what every ray kernel of a frame receives, and what one level of the wavefront path adds.
 struct RtcFrame {
   const DScene& S;
@@ -2291,47 +2306,42 @@ struct RtcVariantOps {
   bool (*launch_wf_ts_lds)(const RtcFrame& F, const RtcLevel& L);  // false: this device refuses the dynamic LDS size, nothing was launched
   int (*wf_ts_blocks_per_cu)(unsigned lds_bytes);
   bool (*wf_ts_lds_refused)(int device);  // a launch on that device was refused the dynamic LDS size: its launches take launch_wf_ts
+  void (*launch_trace_ext[RTC_N_EXT])(const RtcFrame& F, const RtcSceneExt& X, unsigned grid, int fuel, double* rgb);  // by RtcExt: general rows only ([RTC_EXT_NONE]: null)
 };
 template <int V>
 RtcVariantOps rtc_variant_ops();  // defined and explicitly instantiated by the translation unit of variant V
 
-// Scenes with a background (include/rtc.h rtc_background) on the one-kernel path: rtc_trace_kernel's BG build of the general
-// memory-program kernel (feature level 3, KOPS = false: DScene.ops is always in memory, as variant 10 relies on) with the scene's own
-// area / uv / spot flags.  These are not rows of RTC_VARIANTS: rtc_background.hip instantiates them, one object per build (-DRTC_BG_BUILD=<b>),
-// each with its counting form.  No LEAN, 3-wave or kernel-argument build serves a background scene.
-constexpr RtcVariant RTC_BG_BUILDS[] = {
-    {3, false, false, false, false},  // 0
-    {3, false, true, false, false},   // 1: an area light
-    {3, false, false, true, false},   // 2: a UV pattern
-    {3, false, true, true, false},    // 3: both
-    {3, false, true, false, true},    // 4: a light cone (always with the `area` code path)
-    {3, false, true, true, true},     // 5: a light cone and a UV pattern
-};
-constexpr int RTC_N_BG_BUILDS = (int)(sizeof(RTC_BG_BUILDS) / sizeof(RTC_BG_BUILDS[0]));
-constexpr int rtc_pick_bg_build(bool area, bool uv, bool spot) { return spot ? (uv ? 5 : 4) : ((uv ? 2 : 0) + (area ? 1 : 0)); }
-template <int B>
-void rtc_launch_trace_bg_build(const RtcFrame& F, const DBackground& bg, unsigned grid, int fuel, double* rgb);  // defined by the object of build B
-
-// Scenes with a bump record (include/rtc.h rtc_bump) on the one-kernel path: rtc_trace_kernel's NP build of the general memory-program
-// kernel (feature level 3, KOPS = false), with the scene's own area / uv / spot flags as in RTC_BG_BUILDS -- rows 0..5 for scenes
-// without a background, rows 6..11 the same with BG.  rtc_bump.hip instantiates them, one object per row (-DRTC_NP_BUILD=<b>), each
-// with its counting form.  No LEAN, 3-wave or kernel-argument build serves a bumped scene.
-constexpr RtcVariant RTC_NP_BUILDS[] = {
-    {3, false, false, false, false},  // 0
-    {3, false, true, false, false},   // 1: an area light
-    {3, false, false, true, false},   // 2: a UV pattern
-    {3, false, true, true, false},    // 3: both
-    {3, false, true, false, true},    // 4: a light cone (always with the `area` code path)
-    {3, false, true, true, true},     // 5: a light cone and a UV pattern
-    {3, false, false, false, false},  // 6: row 0 with a background
-    {3, false, true, false, false},   // 7: row 1 with a background
-    {3, false, false, true, false},   // 8: row 2 with a background
-    {3, false, true, true, false},    // 9: row 3 with a background
-    {3, false, true, false, true},    // 10: row 4 with a background
-    {3, false, true, true, true},     // 11: row 5 with a background
-};
-constexpr int RTC_N_NP_BUILDS = (int)(sizeof(RTC_NP_BUILDS) / sizeof(RTC_NP_BUILDS[0]));
-constexpr bool rtc_np_build_bg(int b) { return b >= RTC_N_NP_BUILDS / 2; }
-constexpr int rtc_pick_np_build(bool area, bool uv, bool spot, bool bg) { return rtc_pick_bg_build(area, uv, spot) + (bg ? RTC_N_NP_BUILDS / 2 : 0); }
-template <int B>
-void rtc_launch_trace_np_build(const RtcFrame& F, const DSceneNp& S, unsigned grid, int fuel, double* rgb);  // defined by the object of build B
+// The general rows of the table, which the extensions (RtcExt) are built for.
+constexpr bool rtc_v_general(RtcVariant r) { return r.feat == 3 && !r.kops; }
+// The general row that serves a scene's flags (a cone always comes with the `area` code path), or -1 unless exactly one row does.
+constexpr int rtc_general_row(bool area, bool uv, bool spot) {
+  int row = -1;
+  for (int v = 0; v < RTC_N_VARIANTS; v++) {
+    const RtcVariant r = RTC_VARIANTS[v];
+    if (rtc_v_general(r) && r.area == (area || spot) && r.uv == uv && r.spot == spot) row = row == -1 ? v : -2;
+  }
+  return row < 0 ? -1 : row;
+}
+// What rtc_scene_background_info and rtc_scene_bump_info report as trace_build: the general rows numbered in table order -- 0 none,
+// 1 area, 2 uv, 3 area + uv, 4 spot, 5 spot + uv -- and for a bumped scene with a background 6 more.
+constexpr int rtc_general_index(int row) {
+  int n = 0;
+  for (int v = 0; v < row; v++) n += rtc_v_general(RTC_VARIANTS[v]) ? 1 : 0;
+  return n;
+}
+constexpr int RTC_N_GENERAL = rtc_general_index(RTC_N_VARIANTS);
+constexpr int rtc_pick_bg_build(bool area, bool uv, bool spot) { return rtc_general_index(rtc_general_row(area, uv, spot)); }
+constexpr int rtc_pick_np_build(bool area, bool uv, bool spot, bool bg) { return rtc_pick_bg_build(area, uv, spot) + (bg ? RTC_N_GENERAL : 0); }
+// (area, uv, spot) of the six reachable flag sets, in the order of the numbers the ABI reports
+constexpr bool rtc_general_ok(int n, bool area, bool uv, bool spot) {
+  return rtc_general_row(area, uv, spot) >= 0 && rtc_general_row(area, uv, spot) == rtc_pick_variant(3, false, area, uv, spot, false) && rtc_pick_bg_build(area, uv, spot) == n &&
+         rtc_pick_np_build(area, uv, spot, false) == n && rtc_pick_np_build(area, uv, spot, true) == n + 6;
+}
+static_assert(RTC_N_GENERAL == 6, "six general rows: one per reachable flag set");
+static_assert(rtc_general_ok(0, false, false, false) && rtc_general_ok(1, true, false, false) && rtc_general_ok(2, false, true, false) && rtc_general_ok(3, true, true, false),
+              "exactly one general row per flag set, the one rtc_pick_variant picks, numbered in table order");
+static_assert(rtc_general_ok(4, false, false, true) && rtc_general_ok(4, true, false, true) && rtc_general_ok(5, false, true, true) && rtc_general_ok(5, true, true, true),
+              "... and a cone, with or without an area light, takes the spot rows");
+// Defined by the object of extension E of general row V (rtc_feat.hip): widens the scene and launches.
+template <int V, int E>
+void rtc_launch_trace_ext(const RtcFrame& F, const RtcSceneExt& X, unsigned grid, int fuel, double* rgb);

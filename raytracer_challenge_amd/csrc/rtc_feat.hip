@@ -1,6 +1,8 @@
 // rtc_feat.hip — the ray kernels of ONE kernel variant: a row of RTC_VARIANTS (rtc_device.hpp), compiled once per row with
 // -DRTC_VARIANT=<row>, in parallel: each instantiation of the traversal is tens of thousands of instructions and most of the
 // library's build time.  Exports one symbol, rtc_variant_ops<RTC_VARIANT>(): the variant's launchers, for rtc_kernels.hip.
+// With -DRTC_EXT=<e> as well (general rows only; RtcExt): the one-kernel path's builds of that row for scenes with a background, a bump
+// record or both, an object of their own that exports rtc_launch_trace_ext<RTC_VARIANT, RTC_EXT> and nothing else.
 // (The CPU emulator includes this file in rtc_kernels.hip's translation unit and instantiates the rows it uses from there.)
 #include "rtc_device.hpp"
 #ifndef RTC_EMU
@@ -9,9 +11,10 @@
 
 namespace {
 
-template <typename K>
-void launch_trace_kernel(K kernel, const RtcFrame& F, unsigned grid, int fuel, double* rgb) {
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(RTC_BLOCK), rtc_stack_bytes(F.S), F.stream, F.S, F.cam, F.pm, fuel, rgb, F.hit_t, F.hit_prim, F.hit_k, F.stats);
+// (S: F.S, or its widened form for a kernel that takes one)
+template <typename K, typename SceneT>
+void launch_trace_kernel(K kernel, const SceneT& S, const RtcFrame& F, unsigned grid, int fuel, double* rgb) {
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(RTC_BLOCK), rtc_stack_bytes(F.S), F.stream, S, F.cam, F.pm, fuel, rgb, F.hit_t, F.hit_prim, F.hit_k, F.stats);
 }
 template <typename K>
 void launch_wf_ts_kernel(K kernel, unsigned block, unsigned lds_bytes, const RtcFrame& F, const RtcLevel& L) {
@@ -24,13 +27,13 @@ void launch_trace(const RtcFrame& F, bool big_scene, unsigned grid, int fuel, do
   constexpr RtcVariant R = RTC_VARIANTS[V];
   switch (rtc_pick_trace_build(R, F.count, big_scene, F.S.all_plain != 0, F.S.no_glass_mirror != 0)) {
     case RTC_TB_3WAVE:  // (instantiated for the rows that can be told to take it only)
-      if constexpr (rtc_v_trace_3wave(R)) launch_trace_kernel(rtc_trace_kernel<false, R.feat, R.kops, 3>, F, grid, fuel, rgb);
+      if constexpr (rtc_v_trace_3wave(R)) launch_trace_kernel(rtc_trace_kernel<false, R.feat, R.kops, 3>, F.S, F, grid, fuel, rgb);
       return;
     case RTC_TB_LEAN:
-      if constexpr (rtc_v_trace_lean(R)) launch_trace_kernel(rtc_trace_kernel<false, R.feat, R.kops, 0, true>, F, grid, fuel, rgb);
+      if constexpr (rtc_v_trace_lean(R)) launch_trace_kernel(rtc_trace_kernel<false, R.feat, R.kops, 0, true>, F.S, F, grid, fuel, rgb);
       return;
-    case RTC_TB_COUNT: return launch_trace_kernel(rtc_trace_kernel<true, R.feat, R.kops, 0, false, R.area, R.uv, R.spot>, F, grid, fuel, rgb);
-    case RTC_TB_DEFAULT: return launch_trace_kernel(rtc_trace_kernel<false, R.feat, R.kops, 0, false, R.area, R.uv, R.spot>, F, grid, fuel, rgb);
+    case RTC_TB_COUNT: return launch_trace_kernel(rtc_trace_kernel<true, R.feat, R.kops, 0, false, R.area, R.uv, R.spot>, F.S, F, grid, fuel, rgb);
+    case RTC_TB_DEFAULT: return launch_trace_kernel(rtc_trace_kernel<false, R.feat, R.kops, 0, false, R.area, R.uv, R.spot>, F.S, F, grid, fuel, rgb);
   }
 }
 
@@ -97,9 +100,14 @@ int wf_ts_blocks_per_cu(unsigned lds_bytes) {
 template <int V>
 RtcVariantOps rtc_variant_ops() {
   constexpr RtcVariant R = RTC_VARIANTS[V];
-  RtcVariantOps ops = {launch_trace<V>, nullptr, nullptr, nullptr, nullptr};
+  RtcVariantOps ops = {launch_trace<V>, nullptr, nullptr, nullptr, nullptr, {nullptr, nullptr, nullptr, nullptr}};
   if constexpr (rtc_v_wavefront(R)) ops.launch_wf_ts = launch_wf_ts<V>;
 #ifndef RTC_EMU
+  if constexpr (rtc_v_general(R)) {
+    ops.launch_trace_ext[RTC_EXT_BG] = rtc_launch_trace_ext<V, RTC_EXT_BG>;
+    ops.launch_trace_ext[RTC_EXT_NP] = rtc_launch_trace_ext<V, RTC_EXT_NP>;
+    ops.launch_trace_ext[RTC_EXT_NP_BG] = rtc_launch_trace_ext<V, RTC_EXT_NP_BG>;
+  }
   if constexpr (rtc_v_lds(R)) { ops.launch_wf_ts_lds = launch_wf_ts_lds<V>; ops.wf_ts_lds_refused = wf_ts_lds_refused<V>; }
   if constexpr (rtc_v_wavefront(R)) ops.wf_ts_blocks_per_cu = wf_ts_blocks_per_cu<V>;
 #endif
@@ -110,5 +118,18 @@ RtcVariantOps rtc_variant_ops() {
 #ifndef RTC_VARIANT
 #error "compile with -DRTC_VARIANT=<a row of RTC_VARIANTS>"
 #endif
+#ifdef RTC_EXT
+// (Defined in the extension's object alone: the row's own object, which takes its address, must not see a body to instantiate.)
+template <int V, int E>
+void rtc_launch_trace_ext(const RtcFrame& F, const RtcSceneExt& X, unsigned grid, int fuel, double* rgb) {
+  constexpr RtcVariant R = RTC_VARIANTS[V];
+  static_assert(rtc_v_general(R) && E > RTC_EXT_NONE && E < RTC_N_EXT, "an extension of a general row");
+  const DSceneNp S = rtc_widen_scene(F.S, X);
+  if (F.count) launch_trace_kernel(rtc_trace_kernel<true, R.feat, R.kops, 0, false, R.area, R.uv, R.spot, rtc_ext_bg(E), rtc_ext_np(E)>, S, F, grid, fuel, rgb);
+  else launch_trace_kernel(rtc_trace_kernel<false, R.feat, R.kops, 0, false, R.area, R.uv, R.spot, rtc_ext_bg(E), rtc_ext_np(E)>, S, F, grid, fuel, rgb);
+}
+template void rtc_launch_trace_ext<RTC_VARIANT, RTC_EXT>(const RtcFrame&, const RtcSceneExt&, unsigned, int, double*);
+#else
 template RtcVariantOps rtc_variant_ops<RTC_VARIANT>();
+#endif
 #endif

@@ -1,7 +1,8 @@
 // rtc_kernels.hip — hand-written HIP for gfx950 (MI355X): the kernels of the hot path that do not depend on the scene's kernel
 // variant (wf_shade, wf_gather, the quantiser) and the host-callable launchers.  The ray kernels (rtc_trace_kernel, wf_ts) are
-// templates in rtc_device.hpp, instantiated per row of RTC_VARIANTS by rtc_feat.hip (one translation unit per row, built in parallel);
-// the launchers here pick a scene's row (rtc_variant) and call through its RtcVariantOps.
+// templates in rtc_device.hpp, instantiated per row of RTC_VARIANTS by rtc_feat.hip (one translation unit per row, and one more per
+// general row and extension, built in parallel); the launchers here pick a scene's row (rtc_variant; rtc_general_row for a scene with a
+// background or a bump table) and call through its RtcVariantOps.
 #include <cstdio>
 #include <cstdlib>
 #include <utility>
@@ -331,6 +332,11 @@ void rtc_kernel_info_fill(const DScene& S, bool wavefront, bool count, bool big_
     out->trace_build = rtc_pick_trace_build(RTC_VARIANTS[v], count, big_scene, S.all_plain != 0, S.no_glass_mirror != 0);
   }
 }
+// ... and of a scene with a background or a bump table on the one-kernel path (rtc.h rtc_scene_background_info / rtc_scene_bump_info):
+// the number of the general row rtc_launch_trace takes, 6 more for a bumped scene with a background.
+int rtc_ext_trace_build(const DScene& S, const RtcSceneExt& X) {
+  return X.bump ? rtc_pick_np_build(S.has_area != 0, S.has_uv != 0, S.has_spot != 0, X.bg != nullptr) : rtc_pick_bg_build(S.has_area != 0, S.has_uv != 0, S.has_spot != 0);
+}
 bool rtc_scene_is_big(unsigned long long scene_bytes) { return rtc_big_scene(scene_bytes); }
 
 #ifndef RTC_EMU
@@ -355,20 +361,27 @@ uint64_t rtc_wavefront_work(const DCamera& cam, const DPixelMap& pm) {
 // arrays for W.cap >= the work ids of the launch and fuel + 1 levels; `blocks` / `shade_blocks` = grid sizes of the traversal /
 // shading kernels; `lds` = the scene's rtc_wavefront_lds_bytes (0: tables in memory) and `lds_blocks` = the grid of the LDSC traversal build
 // (rtc_wavefront_lds_grid; read only when lds != 0), always given together.
-// `bg` (may be null): the scene's background: wf_background (rtc_background.hip) runs once per level, behind that level's trace role.
-// `bump` (may be null): the scene's bump table: every level is shaded by wf_shade's NP build (COUNT x UV), whatever build the scene takes without.
-// The overload without these four is all a caller without LDSC builds can ask for: tables in memory, no background, no bumps.
+// `X`: the scene's background and bump table, each of which may be null.  With a background, wf_background (rtc_background.hip) runs once
+// per level, behind that level's trace role.  With a bump table, every level is shaded by wf_shade's NP build (COUNT x UV), whatever
+// build the scene takes without.
+// The overload without these three is all a caller without LDSC builds can ask for: tables in memory, no background, no bumps.
 #ifndef RTC_EMU
 void rtc_launch_wf_background(const DScene& S, const DCamera& cam, const DPixelMap& pm, const DWave& W, int level, unsigned n0, const DBackground& bg, unsigned blocks,
                               hipStream_t stream);
 #endif
 void rtc_launch_wavefront(const DScene& S, const DCamera& cam, const DPixelMap& pm, int fuel, const DWave& W, double* rgb, double* hit_t, int* hit_prim, int* hit_k,
-                          DStats* stats, bool count, hipStream_t stream, unsigned blocks, unsigned shade_blocks, unsigned lds, unsigned lds_blocks, const DBackground* bg, const DBumpTable* bump) {
+                          DStats* stats, bool count, hipStream_t stream, unsigned blocks, unsigned shade_blocks, unsigned lds, unsigned lds_blocks, const RtcSceneExt& X) {
   if (pm.n == 0) return;
   const RtcVariantOps& ops = rtc_ops(rtc_variant(S, true));
   const RtcFrame F = {S, cam, pm, hit_t, hit_prim, hit_k, stats, stream, count};
   const unsigned n0 = (unsigned)rtc_wavefront_work(cam, pm);
   const dim3 sgrid(std::max(1u, shade_blocks)), sblock(RTC_WF_SHADE_BLOCK);
+  // one level's shading: a build of wf_shade and the scene argument it takes
+  auto shade = [&](auto kernel, const auto& scene, int level) { hipLaunchKernelGGL(kernel, sgrid, sblock, 0, stream, scene, cam, pm, W, level, n0, fuel, stats); };
+#ifndef RTC_EMU
+  DSceneNp N;  // (the NP builds' scene: assembled once per frame, for a scene with a bump table only)
+  if (X.bump) N = rtc_widen_scene(S, X);
+#endif
   // trace_0; shade_0; [shadow_0 + trace_1]; shade_1; ... [shadow_{fuel-1} + trace_fuel]; shade_fuel; shadow_fuel; sums
   for (int level = 0; level <= fuel + 1; level++) {
     const int tl = level <= fuel ? level : -1, sl = level - 1;
@@ -377,43 +390,37 @@ void rtc_launch_wavefront(const DScene& S, const DCamera& cam, const DPixelMap& 
     if (!lds || !ops.launch_wf_ts_lds(F, RtcLevel{W, tl, sl, n0, level, fuel - level, std::max(1u, lds_blocks), lds}))
 #endif
     ops.launch_wf_ts(F, RtcLevel{W, tl, sl, n0, level, fuel - level, blocks, 0u});
+    if (level > fuel) break;
 #ifndef RTC_EMU
-    if (bg && level <= fuel) rtc_launch_wf_background(S, cam, pm, W, level, n0, *bg, 4u * std::max(1u, shade_blocks), stream);
-#endif
-#ifndef RTC_EMU
-    if (bump && level <= fuel) {
-      DSceneNp N;
-      static_cast<DScene&>(N) = S;
-      N.bg = DBackground{0, 0};
-      N.bump = *bump;
+    if (X.bg) rtc_launch_wf_background(S, cam, pm, W, level, n0, *X.bg, 4u * std::max(1u, shade_blocks), stream);
+    if (X.bump) {
       switch (rtc_pick_wf_shade_np_build(count, S.has_uv != 0)) {
-        case RTC_SH_NP_COUNT_UV: hipLaunchKernelGGL((wf_shade<true, true, true, false, false, true>), sgrid, sblock, 0, stream, N, cam, pm, W, level, n0, fuel, stats); break;
-        case RTC_SH_NP_UV: hipLaunchKernelGGL((wf_shade<false, true, true, false, false, true>), sgrid, sblock, 0, stream, N, cam, pm, W, level, n0, fuel, stats); break;
-        case RTC_SH_NP_COUNT: hipLaunchKernelGGL((wf_shade<true, true, false, false, false, true>), sgrid, sblock, 0, stream, N, cam, pm, W, level, n0, fuel, stats); break;
-        case RTC_SH_NP: hipLaunchKernelGGL((wf_shade<false, true, false, false, false, true>), sgrid, sblock, 0, stream, N, cam, pm, W, level, n0, fuel, stats); break;
+        case RTC_SH_NP_COUNT_UV: shade(wf_shade<true, true, true, false, false, true>, N, level); break;
+        case RTC_SH_NP_UV: shade(wf_shade<false, true, true, false, false, true>, N, level); break;
+        case RTC_SH_NP_COUNT: shade(wf_shade<true, true, false, false, false, true>, N, level); break;
+        case RTC_SH_NP: shade(wf_shade<false, true, false, false, false, true>, N, level); break;
       }
-    } else
+      continue;
+    }
 #endif
-    if (level <= fuel) {
-      switch (rtc_scene_shade_build(S, count, level == 0)) {
+    switch (rtc_scene_shade_build(S, count, level == 0)) {
 #ifndef RTC_EMU
-        case RTC_SH_COUNT_UV: hipLaunchKernelGGL((wf_shade<true, true, true>), sgrid, sblock, 0, stream, S, cam, pm, W, level, n0, fuel, stats); break;
-        case RTC_SH_UV: hipLaunchKernelGGL((wf_shade<false, true, true>), sgrid, sblock, 0, stream, S, cam, pm, W, level, n0, fuel, stats); break;
+      case RTC_SH_COUNT_UV: shade(wf_shade<true, true, true>, S, level); break;
+      case RTC_SH_UV: shade(wf_shade<false, true, true>, S, level); break;
 #else
-        case RTC_SH_COUNT_UV: case RTC_SH_UV: break;  // (never picked here: rtc_scene_shade_build)
+      case RTC_SH_COUNT_UV: case RTC_SH_UV: break;  // (never picked here: rtc_scene_shade_build)
 #endif
-        case RTC_SH_COUNT: hipLaunchKernelGGL((wf_shade<true>), sgrid, sblock, 0, stream, S, cam, pm, W, level, n0, fuel, stats); break;
-        case RTC_SH_PIPE_LV0: hipLaunchKernelGGL((wf_shade<false, false, false, true, true>), sgrid, sblock, 0, stream, S, cam, pm, W, level, n0, fuel, stats); break;
-        case RTC_SH_PIPE: hipLaunchKernelGGL((wf_shade<false, false, false, true, false>), sgrid, sblock, 0, stream, S, cam, pm, W, level, n0, fuel, stats); break;
-        case RTC_SH_PAT: hipLaunchKernelGGL((wf_shade<false>), sgrid, sblock, 0, stream, S, cam, pm, W, level, n0, fuel, stats); break;
-      }
+      case RTC_SH_COUNT: shade(wf_shade<true>, S, level); break;
+      case RTC_SH_PIPE_LV0: shade(wf_shade<false, false, false, true, true>, S, level); break;
+      case RTC_SH_PIPE: shade(wf_shade<false, false, false, true, false>, S, level); break;
+      case RTC_SH_PAT: shade(wf_shade<false>, S, level); break;
     }
   }
   hipLaunchKernelGGL(wf_gather, dim3(std::max(1u, std::min(blocks, (n0 + 255u) / 256u))), dim3(256), 0, stream, cam, pm, W, n0, rgb);
 }
 void rtc_launch_wavefront(const DScene& S, const DCamera& cam, const DPixelMap& pm, int fuel, const DWave& W, double* rgb, double* hit_t, int* hit_prim, int* hit_k,
                           DStats* stats, bool count, hipStream_t stream, unsigned blocks, unsigned shade_blocks) {
-  rtc_launch_wavefront(S, cam, pm, fuel, W, rgb, hit_t, hit_prim, hit_k, stats, count, stream, blocks, shade_blocks, 0u, 0u, nullptr, nullptr);
+  rtc_launch_wavefront(S, cam, pm, fuel, W, rgb, hit_t, hit_prim, hit_k, stats, count, stream, blocks, shade_blocks, 0u, 0u, RtcSceneExt{nullptr, nullptr});
 }
 
 // ---- host-callable launcher (C++ linkage, used by rtc_scene.cpp) ------------------------------------------
@@ -476,11 +483,15 @@ void rtc_launch_deinterleave(const double* slab, double* image, unsigned rowlen,
   launch_deinterleave(slab, image, rowlen, vsize, n, max_rows, band, stream);
 }
 
-// One-kernel path: one lane per work id (tile padding included).  big_scene: the accelerator does not fit the L2s.
+// One-kernel path: one lane per work id (tile padding included).  big_scene: the accelerator does not fit the L2s.  X: the scene's
+// background and bump table (each may be null): a scene with either takes that extension of its general row (rtc_general_row).
+// (A caller without extended builds -- the emulator -- leaves X out, as it takes the short rtc_launch_wavefront.)
 void rtc_launch_trace(const DScene& S, const DCamera& cam, const DPixelMap& pm, int fuel, double* rgb, double* hit_t, int* hit_prim, int* hit_k,
-                      DStats* stats, bool count, hipStream_t stream, bool big_scene) {
+                      DStats* stats, bool count, hipStream_t stream, bool big_scene, const RtcSceneExt& X = RtcSceneExt{nullptr, nullptr}) {
   if (pm.n == 0) return;
   const unsigned grid = (unsigned)((rtc_wavefront_work(cam, pm) + RTC_BLOCK - 1) / RTC_BLOCK);
   const RtcFrame F = {S, cam, pm, hit_t, hit_prim, hit_k, stats, stream, count};
-  rtc_ops(rtc_variant(S, false)).launch_trace(F, big_scene, grid, fuel, rgb);
+  const RtcExt e = rtc_ext_of(X);
+  if (e == RTC_EXT_NONE) rtc_ops(rtc_variant(S, false)).launch_trace(F, big_scene, grid, fuel, rgb);
+  else rtc_ops(rtc_general_row(S.has_area != 0, S.has_uv != 0, S.has_spot != 0)).launch_trace_ext[e](F, X, grid, fuel, rgb);
 }

@@ -33,23 +33,17 @@
 #include "uv_image.h"
 
 void rtc_launch_trace(const DScene& S, const DCamera& cam, const DPixelMap& pm, int fuel, double* rgb, double* hit_t, int* hit_prim, int* hit_k,
-                      DStats* stats, bool count, hipStream_t stream, bool big_scene);
+                      DStats* stats, bool count, hipStream_t stream, bool big_scene, const RtcSceneExt& X);
 void rtc_launch_quantize(const double* rgb, unsigned char* out, unsigned long long n, hipStream_t stream);
 void rtc_launch_pack_hits(const double* t, const int* prim, const int* k, DHit* out, unsigned long long n, hipStream_t stream);
 void rtc_launch_deinterleave(const double* slab, double* image, unsigned rowlen, unsigned vsize, unsigned n, unsigned max_rows, unsigned band, hipStream_t stream);
 void rtc_launch_deinterleave8(const unsigned char* slab, unsigned char* image, unsigned rowlen, unsigned vsize, unsigned n, unsigned max_rows, unsigned band, hipStream_t stream);
 void rtc_launch_wavefront(const DScene& S, const DCamera& cam, const DPixelMap& pm, int fuel, const DWave& W, double* rgb, double* hit_t, int* hit_prim, int* hit_k,
-                          DStats* stats, bool count, hipStream_t stream, unsigned blocks, unsigned shade_blocks, unsigned lds, unsigned lds_blocks, const DBackground* bg,
-                          const DBumpTable* bump);
-void rtc_launch_trace_np(const DScene& S, const DBumpTable& bt, const DBackground* bg, const DCamera& cam, const DPixelMap& pm, int fuel, double* rgb, double* hit_t,
-                         int* hit_prim, int* hit_k, DStats* stats, bool count, hipStream_t stream);
+                          DStats* stats, bool count, hipStream_t stream, unsigned blocks, unsigned shade_blocks, unsigned lds, unsigned lds_blocks, const RtcSceneExt& X);
 void rtc_launch_bump_normals(const DScene& S, const DBumpTable& bt, const int32_t* prims, const double* points, const double* normals, unsigned long long n, double* out,
                              hipStream_t stream);
-int rtc_bump_trace_build(const DScene& S, bool has_bg);
-void rtc_launch_trace_bg(const DScene& S, const DBackground& bg, const DCamera& cam, const DPixelMap& pm, int fuel, double* rgb, double* hit_t, int* hit_prim, int* hit_k,
-                         DStats* stats, bool count, hipStream_t stream);
 void rtc_launch_background_colors(const DScene& S, const DBackground& bg, const double* dirs, unsigned long long n, double* rgb, hipStream_t stream);
-int rtc_background_trace_build(const DScene& S);
+int rtc_ext_trace_build(const DScene& S, const RtcSceneExt& X);
 void rtc_kernel_info_fill(const DScene& S, bool wavefront, bool count, bool big_scene, unsigned lds_bytes, int device, rtc_kernel_info* out);
 bool rtc_scene_is_big(unsigned long long scene_bytes);
 uint64_t rtc_wavefront_work(const DCamera& cam, const DPixelMap& pm);
@@ -101,12 +95,13 @@ struct rtc_scene {
   std::vector<void*> allocs;
   uint64_t bytes = 0;
   DScene d{};
-  bool has_bg = false;  // the scene has a background (rtc_scene_create_ext3): its launches take the BG builds (rtc_background.hip)
+  bool has_bg = false;  // the scene has a background (rtc_scene_create_ext3): its launches take the BG builds (rtc_feat.hip RtcExt; rtc_background.hip)
   DBackground bg{0, 0};
   bool bg_plain = false;  // its root is a Plain colour: no pattern walk
-  bool has_bump = false;  // the scene has bump records (rtc_scene_create_ext4): its launches take the NP builds (rtc_bump.hip, wf_shade's)
+  bool has_bump = false;  // the scene has bump records (rtc_scene_create_ext4): its launches take the NP builds (rtc_feat.hip RtcExt, wf_shade's)
   uint32_t n_bumps = 0;
   DBumpTable bump{nullptr, nullptr};
+  RtcSceneExt ext() const { return RtcSceneExt{has_bg ? &bg : nullptr, has_bump ? &bump : nullptr}; }  // what the launchers take of the two
   DStats* d_stats = nullptr;
   // scratch output buffers (grown on demand)
   double* d_rgb = nullptr;
@@ -421,13 +416,9 @@ int run(rtc_scene* s, const DCamera& cam, DPixelMap pm, int fuel, double* d_rgb,
     HIP_OK(hipMemsetAsync(s->wave.counts, 0, RTC_WF_COUNTS * sizeof(uint32_t), s->stream));
     HIP_OK(hipEventRecord(s->ev0, s->stream));
     rtc_launch_wavefront(s->d, cam, pm, fuel, s->wave, d_rgb, want_hits ? s->d_hit_t : nullptr, s->d_hit_prim, s->d_hit_k, s->d_stats, count, s->stream, s->wave_blocks, s->shade_blocks, s->lds_bytes,
-                         lds_grid(s, will_sync), s->has_bg ? &s->bg : nullptr, s->has_bump ? &s->bump : nullptr);
-  } else if (s->has_bump) {
-    rtc_launch_trace_np(s->d, s->bump, s->has_bg ? &s->bg : nullptr, cam, pm, fuel, d_rgb, want_hits ? s->d_hit_t : nullptr, s->d_hit_prim, s->d_hit_k, s->d_stats, count, s->stream);
-  } else if (s->has_bg) {
-    rtc_launch_trace_bg(s->d, s->bg, cam, pm, fuel, d_rgb, want_hits ? s->d_hit_t : nullptr, s->d_hit_prim, s->d_hit_k, s->d_stats, count, s->stream);
+                         lds_grid(s, will_sync), s->ext());
   } else {
-    rtc_launch_trace(s->d, cam, pm, fuel, d_rgb, want_hits ? s->d_hit_t : nullptr, s->d_hit_prim, s->d_hit_k, s->d_stats, count, s->stream, rtc_scene_is_big(s->bytes));
+    rtc_launch_trace(s->d, cam, pm, fuel, d_rgb, want_hits ? s->d_hit_t : nullptr, s->d_hit_prim, s->d_hit_k, s->d_stats, count, s->stream, rtc_scene_is_big(s->bytes), s->ext());
   }
   HIP_OK(hipGetLastError());
   HIP_OK(hipEventRecord(s->ev1, s->stream));
@@ -1343,7 +1334,7 @@ int rtc_scene_bump_info(const rtc_scene* s, rtc_bump_info* out) {
   if (!s->has_bump) return RTC_OK;
   out->has_bump = 1;
   out->n_bumps = s->n_bumps;
-  out->trace_build = rtc_bump_trace_build(s->d, s->has_bg);
+  out->trace_build = rtc_ext_trace_build(s->d, s->ext());
   out->trace_area = s->d.has_area || s->d.has_spot; out->trace_uv = s->d.has_uv; out->trace_spot = s->d.has_spot; out->trace_bg = s->has_bg ? 1 : 0;
   out->wf_shade_build = s->d.has_uv ? RTC_WF_NP_UV : RTC_WF_NP_PLAIN;
   return RTC_OK;
@@ -1380,7 +1371,7 @@ int rtc_scene_background_info(const rtc_scene* s, rtc_background_info* out) {
   if (!s->has_bg) return RTC_OK;
   out->has_background = 1;
   out->pattern = s->bg.pattern; out->projection = s->bg.projection;
-  out->trace_build = rtc_background_trace_build(s->d);
+  out->trace_build = rtc_ext_trace_build(s->d, RtcSceneExt{&s->bg, nullptr});  // (of the background alone: a bumped scene's is rtc_scene_bump_info's)
   out->trace_area = s->d.has_area || s->d.has_spot; out->trace_uv = s->d.has_uv; out->trace_spot = s->d.has_spot;
   out->wf_background_build = s->d.has_uv ? RTC_WF_BG_UV : RTC_WF_BG_PLAIN;
   out->plain_root = s->bg_plain ? 1 : 0;

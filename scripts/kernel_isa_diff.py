@@ -1,15 +1,19 @@
 #!/usr/bin/env python3
 """Compare the gfx950 device code of two source trees, function by function (no GPU needed).
 
-    scripts/kernel_isa_diff.py OLD_TREE NEW_TREE [--rename 'REGEX=>REPLACEMENT']... [--jobs N] [--keep DIR [--reuse]]
+    scripts/kernel_isa_diff.py OLD_TREE NEW_TREE [--rename 'REGEX=>REPLACEMENT']... [--unit OLD=NEW]... [--jobs N] [--keep DIR [--reuse]]
 
-For each tree: rtc_feat.hip for every variant id of its csrc/Makefile, rtc_kernels.hip and, where the tree has them,
-rtc_camera.hip, rtc_adaptive.hip, rtc_filter.hip, rtc_shutter.hip, rtc_background.hip (once plain, once per BG build id) and rtc_bump.hip (once plain, once per NP build id) are compiled to device-only assembly with that Makefile's FLAGS.  The assembly is split per function; comments, directives and label definitions
-are dropped, local label references (.LBB<fn>_<n> ...) lose their function number, the function's own symbol becomes
-<self>; what remains is counted and hashed.  Printed per function of NEW_TREE: unit, demangled name, instruction
-count, hash, next_free_vgpr, next_free_sgpr, private segment size (device functions that are not kernels: the
+The units of a tree are those of its csrc/Makefile: every source that is built once per id of a list ($(foreach v,$(IDS),$(O)/<name>$(v).o)
+with a rule `$(O)/<name>%.o: <source>` that passes -D<WHAT>=$*: rtc_feat.hip per row of VARIANT_IDS, unit feat<row>; in earlier layouts
+also units background<b> and bump<b>); rtc_feat.hip for every row of GENERAL_IDS and extension of EXT_IDS (-DRTC_VARIANT -DRTC_EXT: unit
+feat<row>_ext<e>); and the small units, SMALL_UNITS or every `$(O)/<name>.o: <name>.hip` rule.  Each is compiled to device-only assembly with that Makefile's FLAGS.  The assembly is split
+per function; comments, directives and label definitions are dropped, local label references (.LBB<fn>_<n> ...) lose their function
+number, .Lpost_getpc<n> labels (numbered per translation unit by the compiler) are renumbered per function in order of appearance, the
+function's own symbol becomes <self>; what remains is counted and hashed.  Printed per function of NEW_TREE: unit, demangled name,
+instruction count, hash, next_free_vgpr, next_free_sgpr, private segment size (device functions that are not kernels: the
 NumVgprs / NumSgprs / ScratchSize the compiler reports), and SAME / DIFF against OLD_TREE's function of that name.
 --rename rewrites OLD_TREE's demangled names (first matching rule only) for functions whose name is meant to change.
+--unit says that OLD_TREE's unit OLD is NEW_TREE's unit NEW, for functions that moved to another translation unit.
 A function only one tree has is ONLY-OLD / ONLY-NEW.  Exit status 1 unless every line is SAME.
 """
 import argparse
@@ -34,20 +38,29 @@ def make_var(makefile, *names):
     raise SystemExit("no %s in the Makefile" % " / ".join(names))
 
 
+def make_var_or(makefile, name, default=None):
+    try:
+        return make_var(makefile, name)
+    except SystemExit:
+        return default
+
+
 def units(tree):
     mk = open(os.path.join(tree, CSRC, "Makefile")).read()
     flags = make_var(mk, "FLAGS")
-    out = [("feat%s" % v, "rtc_feat.hip", flags + ["-DRTC_VARIANT=%s" % v]) for v in make_var(mk, "VARIANT_IDS", "VARIANTS")]
-    out.append(("kernels", "rtc_kernels.hip", flags))
-    for unit, src in (("camera", "rtc_camera.hip"), ("adaptive", "rtc_adaptive.hip"), ("filter", "rtc_filter.hip"), ("shutter", "rtc_shutter.hip")):   # the small kernels beside the ray kernels, where a tree has them
-        if os.path.exists(os.path.join(tree, CSRC, src)):
-            out.append((unit, src, flags))
-    if os.path.exists(os.path.join(tree, CSRC, "rtc_background.hip")):   # the background's kernels, and one unit per BG build of the one-kernel path
-        out.append(("background", "rtc_background.hip", flags))
-        out += [("background%s" % b, "rtc_background.hip", flags + ["-DRTC_BG_BUILD=%s" % b]) for b in make_var(mk, "BG_BUILD_IDS")]
-    if os.path.exists(os.path.join(tree, CSRC, "rtc_bump.hip")):   # the bump records' kernel, and one unit per NP build of the one-kernel path
-        out.append(("bump", "rtc_bump.hip", flags))
-        out += [("bump%s" % b, "rtc_bump.hip", flags + ["-DRTC_NP_BUILD=%s" % b]) for b in make_var(mk, "NP_BUILD_IDS")]
+    out = []
+    # one object per id of a list: $(foreach v,$(IDS),$(O)/<name>$(v).o) in OBJS, built by the rule `$(O)/<name>%.o: <src>` with -D<WHAT>=$*
+    for m in re.finditer(r"\$\(foreach (\w+),\$\((\w+)\),\$\(O\)/(\w+)\$\(\1\)\.o\)", mk):
+        ids, name = make_var_or(mk, m.group(2)), m.group(3)
+        rule = re.search(r"^\$\(O\)/%s%%\.o: (\S+\.hip).*\n\t.*?(-D\w+)=\$\*" % name, mk, re.M)
+        if ids and rule:
+            out += [(re.sub(r"^rtc_", "", name) + v, rule.group(1), flags + ["%s=%s" % (rule.group(2), v)]) for v in ids]
+    for v in make_var_or(mk, "GENERAL_IDS") or []:   # the extended one-kernel builds: a general row x an extension
+        out += [("feat%s_ext%s" % (v, e), "rtc_feat.hip", flags + ["-DRTC_VARIANT=%s" % v, "-DRTC_EXT=%s" % e]) for e in make_var(mk, "EXT_IDS")]
+    small = make_var_or(mk, "SMALL_UNITS") or [m.group(1) for m in re.finditer(r"^\$\(O\)/(\w+)\.o: \1\.hip", mk, re.M)]
+    out += [(re.sub(r"^rtc_", "", name), name + ".hip", flags) for name in small]
+    if not any(u[0].startswith("feat") for u in out):
+        raise SystemExit("no rtc_feat objects in %s's Makefile" % tree)
     return out
 
 
@@ -73,7 +86,7 @@ def demangle(names):
 
 def split_functions(path):
     """{mangled name: (n_instr, hash, vgpr, sgpr, scratch)}"""
-    funcs, cur, body, info, in_code = {}, None, [], {}, False
+    funcs, cur, body, info, in_code, getpc = {}, None, [], {}, False, {}
 
     def close():
         if cur is None:
@@ -85,7 +98,7 @@ def split_functions(path):
         m = re.match(r"\s*\.type\s+(\S+),@function", line)
         if m:
             close()
-            cur, body, info, in_code = m.group(1), [], {}, True
+            cur, body, info, in_code, getpc = m.group(1), [], {}, True, {}
             continue
         if cur is None:
             continue
@@ -99,7 +112,8 @@ def split_functions(path):
         code = line.split(";")[0].strip()
         if not in_code or not code or code.startswith(".") or code.endswith(":"):
             continue
-        body.append(re.sub(r"\.L([A-Za-z_]+)\d+_(\d+)", r".L\1_\2", " ".join(code.split())))
+        code = re.sub(r"\.L([A-Za-z_]+)\d+_(\d+)", r".L\1_\2", " ".join(code.split()))
+        body.append(re.sub(r"\.Lpost_getpc(\d+)", lambda m: ".Lpost_getpc#%d" % getpc.setdefault(m.group(1), len(getpc)), code))
     close()
     return funcs
 
@@ -122,12 +136,14 @@ def main():
     ap.add_argument("old_tree")
     ap.add_argument("new_tree")
     ap.add_argument("--rename", action="append", default=[], metavar="REGEX=>REPL", help="rewrite a demangled name of OLD_TREE (re.fullmatch; first matching rule only)")
+    ap.add_argument("--unit", action="append", default=[], metavar="OLD=NEW", help="OLD_TREE's unit OLD corresponds to NEW_TREE's unit NEW")
     ap.add_argument("--jobs", type=int, default=8, help="compiler processes at a time (at most 16)")
     ap.add_argument("--keep", help="directory for the assembly files (default: a temporary one)")
     ap.add_argument("--reuse", action="store_true", help="with --keep: do not recompile a unit whose assembly file is already there")
     a = ap.parse_args()
     jobs = max(1, min(16, a.jobs))
     rules = [tuple(r.split("=>", 1)) for r in a.rename]
+    moved = dict(u.split("=", 1) for u in a.unit)
 
     def renamed(name):
         for pat, repl in rules:
@@ -137,19 +153,21 @@ def main():
 
     with tempfile.TemporaryDirectory() as tmp:
         base = a.keep or tmp
-        old = {(u, renamed(n)): row for (u, n), row in analyse(a.old_tree, jobs, os.path.join(base, "old"), a.reuse).items()}
+        old = {(moved.get(u, u), renamed(n)): row for (u, n), row in analyse(a.old_tree, jobs, os.path.join(base, "old"), a.reuse).items()}
         new = analyse(a.new_tree, jobs, os.path.join(base, "new"), a.reuse)
     for pat, repl in rules:
         print("# rename: %s => %s" % (pat, repl))
-    print("# %-8s %9s %-12s %5s %5s %8s  %-8s %s" % ("unit", "instr", "hash", "vgpr", "sgpr", "scratch", "", "function"))
+    for u, v in moved.items():
+        print("# unit: %s => %s" % (u, v))
+    print("# %-11s %9s %-12s %5s %5s %8s  %-8s %s" % ("unit", "instr", "hash", "vgpr", "sgpr", "scratch", "", "function"))
     bad = 0
     for key in sorted(set(old) | set(new)):
         row = new.get(key) or old[key]
         verdict = "ONLY-OLD" if key not in new else "ONLY-NEW" if key not in old else "SAME" if old[key] == new[key] else "DIFF"
         bad += verdict != "SAME"
-        print("%-10s %9d %-12s %5s %5s %8s  %-8s %s" % (key[0], row[0], row[1], row[2], row[3], row[4], verdict, key[1]))
+        print("%-13s %9d %-12s %5s %5s %8s  %-8s %s" % (key[0], row[0], row[1], row[2], row[3], row[4], verdict, key[1]))
         if verdict == "DIFF":
-            print("%-10s %9d %-12s %5s %5s %8s  %-8s %s" % ("", *old[key], "(old)", ""))
+            print("%-13s %9d %-12s %5s %5s %8s  %-8s %s" % ("", *old[key], "(old)", ""))
     print("# %d functions, %d not SAME" % (len(set(old) | set(new)), bad))
     return 1 if bad else 0
 

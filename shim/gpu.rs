@@ -183,7 +183,7 @@ pub struct RtcBump {
 pub struct RtcBumpInfo {
     pub has_bump: i32,
     pub n_bumps: u32,
-    pub trace_build: i32,
+    pub trace_build: i32, // path 1: 0..5 by the scene's flags (0 none, 1 area, 2 uv, 3 area + uv, 4 spot, 5 spot + uv), + 6 with a background
     pub trace_area: i32,
     pub trace_uv: i32,
     pub trace_spot: i32,
@@ -198,7 +198,7 @@ pub struct RtcBackgroundInfo {
     pub pattern: i32,
     pub projection: i32,
     pub plain_root: i32,
-    pub trace_build: i32,
+    pub trace_build: i32, // path 1: 0 none, 1 area, 2 uv, 3 area + uv, 4 spot, 5 spot + uv
     pub trace_area: i32,
     pub trace_uv: i32,
     pub trace_spot: i32,

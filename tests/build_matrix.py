@@ -52,6 +52,25 @@ def v_trace_3wave(r): return r[0] == 1 and not r[2] and not r[3]
 def v_trace_lean(r): return r[0] <= 1 and not r[2] and not r[3]
 
 
+# Scenes with a background, a bump record or both take, on the one-kernel path, an EXTENSION of a general row: feature level 3, program read
+# from memory, the scene's own area / uv / spot flags ("a cone always comes with the `area` code path").  The library builds every general
+# row once more per extension and reports the build by number (include/rtc.h rtc_background_info / rtc_bump_info .trace_build).
+EXTENSIONS = ("none", "bg", "np", "np+bg")                    # RtcExt 0..3
+def v_general(r): return r[0] == 3 and not r[1]
+
+
+def general_row(area, uv, spot):
+    """The one general row that serves a scene's flags."""
+    rows = [v for v, r in enumerate(VARIANTS) if v_general(r) and r[2:] == (area or spot, uv, spot)]
+    assert len(rows) == 1, (area, uv, spot, rows)
+    return rows[0]
+
+
+def ext_build(area, uv, spot, bg):
+    """The number reported: "0 none, 1 area, 2 uv, 3 area + uv, 4 spot, 5 spot + uv -- and for a bumped scene with a background 6 more"."""
+    return ((5 if uv else 4) if spot else (2 if uv else 0) + (1 if area else 0)) + (6 if bg else 0)
+
+
 def pick_variant(feat, kops, area, uv, spot, wavefront):
     if spot:
         return 11 if (uv and not wavefront) else 10            # wider light records: no other variant can read them

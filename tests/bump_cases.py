@@ -1,5 +1,5 @@
 """Bumped worlds shared by test_bump_gpu.py and the extended oracle's files (ext_cases.py): a world with bump records put on its
-materials in the order they are met, and one scene per row of RTC_NP_BUILDS.  Pure scene descriptions; nothing here needs a library."""
+materials in the order they are met, and one scene per NP build of the one-kernel path (rtc_bump_info.trace_build 0..11).  Pure scene descriptions; nothing here needs a library."""
 import dataclasses
 
 import build_matrix as bm
@@ -39,7 +39,7 @@ ROWS = {  # row -> (scene of tests/build_matrix.py or the open world with the te
 
 
 def row_world(row, tmp_path=None):
-    """(camera, the unbumped twin) of the scene that takes row `row` of RTC_NP_BUILDS once it carries a record.  None of these scenes
+    """(camera, the unbumped twin) of the scene that takes NP build `row` (rtc_bump_info.trace_build) once it carries a record.  None of these scenes
     writes a file: tmp_path is the build matrix's argument and may stay None."""
     from test_background_gpu import open_world, real_backgrounds
     name, bg = ROWS[row]

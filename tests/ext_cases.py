@@ -257,7 +257,7 @@ def bumped_everything_world(skybox=True):
 
 
 def np_row_case(row):
-    """(camera, world, fuel) of the bumped scene of row `row` of RTC_NP_BUILDS (bump_cases.ROWS; test_bump_gpu.py compares its two paths)."""
+    """(camera, world, fuel) of the bumped scene of NP build `row` (rtc_bump_info.trace_build; bump_cases.ROWS; test_bump_gpu.py compares its two paths)."""
     cam, twin = bc.row_world(row)
     world = bc.bumped(twin, bc.mixed)
     return cam, world, 5 if len(world.lights) <= 2 else 3

@@ -251,14 +251,26 @@ def test_rust_shim_mirrors_rtc_background():
     assert "RTC_BG_DIRECTION = 0, RTC_BG_CUBE = 1" in h
 
 
-def test_variant_table_is_untouched_and_the_background_builds_are_beside_it():
-    """The BG instantiations of the one-kernel path are no rows of RTC_VARIANTS: the table keeps its twelve rows, RtcVariant its five fields,
-    and rtc_background.hip is built once per row of RTC_BG_BUILDS."""
+def test_variant_table_is_untouched_and_the_extended_builds_are_its_general_rows():
+    """The BG and NP instantiations of the one-kernel path are no rows of RTC_VARIANTS and have no table of their own: the table keeps its
+    twelve rows, RtcVariant its five fields, and rtc_feat.hip is built once more per general row of the table and extension."""
+    import re
     csrc = os.path.join(ROOT, "raytracer_challenge_amd", "csrc")
     dev = open(os.path.join(csrc, "rtc_device.hpp")).read()
     table = dev[dev.index("constexpr RtcVariant RTC_VARIANTS[] = {"):dev.index("constexpr int RTC_N_VARIANTS")]
-    assert table.count("},") == 12
-    bg = dev[dev.index("constexpr RtcVariant RTC_BG_BUILDS[] = {"):dev.index("constexpr int RTC_N_BG_BUILDS")]
-    assert bg.count("},") == 6 and all("{3, false," in line for line in bg.splitlines() if line.strip().startswith("{"))
+    rows = [line.split("//")[0].strip() for line in table.splitlines() if line.strip().startswith("{")]
+    assert table.count("},") == 12 and len(rows) == 12 and all(r.count(",") == 5 for r in rows)
+    assert re.findall(r"constexpr RtcVariant (\w+)\[", dev) == ["RTC_VARIANTS"]   # one table
     mk = open(os.path.join(csrc, "Makefile")).read()
-    assert "VARIANT_IDS := 0 1 2 3 4 5 6 7 8 9 10 11\n" in mk and "BG_BUILD_IDS := 0 1 2 3 4 5\n" in mk
+    assert "VARIANT_IDS := 0 1 2 3 4 5 6 7 8 9 10 11\n" in mk and "GENERAL_IDS := 4 6 8 9 10 11\n" in mk and "EXT_IDS := 1 2 3\n" in mk
+    assert [v for v, r in enumerate(rows) if r.startswith("{3, false,")] == [4, 6, 8, 9, 10, 11]   # the general rows, all of them
+    # exactly general rows x extensions: one list of units, in OBJS and in the one rule that builds them; no other -D selects a build
+    assert "EXT_UNITS := $(foreach v,$(GENERAL_IDS),$(foreach e,$(EXT_IDS),$(v)_ext$(e)))\n" in mk
+    assert mk.count("$(foreach x,$(EXT_UNITS),$(O)/rtc_feat$(x).o)") == 2
+    assert ("$(foreach x,$(EXT_UNITS),$(O)/rtc_feat$(x).o): $(O)/rtc_feat%.o: rtc_feat.hip $(KHDRS)\n"
+            "\t$(HIPCC_C) -DRTC_VARIANT=$(firstword $(subst _ext, ,$*)) -DRTC_EXT=$(lastword $(subst _ext, ,$*)) -c $< -o $@\n") in mk
+    assert "$(O)/rtc_feat%.o: rtc_feat.hip $(KHDRS)\n\t$(HIPCC_C) -DRTC_VARIANT=$* -c $< -o $@\n" in mk
+    assert set(re.findall(r"-D(RTC_\w+)", mk[mk.index("$(OUT):"):mk.index("resource-usage:")])) == {"RTC_VARIANT", "RTC_EXT"}
+    # the feature's own files hold its small kernels and nothing that is compiled in or out
+    for name in ("rtc_background.hip", "rtc_bump.hip"):
+        assert "#if" not in open(os.path.join(csrc, name)).read(), name

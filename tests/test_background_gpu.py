@@ -343,7 +343,7 @@ def test_path_against_path_with_real_backgrounds(hip, which, monkeypatch):
 
 @pytest.mark.parametrize("name", ["area_kops_real", "uv_area_real", "spot_real", "uv_spot_real"])
 def test_every_background_build_of_the_one_kernel_path(hip, name, tmp_path, monkeypatch):
-    """Rows 1, 3, 4 and 5 of RTC_BG_BUILDS (rows 0 and 2: the tests above): area lights, cones and UV patterns under a gradient sky, the
+    """BG builds 1, 3, 4 and 5 (rtc_background_info.trace_build; 0 and 2: the tests above): area lights, cones and UV patterns under a gradient sky, the
     one-kernel path's BG build against the wavefront path's kernels."""
     cam, world = bm.BY_NAME[name].make(tmp_path)
     world = World(world.lights, world.elements[:1] + world.elements[2:], real_backgrounds()[0][1])        # without the back wall: the sky is in frame

@@ -395,23 +395,26 @@ def test_rust_shim_mirrors_rtc_bump():
     assert "RTC_BUMP_MAX_OCTAVES: u32 = %d" % MAX_OCTAVES in rs and "#define RTC_BUMP_MAX_OCTAVES %d" % MAX_OCTAVES in h
 
 
-def test_variant_tables_are_untouched_and_the_bump_builds_are_beside_them():
-    """The NP instantiations of the one-kernel path are no rows of RTC_VARIANTS or RTC_BG_BUILDS: those keep twelve and six rows,
-    RtcVariant its five fields, and rtc_bump.hip is built once per row of RTC_NP_BUILDS (and once without one, for rtc_bump_normals)."""
+def test_the_bump_builds_are_extensions_of_the_general_rows_and_the_rule_is_one_function():
+    """The NP instantiations of the one-kernel path are no rows of RTC_VARIANTS and have no table of their own (test_background_cpu.py holds
+    the table and the Makefile's lists to that): they are extensions 2 (NP) and 3 (NP + BG) of the six general rows, rtc_bump.hip is built
+    once, and the rule itself is one function."""
+    import re
     csrc = os.path.join(ROOT, "raytracer_challenge_amd", "csrc")
     dev = open(os.path.join(csrc, "rtc_device.hpp")).read()
-    table = dev[dev.index("constexpr RtcVariant RTC_VARIANTS[] = {"):dev.index("constexpr int RTC_N_VARIANTS")]
-    assert table.count("},") == 12
-    bg = dev[dev.index("constexpr RtcVariant RTC_BG_BUILDS[] = {"):dev.index("constexpr int RTC_N_BG_BUILDS")]
-    assert bg.count("},") == 6
-    rows = lambda t: [line.split("//")[0].strip() for line in t.splitlines() if line.strip().startswith("{")]  # noqa: E731
-    np_ = dev[dev.index("constexpr RtcVariant RTC_NP_BUILDS[] = {"):dev.index("constexpr int RTC_N_NP_BUILDS")]
-    assert rows(np_) == rows(bg) + rows(bg) and all(r.startswith("{3, false,") and r.count(",") == 5 for r in rows(np_))   # without, then with a background
+    assert re.findall(r"constexpr RtcVariant (\w+)\[", dev) == ["RTC_VARIANTS"]
+    ext = dev[dev.index("enum RtcExt {"):]
+    assert "RTC_EXT_NP = 2," in ext and "RTC_EXT_NP_BG = 3," in ext
     mk = open(os.path.join(csrc, "Makefile")).read()
-    assert "VARIANT_IDS := 0 1 2 3 4 5 6 7 8 9 10 11\n" in mk and "BG_BUILD_IDS := 0 1 2 3 4 5\n" in mk and "NP_BUILD_IDS := 0 1 2 3 4 5 6 7 8 9 10 11\n" in mk
-    assert "$(O)/rtc_bump.o $(foreach b,$(NP_BUILD_IDS),$(O)/rtc_bump$(b).o)" in mk
-    assert "$(O)/rtc_bump%.o: rtc_bump.hip $(KHDRS)\n\t$(HIPCC) --offload-arch=$(ARCH) $(FLAGS) $(DEFS) -DRTC_NP_BUILD=$* -c $< -o $@\n" in mk
+    assert "VARIANT_IDS := 0 1 2 3 4 5 6 7 8 9 10 11\n" in mk and "GENERAL_IDS := 4 6 8 9 10 11\n" in mk and "EXT_IDS := 1 2 3\n" in mk
+    small = re.search(r"^SMALL_UNITS := (.*)$", mk, re.M).group(1).split()
+    assert small.count("rtc_bump") == 1 and "$(foreach u,$(SMALL_UNITS),$(O)/$(u).o): $(O)/%.o: %.hip $(SMALL_HDRS)\n\t$(HIPCC_C) -c $< -o $@\n" in mk
     assert "-ffp-contract=off" in mk and "bump_normal.h" in mk and "noise3.h" in mk
+    khdrs = re.search(r"^KHDRS := (.*)$", mk, re.M).group(1).split()
+    assert "bump_normal.h" in khdrs and "noise3.h" in khdrs and "SMALL_HDRS := $(KHDRS) " in mk   # every kernel object depends on them
     # the rule is one function: the kernels and the host entry call it, nothing restates it
+    assert open(os.path.join(csrc, "bump_normal.h")).read().count("void rtc_bump_normal_at(") == 1
     for name in ("rtc_device.hpp", "rtc_bump.hip", "rtc_scene.cpp"):
-        assert "rtc_bump_normal_at(" in open(os.path.join(csrc, name)).read(), name
+        src = open(os.path.join(csrc, name)).read()
+        assert "rtc_bump_normal_at(" in src, name
+        assert "void rtc_bump_normal_at(" not in src, name   # called, not defined again

@@ -1,6 +1,6 @@
 """Normal perturbation (include/rtc.h rtc_bump) on an MI355X, both device paths: amplitude 0 moves nothing, the rule on the device against
 the host entry, the normal through a render (a perfect mirror under a Debug background shows its own reflect vector, exactly), the
-lighting against a numpy Phong over the restated normal, path against path on one scene per row of RTC_NP_BUILDS, the frame shapes that
+lighting against a numpy Phong over the restated normal, path against path on one scene per NP build (rtc_bump_info.trace_build), the frame shapes that
 can go wrong, and every render entry point."""
 import ctypes as C
 import dataclasses
@@ -223,7 +223,7 @@ def test_lighting_follows_the_shading_normal(hip, path, monkeypatch):
         assert float(np.abs(smooth - rgb).max()) > 0.05                            # far outside the tolerance: the bump is in the frame
 
 
-# ---- 5. path against path, one scene per row of RTC_NP_BUILDS ---------------------------------------------------------------------------------
+# ---- 5. path against path, one scene per NP build (trace_build 0..11) ---------------------------------------------------------------------------------
 @pytest.mark.parametrize("row", sorted(ROWS))
 def test_path_against_path_on_every_np_build(hip, row, tmp_path, monkeypatch):
     cam, twin = row_world(row, tmp_path)

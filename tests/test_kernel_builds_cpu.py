@@ -52,6 +52,25 @@ def test_restated_pick_variant_agrees_with_the_table():
     assert [v for v, r in enumerate(bm.VARIANTS) if not bm.v_wavefront(r)] == [8, 9, 11]
 
 
+def test_restated_general_row_serves_every_extended_scene():
+    """All 2*2*2*2 inputs: the restated general row is a row of the table whose flags serve the scene, the row the one-kernel path of a
+    CSG scene with a memory program takes anyway, and its position among the general rows is the number the ABI reports."""
+    general = [v for v, r in enumerate(bm.VARIANTS) if bm.v_general(r)]
+    assert general == [4, 6, 8, 9, 10, 11]
+    numbers = set()
+    for area, uv, spot, bg in itertools.product(*([(False, True)] * 4)):
+        row = bm.general_row(area, uv, spot)
+        what = (area, uv, spot, bg, row)
+        r_feat, r_kops, r_area, r_uv, r_spot = bm.VARIANTS[row]
+        assert r_feat == 3 and not r_kops, what             # every gate and CSG compiled in, the program read from memory
+        assert r_spot == spot and r_uv == uv, what
+        assert r_area == (area or spot), what               # "always with the `area` code path"
+        assert row == bm.pick_variant(3, False, area, uv, spot, False), what
+        assert general.index(row) + (6 if bg else 0) == bm.ext_build(area, uv, spot, bg), what
+        numbers.add(bm.ext_build(area, uv, spot, bg))
+    assert numbers == set(range(12))
+
+
 def test_restatement_follows_the_library_source():
     """The row count and the limits this module restates are the ones the sources define (a row added there needs a scene here)."""
     import os
@@ -64,6 +83,15 @@ def test_restatement_follows_the_library_source():
     scene = open(os.path.join(csrc, "device_scene.h")).read()
     for name, value in (("RTC_KOPS", bm.KOPS), ("RTC_KPLANES", bm.KPLANES), ("RTC_KAUX", bm.KAUX)):
         assert re.search(r"^#define %s (\d+)" % name, scene, re.M).group(1) == str(value)
+    # the lists the build is made from: every row, the general rows, the extensions
+    mk = open(os.path.join(csrc, "Makefile")).read()
+    ids = {name: [int(x) for x in re.search(r"^%s := ([\d ]+)$" % name, mk, re.M).group(1).split()] for name in ("VARIANT_IDS", "GENERAL_IDS", "EXT_IDS")}
+    assert ids["VARIANT_IDS"] == list(range(len(bm.VARIANTS)))
+    assert ids["GENERAL_IDS"] == [v for v, r in enumerate(bm.VARIANTS) if bm.v_general(r)]
+    assert ids["EXT_IDS"] == list(range(1, len(bm.EXTENSIONS)))
+    ext = dict(re.findall(r"^\s*(RTC_EXT_\w+) = (\d),", dev[dev.index("enum RtcExt {"):], re.M))
+    assert ext == {"RTC_EXT_NONE": "0", "RTC_EXT_BG": "1", "RTC_EXT_NP": "2", "RTC_EXT_NP_BG": "3"}
+    assert "constexpr bool rtc_v_general(RtcVariant r) { return r.feat == 3 && !r.kops; }" in dev
 
 
 def test_ledger_in_the_emulator(emu, tmp_path):

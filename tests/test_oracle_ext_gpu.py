@@ -37,7 +37,7 @@ def test_showcases_fixtures_and_the_everything_scene(hip, ext, name, path, monke
     """The committed showcases and fixtures at fuel 5 (texture / spot / sky showcases at 96x54, the jittered penumbra and mirror worlds at
     96x64, the build matrix's uv scene under a background) and the scene that holds every extension at once, with a skybox and with a
     gradient over RTC_BG_DIRECTION, at 64x36 and at 13x7 (less than a wave wide, a multiple of nothing).  Bumped worlds (include/rtc.h
-    rtc_bump; the oracle's steps 5-7 sit in rt_oracle.hpp's prepare_state): one scene per row of RTC_NP_BUILDS at 48x32, each asserted to
+    rtc_bump; the oracle's steps 5-7 sit in rt_oracle.hpp's prepare_state): one scene per NP build (rtc_bump_info.trace_build 0..11) at 48x32, each asserted to
     run that row; the everything scene with a record on every material (one of amplitude 0); bump_showcase at 48x27; amplitude 2.0 on a
     glass-and-mirror sphere and a mirror plane, where a third of the hit pixels have ns . eye < 0."""
     cam, world, fuel = ec.frame_case(name)
