@@ -12,6 +12,20 @@
  * Ownership: `rtc_scene_create` copies everything it needs (the caller may free the arrays on return) and owns
  * all device memory; the caller owns output buffers.  Errors: status code + `rtc_last_error()`; nothing unwinds.
  * Threading: calls are blocking; distinct scenes may be used from distinct threads; one HIP stream per scene.
+ *   - "Distinct": an object and everything a call on it touches belong to one thread at a time.  An `rtc_scene` is one object; an
+ *     `rtc_multi` with all its replicas is one object of its caller; the K scenes handed to one rtc_render_shutter call belong to that
+ *     caller for the length of the call.  Two threads on one scene at once are undefined.  Scene creation and destruction count as calls:
+ *     any number of threads may create, render and destroy scenes of their own at the same time, on one device or several.
+ *   - A scene rendered from a thread beside others gives the frame, hit records, digests and counters it gives alone, bit for bit
+ *     (tests/test_threads_gpu.py); company changes only how many CUs an unsynchronised wavefront launch takes (rtc_scene_wavefront_ts_grid).
+ *   - `rtc_last_error()` (and rtw.h's `rtw_last_error()`) is per thread: it returns the text of the calling thread's own most recent
+ *     failed call, valid until that thread's next failing call.  A successful call leaves it unchanged; no call clears it.
+ *   - Handles are not tied to a thread: a scene may be created on one thread, used on another and destroyed on a third, one at a time.
+ *     Every entry point selects the scene's device itself.
+ *   - Environment variables are read with getenv, never written: RTC_KERNEL, RTC_WF_*, RTC_NO_KOPS, RTC_KOPS_GROUPS, RTC_DEVICE_BVH*,
+ *     RTC_LIGHT_GRID*, RTC_BUILD_THREADS and the other build switches when a scene is created; RTC_SAMPLED_MAX_RAYS, RTC_FILTER_LDS,
+ *     RTC_FIRST_GUESS, RTC_WF_MAX_BYTES and RTC_CSG_MAX_BYTES at each launch.  A host that changes them does so before it starts threads.
+ *   - Scene creation may start a few host threads of its own inside the call (large meshes); they are joined before it returns.
  * There is no CPU fallback: without a HIP device every entry point that computes returns RTC_ERR_DEVICE.
  */
 #ifndef RTC_H
