@@ -844,6 +844,22 @@ int rtc_light_grid_build_raw(const int32_t* geometry, const double* limits, cons
  * `values` with n > 0; RTC_ERR_UNSUPPORTED for n >= 2^39 with a scene (the limit of the frames the compaction accepts). */
 int rtc_scan_raw(rtc_scene* scene, uint64_t* values, uint64_t n, uint64_t* total);
 
+/* Test hook, not part of the rendering surface: ONE culling predicate of the ray kernels (csrc/rtc_device.hpp; DESIGN.md 4, "culling only")
+ * on n caller-supplied records, one uint8_t answer (0 / 1) per record.  No scene geometry is involved: the scene only names the device and
+ * the stream, and the records and answers travel in device buffers of the call's own, freed before it returns (csrc/rtc_probe.hip; the
+ * CPU emulator runs the same functions in a host loop and ignores the scene).  A record is an array of doubles:
+ *   RTC_CULL_SLAB   (18) fr[4] = a BVH's centre and radius, ray o[3] d[3] in the BVH's space, tlo, thi, box lo[3] hi[3] (f32 values, relative
+ *                        to the centre, within the radius of it): make_frame + t_interval32 + slab32c, 1 = the box is taken
+ *   RTC_CULL_POINT  (17) fr[4], ray, t_hit, box: make_frame_point + point_in_box, 1 = the hit point counts as inside the box
+ *   RTC_CULL_GATE   (12) box lo[3] hi[3] (f64), ray: group_box_hit, 1 = the ray passes the group's box
+ *   RTC_CULL_PLANE   (3) oy, dy, mode (0 closest, 1 any-hit shadow, 2 closest shadow, 3 containers): plane_behind where the kernels ask it, that is
+ *                        after the reference's |dy| < EPSILON rule has let the ray through; 1 = the plane is skipped as behind the origin
+ *   RTC_CULL_BEHIND  (9) point[3], light[3], unit normal[3], in a scene with backface_skip = 1: light_is_behind, 1 = the shadow ray is skipped
+ * n == 0 reads and writes nothing.  RTC_ERR_INVALID for another kind, NULL records or answers with n > 0, or a NULL scene where a
+ * device is needed (librtc_amd.so); RTC_ERR_UNSUPPORTED for n >= 2^32 on the device. */
+enum { RTC_CULL_SLAB = 0, RTC_CULL_POINT = 1, RTC_CULL_GATE = 2, RTC_CULL_PLANE = 3, RTC_CULL_BEHIND = 4 };
+int rtc_cull_probe_raw(rtc_scene* scene, int32_t kind, const double* records, uint64_t n, uint8_t* answers);
+
 /* Dynamic LDS (bytes per block) the wavefront traversal kernel uses for this scene: > 0 = the scene's accelerator nodes, intersection
  * records and mesh triangles are copied into every CU's LDS and walks read them there (small scenes: the tables and the traversal
  * stacks fit 160 KB); 0 = they are read from memory.  bench.py's byte accounting counts LDS-resident records as 0 bytes. */

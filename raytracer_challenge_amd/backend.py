@@ -605,6 +605,33 @@ class Backend:
             raise RtwError("rtc_scan_raw: %s" % (lib.rtc_last_error() or b"").decode())
         return out, int(total.value)
 
+    def cull_probe(self, kind: int, records: np.ndarray, nw: Optional[NativeWorld] = None, device: int = 0) -> np.ndarray:
+        """include/rtc.h rtc_cull_probe_raw (test infrastructure): one culling predicate of the ray kernels on `records` (one row of
+        doubles each, the layout of RTC_CULL_* `kind`); returns one bool per record.  librtc_amd.so runs the probe kernel on the world's
+        device and needs a world; the CPU emulator evaluates the same functions on the host and needs none."""
+        lib = self.lib
+        if not hasattr(lib, "rtc_cull_probe_raw"):
+            raise RtwError("backend %r has no rtc_cull_probe_raw" % self.name)
+        vp = C.c_void_p
+        lib.rtw_world_scene.restype, lib.rtw_world_scene.argtypes = vp, [vp, C.c_int]
+        lib.rtc_cull_probe_raw.restype = C.c_int
+        lib.rtc_cull_probe_raw.argtypes = [vp, C.c_int32, vp, C.c_uint64, vp]
+        lib.rtc_last_error.restype = C.c_char_p
+        scene = None
+        if nw is not None:
+            scene = lib.rtw_world_scene(nw.handle, int(device))
+            if not scene:
+                raise RtwError("scene upload failed: %s" % self._err())
+        rec = np.ascontiguousarray(records, dtype=np.float64)
+        width = {0: 18, 1: 17, 2: 12, 3: 3, 4: 9}.get(int(kind))
+        if rec.ndim != 2 or rec.shape[1] != width:
+            raise ValueError("cull_probe: kind %r takes rows of %r doubles, got an array of shape %r" % (kind, width, rec.shape))
+        n = rec.shape[0]
+        out = np.zeros(n, dtype=np.uint8)
+        if lib.rtc_cull_probe_raw(scene, int(kind), rec.ctypes.data if n else None, n, out.ctypes.data if n else None) != 0:
+            raise RtwError("rtc_cull_probe_raw: %s" % (lib.rtc_last_error() or b"").decode())
+        return out.astype(bool)
+
     def color_at(self, nw: NativeWorld, rays: np.ndarray, fuel: int = FUEL):
         """World::color_at for rays given as rows {ox,oy,oz,dx,dy,dz}.  Returns (rgb[n,3], hits[n])."""
         rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)

@@ -251,7 +251,9 @@ __device__ __forceinline__ bool key_before(double t, int prim, int k, double ht,
 // The reference sorts the list of a closest-hit or shadow pass with `partial_cmp().unwrap()` (src/intersection.rs:123-125): a NaN t
 // panics when the comparator sees it, which is when the list holds at least two entries (a slice of 0 or 1 is returned as it is).
 // A NaN t comes from a ray with a NaN in it (e.g. the zero-length normal at a cone's apex), and such a ray takes every box of the
-// accelerators, so the pushes counted here are the reference's list.  Called once after a closest / shadow pass.
+// accelerators -- make_frame() hands a ray with a NaN or infinite component the take-every-box frame; slab32c alone would only drop
+// the NaN axis and go on rejecting with the other two --, so the pushes counted here are the reference's list.  Called once after a
+// closest / shadow pass.
 __device__ __forceinline__ void nan_commit(const Trav& T, Counters& C) {
   if ((T.flags & TF_NAN) && (T.flags >> TF_PUSH_SHIFT) >= 2) C.nan_ts++;
 }
@@ -591,12 +593,21 @@ __device__ __forceinline__ bool light_grid_candidates(const DScene& S, const Lig
 //   every box is inflated by eps by testing its low faces against of + eps and its high faces against of - eps,
 //   and the pass's t interval is widened by 2^-18 relative.  A face's distance is ONE fused multiply-add, face * i - (of +- eps) * i
 //   with i = 1 / direction: the product is rounded once per ray (2^-24 |of * i|, an eighth of what eps moves the face by), the fma
-//   once per face as a multiplication would be.  |i| is capped at 1e30 (a zero direction component: +-1e30 decides inside /
-//   outside the slab like +-inf would, but inf - inf would be NaN); a product that still overflows makes a NaN, which the
-//   min / max ignore: the box is taken.
-// So a box is rejected only if the f64 ray misses the box inflated by ~15 eps or its [tn, tf] misses [t_lo, t_hi]; NaN
-// (0 * inf) operands are ignored by fminf/fmaxf exactly as in the f64 version.  A ray whose origin does not fit f32
-// relative to c takes every box (id = 0 makes every slab interval [0, 0]).
+//   once per face as a multiplication would be.  |i| is capped at 1e30, which stands for 1 / 0: +-1e30 decides inside / outside the
+//   slab like +-inf would, but inf - inf would be NaN.
+// So a box is rejected only if the f64 ray misses the box inflated by ~15 eps or its [tn, tf] misses [t_lo, t_hi].
+// Frames the test cannot be trusted in take EVERY box (i = 0 and scaled origins 0 make every slab interval [0, 0], and every pass's
+// interval holds 0) -- make_frame decides that once per ray and BVH:
+//   - |of|_inf + R >= 1e30, or a NaN origin component: the origin does not fit f32 relative to c;
+//   - a direction component that is NaN or infinite (a NaN component used to be dropped by fminf / fmaxf while the two finite axes
+//     went on rejecting; the reference pushes a NaN t for every primitive of such a ray, nan_commit());
+//   - a smallest |i| -- the axis the ray mostly runs along -- above 2.3e22.  The cap is a different t scale from a true 1 / d, and
+//     what makes it harmless is that scale's distance from the t's that matter, |t| <= 2 m |i|_min (m = |of|_inf + R; the box's extent
+//     on that axis): a slab the origin is inside of spans +-2^-21 m 1e30 around 0, which holds them all, and a capped axis whose
+//     component is not exactly zero drifts by at most 2 m |i|_min / 1e30 < eps / 16 meanwhile -- both while |i|_min < 2^-25 1e30;
+//   - a scaled origin (of +- eps) * i that is not finite: |of| > 3.4e8 on a capped axis, 3.4e18 at i = 1e20, ...  The fused face
+//     distance would be -inf (or +inf) on BOTH faces of that axis -- an empty interval, the box rejected though the ray enters it.
+//     (Before the fma form the difference of two infinite products was a NaN, which the min / max ignore.)
 struct Frame32 {
   float olx, oly, olz, ohx, ohy, ohz, ix, iy, iz;  // ol / oh: (origin + eps) * i and (origin - eps) * i, see make_frame
   float px, py, pz, pm;  // container passes of the wavefront path: the hit point in the frame and its margin (make_frame_point)
@@ -628,12 +639,21 @@ __device__ __forceinline__ void make_frame(const double* __restrict__ fr, const 
   float eps = m * 9.5367431640625e-07f + 1e-30f;
   f.olx = ox + eps; f.oly = oy + eps; f.olz = oz + eps;
   f.ohx = ox - eps; f.ohy = oy - eps; f.ohz = oz - eps;
-  f.ix = 1.0f / (float)o.dx; f.iy = 1.0f / (float)o.dy; f.iz = 1.0f / (float)o.dz;
-  f.ix = f.ix > 1e30f ? 1e30f : (f.ix < -1e30f ? -1e30f : f.ix);  // (a NaN stays a NaN: every box is taken, as before)
+  const float dx = (float)o.dx, dy = (float)o.dy, dz = (float)o.dz;
+  f.ix = 1.0f / dx; f.iy = 1.0f / dy; f.iz = 1.0f / dz;
+  f.ix = f.ix > 1e30f ? 1e30f : (f.ix < -1e30f ? -1e30f : f.ix);  // (a NaN stays a NaN)
   f.iy = f.iy > 1e30f ? 1e30f : (f.iy < -1e30f ? -1e30f : f.iy);
   f.iz = f.iz > 1e30f ? 1e30f : (f.iz < -1e30f ? -1e30f : f.iz);
   f.olx *= f.ix; f.oly *= f.iy; f.olz *= f.iz;
   f.ohx *= f.ix; f.ohy *= f.iy; f.ohz *= f.iz;
+  // ONE number that is finite iff the frame can be trusted (see above): the six scaled origins (overflowed, or NaN from a NaN origin
+  // or direction component), 0 * the direction (NaN for an infinite component), and 1.5e16 * the smallest |i| (inf above 2.3e22)
+  const float ok = fabsf(f.olx) + fabsf(f.oly) + fabsf(f.olz) + fabsf(f.ohx) + fabsf(f.ohy) + fabsf(f.ohz) + (dx + dy + dz) * 0.0f +
+                   fminf(fminf(fabsf(f.ix), fabsf(f.iy)), fabsf(f.iz)) * 1.5e16f;
+  if (!(ok < __builtin_inff())) {
+    f.olx = f.oly = f.olz = f.ohx = f.ohy = f.ohz = 0.0f;
+    f.ix = f.iy = f.iz = 0.0f;
+  }
 }
 __device__ __forceinline__ void t_interval32(const Trav& T, float& lo, float& hi) {
   const double SL = 3.814697265625e-06;  // 2^-18

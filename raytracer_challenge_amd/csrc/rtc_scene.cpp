@@ -58,6 +58,8 @@ unsigned long long rtc_contrast_blocks(unsigned long long n);
 unsigned long long rtc_contrast_work_words(unsigned long long n);
 unsigned long long rtc_scan_work_words(unsigned long long n);
 unsigned rtc_launch_scan(unsigned long long* v, unsigned long long n, unsigned long long* levels, unsigned long long* total, hipStream_t stream);
+int rtc_cull_probe_doubles(int kind);
+void rtc_launch_cull_probe(int kind, const double* records, unsigned long long n, unsigned char* out, hipStream_t stream);
 unsigned rtc_launch_contrast_compact(const double* frame, unsigned long long hsize, unsigned long long vsize, double threshold, unsigned neighbours,
                                      unsigned long long* work, unsigned long long* list, unsigned long long* count, hipStream_t stream);
 void rtc_launch_resolve_samples_scatter(const double* ray_rgb, unsigned n_samples, unsigned long long n_slots, const unsigned long long* indices, double* frame,
@@ -2301,6 +2303,30 @@ int rtc_scan_raw(rtc_scene* s, uint64_t* values, uint64_t n, uint64_t* total) {
   HIP_OK(e);
   HIP_OK(e_sync);
   *total = sum;
+  return RTC_OK;
+}
+
+// Test hook: one culling predicate of rtc_device.hpp on the caller's records (rtc_probe.hip), in buffers of its own (include/rtc.h).
+int rtc_cull_probe_raw(rtc_scene* s, int32_t kind, const double* records, uint64_t n, uint8_t* answers) {
+  const int stride = rtc_cull_probe_doubles(kind);
+  if (stride == 0) return rtc_fail(RTC_ERR_INVALID, "cull probe: no such predicate");
+  if (n == 0) return RTC_OK;
+  if (!records || !answers || !s) return rtc_fail(RTC_ERR_INVALID, "NULL argument");
+  if (n >= (1ull << 32)) return rtc_fail(RTC_ERR_UNSUPPORTED, "cull probe: 2^32 records or more");
+  HIP_OK(hipSetDevice(s->device));
+  const uint64_t rec_bytes = n * (uint64_t)stride * sizeof(double);
+  unsigned char* d = nullptr;  // the records, then the answers
+  HIP_OK(hipMalloc((void**)&d, rec_bytes + n));
+  hipError_t e = hipMemcpyAsync(d, records, rec_bytes, hipMemcpyHostToDevice, s->stream);
+  if (e == hipSuccess) {
+    rtc_launch_cull_probe(kind, (const double*)d, n, d + rec_bytes, s->stream);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(answers, d + rec_bytes, n, hipMemcpyDeviceToHost, s->stream);
+  const hipError_t e_sync = hipStreamSynchronize(s->stream);  // (before the buffer goes, whatever happened)
+  (void)hipFree(d);
+  HIP_OK(e);
+  HIP_OK(e_sync);
   return RTC_OK;
 }
 

@@ -356,3 +356,80 @@ def special_rays(world, n=2048, seed=11):
             d, ln = np.array([0.0, 0.0, 1.0]), 1.0
         rays[i, :3], rays[i, 3:] = o, d / ln   # unit directions (an exactly axis-parallel one stays exactly so)
     return rays
+
+
+# The seven small spheres of huge_world, in units of its size S: centres, and their common radius
+HUGE_CENTRES = ((0.5, 0.0, -0.5), (-0.5, 0.0, -0.5), (0.5, 0.0, 0.5), (-0.5, 0.0, 0.5), (0.0, 0.5, 0.0), (0.0, -0.5, 0.0), (0.5, 0.001, -1.0))
+HUGE_RADIUS = 0.02
+
+
+def huge_world(S):
+    """Seven spheres of radius 0.02 S inside one of radius 2 S around the origin, no plane: from S of about 4e8 on, the origin of a ray
+    inside the big sphere times the capped reciprocal of a zero direction component exceeds the f32 range in the analytic BVH's frame
+    (rtc_device.hpp make_frame).  The culling must not show: axis-parallel rays hit what the oracle hits."""
+    mat = lambda i: Material(pattern=Pattern.plain(Color.new(0.2 + 0.1 * i, 0.9 - 0.1 * i, 0.5)), ambient=0.3, reflective=0.2 if i % 3 == 0 else 0.0)
+    r = HUGE_RADIUS * S
+    els = [Element.sphere(ShapeArgs(transform=Matrix.translation(x * S, y * S, z * S) * Matrix.scaling(r, r, r), material=mat(i))) for i, (x, y, z) in enumerate(HUGE_CENTRES)]
+    els.append(Element.sphere(ShapeArgs(transform=Matrix.scaling(2.0 * S, 2.0 * S, 2.0 * S), material=mat(7))))
+    return World([PointLight(Color.white(), Vector.point(-0.3 * S, 0.8 * S, -0.2 * S))], els)
+
+
+def huge_world_rays(S, seed=13):
+    """From inside the big sphere: axis-parallel rays (the other two components 0, -0 or +-1e-35) through the small spheres' centres,
+    past their rims (grazing within 1e-6 radii on either side), and through nothing but the big sphere; skew rays at the same targets
+    as controls.  The first ray is the one of the report: from (S / 2, S / 1000, 0) along -z."""
+    rng = np.random.default_rng(seed)
+    rays = [[0.5 * S, 0.001 * S, 0.0, 0.0, 0.0, -1.0]]
+    r = HUGE_RADIUS * S
+    for cx, cy, cz in HUGE_CENTRES + ((0.9, 0.9, 0.9), (-1.1, 0.3, 0.2)):   # (the last two: empty space)
+        c = np.array([cx, cy, cz]) * S
+        for k in range(3):
+            for sign in (1.0, -1.0):
+                for off in (0.0, 0.5, 1.0 - 1e-6, 1.0, 1.0 + 1e-6):
+                    d = np.array(rng.choice([0.0, -0.0, 1e-35, -1e-35, 0.0], 3))
+                    d[k] = sign
+                    o = c.copy()
+                    o[(k + 1) % 3] += off * r
+                    o[k] -= sign * rng.choice([0.1, 0.37, 1.0]) * S
+                    rays.append(np.concatenate([o, d]))
+        for _ in range(6):   # controls: skew rays towards the same sphere
+            o = rng.uniform(-0.9, 0.9, 3) * S
+            d = c + rng.normal(size=3) * r * 0.7 - o
+            rays.append(np.concatenate([o, d / np.linalg.norm(d)]))
+    return np.array(rays)
+
+
+def huge_world_camera(S, n=9):
+    """n x n (odd) from (S / 2, S / 1000, 0) looking exactly down -z: the centre pixel's ray is parallel to the z axis."""
+    return Camera.new(n, n, 0.6, Camera.transform(Vector.point(0.5 * S, 0.001 * S, 0.0), Vector.point(0.5 * S, 0.001 * S, -1.0 * S), Vector.vector(0, 1, 0)))
+
+
+def bvh_only_world():
+    """Eight unit spheres in a row along x and no plane: whatever a ray meets, it meets through the analytic BVH."""
+    mat = Material(pattern=Pattern.plain(Color.new(0.3, 0.5, 0.8)), ambient=0.3)
+    els = [Element.sphere(ShapeArgs(transform=Matrix.translation(3.0 * i - 10.5, 0.0, 0.0), material=mat)) for i in range(8)]
+    return World([PointLight(Color.white(), Vector.point(-4.0, 12.0, -9.0))], els)
+
+
+def bvh_only_rays():
+    """Rays with ONE NaN or +-inf direction component (and a few with two or three), whose finite axes miss the row of spheres, graze
+    its boxes, and cross them.  A sphere's discriminant is NaN for such a ray, so the reference pushes NaN t's for every sphere and its
+    sort panics -- whatever the finite axes do; the oracle alone decides which rays are refused.  Finite controls at the end."""
+    rays = []
+    for bad in (math.nan, math.inf, -math.inf):
+        for k in range(3):
+            for o, d in (((0.0, 30.0, -10.0), (0.0, 0.0, 1.0)),     # finite axes miss by far (the ray of the report)
+                         ((0.0, 0.0, -10.0), (0.0, 0.0, 1.0)),      # ... cross the row
+                         ((-10.5, 1.0, -10.0), (0.0, 0.0, 1.0)),    # ... graze the top of the first sphere's box
+                         ((-10.5, 1.0 + 1e-6, -10.0), (0.0, 0.0, 1.0)),
+                         ((0.0, 30.0, 0.0), (0.0, -1.0, 0.0)),
+                         ((-20.0, 0.5, 0.2), (1.0, 0.0, 0.0)),      # along the row
+                         ((-20.0, 5.0, 0.2), (1.0, 0.0, 0.0)),
+                         ((3.0, 4.0, -6.0), (-0.3, -0.5, 0.8))):
+                d = list(d)
+                d[k] = bad
+                rays.append(list(o) + d)
+    rays += [[0.0, 30.0, -10.0, math.nan, math.nan, 1.0], [0.0, 0.0, -10.0, math.nan, math.nan, math.nan], [0.0, 30.0, -10.0, 0.0, math.nan, -1.0],
+             [math.nan, 0.0, -10.0, 0.0, 0.0, 1.0], [0.0, 30.0, math.nan, 0.0, 0.0, 1.0]]
+    rays += [[0.0, 0.0, -10.0, 0.0, 0.0, 1.0], [0.0, 30.0, -10.0, 0.0, 0.0, 1.0], [-20.0, 0.5, 0.2, 1.0, 0.0, 0.0]]
+    return np.array(rays)

@@ -6,6 +6,7 @@
 #include "shim/hip/hip_runtime.h"
 
 #include "../../raytracer_challenge_amd/csrc/rtc_kernels.hip"
+#include "../../raytracer_challenge_amd/csrc/cull_probe.h"
 
 #include <algorithm>
 #include <chrono>
@@ -93,6 +94,16 @@ extern "C" {
 int rtc_emu_group_box_hit(const double* box6, const double* ray6) {
   Ray r{ray6[0], ray6[1], ray6[2], ray6[3], ray6[4], ray6[5]};
   return group_box_hit(box6, r) ? 1 : 0;
+}
+
+// rtc.h rtc_cull_probe_raw: the host loop over the functions the probe kernel calls (the scene is not needed here)
+int rtc_cull_probe_raw(rtc_scene*, int32_t kind, const double* records, uint64_t n, uint8_t* answers) {
+  const int stride = cull_probe_doubles(kind);
+  if (stride == 0) return efail(RTC_ERR_INVALID, "cull probe: no such predicate");
+  if (n == 0) return RTC_OK;
+  if (!records || !answers) return efail(RTC_ERR_INVALID, "NULL argument");
+  for (uint64_t i = 0; i < n; i++) answers[i] = cull_probe_eval(kind, records + i * (uint64_t)stride);
+  return RTC_OK;
 }
 
 const char* rtc_last_error(void) { return g_err.c_str(); }
