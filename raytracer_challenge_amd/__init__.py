@@ -4,6 +4,7 @@ Layout:
   scene.py    host mirror of the reference's scene API (Matrix, Material, Pattern, Element, World, Camera ...)
   texture.py  texture mapping (the book's bonus chapter): Texture, UvPattern, the PPM reader
   scenes.py   the reference's scene programs + the BASELINE synthetic scenes, as data
+  cabi.py     include/rtc.h and include/rtw.h as ctypes sees them: every struct and every signature, declared once
   backend.py  ctypes binding of include/rtw.h
   image.py    Image::par_render / read / ppm on the HIP backend
   csrc/       hand-written HIP kernels (gfx950) + the C ABI (include/rtc.h, include/rtw.h) -> librtc_amd.so

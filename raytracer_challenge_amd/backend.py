@@ -14,59 +14,12 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 
 from .scene import (BACKGROUND_PROJECTIONS, BUMP_KINDS, FUEL, GEOMETRY, GROUP_KINDS, JITTER_KINDS, MIXTURE_KINDS, Adaptive, AreaLight, Camera, Cone, Element, FILTER_KINDS, Filter, Material, Pattern, SHUTTER_MAX_POSES, Sampling, Shutter, World)
+from .cabi import HIT_DTYPE, AdaptiveC, CameraC, FilterC, MaterialC as _MaterialC, SamplingC, ShutterC, UvFaceC as _UvFaceC, RtcCameraC, bind  # noqa: F401
 from .texture import UV_MAPS, Texture
-
-HIT_DTYPE = np.dtype([("t", "<f8"), ("prim", "<i4"), ("push_idx", "<i4")])
 
 
 class RtwError(RuntimeError):
     pass
-
-
-class _MaterialC(C.Structure):
-    _fields_ = [("ambient", C.c_double), ("diffuse", C.c_double), ("specular", C.c_double), ("shininess", C.c_double),
-                ("reflective", C.c_double), ("transparency", C.c_double), ("refractive_index", C.c_double),
-                ("pattern", C.c_void_p)]
-
-
-class _UvFaceC(C.Structure):  # include/rtw.h rtw_uv_pattern
-    _fields_ = [("kind", C.c_int), ("width", C.c_double), ("height", C.c_double), ("texture", C.c_void_p), ("child", C.c_void_p * 5)]
-
-
-class CameraC(C.Structure):
-    _fields_ = [("hsize", C.c_uint64), ("vsize", C.c_uint64), ("field_of_view", C.c_double), ("transform", C.c_double * 16)]
-
-
-class SamplingC(C.Structure):  # include/rtc.h rtc_sampling
-    _fields_ = [("side", C.c_uint32), ("flags", C.c_uint32), ("seed", C.c_uint64), ("lens_radius", C.c_double), ("focal_distance", C.c_double)]
-
-    @staticmethod
-    def of(s: Sampling) -> "SamplingC":
-        return SamplingC(int(s.side), 1 if s.jitter else 0, int(s.seed), float(s.lens_radius), float(s.focal_distance))
-
-
-class AdaptiveC(C.Structure):  # include/rtc.h rtc_adaptive
-    _fields_ = [("base", SamplingC), ("fine", SamplingC), ("threshold", C.c_double), ("neighbours", C.c_uint32), ("_pad", C.c_uint32)]
-
-    @staticmethod
-    def of(a: Adaptive) -> "AdaptiveC":
-        return AdaptiveC(SamplingC.of(a.base), SamplingC.of(a.fine), float(a.threshold), int(a.neighbours), 0)
-
-
-class FilterC(C.Structure):  # include/rtc.h rtc_filter
-    _fields_ = [("kind", C.c_int32), ("_pad", C.c_uint32), ("radius", C.c_double), ("alpha", C.c_double)]
-
-    @staticmethod
-    def of(f: Filter) -> "FilterC":
-        return FilterC(FILTER_KINDS.index(f.kind), 0, float(f.radius), float(f.alpha))
-
-
-class ShutterC(C.Structure):  # include/rtc.h rtc_shutter
-    _fields_ = [("flags", C.c_uint32), ("_pad", C.c_uint32)]
-
-    @staticmethod
-    def of(s: Shutter) -> "ShutterC":
-        return ShutterC(1 if s.hashed else 0, 0)
 
 
 RTW_SYMBOLS = [
@@ -88,11 +41,11 @@ class NativeWorld:
 
     @property
     def primitive_count(self) -> int:
-        return int(self.backend.lib.rtw_world_primitive_count(self.handle))
+        return int(self.backend._lib.rtw_world_primitive_count(self.handle))
 
     def close(self):
         if self.handle:
-            self.backend.lib.rtw_world_release(self.handle)
+            self.backend._lib.rtw_world_release(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -107,66 +60,24 @@ class Backend:
         if not os.path.exists(lib_path):
             raise RtwError("native library not found: %s (run `python -c 'import __graft_entry__ as g; g.build()'`)" % lib_path)
         self.path = lib_path
-        self.lib = lib = C.CDLL(lib_path)
-        vp, d, i, u64, sz = C.c_void_p, C.c_double, C.c_int, C.c_uint64, C.c_size_t
-        dp = C.POINTER(C.c_double)
-        sig = {
-            "rtw_last_error": (C.c_char_p, []),
-            "rtw_backend": (C.c_char_p, []),
-            "rtw_pattern_debug": (vp, []),
-            "rtw_pattern_plain": (vp, [d, d, d]),
-            "rtw_pattern_jitter": (vp, [i, i, d, u64, vp]),
-            "rtw_pattern_mixture": (vp, [i, dp, vp, vp]),
-            "rtw_pattern_release": (None, [vp]),
-            "rtw_shape": (vp, [i, dp, C.POINTER(_MaterialC), i, dp, sz]),
-            "rtw_composite": (vp, [dp, C.POINTER(_MaterialC), i, C.POINTER(vp), sz]),
-            "rtw_parse_obj": (vp, [C.c_char_p, dp, C.POINTER(_MaterialC), C.POINTER(u64), C.POINTER(u64)]),
-            "rtw_element_release": (None, [vp]),
-            "rtw_world_create": (vp, []),
-            "rtw_world_add_light": (i, [vp, dp, dp]),
-            "rtw_world_add_element": (i, [vp, vp]),
-            "rtw_world_primitive_count": (u64, [vp]),
-            "rtw_world_release": (None, [vp]),
-            "rtw_render": (i, [vp, C.POINTER(CameraC), i, vp, u64, vp, vp]),
-            "rtw_color_at": (i, [vp, vp, u64, i, vp, vp]),
-        }
-        for name, (res, args) in sig.items():
-            fn = getattr(lib, name)  # AttributeError = missing export: fail loudly
-            fn.restype, fn.argtypes = res, args
+        # two handles on the one loaded library, each with its own function objects.  `lib` is for callers of the raw entry points
+        # (tests, probes, bench.py): whatever they assign to its argtypes afterwards cannot reach the package's own calls, which
+        # go through `_lib` and rely on the table's types.
+        self.lib = bind(C.CDLL(lib_path))
+        self._lib = lib = bind(C.CDLL(lib_path))
+        for name in RTW_SYMBOLS:
+            getattr(lib, name)  # AttributeError = missing export: fail loudly
         self.name = lib.rtw_backend().decode()
-        # area lights: the product library's extension of rtw.h (the oracle restates the reference, which has none)
+        # the product library's extensions of rtw.h (the oracle restates the reference, which has none)
         self.has_area_lights = hasattr(lib, "rtw_world_add_area_light")
-        if self.has_area_lights:
-            lib.rtw_world_add_area_light.restype = i
-            lib.rtw_world_add_area_light.argtypes = [vp, dp, dp, dp, C.c_uint32, dp, C.c_uint32, i]
-        # light cones: the same
         self.has_light_cones = hasattr(lib, "rtw_world_set_light_cone")
-        if self.has_light_cones:
-            lib.rtw_world_set_light_cone.restype = i
-            lib.rtw_world_set_light_cone.argtypes = [vp, C.c_uint32, dp, d, d]
-        # a background: the same
         self.has_background = hasattr(lib, "rtw_world_set_background")
-        if self.has_background:
-            lib.rtw_world_set_background.restype = i
-            lib.rtw_world_set_background.argtypes = [vp, vp, C.c_int32]
-        # bumps (normal perturbation): the same
         self.has_bump = hasattr(lib, "rtw_element_set_bump")
-        if self.has_bump:
-            lib.rtw_element_set_bump.restype = i
-            lib.rtw_element_set_bump.argtypes = [vp, C.c_int32, C.c_uint32, d, d]
-        # texture-mapped patterns: the same (the oracle has none)
         self.has_texture_map = hasattr(lib, "rtw_pattern_uv")
-        if self.has_texture_map:
-            lib.rtw_texture_create.restype = vp
-            lib.rtw_texture_create.argtypes = [C.c_uint32, C.c_uint32, dp]
-            lib.rtw_texture_release.restype = None
-            lib.rtw_texture_release.argtypes = [vp]
-            lib.rtw_pattern_uv.restype = vp
-            lib.rtw_pattern_uv.argtypes = [i, dp, C.POINTER(_UvFaceC), sz]
 
     # ---- errors
     def _err(self) -> str:
-        return (self.lib.rtw_last_error() or b"").decode()
+        return (self._lib.rtw_last_error() or b"").decode()
 
     def _check_ptr(self, p, what):
         if not p:
@@ -182,7 +93,7 @@ class Backend:
         key = id(p)
         if key in cache:
             return cache[key]
-        lib = self.lib
+        lib = self._lib
         if p.tag == "debug":
             h = lib.rtw_pattern_debug()
         elif p.tag == "plain":
@@ -214,7 +125,7 @@ class Backend:
         key = ("texture", id(t))
         if key not in cache:
             rgb = np.ascontiguousarray(t.rgb, dtype=np.float64)
-            h = self._check_ptr(self.lib.rtw_texture_create(t.width, t.height, rgb.ctypes.data_as(C.POINTER(C.c_double))), "texture")
+            h = self._check_ptr(self._lib.rtw_texture_create(t.width, t.height, rgb.ctypes.data), "texture")
             cache[key] = h
             owned.append(("texture", h))
         return cache[key]
@@ -229,16 +140,16 @@ class Backend:
         if b is None:
             return h
         if not self.has_bump:
-            self.lib.rtw_element_release(h)
+            self._lib.rtw_element_release(h)
             raise RtwError("a bump needs librtc_amd.so (backend %r has no rtw_element_set_bump)" % self.name)
-        if self.lib.rtw_element_set_bump(h, BUMP_KINDS.index(b.kind), int(b.octaves), float(b.amplitude), float(b.frequency)) != 0:
+        if self._lib.rtw_element_set_bump(h, BUMP_KINDS.index(b.kind), int(b.octaves), float(b.amplitude), float(b.frequency)) != 0:
             msg = self._err()
-            self.lib.rtw_element_release(h)
+            self._lib.rtw_element_release(h)
             raise RtwError("set_bump failed: %s" % msg)
         return h
 
     def _element(self, e: Element, cache, owned) -> int:
-        lib = self.lib
+        lib = self._lib
         if e.tag == "shape":
             mat = self._material(e.args.material, cache, owned)
             params = (C.c_double * max(1, len(e.params)))(*e.params)
@@ -258,7 +169,7 @@ class Backend:
         raise RtwError("unknown element tag %r" % (e.tag,))
 
     def build_world(self, world: World) -> NativeWorld:
-        lib = self.lib
+        lib = self._lib
         w = self._check_ptr(lib.rtw_world_create(), "world_create")
         cache: Dict[int, int] = {}
         owned: list = []
@@ -309,133 +220,87 @@ class Backend:
     def render(self, nw: NativeWorld, camera: Camera, fuel: int = FUEL, pixel_indices: Optional[np.ndarray] = None, want_hits: bool = True):
         """Image::par_render over all pixels (row-major) or the listed pixel indices.  Returns (rgb[n,3], hits[n])."""
         cam = self.camera_c(camera)
-        if pixel_indices is None:
-            n, idx_p = camera.hsize * camera.vsize, None
-        else:
-            pixel_indices = np.ascontiguousarray(pixel_indices, dtype=np.uint64)
-            n, idx_p = pixel_indices.size, pixel_indices.ctypes.data
+        n, idx_p, _keep = self._pixels(pixel_indices, camera.hsize * camera.vsize)
         rgb = np.empty((n, 3), dtype=np.float64)
         hits = np.empty(n, dtype=HIT_DTYPE) if want_hits else None
-        self._check(self.lib.rtw_render(nw.handle, C.byref(cam), int(fuel), idx_p, n, rgb.ctypes.data, hits.ctypes.data if want_hits else None), "render")
+        self._check(self._lib.rtw_render(nw.handle, cam, int(fuel), idx_p, n, rgb.ctypes.data, hits.ctypes.data if want_hits else None), "render")
         return rgb, hits
+
+    @staticmethod
+    def _pixels(pixel_indices: Optional[np.ndarray], n_all):
+        """(n, address or None, the array that owns the address) of a pixel list; None lists every pixel."""
+        if pixel_indices is None:
+            return n_all, None, None
+        pixel_indices = np.ascontiguousarray(pixel_indices, dtype=np.uint64)
+        return pixel_indices.size, pixel_indices.ctypes.data, pixel_indices
+
+    def _scene(self, nw: Optional[NativeWorld], device: int):
+        """The world's rtc_scene* on `device` (flattened and uploaded at the first request); None for no world."""
+        if nw is None:
+            return None
+        scene = self._lib.rtw_world_scene(nw.handle, int(device))
+        if not scene:
+            raise RtwError("scene upload failed: %s" % self._err())
+        return scene
+
+    def _need(self, what: str, *symbols: str):
+        """RtwError for a library without `symbols` (the CPU emulator, the oracle); the message names the first."""
+        if not all(hasattr(self._lib, s) for s in symbols):
+            raise RtwError("%s librtc_amd.so (backend %r has no %s)" % (what, self.name, symbols[0]))
+        return self._lib
+
+    def _rtc(self, rc, what):
+        if rc != 0:
+            raise RtwError("%s: %s" % (what, (self._lib.rtc_last_error() or b"").decode()))
+
+    def _rtc_camera(self, camera: Camera, out: Optional[RtcCameraC] = None) -> RtcCameraC:
+        out = RtcCameraC() if out is None else out
+        if self._lib.rtw_make_camera(self.camera_c(camera), out) != 0:
+            raise RtwError("camera: %s" % self._err())
+        return out
 
     def render_digest(self, nw: NativeWorld, camera: Camera, fuel: int = FUEL, pixel_indices: Optional[np.ndarray] = None, device: int = 0) -> np.ndarray:
         """include/rtc.h rtc_render_hit_digest: per pixel, the digest of every closest hit of its ray tree (parity channel)."""
-        lib = self.lib
-        lib.rtw_world_scene.restype = C.c_void_p
-        lib.rtw_world_scene.argtypes = [C.c_void_p, C.c_int]
-        lib.rtw_make_camera.restype = C.c_int
-        lib.rtw_make_camera.argtypes = [C.c_void_p, C.c_void_p]
-        lib.rtc_render_hit_digest.restype = C.c_int
-        lib.rtc_render_hit_digest.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
-        lib.rtc_last_error.restype = C.c_char_p
-        scene = lib.rtw_world_scene(nw.handle, int(device))
-        if not scene:
-            raise RtwError("scene upload failed: %s" % self._err())
-        cc = self.camera_c(camera)
-        rc_cam = (C.c_double * 21)()   # rtc_camera: 2 x u64 + 3 + 16 doubles
-        if lib.rtw_make_camera(C.byref(cc), C.byref(rc_cam)) != 0:
-            raise RtwError("camera: %s" % self._err())
-        if pixel_indices is None:
-            n, idx_p = camera.hsize * camera.vsize, None
-        else:
-            pixel_indices = np.ascontiguousarray(pixel_indices, dtype=np.uint64)
-            n, idx_p = pixel_indices.size, pixel_indices.ctypes.data
+        scene = self._scene(nw, device)
+        n, idx_p, _keep = self._pixels(pixel_indices, camera.hsize * camera.vsize)
         out = np.empty(n, dtype=np.uint64)
-        if lib.rtc_render_hit_digest(scene, C.byref(rc_cam), int(fuel), idx_p, 0, n, out.ctypes.data) != 0:
-            raise RtwError("rtc_render_hit_digest: %s" % (lib.rtc_last_error() or b"").decode())
+        self._rtc(self._lib.rtc_render_hit_digest(scene, self._rtc_camera(camera), int(fuel), idx_p, 0, n, out.ctypes.data), "rtc_render_hit_digest")
         return out
-
-    def _sampled_lib(self):
-        """The rtc_* entry points of the sampled camera, bound; RtwError for a library that has none (the CPU emulator, the oracle)."""
-        lib = self.lib
-        if not (hasattr(lib, "rtc_render_sampled") and hasattr(lib, "rtc_camera_rays")):
-            raise RtwError("sampled cameras need librtc_amd.so (backend %r has no rtc_render_sampled)" % self.name)
-        vp = C.c_void_p
-        lib.rtw_world_scene.restype, lib.rtw_world_scene.argtypes = vp, [vp, C.c_int]
-        lib.rtw_make_camera.restype, lib.rtw_make_camera.argtypes = C.c_int, [vp, vp]
-        lib.rtc_render_sampled.restype = C.c_int
-        lib.rtc_render_sampled.argtypes = [vp, vp, C.POINTER(SamplingC), C.c_int32, vp, C.c_uint64, C.c_uint64, vp, vp]
-        lib.rtc_camera_rays.restype = C.c_int
-        lib.rtc_camera_rays.argtypes = [vp, vp, C.POINTER(SamplingC), vp, C.c_uint64, C.c_uint64, vp]
-        lib.rtc_last_error.restype = C.c_char_p
-        return lib
-
-    def _rtc_camera(self, lib, camera: Camera):
-        cc = self.camera_c(camera)
-        rc_cam = (C.c_double * 21)()   # rtc_camera: 2 x u64 + 3 + 16 doubles
-        if lib.rtw_make_camera(C.byref(cc), C.byref(rc_cam)) != 0:
-            raise RtwError("camera: %s" % self._err())
-        return rc_cam
 
     def render_sampled(self, nw: NativeWorld, camera: Camera, sampling: Sampling, fuel: int = FUEL, pixel_indices: Optional[np.ndarray] = None,
                        device: int = 0) -> np.ndarray:
         """include/rtc.h rtc_render_sampled: every pixel (row-major) or the listed pixel indices as the mean of `sampling`'s rays.
         Returns rgb[n,3]."""
-        lib = self._sampled_lib()
-        scene = lib.rtw_world_scene(nw.handle, int(device))
-        if not scene:
-            raise RtwError("scene upload failed: %s" % self._err())
-        rc_cam, sp = self._rtc_camera(lib, camera), SamplingC.of(sampling)
-        if pixel_indices is None:
-            n, idx_p = camera.hsize * camera.vsize, None
-        else:
-            pixel_indices = np.ascontiguousarray(pixel_indices, dtype=np.uint64)
-            n, idx_p = pixel_indices.size, pixel_indices.ctypes.data
+        lib = self._need("sampled cameras need", "rtc_render_sampled", "rtc_camera_rays")
+        scene = self._scene(nw, device)
+        rc_cam, sp = self._rtc_camera(camera), SamplingC.of(sampling)
+        n, idx_p, _keep = self._pixels(pixel_indices, camera.hsize * camera.vsize)
         rgb = np.empty((n, 3), dtype=np.float64)
-        if lib.rtc_render_sampled(scene, C.byref(rc_cam), C.byref(sp), int(fuel), idx_p, 0, n, rgb.ctypes.data, None) != 0:
-            raise RtwError("rtc_render_sampled: %s" % (lib.rtc_last_error() or b"").decode())
+        self._rtc(lib.rtc_render_sampled(scene, rc_cam, sp, int(fuel), idx_p, 0, n, rgb.ctypes.data, None), "rtc_render_sampled")
         return rgb
 
     def camera_rays(self, camera: Camera, sampling: Sampling, pixel_indices: Optional[np.ndarray] = None, nw: Optional[NativeWorld] = None,
                     device: int = 0) -> np.ndarray:
         """include/rtc.h rtc_camera_rays: the sample rays {o, d} of every pixel or of the listed ones, [n, side*side, 6].  With a world
         they come from the device's generator kernel, without one from the same function evaluated on the host (no GPU needed)."""
-        lib = self._sampled_lib()
-        scene = None
-        if nw is not None:
-            scene = lib.rtw_world_scene(nw.handle, int(device))
-            if not scene:
-                raise RtwError("scene upload failed: %s" % self._err())
-        rc_cam, sp = self._rtc_camera(lib, camera), SamplingC.of(sampling)
-        if pixel_indices is None:
-            n, idx_p = camera.hsize * camera.vsize, None
-        else:
-            pixel_indices = np.ascontiguousarray(pixel_indices, dtype=np.uint64)
-            n, idx_p = pixel_indices.size, pixel_indices.ctypes.data
+        lib = self._need("sampled cameras need", "rtc_render_sampled", "rtc_camera_rays")
+        scene = self._scene(nw, device)
+        rc_cam, sp = self._rtc_camera(camera), SamplingC.of(sampling)
+        n, idx_p, _keep = self._pixels(pixel_indices, camera.hsize * camera.vsize)
         rays = np.empty((n, sampling.samples, 6), dtype=np.float64)
-        if lib.rtc_camera_rays(scene, C.byref(rc_cam), C.byref(sp), idx_p, 0, n, rays.ctypes.data) != 0:
-            raise RtwError("rtc_camera_rays: %s" % (lib.rtc_last_error() or b"").decode())
+        self._rtc(lib.rtc_camera_rays(scene, rc_cam, sp, idx_p, 0, n, rays.ctypes.data), "rtc_camera_rays")
         return rays
-
-    def _adaptive_lib(self):
-        """The rtc_* entry points of adaptive sampling, bound; RtwError for a library that has none (the CPU emulator, the oracle)."""
-        lib = self.lib
-        if not (hasattr(lib, "rtc_render_adaptive") and hasattr(lib, "rtc_contrast_pixels")):
-            raise RtwError("adaptive sampling needs librtc_amd.so (backend %r has no rtc_render_adaptive)" % self.name)
-        vp = C.c_void_p
-        lib.rtw_world_scene.restype, lib.rtw_world_scene.argtypes = vp, [vp, C.c_int]
-        lib.rtw_make_camera.restype, lib.rtw_make_camera.argtypes = C.c_int, [vp, vp]
-        lib.rtc_render_adaptive.restype = C.c_int
-        lib.rtc_render_adaptive.argtypes = [vp, vp, C.POINTER(AdaptiveC), C.c_int32, vp, vp, C.POINTER(C.c_uint64), vp]
-        lib.rtc_contrast_pixels.restype = C.c_int
-        lib.rtc_contrast_pixels.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.c_double, C.c_uint32, vp, C.POINTER(C.c_uint64)]
-        lib.rtc_last_error.restype = C.c_char_p
-        return lib
 
     def render_adaptive(self, nw: NativeWorld, camera: Camera, adaptive: Adaptive, fuel: int = FUEL, want_mask: bool = False, device: int = 0):
         """include/rtc.h rtc_render_adaptive: the whole frame, base pass plus the refined pixels' fine pass.  Returns rgb[n,3] or, with
         want_mask, (rgb[n,3], mask[n] of bool: the refined pixels)."""
-        lib = self._adaptive_lib()
-        scene = lib.rtw_world_scene(nw.handle, int(device))
-        if not scene:
-            raise RtwError("scene upload failed: %s" % self._err())
-        rc_cam, ad = self._rtc_camera(lib, camera), AdaptiveC.of(adaptive)
+        lib = self._need("adaptive sampling needs", "rtc_render_adaptive", "rtc_contrast_pixels")
+        scene = self._scene(nw, device)
+        rc_cam, ad = self._rtc_camera(camera), AdaptiveC.of(adaptive)
         n = camera.hsize * camera.vsize
         rgb = np.empty((n, 3), dtype=np.float64)
         mask = np.zeros(n, dtype=np.uint8) if want_mask else None
-        if lib.rtc_render_adaptive(scene, C.byref(rc_cam), C.byref(ad), int(fuel), rgb.ctypes.data, mask.ctypes.data if want_mask else None, None, None) != 0:
-            raise RtwError("rtc_render_adaptive: %s" % (lib.rtc_last_error() or b"").decode())
+        self._rtc(lib.rtc_render_adaptive(scene, rc_cam, ad, int(fuel), rgb.ctypes.data, mask.ctypes.data if want_mask else None, None, None), "rtc_render_adaptive")
         return (rgb, mask.astype(bool)) if want_mask else rgb
 
     def contrast_pixels(self, frame: np.ndarray, hsize: int, vsize: int, threshold: float, neighbours: int = 4, nw: Optional[NativeWorld] = None,
@@ -443,50 +308,28 @@ class Backend:
         """include/rtc.h rtc_contrast_pixels: the image indices (ascending, uint64) of the pixels of `frame` (hsize*vsize rows of r, g, b)
         that adaptive sampling would refine.  With a world the device kernels flag and compact them, without one the same function
         is evaluated on the host (no GPU needed)."""
-        lib = self._adaptive_lib()
-        scene = None
-        if nw is not None:
-            scene = lib.rtw_world_scene(nw.handle, int(device))
-            if not scene:
-                raise RtwError("scene upload failed: %s" % self._err())
+        lib = self._need("adaptive sampling needs", "rtc_render_adaptive", "rtc_contrast_pixels")
+        scene = self._scene(nw, device)
         frame = np.ascontiguousarray(frame, dtype=np.float64)
         if frame.size != int(hsize) * int(vsize) * 3:
             raise ValueError("frame must hold hsize * vsize * 3 values")
         out = np.empty(max(1, int(hsize) * int(vsize)), dtype=np.uint64)
         n = C.c_uint64(0)
-        if lib.rtc_contrast_pixels(scene, int(hsize), int(vsize), frame.ctypes.data, float(threshold), int(neighbours), out.ctypes.data, C.byref(n)) != 0:
-            raise RtwError("rtc_contrast_pixels: %s" % (lib.rtc_last_error() or b"").decode())
+        self._rtc(lib.rtc_contrast_pixels(scene, int(hsize), int(vsize), frame.ctypes.data, float(threshold), int(neighbours), out.ctypes.data, C.byref(n)),
+                  "rtc_contrast_pixels")
         return out[:n.value].copy()
-
-    def _filter_lib(self):
-        """The rtc_* entry points of the reconstruction filters, bound; RtwError for a library that has none (the CPU emulator, the oracle)."""
-        lib = self.lib
-        if not (hasattr(lib, "rtc_render_filtered") and hasattr(lib, "rtc_filter_frame")):
-            raise RtwError("reconstruction filters need librtc_amd.so (backend %r has no rtc_render_filtered)" % self.name)
-        vp = C.c_void_p
-        lib.rtw_world_scene.restype, lib.rtw_world_scene.argtypes = vp, [vp, C.c_int]
-        lib.rtw_make_camera.restype, lib.rtw_make_camera.argtypes = C.c_int, [vp, vp]
-        lib.rtc_render_filtered.restype = C.c_int
-        lib.rtc_render_filtered.argtypes = [vp, vp, C.POINTER(SamplingC), C.POINTER(FilterC), C.c_int32, C.c_uint32, C.c_uint32, vp, vp]
-        lib.rtc_filter_frame.restype = C.c_int
-        lib.rtc_filter_frame.argtypes = [vp, C.c_uint64, C.c_uint64, C.POINTER(SamplingC), C.POINTER(FilterC), vp, vp]
-        lib.rtc_last_error.restype = C.c_char_p
-        return lib
 
     def render_filtered(self, nw: NativeWorld, camera: Camera, sampling: Sampling, filter: Filter, fuel: int = FUEL, row_first: int = 0,
                         n_rows: Optional[int] = None, device: int = 0) -> np.ndarray:
         """include/rtc.h rtc_render_filtered: the rows row_first .. row_first + n_rows - 1 (default: to the last row) of the frame, every
         pixel the `filter`-weighted mean of `sampling`'s samples around it -- neighbours outside the row range included.  Returns rgb[n,3]."""
-        lib = self._filter_lib()
-        scene = lib.rtw_world_scene(nw.handle, int(device))
-        if not scene:
-            raise RtwError("scene upload failed: %s" % self._err())
-        rc_cam, sp, fl = self._rtc_camera(lib, camera), SamplingC.of(sampling), FilterC.of(filter)
+        lib = self._need("reconstruction filters need", "rtc_render_filtered", "rtc_filter_frame")
+        scene = self._scene(nw, device)
+        rc_cam, sp, fl = self._rtc_camera(camera), SamplingC.of(sampling), FilterC.of(filter)
         if n_rows is None:
             n_rows = camera.vsize - int(row_first)
         rgb = np.empty((max(0, int(n_rows)) * camera.hsize, 3), dtype=np.float64)
-        if lib.rtc_render_filtered(scene, C.byref(rc_cam), C.byref(sp), C.byref(fl), int(fuel), int(row_first), int(n_rows), rgb.ctypes.data, None) != 0:
-            raise RtwError("rtc_render_filtered: %s" % (lib.rtc_last_error() or b"").decode())
+        self._rtc(lib.rtc_render_filtered(scene, rc_cam, sp, fl, int(fuel), int(row_first), int(n_rows), rgb.ctypes.data, None), "rtc_render_filtered")
         return rgb
 
     def filter_frame(self, samples: np.ndarray, hsize: int, vsize: int, sampling: Sampling, filter: Filter, nw: Optional[NativeWorld] = None,
@@ -494,35 +337,15 @@ class Backend:
         """include/rtc.h rtc_filter_frame: the filter step alone over `samples` (hsize*vsize*side*side rows of r, g, b: pixel-major, k
         inner).  With a world the device kernel filters them, without one the same function is evaluated on the host (no GPU needed).
         Returns rgb[hsize*vsize,3]."""
-        lib = self._filter_lib()
-        scene = None
-        if nw is not None:
-            scene = lib.rtw_world_scene(nw.handle, int(device))
-            if not scene:
-                raise RtwError("scene upload failed: %s" % self._err())
+        lib = self._need("reconstruction filters need", "rtc_render_filtered", "rtc_filter_frame")
+        scene = self._scene(nw, device)
         samples = np.ascontiguousarray(samples, dtype=np.float64)
         if samples.size != int(hsize) * int(vsize) * sampling.samples * 3:
             raise ValueError("samples must hold hsize * vsize * side * side * 3 values")
         sp, fl = SamplingC.of(sampling), FilterC.of(filter)
         rgb = np.empty((int(hsize) * int(vsize), 3), dtype=np.float64)
-        if lib.rtc_filter_frame(scene, int(hsize), int(vsize), C.byref(sp), C.byref(fl), samples.ctypes.data, rgb.ctypes.data) != 0:
-            raise RtwError("rtc_filter_frame: %s" % (lib.rtc_last_error() or b"").decode())
+        self._rtc(lib.rtc_filter_frame(scene, int(hsize), int(vsize), sp, fl, samples.ctypes.data, rgb.ctypes.data), "rtc_filter_frame")
         return rgb
-
-    def _shutter_lib(self):
-        """The rtc_* entry points of the shutter, bound; RtwError for a library that has none (the CPU emulator, the oracle)."""
-        lib = self.lib
-        if not (hasattr(lib, "rtc_render_shutter") and hasattr(lib, "rtc_shutter_deal")):
-            raise RtwError("a shutter needs librtc_amd.so (backend %r has no rtc_render_shutter)" % self.name)
-        vp = C.c_void_p
-        lib.rtw_world_scene.restype, lib.rtw_world_scene.argtypes = vp, [vp, C.c_int]
-        lib.rtw_make_camera.restype, lib.rtw_make_camera.argtypes = C.c_int, [vp, vp]
-        lib.rtc_render_shutter.restype = C.c_int
-        lib.rtc_render_shutter.argtypes = [vp, vp, C.c_uint32, C.POINTER(ShutterC), C.POINTER(SamplingC), C.c_int32, vp, C.c_uint64, C.c_uint64, vp, vp]
-        lib.rtc_shutter_deal.restype = C.c_int
-        lib.rtc_shutter_deal.argtypes = [vp, C.c_uint64, C.c_uint32, C.POINTER(ShutterC), C.POINTER(SamplingC), vp, C.c_uint64, C.c_uint64, vp, vp]
-        lib.rtc_last_error.restype = C.c_char_p
-        return lib
 
     def render_shutter(self, nws: Sequence[NativeWorld], cameras: Sequence[Camera], sampling: Sampling, shutter: Shutter, fuel: int = FUEL,
                        pixel_indices: Optional[np.ndarray] = None, stats=None, device: int = 0) -> np.ndarray:
@@ -535,27 +358,16 @@ class Backend:
             raise ValueError("render_shutter: 1 to %d poses" % SHUTTER_MAX_POSES)
         if any((c.hsize, c.vsize) != (cameras[0].hsize, cameras[0].vsize) for c in cameras):
             raise ValueError("render_shutter: the cameras' hsize or vsize differ")
-        lib = self._shutter_lib()
+        lib = self._need("a shutter needs", "rtc_render_shutter", "rtc_shutter_deal")
         K = len(nws)
-        scenes = (C.c_void_p * K)()
-        for p, nw in enumerate(nws):
-            scenes[p] = lib.rtw_world_scene(nw.handle, int(device))
-            if not scenes[p]:
-                raise RtwError("scene upload failed: %s" % self._err())
-        cams = ((C.c_double * 21) * K)()   # rtc_camera: 2 x u64 + 3 + 16 doubles
+        scenes = (C.c_void_p * K)(*[self._scene(nw, device) for nw in nws])
+        cams = (RtcCameraC * K)()
         for p, cam in enumerate(cameras):
-            cc = self.camera_c(cam)
-            if lib.rtw_make_camera(C.byref(cc), C.byref(cams[p])) != 0:
-                raise RtwError("camera: %s" % self._err())
+            self._rtc_camera(cam, cams[p])
         sp, sh = SamplingC.of(sampling), ShutterC.of(shutter)
-        if pixel_indices is None:
-            n, idx_p = cameras[0].hsize * cameras[0].vsize, None
-        else:
-            pixel_indices = np.ascontiguousarray(pixel_indices, dtype=np.uint64)
-            n, idx_p = pixel_indices.size, pixel_indices.ctypes.data
+        n, idx_p, _keep = self._pixels(pixel_indices, cameras[0].hsize * cameras[0].vsize)
         rgb = np.empty((n, 3), dtype=np.float64)
-        if lib.rtc_render_shutter(scenes, cams, K, C.byref(sh), C.byref(sp), int(fuel), idx_p, 0, n, rgb.ctypes.data, None if stats is None else C.addressof(stats)) != 0:
-            raise RtwError("rtc_render_shutter: %s" % (lib.rtc_last_error() or b"").decode())
+        self._rtc(lib.rtc_render_shutter(scenes, cams, K, sh, sp, int(fuel), idx_p, 0, n, rgb.ctypes.data, stats), "rtc_render_shutter")
         return rgb
 
     def shutter_deal(self, hsize: int, n_poses: int, sampling: Sampling, shutter: Shutter, pixel_indices: Optional[np.ndarray] = None, first: int = 0,
@@ -563,73 +375,42 @@ class Backend:
         """include/rtc.h rtc_shutter_deal: the dealing alone for the pixels first .. first + n - 1 or the listed ones of a frame `hsize`
         wide.  Returns (order[n * side * side] of uint32: the sample ids pose-major, offsets[n_poses + 1] of uint64: the runs' starts).
         With a world the device kernels deal, without one the same rule is evaluated on the host (no GPU needed)."""
-        lib = self._shutter_lib()
-        scene = None
-        if nw is not None:
-            scene = lib.rtw_world_scene(nw.handle, int(device))
-            if not scene:
-                raise RtwError("scene upload failed: %s" % self._err())
-        if pixel_indices is None:
-            if n is None:
-                raise ValueError("shutter_deal: give pixel_indices or n")
-            idx_p = None
-        else:
-            pixel_indices = np.ascontiguousarray(pixel_indices, dtype=np.uint64)
-            n, idx_p = pixel_indices.size, pixel_indices.ctypes.data
+        lib = self._need("a shutter needs", "rtc_render_shutter", "rtc_shutter_deal")
+        scene = self._scene(nw, device)
+        if pixel_indices is None and n is None:
+            raise ValueError("shutter_deal: give pixel_indices or n")
+        n, idx_p, _keep = self._pixels(pixel_indices, n)
         sp, sh = SamplingC.of(sampling), ShutterC.of(shutter)
         order = np.empty(int(n) * sampling.samples, dtype=np.uint32)
         offsets = np.empty(max(0, int(n_poses)) + 1, dtype=np.uint64)
-        if lib.rtc_shutter_deal(scene, int(hsize), int(n_poses), C.byref(sh), C.byref(sp), idx_p, int(first), int(n), order.ctypes.data, offsets.ctypes.data) != 0:
-            raise RtwError("rtc_shutter_deal: %s" % (lib.rtc_last_error() or b"").decode())
+        self._rtc(lib.rtc_shutter_deal(scene, int(hsize), int(n_poses), sh, sp, idx_p, int(first), int(n), order.ctypes.data, offsets.ctypes.data), "rtc_shutter_deal")
         return order, offsets
 
     def scan_raw(self, values: np.ndarray, nw: Optional[NativeWorld] = None, device: int = 0):
         """include/rtc.h rtc_scan_raw (test infrastructure): (the exclusive prefix sums of `values` as a new uint64 array, their total),
         sums modulo 2^64.  With a world the device's scan kernels form them, without one a plain loop on the host (no GPU needed)."""
-        lib = self.lib
-        if not hasattr(lib, "rtc_scan_raw"):
-            raise RtwError("the scan hook needs librtc_amd.so (backend %r has no rtc_scan_raw)" % self.name)
-        vp = C.c_void_p
-        lib.rtw_world_scene.restype, lib.rtw_world_scene.argtypes = vp, [vp, C.c_int]
-        lib.rtc_scan_raw.restype = C.c_int
-        lib.rtc_scan_raw.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
-        lib.rtc_last_error.restype = C.c_char_p
-        scene = None
-        if nw is not None:
-            scene = lib.rtw_world_scene(nw.handle, int(device))
-            if not scene:
-                raise RtwError("scene upload failed: %s" % self._err())
+        lib = self._need("the scan hook needs", "rtc_scan_raw")
+        scene = self._scene(nw, device)
         out = np.array(values, dtype=np.uint64, order="C", copy=True).reshape(-1)
         total = C.c_uint64(0)
-        if lib.rtc_scan_raw(scene, out.ctypes.data if out.size else None, out.size, C.byref(total)) != 0:
-            raise RtwError("rtc_scan_raw: %s" % (lib.rtc_last_error() or b"").decode())
+        self._rtc(lib.rtc_scan_raw(scene, out.ctypes.data if out.size else None, out.size, C.byref(total)), "rtc_scan_raw")
         return out, int(total.value)
 
     def cull_probe(self, kind: int, records: np.ndarray, nw: Optional[NativeWorld] = None, device: int = 0) -> np.ndarray:
         """include/rtc.h rtc_cull_probe_raw (test infrastructure): one culling predicate of the ray kernels on `records` (one row of
         doubles each, the layout of RTC_CULL_* `kind`); returns one bool per record.  librtc_amd.so runs the probe kernel on the world's
         device and needs a world; the CPU emulator evaluates the same functions on the host and needs none."""
-        lib = self.lib
+        lib = self._lib
         if not hasattr(lib, "rtc_cull_probe_raw"):
             raise RtwError("backend %r has no rtc_cull_probe_raw" % self.name)
-        vp = C.c_void_p
-        lib.rtw_world_scene.restype, lib.rtw_world_scene.argtypes = vp, [vp, C.c_int]
-        lib.rtc_cull_probe_raw.restype = C.c_int
-        lib.rtc_cull_probe_raw.argtypes = [vp, C.c_int32, vp, C.c_uint64, vp]
-        lib.rtc_last_error.restype = C.c_char_p
-        scene = None
-        if nw is not None:
-            scene = lib.rtw_world_scene(nw.handle, int(device))
-            if not scene:
-                raise RtwError("scene upload failed: %s" % self._err())
+        scene = self._scene(nw, device)
         rec = np.ascontiguousarray(records, dtype=np.float64)
         width = {0: 18, 1: 17, 2: 12, 3: 3, 4: 9}.get(int(kind))
         if rec.ndim != 2 or rec.shape[1] != width:
             raise ValueError("cull_probe: kind %r takes rows of %r doubles, got an array of shape %r" % (kind, width, rec.shape))
         n = rec.shape[0]
         out = np.zeros(n, dtype=np.uint8)
-        if lib.rtc_cull_probe_raw(scene, int(kind), rec.ctypes.data if n else None, n, out.ctypes.data if n else None) != 0:
-            raise RtwError("rtc_cull_probe_raw: %s" % (lib.rtc_last_error() or b"").decode())
+        self._rtc(lib.rtc_cull_probe_raw(scene, int(kind), rec.ctypes.data if n else None, n, out.ctypes.data if n else None), "rtc_cull_probe_raw")
         return out.astype(bool)
 
     def color_at(self, nw: NativeWorld, rays: np.ndarray, fuel: int = FUEL):
@@ -638,5 +419,5 @@ class Backend:
         n = rays.shape[0]
         rgb = np.empty((n, 3), dtype=np.float64)
         hits = np.empty(n, dtype=HIT_DTYPE)
-        self._check(self.lib.rtw_color_at(nw.handle, rays.ctypes.data, n, int(fuel), rgb.ctypes.data, hits.ctypes.data), "color_at")
+        self._check(self._lib.rtw_color_at(nw.handle, rays.ctypes.data, n, int(fuel), rgb.ctypes.data, hits.ctypes.data), "color_at")
         return rgb, hits

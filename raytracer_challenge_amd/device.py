@@ -7,29 +7,9 @@ from __future__ import annotations
 
 import ctypes as C
 
-from .backend import Backend, CameraC, NativeWorld, RtwError, SamplingC
+from .backend import Backend, NativeWorld, RtwError
+from .cabi import RtcCameraC, RtcStatsC, SamplingC  # noqa: F401
 from .scene import Camera, Sampling
-
-
-class RtcCameraC(C.Structure):
-    _fields_ = [("hsize", C.c_uint64), ("vsize", C.c_uint64), ("half_width", C.c_double), ("half_height", C.c_double),
-                ("pixel_size", C.c_double), ("transform_inv", C.c_double * 16)]
-
-
-class RtcStatsC(C.Structure):
-    _COUNTERS = ("pixels", "rays_primary", "rays_shadow", "rays_reflect", "rays_refract", "rays_container",
-                 "accel_nodes", "group_tests", "tri_tests", "analytic_tests", "nan_ts")
-    _fields_ = [(n, C.c_uint64) for n in _COUNTERS] + \
-               [("kernel_ms", C.c_double), ("n_launches", C.c_uint32), ("_pad", C.c_uint32),
-                ("accel_nodes_kernarg", C.c_uint64), ("analytic_tests_kernarg", C.c_uint64), ("light_grid_cells", C.c_uint64),
-                ("group_tests_uniform", C.c_uint64)]
-
-    def as_dict(self):
-        d = {n: int(getattr(self, n)) for n in self._COUNTERS + ("accel_nodes_kernarg", "analytic_tests_kernarg", "light_grid_cells", "group_tests_uniform")}
-        d["kernel_ms"] = float(self.kernel_ms)
-        d["n_launches"] = int(self.n_launches)
-        d["unique_rays"] = d["rays_primary"] + d["rays_shadow"] + d["rays_reflect"] + d["rays_refract"]
-        return d
 
 
 # Algorithmic bytes per unit of work (with the record sizes this build really uses).  Only
@@ -88,52 +68,18 @@ class DeviceRenderer:
         self._cpu_standin = bool(_cpu_standin) and backend.name == "hip-emu-cpu"
         if backend.name != "hip" and not self._cpu_standin:
             raise RtwError("DeviceRenderer needs the HIP backend, got %r" % backend.name)
-        lib = backend.lib
-        lib.rtw_world_scene.restype = C.c_void_p
-        lib.rtw_world_scene.argtypes = [C.c_void_p, C.c_int]
-        lib.rtw_make_camera.restype = C.c_int
-        lib.rtw_make_camera.argtypes = [C.POINTER(CameraC), C.POINTER(RtcCameraC)]
-        lib.rtc_render_bands_device.restype = C.c_int
-        lib.rtc_render_bands_device.argtypes = [C.c_void_p, C.POINTER(RtcCameraC), C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
-                                                C.c_void_p, C.POINTER(RtcStatsC), C.c_int, C.c_int]
-        lib.rtc_scene_sync.restype = C.c_int
-        lib.rtc_scene_sync.argtypes = [C.c_void_p]
-        for name in ("rtc_scene_record", "rtc_scene_wait"):
-            getattr(lib, name).restype = C.c_int
-            getattr(lib, name).argtypes = [C.c_void_p, C.c_int]
-        lib.rtc_scene_check.restype = C.c_int
-        lib.rtc_scene_check.argtypes = [C.c_void_p]
-        lib.rtc_scene_elapsed_ms.restype = C.c_int
-        lib.rtc_scene_elapsed_ms.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
-        lib.rtc_last_error.restype = C.c_char_p
-        lib.rtc_scene_device_bytes.restype = C.c_uint64
-        lib.rtc_scene_device_bytes.argtypes = [C.c_void_p]
-        lib.rtc_scene_wavefront_lds_bytes.restype = C.c_uint32
-        lib.rtc_scene_wavefront_lds_bytes.argtypes = [C.c_void_p]
-        lib.rtc_scene_accel_info.restype = None
-        lib.rtc_scene_accel_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint32)] * 4
         self.backend, self.world, self.camera = backend, world, camera
-        self.scene = lib.rtw_world_scene(world.handle, int(device))
-        if not self.scene:
-            raise RtwError("scene upload failed: %s" % backend._err())
-        self.cam = RtcCameraC()
-        cc = backend.camera_c(camera)
-        if lib.rtw_make_camera(C.byref(cc), C.byref(self.cam)) != 0:
-            raise RtwError("camera: %s" % backend._err())
+        self.scene = backend._scene(world, device)
+        self.cam = backend._rtc_camera(camera)
 
     def _bands(self, sampling, fuel, band_rows, row_first, row_step, n_rows, out_tensor, stats, count, sync) -> int:
         """rtc_render_bands_device, or with a Sampling rtc_render_sampled_bands_device."""
-        lib = self.backend.lib
+        lib = self.backend._lib
         tail = (int(fuel), int(band_rows), int(row_first), int(row_step), int(n_rows), C.c_void_p(out_tensor.data_ptr()), stats, 1 if count else 0, 1 if sync else 0)
         if sampling is None:
-            return lib.rtc_render_bands_device(self.scene, C.byref(self.cam), *tail)
-        if not hasattr(lib, "rtc_render_sampled_bands_device"):
-            raise RtwError("sampled cameras need librtc_amd.so (backend %r has no rtc_render_sampled_bands_device)" % self.backend.name)
-        lib.rtc_render_sampled_bands_device.restype = C.c_int
-        lib.rtc_render_sampled_bands_device.argtypes = [C.c_void_p, C.POINTER(RtcCameraC), C.POINTER(SamplingC), C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32,
-                                                        C.c_uint32, C.c_void_p, C.POINTER(RtcStatsC), C.c_int, C.c_int]
-        sp = SamplingC.of(sampling)
-        return lib.rtc_render_sampled_bands_device(self.scene, C.byref(self.cam), C.byref(sp), *tail)
+            return lib.rtc_render_bands_device(self.scene, self.cam, *tail)
+        self.backend._need("sampled cameras need", "rtc_render_sampled_bands_device")
+        return lib.rtc_render_sampled_bands_device(self.scene, self.cam, SamplingC.of(sampling), *tail)
 
     def render_rows(self, fuel: int, row_first: int, row_step: int, n_rows: int, out_tensor, count: bool = False, sync: bool = True,
                     want_stats: bool = True, band_rows: int = 1, sampling: Sampling = None) -> dict:
@@ -146,12 +92,12 @@ class DeviceRenderer:
         st = RtcStatsC()
         rc = self._bands(sampling, fuel, band_rows, row_first, row_step, n_rows, out_tensor, C.byref(st) if want_stats else None, count, sync)
         if rc != 0:
-            raise RtwError("rtc_render_bands_device: %s" % (self.backend.lib.rtc_last_error() or b"").decode())
+            raise RtwError("rtc_render_bands_device: %s" % (self.backend._lib.rtc_last_error() or b"").decode())
         return st.as_dict() if want_stats else {}
 
     def _rc(self, rc, what):
         if rc != 0:
-            raise RtwError("%s: %s" % (what, (self.backend.lib.rtc_last_error() or b"").decode()))
+            raise RtwError("%s: %s" % (what, (self.backend._lib.rtc_last_error() or b"").decode()))
 
     def render_rows_async(self, fuel: int, row_first: int, row_step: int, n_rows: int, out_tensor, band_rows: int = 1, sampling: Sampling = None):
         """Queue a render on the scene's stream and return immediately (errors are reported by check())."""
@@ -161,21 +107,21 @@ class DeviceRenderer:
         self._rc(self._bands(sampling, fuel, band_rows, row_first, row_step, n_rows, out_tensor, None, False, False), "rtc_render_bands_device")
 
     def record(self, slot: int):
-        self._rc(self.backend.lib.rtc_scene_record(self.scene, slot), "rtc_scene_record")
+        self._rc(self.backend._lib.rtc_scene_record(self.scene, slot), "rtc_scene_record")
 
     def wait(self, slot: int):
-        self._rc(self.backend.lib.rtc_scene_wait(self.scene, slot), "rtc_scene_wait")
+        self._rc(self.backend._lib.rtc_scene_wait(self.scene, slot), "rtc_scene_wait")
 
     def elapsed_ms(self, slot_from: int, slot_to: int) -> float:
         ms = C.c_double(0.0)
-        self._rc(self.backend.lib.rtc_scene_elapsed_ms(self.scene, slot_from, slot_to, C.byref(ms)), "rtc_scene_elapsed_ms")
+        self._rc(self.backend._lib.rtc_scene_elapsed_ms(self.scene, slot_from, slot_to, C.byref(ms)), "rtc_scene_elapsed_ms")
         return ms.value
 
     def check(self):
-        self._rc(self.backend.lib.rtc_scene_check(self.scene), "rtc_scene_check")
+        self._rc(self.backend._lib.rtc_scene_check(self.scene), "rtc_scene_check")
 
     def sync(self):
-        self.backend.lib.rtc_scene_sync(self.scene)
+        self.backend._lib.rtc_scene_sync(self.scene)
 
     def tune(self, fuel: int, row_first: int, row_step: int, n_rows: int, out_tensor, band_rows: int = 1) -> dict:
         """Lets the library measure both device paths for this launch shape (four synchronous renders into out_tensor, two
@@ -185,27 +131,21 @@ class DeviceRenderer:
         return self.path_info()
 
     def path_info(self) -> dict:
-        lib = self.backend.lib
-        lib.rtc_scene_path_info.restype = None
-        lib.rtc_scene_path_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         ch, a, b = C.c_int32(0), C.c_double(-1), C.c_double(-1)
-        lib.rtc_scene_path_info(self.scene, C.byref(ch), C.byref(a), C.byref(b))
+        self.backend._lib.rtc_scene_path_info(self.scene, C.byref(ch), C.byref(a), C.byref(b))
         return {"path": {0: "undecided", 1: "one kernel", 4: "wavefront"}.get(ch.value, str(ch.value)),
                 "one_kernel_ms": a.value, "wavefront_ms": b.value}
 
     def wavefront_grid(self, sync: bool) -> dict:
         """include/rtc.h rtc_scene_wavefront_ts_grid: the traversal kernel's grid in a synchronous / an unsynchronised launch made
         now, the device's CUs, the scene's spare CUs (RTC_WF_SPARE_CUS when it was created) and the scenes alive on the device."""
-        lib = self.backend.lib
-        lib.rtc_scene_wavefront_ts_grid.restype = C.c_int
-        lib.rtc_scene_wavefront_ts_grid.argtypes = [C.c_void_p, C.c_int32] + [C.POINTER(C.c_uint32)] * 4
         a = [C.c_uint32(0) for _ in range(4)]
-        self._rc(lib.rtc_scene_wavefront_ts_grid(self.scene, 1 if sync else 0, *[C.byref(x) for x in a]), "rtc_scene_wavefront_ts_grid")
+        self._rc(self.backend._lib.rtc_scene_wavefront_ts_grid(self.scene, 1 if sync else 0, *[C.byref(x) for x in a]), "rtc_scene_wavefront_ts_grid")
         return {"grid": a[0].value, "n_cu": a[1].value, "spare_cus": a[2].value, "live_scenes": a[3].value}
 
     def info(self) -> dict:
         a = [C.c_uint32(0) for _ in range(4)]
-        self.backend.lib.rtc_scene_accel_info(self.scene, *[C.byref(x) for x in a])
-        return {"scene_device_bytes": int(self.backend.lib.rtc_scene_device_bytes(self.scene)), "program_ops": a[0].value,
+        self.backend._lib.rtc_scene_accel_info(self.scene, *[C.byref(x) for x in a])
+        return {"scene_device_bytes": int(self.backend._lib.rtc_scene_device_bytes(self.scene)), "program_ops": a[0].value,
                 "bvh_nodes": a[1].value, "mesh_triangles": a[2].value, "bvh_depth": a[3].value,
-                "wavefront_lds_bytes_per_block": int(self.backend.lib.rtc_scene_wavefront_lds_bytes(self.scene))}
+                "wavefront_lds_bytes_per_block": int(self.backend._lib.rtc_scene_wavefront_lds_bytes(self.scene))}

@@ -11,6 +11,7 @@ from typing import Sequence, Tuple
 
 import numpy as np
 
+from . import cabi
 from .scene import FUEL, Adaptive, Camera, Color, Filter, Sampling, Shutter, World
 
 
@@ -90,23 +91,17 @@ class Image:
             be = hip_backend()
             self._native = (be, be.build_world(_W([], [])))
         be, nw = self._native
-        lib = be.lib
-        lib.rtw_world_scene.restype = C.c_void_p
-        lib.rtw_world_scene.argtypes = [C.c_void_p, C.c_int]
-        scene = lib.rtw_world_scene(nw.handle, 0)
+        scene = be._lib.rtw_world_scene(nw.handle, 0)
         if not scene:
             raise RuntimeError("scene upload failed: %s" % be._err())
-        return lib, scene
+        return be._lib, scene
 
     def quantized(self) -> np.ndarray:
         """Color::clamp of every channel, on the GPU: (vsize*hsize, 3) uint8."""
         lib, scene = self._lib_and_scene()
-        lib.rtc_quantize.restype = C.c_int
-        lib.rtc_quantize.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         src = np.ascontiguousarray(self.pixels, dtype=np.float64)
         out = np.empty(src.shape, dtype=np.uint8)
         if lib.rtc_quantize(scene, src.ctypes.data, src.size, out.ctypes.data) != 0:
-            lib.rtc_last_error.restype = C.c_char_p
             raise RuntimeError("rtc_quantize: %s" % (lib.rtc_last_error() or b"").decode())
         return out
 
@@ -118,9 +113,7 @@ def ppm_text(hsize: int, vsize: int, rgb8: np.ndarray, lib=None) -> str:
     """Image::ppm layout from quantised pixels (host-side formatting in librtc_amd.so; needs no GPU)."""
     if lib is None:
         from . import _LIB
-        lib = C.CDLL(_LIB)
-    lib.rtc_ppm.restype = C.c_uint64
-    lib.rtc_ppm.argtypes = [C.c_uint64, C.c_uint64, C.c_void_p, C.c_char_p, C.c_uint64]
+        lib = cabi.load(_LIB)
     rgb8 = np.ascontiguousarray(rgb8, dtype=np.uint8)
     assert rgb8.size == hsize * vsize * 3
     need = lib.rtc_ppm(hsize, vsize, rgb8.ctypes.data, None, 0)

@@ -70,18 +70,8 @@ def main(k, rounds):
     be = rt.hip_backend()
     lib = be.lib
     vp = C.c_void_p
-    lib.rtw_world_scene.restype, lib.rtw_world_scene.argtypes = vp, [vp, C.c_int]
-    lib.rtw_make_camera.restype, lib.rtw_make_camera.argtypes = C.c_int, [vp, vp]
-    lib.rtc_render.restype, lib.rtc_render.argtypes = C.c_int, [vp, vp, C.c_int32, vp, C.c_uint64, C.c_uint64, vp, vp, vp]
-    lib.rtc_render_sampled.restype, lib.rtc_render_sampled.argtypes = C.c_int, [vp, vp, vp, C.c_int32, vp, C.c_uint64, C.c_uint64, vp, vp]
-    lib.rtc_render_adaptive.restype, lib.rtc_render_adaptive.argtypes = C.c_int, [vp, vp, vp, C.c_int32, vp, vp, C.POINTER(C.c_uint64), C.POINTER(RtcStatsC)]
-    for f in ("rtc_scene_record", "rtc_scene_wait"):
-        getattr(lib, f).restype, getattr(lib, f).argtypes = C.c_int, [vp, C.c_int]
-    lib.rtc_scene_elapsed_ms.restype, lib.rtc_scene_elapsed_ms.argtypes = C.c_int, [vp, C.c_int, C.c_int, C.POINTER(C.c_double)]
-    lib.rtc_last_error.restype = C.c_char_p
 
-    rc_cam = (C.c_double * 21)()
-    assert lib.rtw_make_camera(C.byref(be.camera_c(cam)), rc_cam) == 0
+    rc_cam = be._rtc_camera(cam)
     n = 1920 * 1080
     rgb = np.zeros((n, 3))   # (written once here: every call finds the pages present)
     fine = Sampling(side=4, jitter=True, seed=1)

@@ -63,17 +63,11 @@ def main(rounds, out_path):
     be = rt.hip_backend()
     lib = be.lib
     vp = C.c_void_p
-    lib.rtw_world_scene.restype, lib.rtw_world_scene.argtypes = vp, [vp, C.c_int]
-    lib.rtw_make_camera.restype, lib.rtw_make_camera.argtypes = C.c_int, [vp, vp]
-    lib.rtc_render.restype = C.c_int
-    lib.rtc_render.argtypes = [vp, vp, C.c_int32, vp, C.c_uint64, C.c_uint64, vp, vp, vp]
-    lib.rtc_last_error.restype = C.c_char_p
     n = W * H
     rgb, hits = np.empty((n, 3)), np.empty(n, dtype=HIT_DTYPE)
     scene_of, cams, keep = {}, {}, []
     for config, (cam, frames) in worlds().items():
-        rc = (C.c_double * 21)()
-        assert lib.rtw_make_camera(C.byref(be.camera_c(cam)), rc) == 0
+        rc = be._rtc_camera(cam)
         cams[config] = rc
         for path in ("1", "4"):   # RTC_KERNEL is read when a scene is created
             os.environ["RTC_KERNEL"] = path

@@ -55,13 +55,7 @@ def main(rounds, out_path):
     be = rt.hip_backend()
     lib = be.lib
     vp = C.c_void_p
-    lib.rtw_world_scene.restype, lib.rtw_world_scene.argtypes = vp, [vp, C.c_int]
-    lib.rtw_make_camera.restype, lib.rtw_make_camera.argtypes = C.c_int, [vp, vp]
-    lib.rtc_render_sampled.restype, lib.rtc_render_sampled.argtypes = C.c_int, [vp, vp, vp, C.c_int32, vp, C.c_uint64, C.c_uint64, vp, vp]
-    lib.rtc_render_filtered.restype, lib.rtc_render_filtered.argtypes = C.c_int, [vp, vp, vp, vp, C.c_int32, C.c_uint32, C.c_uint32, vp, vp]
-    lib.rtc_last_error.restype = C.c_char_p
-    rc = (C.c_double * 21)()
-    assert lib.rtw_make_camera(C.byref(be.camera_c(cam)), rc) == 0
+    rc = be._rtc_camera(cam)
     sp = SamplingC.of(Sampling(side=SIDE, jitter=True, seed=1))
     n = W * H
     rgb = np.empty((n, 3))

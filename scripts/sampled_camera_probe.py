@@ -48,24 +48,9 @@ def main(k, rounds):
     be = rt.hip_backend()
     lib = be.lib
     vp = C.c_void_p
-    lib.rtw_world_scene.restype, lib.rtw_world_scene.argtypes = vp, [vp, C.c_int]
-    lib.rtw_make_camera.restype, lib.rtw_make_camera.argtypes = C.c_int, [vp, vp]
-    lib.rtc_render.restype, lib.rtc_render.argtypes = C.c_int, [vp, vp, C.c_int32, vp, C.c_uint64, C.c_uint64, vp, vp, vp]
-    lib.rtc_render_sampled.restype, lib.rtc_render_sampled.argtypes = C.c_int, [vp, vp, vp, C.c_int32, vp, C.c_uint64, C.c_uint64, vp, vp]
-    lib.rtc_render_rows_device.restype = C.c_int
-    lib.rtc_render_rows_device.argtypes = [vp, vp, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.POINTER(RtcStatsC), C.c_int, C.c_int]
-    lib.rtc_render_sampled_bands_device.restype = C.c_int
-    lib.rtc_render_sampled_bands_device.argtypes = [vp, vp, vp, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.POINTER(RtcStatsC), C.c_int, C.c_int]
-    for f in ("rtc_scene_record", "rtc_scene_wait"):
-        getattr(lib, f).restype, getattr(lib, f).argtypes = C.c_int, [vp, C.c_int]
-    lib.rtc_scene_check.restype, lib.rtc_scene_check.argtypes = C.c_int, [vp]
-    lib.rtc_scene_elapsed_ms.restype, lib.rtc_scene_elapsed_ms.argtypes = C.c_int, [vp, C.c_int, C.c_int, C.POINTER(C.c_double)]
-    lib.rtc_scene_path_info.restype, lib.rtc_scene_path_info.argtypes = None, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    lib.rtc_last_error.restype = C.c_char_p
 
     def rtc_camera(c):
-        out = (C.c_double * 21)()
-        assert lib.rtw_make_camera(C.byref(be.camera_c(c)), out) == 0
+        out = be._rtc_camera(c)
         return out
     cams = {s: Camera.new(1920 * s, 1080 * s, cam.field_of_view, cam.transform_matrix) for s in (1, 2, 4)}
     rcs = {s: rtc_camera(c) for s, c in cams.items()}

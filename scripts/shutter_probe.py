@@ -39,18 +39,15 @@ def main(frames, rounds):
     import raytracer_challenge_amd as rt
     from raytracer_challenge_amd import scenes
     from raytracer_challenge_amd.backend import SamplingC, ShutterC
-    from raytracer_challenge_amd.device import RtcStatsC
+    from raytracer_challenge_amd.device import RtcCameraC, RtcStatsC
     from raytracer_challenge_amd.scene import Sampling, Shutter
 
     cam, world = scenes.synthetic_analytic(n_primitives=512, seed=12345, cones=False, grouped=False, hsize=1920, vsize=1080)
     be = rt.hip_backend()
-    lib = be._shutter_lib()
-    be._sampled_lib()
+    lib = be.lib
     vp = C.c_void_p
-    rc_cam = be._rtc_camera(lib, cam)
-    cams = ((C.c_double * 21) * max(POSES))()
-    for p in range(max(POSES)):
-        C.memmove(cams[p], rc_cam, C.sizeof(rc_cam))
+    rc_cam = be._rtc_camera(cam)
+    cams = (RtcCameraC * max(POSES))(*[rc_cam] * max(POSES))
     sp, sh = SamplingC.of(Sampling(side=4, jitter=True, seed=1)), ShutterC.of(Shutter(hashed=True))
     n = 1920 * 1080
     rgb, ref = np.empty((n, 3)), np.empty((n, 3))
@@ -69,7 +66,7 @@ def main(frames, rounds):
     os.environ.pop("RTC_KERNEL", None)
 
     def frame(scene, K, out, stats=None):
-        st = None if stats is None else C.addressof(stats)
+        st = None if stats is None else C.byref(stats)
         if K == 0:
             code = lib.rtc_render_sampled(scene, C.byref(rc_cam), C.byref(sp), 5, None, 0, n, out.ctypes.data, st)
         else:

@@ -78,19 +78,8 @@ def main(k, repeats=1, rows=("plain", "checkers", "textured", "linear")):
     be = rt.hip_backend()
     lib = be.lib
     vp = C.c_void_p
-    lib.rtw_world_scene.restype, lib.rtw_world_scene.argtypes = vp, [vp, C.c_int]
-    lib.rtw_make_camera.restype, lib.rtw_make_camera.argtypes = C.c_int, [vp, vp]
-    lib.rtc_render.restype, lib.rtc_render.argtypes = C.c_int, [vp, vp, C.c_int32, vp, C.c_uint64, C.c_uint64, vp, vp, C.POINTER(RtcStatsC)]
-    lib.rtc_render_rows_device.restype = C.c_int
-    lib.rtc_render_rows_device.argtypes = [vp, vp, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.POINTER(RtcStatsC), C.c_int, C.c_int]
-    for f in ("rtc_scene_record", "rtc_scene_wait"):
-        getattr(lib, f).restype, getattr(lib, f).argtypes = C.c_int, [vp, C.c_int]
-    lib.rtc_scene_elapsed_ms.restype, lib.rtc_scene_elapsed_ms.argtypes = C.c_int, [vp, C.c_int, C.c_int, C.POINTER(C.c_double)]
-    lib.rtc_scene_device_bytes.restype, lib.rtc_scene_device_bytes.argtypes = C.c_uint64, [vp]
-    lib.rtc_last_error.restype = C.c_char_p
     n = cam.hsize * cam.vsize
-    rc_cam = (C.c_double * 21)()
-    assert lib.rtw_make_camera(C.byref(be.camera_c(cam)), rc_cam) == 0
+    rc_cam = be._rtc_camera(cam)
     out = torch.empty(n * 3, dtype=torch.float64, device="cuda:0")
     rgb = np.empty((n, 3))
     results = {}

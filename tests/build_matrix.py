@@ -13,6 +13,7 @@ import os
 
 import numpy as np
 
+from raytracer_challenge_amd.cabi import HIT_DTYPE, RtcCameraC, RtcKernelInfo as KernelInfo, RtcStatsC
 from raytracer_challenge_amd.scene import (AreaLight, Camera, Cone, Color, Element, GroupKind, Material, Matrix, Pattern, PointLight, ShapeArgs, SpotLight, Vector, World)
 
 import cases
@@ -206,36 +207,20 @@ class Facts:
 
 
 # ---- the hook ---------------------------------------------------------------------------------------------------------------------------
-class KernelInfo(C.Structure):  # include/rtc.h rtc_kernel_info
-    _fields_ = ([(n, C.c_int32) for n in ("variant", "n_kops", "n_kplanes", "n_kaux", "has_recs", "all_plain", "no_glass_mirror", "big_scene")] +
-                [("lds_bytes", C.c_uint32)] +
-                [(n, C.c_int32) for n in ("trace_build", "wf_ts_build", "wf_shade_build0", "wf_shade_build", "n_bvh_nodes", "n_recs", "n_mesh_tris", "has_mesh", "bvh_stack", "lds_refused")])
-
-    def reported(self, path):
-        """The same record Facts.predict gives."""
-        out = {"variant": self.variant, "kops": self.n_kops > 0, "lds": self.lds_bytes > 0}
-        if path == 4:
-            assert self.trace_build == -1
-            out.update(wf_ts=WF_TS[self.wf_ts_build], wf_shade0=WF_SHADE[self.wf_shade_build0], wf_shade=WF_SHADE[self.wf_shade_build])
-        else:
-            assert self.wf_ts_build == self.wf_shade_build0 == self.wf_shade_build == -1 and self.lds_bytes == 0
-            out.update(trace=TRACE[self.trace_build])
-        return out
-
-
-def bind(lib):
-    vp = C.c_void_p
-    lib.rtw_world_scene.restype, lib.rtw_world_scene.argtypes = vp, [vp, C.c_int]
-    lib.rtc_scene_kernel_info.restype, lib.rtc_scene_kernel_info.argtypes = C.c_int, [vp, C.c_int32, C.c_int32, C.POINTER(KernelInfo)]
-    lib.rtc_scene_accel_info.restype, lib.rtc_scene_accel_info.argtypes = None, [vp] + [C.POINTER(C.c_uint32)] * 4
-    lib.rtc_scene_device_bytes.restype, lib.rtc_scene_device_bytes.argtypes = C.c_uint64, [vp]
-    lib.rtc_scene_wavefront_lds_bytes.restype, lib.rtc_scene_wavefront_lds_bytes.argtypes = C.c_uint32, [vp]
-    lib.rtc_last_error.restype = C.c_char_p
-    return lib
+def reported(self, path):
+    """The same record Facts.predict gives, from an rtc_kernel_info (`self`)."""
+    out = {"variant": self.variant, "kops": self.n_kops > 0, "lds": self.lds_bytes > 0}
+    if path == 4:
+        assert self.trace_build == -1
+        out.update(wf_ts=WF_TS[self.wf_ts_build], wf_shade0=WF_SHADE[self.wf_shade_build0], wf_shade=WF_SHADE[self.wf_shade_build])
+    else:
+        assert self.wf_ts_build == self.wf_shade_build0 == self.wf_shade_build == -1 and self.lds_bytes == 0
+        out.update(trace=TRACE[self.trace_build])
+    return out
 
 
 def scene_of(backend, nw, device=0):
-    scene = bind(backend.lib).rtw_world_scene(nw.handle, device)
+    scene = backend.lib.rtw_world_scene(nw.handle, device)
     assert scene, backend._err()
     return scene
 
@@ -254,7 +239,7 @@ def n_ops(backend, nw):
 
 def ledger_items(info, path):
     """The (row, kernel, build) triples a launch with this report runs."""
-    r = info.reported(path)
+    r = reported(info, path)
     if path == 1:
         return {(r["variant"], "trace", r["trace"])}
     return {(r["variant"], "wf_ts", r["wf_ts"]), (None, "wf_shade0", r["wf_shade0"]), (None, "wf_shade", r["wf_shade"])}
@@ -568,12 +553,7 @@ def panic_free(orc, world, rays, fuel=FUEL):
 # ---- rendering one entry under every build -------------------------------------------------------------------------------------------
 def render_with_stats(backend, nw, cam, fuel=FUEL):
     """rtc_render with a stats pointer (the counting builds): (rgb, hits)."""
-    from raytracer_challenge_amd.backend import HIT_DTYPE
-    from raytracer_challenge_amd.device import RtcCameraC, RtcStatsC
-    lib = bind(backend.lib)
-    lib.rtw_make_camera.restype, lib.rtw_make_camera.argtypes = C.c_int, [C.c_void_p, C.c_void_p]
-    lib.rtc_render.restype = C.c_int
-    lib.rtc_render.argtypes = [C.c_void_p, C.POINTER(RtcCameraC), C.c_int32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(RtcStatsC)]
+    lib = backend.lib
     cc, rc = backend.camera_c(cam), RtcCameraC()
     assert lib.rtw_make_camera(C.byref(cc), C.byref(rc)) == 0
     n = cam.hsize * cam.vsize
@@ -608,14 +588,14 @@ def check_hook(backend, entry, world, switch, emulator, ledger=None):
     if switch != "default":
         with switched("default", 1):
             nw = backend.build_world(world)
-            base = {(p, c): kernel_info(backend, nw, p, c).reported(p) for p in (1, 4) for c in (False, True)}
+            base = {(p, c): reported(kernel_info(backend, nw, p, c), p) for p in (1, 4) for c in (False, True)}
             nw.close()
     with switched(switch, 1):
         nw = backend.build_world(world)
         for path in (1, 4):
             for count in (False, True):
                 info = kernel_info(backend, nw, path, count)
-                got, want = info.reported(path), entry.facts.predict(switch, path, count, emulator)
+                got, want = reported(info, path), entry.facts.predict(switch, path, count, emulator)
                 assert got == want, "%s under %s, path %d, count %d: the library reports %s, the table says %s" % (entry.name, switch, path, count, got, want)
                 assert (info.all_plain, info.no_glass_mirror) == (int(entry.facts.all_plain), int(entry.facts.no_glass_mirror)), entry.name
                 assert info.big_scene == int(entry.facts.big and not emulator), entry.name

@@ -13,15 +13,6 @@ RTC_BVH_STACK = 64      # csrc/device_scene.h: a tree whose stack_need exceeds R
 
 
 # ---- the hook -------------------------------------------------------------------------------------------------------------------------
-def bind(lib):
-    lib.rtc_bvh_build_raw.restype = C.c_int
-    lib.rtc_bvh_build_raw.argtypes = [vp, C.c_uint32, C.c_int32, C.c_uint32, C.c_int32, vp, C.c_uint32, vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp]
-    lib.rtc_bvh_collapse_raw.restype = C.c_int
-    lib.rtc_bvh_collapse_raw.argtypes = [vp, C.c_uint32, C.c_int32, vp, vp]
-    lib.rtc_last_error.restype = C.c_char_p
-    return lib
-
-
 class Built:
     def __init__(self, rc, nodes=None, root=-1, order=None, keys=None, frame=None, depth=0, stack_need=0, n_nodes=0):
         self.rc, self.nodes, self.root, self.order, self.keys, self.frame = rc, nodes, root, order, keys, frame

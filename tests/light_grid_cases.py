@@ -55,13 +55,6 @@ def triangle(p1, p2, p3):
 
 
 # ---- the hook -------------------------------------------------------------------------------------------------------------------------
-def bind(lib):
-    lib.rtc_light_grid_build_raw.restype = C.c_int
-    lib.rtc_light_grid_build_raw.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_uint32, vp, C.c_uint32, vp]
-    lib.rtc_last_error.restype = C.c_char_p
-    return lib
-
-
 class Grid:
     """cells[6 n n + 1]: first item of each cell; prim / dmin: the items; walk: cells left to the BVH walk (their one item is not a primitive)."""
     def __init__(self, n, n_prims, cells, items):

@@ -10,8 +10,7 @@ import build_matrix as bm
 import cases
 import ext_cases as ec
 from raytracer_challenge_amd import scenes
-from raytracer_challenge_amd.backend import HIT_DTYPE, AdaptiveC, FilterC, SamplingC, ShutterC
-from raytracer_challenge_amd.device import RtcCameraC, RtcStatsC
+from raytracer_challenge_amd.cabi import HIT_DTYPE, AdaptiveC, FilterC, RtcCameraC, RtcStatsC, SamplingC
 from raytracer_challenge_amd.scene import Camera, Color, Element, Material, Matrix, Pattern, PointLight, ShapeArgs, Vector, World
 
 COUNTERS = ("pixels", "rays_primary", "rays_shadow", "rays_reflect", "rays_refract", "rays_container")
@@ -111,28 +110,9 @@ def assert_counts(got, want, label):
 
 
 # ---- the entry points that fill an rtc_stats ------------------------------------------------------------------------------------------
-def bind(backend):
-    lib = bm.bind(backend.lib)
-    lib.rtw_make_camera.restype, lib.rtw_make_camera.argtypes = C.c_int, [vp, vp]
-    cam = st = vp    # (plain pointers: other test modules hand these functions their own structure classes through the same library object)
-    sigs = {"rtc_render": [vp, cam, C.c_int32, vp, C.c_uint64, C.c_uint64, vp, vp, st],
-            "rtc_render_rgb8": [vp, cam, C.c_int32, vp, st],
-            "rtc_trace_rays": [vp, vp, C.c_uint64, C.c_int32, vp, vp, st],
-            "rtc_render_bands_device": [vp, cam, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, st, C.c_int, C.c_int],
-            "rtc_render_rows_device": [vp, cam, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, vp, st, C.c_int, C.c_int],
-            "rtc_render_sampled": [vp, cam, C.POINTER(SamplingC), C.c_int32, vp, C.c_uint64, C.c_uint64, vp, st],
-            "rtc_render_adaptive": [vp, cam, C.POINTER(AdaptiveC), C.c_int32, vp, vp, C.POINTER(C.c_uint64), st],
-            "rtc_render_filtered": [vp, cam, C.POINTER(SamplingC), C.POINTER(FilterC), C.c_int32, C.c_uint32, C.c_uint32, vp, st],
-            "rtc_render_shutter": [vp, vp, C.c_uint32, C.POINTER(ShutterC), C.POINTER(SamplingC), C.c_int32, vp, C.c_uint64, C.c_uint64, vp, st]}
-    for name, args in sigs.items():
-        if hasattr(lib, name):
-            getattr(lib, name).restype, getattr(lib, name).argtypes = C.c_int, args
-    return lib
-
-
 def rtc_camera(backend, cam):
     cc, rc = backend.camera_c(cam), RtcCameraC()
-    assert bind(backend).rtw_make_camera(C.byref(cc), C.byref(rc)) == 0, backend._err()
+    assert backend.lib.rtw_make_camera(C.byref(cc), C.byref(rc)) == 0, backend._err()
     return rc
 
 
@@ -142,7 +122,7 @@ def _ok(lib, code, what):
 
 def render_stats(backend, nw, cam, fuel, pixel_indices=None, first=0, n=None):
     """rtc_render over the whole frame, the range first .. first + n - 1, or a pixel list."""
-    lib, rc = bind(backend), rtc_camera(backend, cam)
+    lib, rc = backend.lib, rtc_camera(backend, cam)
     idx_p = None
     if pixel_indices is not None:
         pixel_indices = np.ascontiguousarray(pixel_indices, dtype=np.uint64)
@@ -155,14 +135,14 @@ def render_stats(backend, nw, cam, fuel, pixel_indices=None, first=0, n=None):
 
 
 def rgb8_stats(backend, nw, cam, fuel):
-    lib, rc = bind(backend), rtc_camera(backend, cam)
+    lib, rc = backend.lib, rtc_camera(backend, cam)
     out, st = np.empty(cam.hsize * cam.vsize * 3, dtype=np.uint8), RtcStatsC()
     _ok(lib, lib.rtc_render_rgb8(bm.scene_of(backend, nw), C.byref(rc), int(fuel), out.ctypes.data, C.byref(st)), "rtc_render_rgb8")
     return st
 
 
 def trace_stats(backend, nw, rays, fuel):
-    lib = bind(backend)
+    lib = backend.lib
     rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
     rgb, hits, st = np.empty((len(rays), 3)), np.empty(len(rays), dtype=HIT_DTYPE), RtcStatsC()
     _ok(lib, lib.rtc_trace_rays(bm.scene_of(backend, nw), rays.ctypes.data, len(rays), int(fuel), rgb.ctypes.data, hits.ctypes.data, C.byref(st)), "rtc_trace_rays")
@@ -180,7 +160,7 @@ def band_rows_of(vsize, band_rows, band_first, band_step):
 def bands_stats(backend, nw, cam, fuel, band_rows, band_first, band_step, n_rows, out_ptr):
     """rtc_render_bands_device (band_rows = 1 through rtc_render_rows_device) into the caller's buffer (device memory on the GPU, host
     memory in the emulator), counting and synchronous."""
-    lib, rc, st = bind(backend), rtc_camera(backend, cam), RtcStatsC()
+    lib, rc, st = backend.lib, rtc_camera(backend, cam), RtcStatsC()
     scene = bm.scene_of(backend, nw)
     if band_rows == 1:
         _ok(lib, lib.rtc_render_rows_device(scene, C.byref(rc), int(fuel), band_first, band_step, n_rows, out_ptr, C.byref(st), 1, 1), "rtc_render_rows_device")
@@ -194,7 +174,7 @@ def rows_pixels(cam, rows):
 
 
 def sampled_stats(backend, nw, cam, sp, fuel, pixel_indices=None):
-    lib, rc, spc, st = bind(backend), rtc_camera(backend, cam), SamplingC.of(sp), RtcStatsC()
+    lib, rc, spc, st = backend.lib, rtc_camera(backend, cam), SamplingC.of(sp), RtcStatsC()
     idx_p, n = None, cam.hsize * cam.vsize
     if pixel_indices is not None:
         pixel_indices = np.ascontiguousarray(pixel_indices, dtype=np.uint64)
@@ -206,7 +186,7 @@ def sampled_stats(backend, nw, cam, sp, fuel, pixel_indices=None):
 
 def adaptive_stats(backend, nw, cam, adaptive, fuel):
     """(rtc_stats, the refined pixels' mask) of rtc_render_adaptive."""
-    lib, rc, ad, st = bind(backend), rtc_camera(backend, cam), AdaptiveC.of(adaptive), RtcStatsC()
+    lib, rc, ad, st = backend.lib, rtc_camera(backend, cam), AdaptiveC.of(adaptive), RtcStatsC()
     n = cam.hsize * cam.vsize
     rgb, mask, n_ref = np.empty((n, 3)), np.zeros(n, dtype=np.uint8), C.c_uint64(0)
     _ok(lib, lib.rtc_render_adaptive(bm.scene_of(backend, nw), C.byref(rc), C.byref(ad), int(fuel), rgb.ctypes.data, mask.ctypes.data, C.byref(n_ref), C.byref(st)), "rtc_render_adaptive")
@@ -215,7 +195,7 @@ def adaptive_stats(backend, nw, cam, adaptive, fuel):
 
 
 def filtered_stats(backend, nw, cam, sp, flt, fuel, row_first=0, n_rows=None):
-    lib, rc, spc, flc, st = bind(backend), rtc_camera(backend, cam), SamplingC.of(sp), FilterC.of(flt), RtcStatsC()
+    lib, rc, spc, flc, st = backend.lib, rtc_camera(backend, cam), SamplingC.of(sp), FilterC.of(flt), RtcStatsC()
     n_rows = cam.vsize - row_first if n_rows is None else n_rows
     rgb = np.empty((n_rows * cam.hsize, 3))
     _ok(lib, lib.rtc_render_filtered(bm.scene_of(backend, nw), C.byref(rc), C.byref(spc), C.byref(flc), int(fuel), row_first, n_rows, rgb.ctypes.data, C.byref(st)), "rtc_render_filtered")

@@ -15,6 +15,7 @@ import pytest
 
 import foreign_flattener as ff
 import test_shim_layout
+from raytracer_challenge_amd.cabi import load
 from raytracer_challenge_amd import scenes
 from raytracer_challenge_amd.backend import AdaptiveC, Backend, RtwError, SamplingC
 from raytracer_challenge_amd.scene import Adaptive, Sampling
@@ -116,18 +117,8 @@ def test_the_rule_on_frames_written_by_hand(host):
 
 
 # ---- API and mirrors ---------------------------------------------------------------------------------------------------------------
-def bind(lib):
-    lib.rtc_last_error.restype = C.c_char_p
-    lib.rtc_contrast_pixels.restype = C.c_int
-    lib.rtc_contrast_pixels.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.c_double, C.c_uint32, vp, vp]
-    for name in ("rtc_render_adaptive", "rtc_render_adaptive_rgb8"):
-        getattr(lib, name).restype = C.c_int
-        getattr(lib, name).argtypes = [vp, vp, vp, C.c_int32, vp, vp, vp, vp]
-    return lib
-
-
 def test_validation_through_c(host):
-    lib = bind(host.lib)
+    lib = host.lib
     frame, out, n = np.full((6, 3), 0.5), np.zeros(6, dtype=np.uint64), C.c_uint64(99)
 
     def contrast(hsize=3, vsize=2, rgb=frame.ctypes.data, thr=0.1, nb=4, idx=out.ctypes.data, np_=C.byref(n)):
@@ -203,7 +194,7 @@ def test_par_render_takes_adaptive_or_sampling_not_both(emu):
 
 
 def test_exports_and_rust_mirror(monkeypatch):
-    lib = C.CDLL(LIB)
+    lib = load(LIB)
     names = ("rtc_render_adaptive", "rtc_render_adaptive_rgb8", "rtc_contrast_pixels")
     for name in names:
         assert hasattr(lib, name), name

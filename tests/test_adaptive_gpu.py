@@ -29,18 +29,6 @@ vp = C.c_void_p
 FINE = Sampling(side=4, jitter=True, seed=31)
 
 
-def bind(lib):
-    lib.rtc_last_error.restype = C.c_char_p
-    lib.rtw_world_scene.restype, lib.rtw_world_scene.argtypes = vp, [vp, C.c_int]
-    cam, ad, st, u64p = C.POINTER(ff.RtcCamera), C.POINTER(AdaptiveC), C.POINTER(RtcStatsC), C.POINTER(C.c_uint64)
-    for name, args in (("rtc_render_adaptive", [vp, cam, ad, C.c_int32, vp, vp, u64p, st]),
-                       ("rtc_render_adaptive_rgb8", [vp, cam, ad, C.c_int32, vp, vp, u64p, st]),
-                       ("rtc_quantize", [vp, vp, C.c_uint64, vp])):
-        getattr(lib, name).restype = C.c_int
-        getattr(lib, name).argtypes = args
-    return lib
-
-
 def adaptive(lib, scene, cam, ad, fuel=5, stats=None):
     """rtc_render_adaptive through C: (frame, mask, n_refined)."""
     rc, adc = ff.make_camera(cam), AdaptiveC.of(ad)
@@ -54,7 +42,7 @@ def adaptive(lib, scene, cam, ad, fuel=5, stats=None):
 
 def setup(hip, name, w, h):
     """(lib, world handle, scene, camera) of a scene of `scenes` at w x h."""
-    lib = bind(hip.lib)
+    lib = hip.lib
     cam, world = getattr(scenes, name)(w, h)
     nw = hip.build_world(world)
     return lib, nw, lib.rtw_world_scene(nw.handle, 0), cam
@@ -181,7 +169,7 @@ KINDS = {  # scene -> (frame, threshold): thresholds at which the base frame has
 @pytest.mark.parametrize("path", PATHS)
 def test_scene_kinds_through_the_refine_pass(hip, path, name, monkeypatch):
     monkeypatch.setenv("RTC_KERNEL", path)
-    lib = bind(hip.lib)
+    lib = hip.lib
     (w, h), threshold = KINDS[name]
     cam0, world = scenes.chapter11_glass_air_bubble(w, h) if name == "glass_and_mirrors" else scene_of(name)
     cam = resized(cam0, w, h)

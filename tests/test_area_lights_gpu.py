@@ -11,9 +11,10 @@ import pytest
 
 import cases
 import foreign_flattener as ff
+from foreign_flattener import render_scene
 from parity import assert_parity
+from raytracer_challenge_amd.cabi import RtcLightEx
 from raytracer_challenge_amd import scenes
-from raytracer_challenge_amd.device import RtcStatsC
 from raytracer_challenge_amd.image import Image
 from raytracer_challenge_amd.scene import (AreaLight, Camera, Color, Element, Material, Matrix, Pattern, PointLight, ShapeArgs, Vector, World)
 from test_area_lights_cpu import area_hash, equivalent_point_lights, sample_positions
@@ -21,30 +22,6 @@ from test_area_lights_cpu import area_hash, equivalent_point_lights, sample_posi
 pytestmark = pytest.mark.gpu
 PATHS = ["1", "4"]
 vp = C.c_void_p
-
-
-class RtcLightEx(C.Structure):
-    _fields_ = [("kind", C.c_int32), ("usteps", C.c_uint32), ("vsteps", C.c_uint32), ("flags", C.c_uint32), ("intensity", C.c_double * 3),
-                ("corner", C.c_double * 3), ("uvec", C.c_double * 3), ("vvec", C.c_double * 3)]
-
-
-def bind(lib):
-    lib.rtc_last_error.restype = C.c_char_p
-    for name, args in (("rtc_scene_create", [C.POINTER(ff.RtcSceneDesc), C.c_int, C.POINTER(vp)]),
-                       ("rtc_scene_create_ex", [C.POINTER(ff.RtcSceneDesc), C.POINTER(RtcLightEx), C.c_uint32, C.c_int, C.POINTER(vp)]),
-                       ("rtc_multi_create_ex", [C.POINTER(ff.RtcSceneDesc), C.POINTER(RtcLightEx), C.c_uint32, C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]),
-                       ("rtc_render", [vp, C.POINTER(ff.RtcCamera), C.c_int32, vp, C.c_uint64, C.c_uint64, vp, vp, C.POINTER(RtcStatsC)]),
-                       ("rtc_render_hit_digest", [vp, C.POINTER(ff.RtcCamera), C.c_int32, vp, C.c_uint64, C.c_uint64, vp]),
-                       ("rtc_render_rgb8", [vp, C.POINTER(ff.RtcCamera), C.c_int32, vp, C.POINTER(RtcStatsC)]),
-                       ("rtc_quantize", [vp, vp, C.c_uint64, vp]),
-                       ("rtc_render_multi", [vp, C.POINTER(ff.RtcCamera), C.c_int32, vp, C.POINTER(RtcStatsC)])):
-        getattr(lib, name).restype = C.c_int
-        getattr(lib, name).argtypes = args
-    lib.rtc_scene_destroy.restype = None
-    lib.rtc_scene_destroy.argtypes = [vp]
-    lib.rtc_multi_destroy.restype = None
-    lib.rtc_multi_destroy.argtypes = [vp]
-    return lib
 
 
 def ex_lights(lights):
@@ -63,16 +40,6 @@ def geometry_desc(world):
     """The foreign flattener's descriptor of the world's elements, with no lights (the _ex list carries them)."""
     flat = ff.flatten(World([], world.elements))
     return flat, flat.desc()
-
-
-def render_scene(lib, scene, cam, fuel):
-    rc = ff.make_camera(cam)
-    n = cam.hsize * cam.vsize
-    rgb, hits, dig = np.empty((n, 3)), np.empty(n, dtype=[("t", "<f8"), ("prim", "<i4"), ("push_idx", "<i4")]), np.empty(n, dtype=np.uint64)
-    st = RtcStatsC()
-    assert lib.rtc_render(scene, C.byref(rc), fuel, None, 0, n, rgb.ctypes.data, hits.ctypes.data, C.byref(st)) == 0, lib.rtc_last_error()
-    assert lib.rtc_render_hit_digest(scene, C.byref(rc), fuel, None, 0, n, dig.ctypes.data) == 0, lib.rtc_last_error()
-    return rgb, hits, dig, st
 
 
 def matte(rgb, **kw):
@@ -262,7 +229,7 @@ def test_jittered_1080p_frame_is_identical_on_both_paths(hip, monkeypatch):
 @pytest.mark.parametrize("path", PATHS)
 def test_create_ex_with_point_lights_is_create(hip, path, monkeypatch):
     monkeypatch.setenv("RTC_KERNEL", path)
-    lib = bind(hip.lib)
+    lib = hip.lib
     for name in ("nested_glass", "synthetic_cones_grouped", "csg_scene"):
         cam, world = cases.SMALL_CASES[name]()
         flat = ff.flatten(world)
@@ -284,7 +251,7 @@ def test_create_ex_with_point_lights_is_create(hip, path, monkeypatch):
 @pytest.mark.parametrize("path", PATHS)
 def test_multi_rgb8_and_par_render_with_area_lights(hip, path, monkeypatch):
     monkeypatch.setenv("RTC_KERNEL", path)
-    lib = bind(hip.lib)
+    lib = hip.lib
     world, cam = penumbra_world(jit=True), camera(100, 61)
     gflat, gdesc = geometry_desc(world)
     lx = ex_lights(world.lights)
@@ -312,7 +279,7 @@ def test_multi_rgb8_and_par_render_with_area_lights(hip, path, monkeypatch):
 
 # ---- 6. validation ------------------------------------------------------------------------------------------------------------------
 def test_area_light_validation(hip):
-    lib = bind(hip.lib)
+    lib = hip.lib
     world = penumbra_world()
     flat = ff.flatten(World([world.lights[0]], world.elements))   # a descriptor with a point light of its own
     full = flat.desc()

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import foreign_flattener as ff
+from raytracer_challenge_amd.cabi import RtcBackground, RtcBackgroundInfo, load
 from raytracer_challenge_amd.backend import RtwError
 from raytracer_challenge_amd.scene import (Background, Camera, Color, Element, Matrix, Pattern, PointLight, ShapeArgs, Vector, World)
 from test_shim_layout import c_struct, rust_struct
@@ -17,30 +18,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "raytracer_challenge_amd", "csrc", "librtc_amd.so")
 vp = C.c_void_p
 BG_DIRECTION, BG_CUBE = 0, 1
-
-
-class RtcBackground(C.Structure):  # include/rtc.h rtc_background
-    _fields_ = [("pattern", C.c_int32), ("projection", C.c_int32)]
-
-
-class RtcBackgroundInfo(C.Structure):  # include/rtc.h rtc_background_info
-    _fields_ = [(n, C.c_int32) for n in ("has_background", "pattern", "projection", "plain_root", "trace_build", "trace_area", "trace_uv", "trace_spot",
-                                          "wf_background_build", "_pad")]
-
-
-def bind_background(lib):
-    dp = C.POINTER(C.c_double)
-    lib.rtc_last_error.restype = C.c_char_p
-    lib.rtc_background_point.restype, lib.rtc_background_point.argtypes = C.c_int, [C.c_int32, dp, dp]
-    lib.rtc_background_colors.restype, lib.rtc_background_colors.argtypes = C.c_int, [vp, vp, C.c_uint64, vp]
-    lib.rtc_scene_background_info.restype, lib.rtc_scene_background_info.argtypes = C.c_int, [vp, C.POINTER(RtcBackgroundInfo)]
-    lib.rtc_scene_create_ext3.restype = C.c_int
-    lib.rtc_scene_create_ext3.argtypes = [C.POINTER(ff.RtcSceneDesc), vp, vp, C.c_uint32, C.POINTER(RtcBackground), C.c_int, C.POINTER(vp)]
-    lib.rtc_multi_create_ext3.restype = C.c_int
-    lib.rtc_multi_create_ext3.argtypes = [C.POINTER(ff.RtcSceneDesc), vp, vp, C.c_uint32, C.POINTER(RtcBackground), C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
-    lib.rtc_scene_destroy.restype, lib.rtc_scene_destroy.argtypes = None, [vp]
-    lib.rtc_multi_destroy.restype, lib.rtc_multi_destroy.argtypes = None, [vp]
-    return lib
 
 
 # ---- the numpy restatement of the projection rule (shared with test_background_gpu.py) -------------------------------------------------
@@ -82,7 +59,7 @@ def edge_directions():
 
 
 def test_restated_point_is_rtc_background_point_bit_for_bit():
-    lib = bind_background(C.CDLL(LIB))
+    lib = load(LIB)
     rng = np.random.default_rng(2026)
     unit = rng.normal(size=(300, 3))
     unit /= np.linalg.norm(unit, axis=1, keepdims=True)
@@ -106,7 +83,7 @@ def test_restated_point_is_rtc_background_point_bit_for_bit():
 
 
 def test_point_refuses_null_and_unknown_projections():
-    lib = bind_background(C.CDLL(LIB))
+    lib = load(LIB)
     d, p = (C.c_double * 3)(1.0, 2.0, 3.0), (C.c_double * 3)()
     assert lib.rtc_background_point(2, d, p) == 1 and b"projection" in lib.rtc_last_error()
     assert lib.rtc_background_point(-1, d, p) == 1
@@ -123,7 +100,7 @@ def floor_world(background=None):
 def test_limits_through_c_need_no_device():
     """The background's own numbers are validated before the device is looked for: every limit answers RTC_ERR_INVALID (1) here, where a
     valid background gets as far as RTC_ERR_DEVICE (3) on a machine without one (or succeeds on one with)."""
-    lib = bind_background(C.CDLL(LIB))
+    lib = load(LIB)
     flat = ff.flatten(floor_world())
     sky = flat.pattern(Pattern.gradient(Matrix.id(), Pattern.plain(Color(1, 1, 1)), Pattern.plain(Color(0, 0, 1))))
     desc = flat.desc()
@@ -181,10 +158,7 @@ def test_rtw_set_background_limits_and_flatten_helpers():
     hip = rt.hip_backend()
     assert hip.has_background
     lib = hip.lib
-    lib.rtw_world_flatten_counts.restype, lib.rtw_world_flatten_counts.argtypes = C.c_int, [vp, C.POINTER(C.c_uint32)]
-    lib.rtw_world_flatten_desc.restype, lib.rtw_world_flatten_desc.argtypes = C.c_int, [vp, vp]
-    lib.rtw_pattern_plain.restype = vp
-    counts, desc = (C.c_uint32 * 8)(), C.create_string_buffer(256)
+    counts, desc = (C.c_uint32 * 8)(), ff.RtcSceneDesc()
     nw = hip.build_world(floor_world())
     assert lib.rtw_world_flatten_counts(nw.handle, counts) == 0 and counts[7] == 1
     pat = lib.rtw_pattern_plain(0.1, 0.2, 0.3)
@@ -202,7 +176,7 @@ def test_rtw_set_background_limits_and_flatten_helpers():
 
 # ---- the libraries ----------------------------------------------------------------------------------------------------------------
 def test_exports_and_package_names():
-    lib = C.CDLL(LIB)
+    lib = load(LIB)
     for name in ("rtc_scene_create_ext3", "rtc_multi_create_ext3", "rtc_background_point", "rtc_background_colors", "rtc_scene_background_info",
                  "rtw_world_set_background"):
         assert hasattr(lib, name), name

@@ -9,50 +9,26 @@ import pytest
 
 import build_matrix as bm
 import foreign_flattener as ff
+from foreign_flattener import render_scene
 import parity
 from raytracer_challenge_amd import scenes
-from raytracer_challenge_amd.device import RtcStatsC
 from raytracer_challenge_amd.image import Image
 from raytracer_challenge_amd.scene import (Adaptive, Background, Camera, Color, Element, Filter, GroupKind, Material, Matrix, Noise, Pattern, PointLight, Sampling,
                                            ShapeArgs, Vector, World)
 from raytracer_challenge_amd.texture import Texture, UvPattern
-from test_background_cpu import BG_CUBE, BG_DIRECTION, RtcBackground, RtcBackgroundInfo, background_points, bind_background
+from test_background_cpu import BG_CUBE, BG_DIRECTION, RtcBackground, RtcBackgroundInfo, background_points
 
 pytestmark = pytest.mark.gpu
 PATHS = ["1", "4"]
 vp = C.c_void_p
-HIT = [("t", "<f8"), ("prim", "<i4"), ("push_idx", "<i4")]
 FUEL = 5
 SKY = Color(0.25, 0.5, 1.0)
 SKY_RGB = np.array([0.25, 0.5, 1.0])
 
 
-def bind(lib):
-    bind_background(lib)
-    bm.bind(lib)
-    for name, args in (("rtc_render", [vp, C.POINTER(ff.RtcCamera), C.c_int32, vp, C.c_uint64, C.c_uint64, vp, vp, C.POINTER(RtcStatsC)]),
-                       ("rtc_render_hit_digest", [vp, C.POINTER(ff.RtcCamera), C.c_int32, vp, C.c_uint64, C.c_uint64, vp]),
-                       ("rtc_render_rgb8", [vp, C.POINTER(ff.RtcCamera), C.c_int32, vp, C.POINTER(RtcStatsC)]),
-                       ("rtc_render_multi", [vp, C.POINTER(ff.RtcCamera), C.c_int32, vp, C.POINTER(RtcStatsC)])):
-        getattr(lib, name).restype = C.c_int
-        getattr(lib, name).argtypes = args
-    return lib
-
-
-def render_scene(lib, scene, cam, fuel):
-    """(rgb, primary hits, hit-tree digests, stats) of an rtc_scene."""
-    rc = ff.make_camera(cam)
-    n = cam.hsize * cam.vsize
-    rgb, hits, dig = np.empty((n, 3)), np.empty(n, dtype=HIT), np.empty(n, dtype=np.uint64)
-    st = RtcStatsC()
-    assert lib.rtc_render(scene, C.byref(rc), fuel, None, 0, n, rgb.ctypes.data, hits.ctypes.data, C.byref(st)) == 0, lib.rtc_last_error()
-    assert lib.rtc_render_hit_digest(scene, C.byref(rc), fuel, None, 0, n, dig.ctypes.data) == 0, lib.rtc_last_error()
-    return rgb, hits, dig, st
-
-
 def render_world(hip, world, cam, fuel=FUEL):
     """The same through the Python layer: World(background=) -> rtw -> rtc_scene_create_ext3."""
-    lib = bind(hip.lib)
+    lib = hip.lib
     nw = hip.build_world(world)
     out = render_scene(lib, bm.scene_of(hip, nw), cam, fuel)
     nw.close()
@@ -73,14 +49,14 @@ def with_background(world, background):
 
 
 def background_info(hip, nw):
-    lib = bind(hip.lib)
+    lib = hip.lib
     info = RtcBackgroundInfo()
     assert lib.rtc_scene_background_info(bm.scene_of(hip, nw), C.byref(info)) == 0, lib.rtc_last_error()
     return info
 
 
 def background_colors(hip, nw, dirs):
-    lib = bind(hip.lib)
+    lib = hip.lib
     dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
     rgb = np.full((len(dirs), 3), np.nan)
     assert lib.rtc_background_colors(bm.scene_of(hip, nw), dirs.ctypes.data, len(dirs), rgb.ctypes.data) == 0, lib.rtc_last_error()
@@ -116,7 +92,7 @@ def test_nothing_moves_without_a_background(hip, name, tmp_path, monkeypatch):
     not see them); ops12_gated: row 5, LDS tables; uv: wf_shade's UV builds and row 8."""
     cam, world = bm.BY_NAME[name].make(tmp_path)
     black = with_background(world, Background(Pattern.plain(Color.black())))
-    lib = bind(hip.lib)
+    lib = hip.lib
     for path in PATHS:
         monkeypatch.setenv("RTC_KERNEL", path)
         nw, nb = hip.build_world(world), hip.build_world(black)
@@ -321,7 +297,7 @@ def test_path_against_path_with_real_backgrounds(hip, which, monkeypatch):
     for path in PATHS:
         monkeypatch.setenv("RTC_KERNEL", path)
         nw = hip.build_world(open_world(background))
-        frames.append(render_scene(bind(hip.lib), bm.scene_of(hip, nw), cam, FUEL))
+        frames.append(render_scene(hip.lib, bm.scene_of(hip, nw), cam, FUEL))
         rays = bm.rays_for(open_world(), 256)
         frames[-1] += (hip.color_at(nw, rays, FUEL),)
         texels = texel_directions_spherical() if which == 3 else texel_directions_cube() if which == 4 else []
@@ -353,7 +329,7 @@ def test_every_background_build_of_the_one_kernel_path(hip, name, tmp_path, monk
         nw = hip.build_world(world)
         info = background_info(hip, nw)
         assert info.trace_build == {"area_kops_real": 1, "uv_area_real": 3, "spot_real": 4, "uv_spot_real": 5}[name]
-        frames.append(render_scene(bind(hip.lib), bm.scene_of(hip, nw), cam, FUEL))
+        frames.append(render_scene(hip.lib, bm.scene_of(hip, nw), cam, FUEL))
     same_frames(frames[0], frames[1], "%s under a sky, both paths" % name)
     assert (frames[0][1]["prim"] == -1).sum() >= 48 * 2
 
@@ -365,7 +341,7 @@ def test_frame_shapes_and_pixel_lists(hip, path, monkeypatch):
     background = real_backgrounds()[2][1]
     world = open_world(background)
     nw = hip.build_world(world)
-    lib = bind(hip.lib)
+    lib = hip.lib
     monkeypatch.setenv("RTC_KERNEL", "1" if path == "4" else "4")
     other = hip.build_world(world)
     for h, v in ((37, 19), (1, 1)):                                   # tile padding on the wavefront path
@@ -407,7 +383,7 @@ def quantised(rgb):
 @pytest.mark.parametrize("path", PATHS)
 def test_every_entry_point_carries_the_background(hip, path, monkeypatch):
     monkeypatch.setenv("RTC_KERNEL", path)
-    lib = bind(hip.lib)
+    lib = hip.lib
     background = real_backgrounds()[0][1]
     world = open_world(background)
     cam = bm.camera()

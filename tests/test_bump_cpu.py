@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import foreign_flattener as ff
+from raytracer_challenge_amd.cabi import RtcBump, RtcBumpInfo, load
 from raytracer_challenge_amd.backend import RtwError
 from raytracer_challenge_amd.scene import (Bump, Camera, Color, Element, Material, Matrix, Pattern, PointLight, ShapeArgs, Vector, World)
 from test_shim_layout import c_struct, rust_struct
@@ -20,29 +21,6 @@ LIB = os.path.join(ROOT, "raytracer_challenge_amd", "csrc", "librtc_amd.so")
 vp = C.c_void_p
 SIMPLEX, FRACTAL, RIPPLE = 0, 1, 2
 MAX_OCTAVES = 64
-
-
-class RtcBump(C.Structure):  # include/rtc.h rtc_bump
-    _fields_ = [("material", C.c_uint32), ("kind", C.c_int32), ("octaves", C.c_uint32), ("_pad", C.c_uint32), ("amplitude", C.c_double), ("frequency", C.c_double)]
-
-
-class RtcBumpInfo(C.Structure):  # include/rtc.h rtc_bump_info
-    _fields_ = [("has_bump", C.c_int32), ("n_bumps", C.c_uint32)] + [(n, C.c_int32) for n in ("trace_build", "trace_area", "trace_uv", "trace_spot", "trace_bg", "wf_shade_build")]
-
-
-def bind_bump(lib):
-    dp = C.POINTER(C.c_double)
-    lib.rtc_last_error.restype = C.c_char_p
-    lib.rtc_bump_normal.restype, lib.rtc_bump_normal.argtypes = C.c_int, [C.POINTER(RtcBump), dp, dp, dp, dp]
-    lib.rtc_bump_normals.restype, lib.rtc_bump_normals.argtypes = C.c_int, [vp, vp, vp, vp, C.c_uint64, vp]
-    lib.rtc_scene_bump_info.restype, lib.rtc_scene_bump_info.argtypes = C.c_int, [vp, C.POINTER(RtcBumpInfo)]
-    lib.rtc_scene_create_ext4.restype = C.c_int
-    lib.rtc_scene_create_ext4.argtypes = [C.POINTER(ff.RtcSceneDesc), vp, vp, C.c_uint32, vp, C.POINTER(RtcBump), C.c_uint32, C.c_int, C.POINTER(vp)]
-    lib.rtc_multi_create_ext4.restype = C.c_int
-    lib.rtc_multi_create_ext4.argtypes = [C.POINTER(ff.RtcSceneDesc), vp, vp, C.c_uint32, vp, C.POINTER(RtcBump), C.c_uint32, C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
-    lib.rtc_scene_destroy.restype, lib.rtc_scene_destroy.argtypes = None, [vp]
-    lib.rtc_multi_destroy.restype, lib.rtc_multi_destroy.argtypes = None, [vp]
-    return lib
 
 
 def same_bits(a, b):
@@ -103,7 +81,7 @@ def unit(v):
 
 
 def test_restated_rule_is_rtc_bump_normal_bit_for_bit(orc):
-    lib = bind_bump(C.CDLL(LIB))
+    lib = load(LIB)
     rng = np.random.default_rng(2026)
     n_checked = 0
     moved = 0
@@ -127,7 +105,7 @@ def test_restated_rule_is_rtc_bump_normal_bit_for_bit(orc):
 
 
 def test_fractal_with_one_octave_is_simplex_and_the_noise_is_the_oracles(orc):
-    lib = bind_bump(C.CDLL(LIB))
+    lib = load(LIB)
     m = Matrix.id().flat()
     for X in ((0.3, 1.7, -2.2), (12.5, -0.01, 3.0)):
         n = unit((0.2, 1.0, -0.4))
@@ -138,7 +116,7 @@ def test_fractal_with_one_octave_is_simplex_and_the_noise_is_the_oracles(orc):
 
 
 def test_ripple_edges(orc):
-    lib = bind_bump(C.CDLL(LIB))
+    lib = load(LIB)
     m = Matrix.id().flat()
     n = (0.0, 1.0, 0.0)
     cases = {
@@ -163,7 +141,7 @@ def test_ripple_edges(orc):
 
 
 def test_nan_and_infinite_points_give_what_ieee_gives(orc):
-    lib = bind_bump(C.CDLL(LIB))
+    lib = load(LIB)
     nan, inf = math.nan, math.inf
     n = unit((0.0, 1.0, 1.0))
     for M in (Matrix.id(), Matrix.scaling(2.0, 3.0, 0.5)):
@@ -179,7 +157,7 @@ def test_nan_and_infinite_points_give_what_ieee_gives(orc):
 
 def test_amplitude_zero_returns_the_normals_own_bits(orc):
     """... for a normal whose length is one rounding off 1 as well: no renormalisation happens."""
-    lib = bind_bump(C.CDLL(LIB))
+    lib = load(LIB)
     rng = np.random.default_rng(7)
     m = ff.inverse(matrices()["all"]).flat()
     normals = [unit(rng.normal(size=3)) for _ in range(40)]
@@ -225,7 +203,7 @@ def bad_records(n_materials):
 def test_limits_through_c_need_no_device():
     """The records' own numbers are validated before the device is looked for: every limit answers RTC_ERR_INVALID (1) here, where valid
     records get as far as RTC_ERR_DEVICE (3) on a machine without one (or succeed on one with)."""
-    lib = bind_bump(C.CDLL(LIB))
+    lib = load(LIB)
     desc = ff.flatten(two_material_world()).desc()
     assert desc.n_materials == 2
     devs = (C.c_int * 1)(0)
@@ -252,7 +230,7 @@ def test_limits_through_c_need_no_device():
 
 
 def test_host_entry_refuses_null_and_bad_records():
-    lib = bind_bump(C.CDLL(LIB))
+    lib = load(LIB)
     m, p, n, o = (C.c_double * 16)(*Matrix.id().flat()), (C.c_double * 3)(1, 2, 3), (C.c_double * 3)(0, 1, 0), (C.c_double * 3)()
     ok = RtcBump(12345, RIPPLE, 0, 0, 0.1, 1.0)                                               # (`material` is not read)
     assert lib.rtc_bump_normal(C.byref(ok), m, p, n, o) == 0
@@ -301,10 +279,7 @@ def test_rtw_set_bump_limits_and_flatten_helpers():
     hip = rt.hip_backend()
     assert hip.has_bump
     lib = hip.lib
-    lib.rtw_world_flatten_counts.restype, lib.rtw_world_flatten_counts.argtypes = C.c_int, [vp, C.POINTER(C.c_uint32)]
-    lib.rtw_world_flatten_desc.restype, lib.rtw_world_flatten_desc.argtypes = C.c_int, [vp, vp]
-    lib.rtw_shape.restype = vp
-    counts, desc = (C.c_uint32 * 8)(), C.create_string_buffer(256)
+    counts, desc = (C.c_uint32 * 8)(), ff.RtcSceneDesc()
     nw = hip.build_world(bumped_world())
     assert lib.rtw_world_flatten_counts(nw.handle, counts) == 0 and counts[5] == 1            # the two shapes share one material row
     e = lib.rtw_shape(0, (C.c_double * 16)(*Matrix.id().flat()), None, 1, None, 0)
@@ -333,7 +308,7 @@ def test_rtw_set_bump_limits_and_flatten_helpers():
 
 
 def test_exports_and_package_names():
-    lib = C.CDLL(LIB)
+    lib = load(LIB)
     for name in ("rtc_scene_create_ext4", "rtc_multi_create_ext4", "rtc_bump_normal", "rtc_bump_normals", "rtc_scene_bump_info", "rtw_element_set_bump"):
         assert hasattr(lib, name), name
     import raytracer_challenge_amd as rt

@@ -20,7 +20,7 @@ CASES = bvh_cases.cases(4099)
 @pytest.fixture(scope="module")
 def lib():
     """librtc_amd.so without a device: loading it and the host-only entry points need none."""
-    return bvh_cases.bind(Backend(LIB).lib)
+    return Backend(LIB).lib
 
 
 # ---- ref_store's rounding rule, on values whose answer is known -----------------------------------------------------------------------

@@ -23,7 +23,7 @@ _built = {}
 
 @pytest.fixture(scope="module")
 def lib(hip):
-    return bvh_cases.bind(hip.lib)
+    return hip.lib
 
 
 @pytest.fixture(scope="module")
@@ -31,7 +31,6 @@ def hip_error(hip):
     """hipPeekAtLastError of the HIP runtime the library is linked to."""
     path = [line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line][0]
     rt = C.CDLL(path)
-    rt.hipPeekAtLastError.restype = C.c_int
     return rt.hipPeekAtLastError
 
 
@@ -135,10 +134,6 @@ def test_device_builder_clamps_leaf_max(lib, leaf_max, used):
 # ---- render level ----------------------------------------------------------------------------------------------------------------------
 def built_on_device(hip, nw):
     lib = hip.lib
-    lib.rtw_world_scene.restype = C.c_void_p
-    lib.rtw_world_scene.argtypes = [C.c_void_p, C.c_int]
-    lib.rtc_scene_bvh_built_on_device.restype = C.c_int
-    lib.rtc_scene_bvh_built_on_device.argtypes = [C.c_void_p]
     return lib.rtc_scene_bvh_built_on_device(lib.rtw_world_scene(nw.handle, 0))
 
 

@@ -45,21 +45,8 @@ DESC_CASES = {
 }
 
 
-def bind(lib):
-    vp = C.c_void_p
-    lib.rtc_scene_create.restype = C.c_int
-    lib.rtc_scene_create.argtypes = [C.POINTER(ff.RtcSceneDesc), C.c_int, C.POINTER(vp)]
-    lib.rtc_scene_destroy.restype = None
-    lib.rtc_scene_destroy.argtypes = [vp]
-    lib.rtc_render.restype = C.c_int
-    lib.rtc_render.argtypes = [vp, C.POINTER(ff.RtcCamera), C.c_int32, vp, C.c_uint64, C.c_uint64, vp, vp, vp]
-    lib.rtc_last_error.restype = C.c_char_p
-    return lib
-
-
 def render_desc(lib, world, cam, fuel=5):
     """Foreign flattener -> rtc_scene_create -> rtc_render (all pixels, with the primary-hit channel)."""
-    bind(lib)
     flat = ff.flatten(world)
     desc = flat.desc()
     scene = C.c_void_p()
@@ -84,7 +71,6 @@ def test_foreign_descriptor_renders_identically_on_the_emulated_kernels(name):
     assert np.array_equal(rgb, want_rgb), name
     # and the foreign walk agrees with the product's flattener on the array sizes a Rust shim would hand over
     counts = (C.c_uint32 * 8)()
-    be.lib.rtw_world_flatten_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     nw = be.build_world(world)
     assert be.lib.rtw_world_flatten_counts(nw.handle, counts) == 0
     assert (counts[0], counts[1], counts[3], counts[4], counts[7]) == (len(flat.nodes), len(flat.prims), len(flat.limits) // 2, len(flat.tri_geo) // 9, len(flat.lights))
@@ -103,7 +89,7 @@ def test_foreign_descriptor_matches_the_oracle(orc):
 def test_malformed_descriptors_are_refused():
     """rtc_scene_create validates what a foreign flattener can get wrong: indices out of range, a `skip` that leaves the array."""
     from emu_lib import emu
-    lib = bind(emu().lib)
+    lib = emu().lib
     cam, world = cases.SMALL_CASES["nested_groups"]()
     for breaker in ("material", "xform", "skip", "pattern"):
         flat = ff.flatten(world)
@@ -137,21 +123,9 @@ def test_hip_foreign_descriptor_renders_identically(hip, name):
 def test_hip_render_multi_equals_one_device(hip, devices):
     """rtc_multi_*: replicas on the listed devices (the test box has one GPU, so one device is listed several times: every code
     path but the cross-device copy itself runs), rows interleaved by replica, gather + de-interleave on the first device."""
-    lib = bind(hip.lib)
+    lib = hip.lib
     vp = C.c_void_p
-    lib.rtc_multi_create.restype = C.c_int
-    lib.rtc_multi_create.argtypes = [C.POINTER(ff.RtcSceneDesc), C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
-    lib.rtc_multi_destroy.restype = None
-    lib.rtc_multi_destroy.argtypes = [vp]
-    lib.rtc_render_multi.restype = C.c_int
     from raytracer_challenge_amd.device import RtcStatsC
-    lib.rtc_render_multi.argtypes = [vp, C.POINTER(ff.RtcCamera), C.c_int32, vp, C.POINTER(RtcStatsC)]
-    lib.rtc_render_multi_device.restype = C.c_int
-    lib.rtc_render_multi_device.argtypes = [vp, C.POINTER(ff.RtcCamera), C.c_int32, vp, C.c_int]
-    lib.rtc_multi_sync.restype = C.c_int
-    lib.rtc_multi_sync.argtypes = [vp]
-    lib.rtc_multi_device_count.restype = C.c_int
-    lib.rtc_multi_device_count.argtypes = [vp]
     import torch
     for name, (hs, vs) in (("synthetic_cones_grouped", (None, None)), ("smooth_triangles", (None, None)), ("nested_glass", (61, 37))):   # 37 rows: uneven split
         cam, world = (DESC_CASES.get(name) or cases.SMALL_CASES[name])()
@@ -173,8 +147,6 @@ def test_hip_render_multi_equals_one_device(hip, devices):
         rgb2 = np.full((n, 3), np.nan)
         assert lib.rtc_render_multi(m, C.byref(rc), 5, rgb2.ctypes.data, None) == 0, lib.rtc_last_error()   # the timed form: no counters
         # the quantised form (each replica quantises its rows, 3 B/px gathered): Color::clamp of the f64 image, byte for byte
-        lib.rtc_render_multi_rgb8.restype = C.c_int
-        lib.rtc_render_multi_rgb8.argtypes = [vp, C.POINTER(ff.RtcCamera), C.c_int32, vp, C.POINTER(RtcStatsC)]
         rgb8 = np.zeros(rgb.size, dtype=np.uint8)
         assert lib.rtc_render_multi_rgb8(m, C.byref(rc), 5, rgb8.ctypes.data, None) == 0, lib.rtc_last_error()
         c = np.where(np.isnan(rgb.reshape(-1)), 1.0, np.minimum(rgb.reshape(-1), 1.0))
@@ -187,7 +159,6 @@ def test_hip_render_multi_equals_one_device(hip, devices):
         assert lib.rtc_multi_sync(m) == 0, lib.rtc_last_error()
         assert np.array_equal(out.cpu().numpy().reshape(-1, 3), want_rgb), (name, devices)
         # the counters of the replicas' (side by side, asynchronous) counting launches add up to the one-device launch's
-        lib.rtc_render.restype = C.c_int
         one = RtcStatsC()
         scene = vp()
         assert lib.rtc_scene_create(C.byref(desc), 0, C.byref(scene)) == 0
@@ -197,8 +168,6 @@ def test_hip_render_multi_equals_one_device(hip, devices):
         for f in ("rays_primary", "rays_shadow", "rays_reflect", "rays_refract", "rays_container", "analytic_tests_kernarg"):
             assert getattr(st, f) == getattr(one, f), (f, name, devices)
         # other band heights (default 8): single rows interleaved, and a height that leaves a short last band
-        lib.rtc_multi_set_band_rows.restype = C.c_int
-        lib.rtc_multi_set_band_rows.argtypes = [vp, C.c_uint32]
         for band in (1, 5):
             assert lib.rtc_multi_set_band_rows(m, band) == 0
             rgb4 = np.full((n, 3), np.nan)
@@ -211,11 +180,9 @@ def test_hip_render_multi_equals_one_device(hip, devices):
 @pytest.mark.gpu
 def test_hip_render_rgb8_is_color_clamp_of_the_f64_frame(hip):
     """rtc_render_rgb8: the frame quantised on the device (src/color.rs:42-46), 3 bytes per pixel to the host."""
-    lib = bind(hip.lib)
+    lib = hip.lib
     vp = C.c_void_p
     from raytracer_challenge_amd.device import RtcStatsC
-    lib.rtc_render_rgb8.restype = C.c_int
-    lib.rtc_render_rgb8.argtypes = [vp, C.POINTER(ff.RtcCamera), C.c_int32, vp, C.POINTER(RtcStatsC)]
     for name in ("synthetic_cones_grouped", "nested_glass"):
         cam, world = (DESC_CASES.get(name) or cases.SMALL_CASES[name])()
         rgb, _, flat = render_desc(lib, world, cam)
@@ -238,19 +205,9 @@ def test_hip_render_rgb8_is_color_clamp_of_the_f64_frame(hip):
 def test_hip_render_multi_random_partitions(hip):
     """rtc_render_multi over 1-4 replicas with random image sizes (rows not a multiple of the band, fewer bands than replicas, one-row
     images) and band heights: always the one-device frame, bit for bit; the quantised form too."""
-    lib = bind(hip.lib)
+    lib = hip.lib
     vp = C.c_void_p
     from raytracer_challenge_amd.device import RtcStatsC
-    lib.rtc_multi_create.restype = C.c_int
-    lib.rtc_multi_create.argtypes = [C.POINTER(ff.RtcSceneDesc), C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
-    lib.rtc_multi_destroy.restype = None
-    lib.rtc_multi_destroy.argtypes = [vp]
-    lib.rtc_render_multi.restype = C.c_int
-    lib.rtc_render_multi.argtypes = [vp, C.POINTER(ff.RtcCamera), C.c_int32, vp, C.POINTER(RtcStatsC)]
-    lib.rtc_render_multi_rgb8.restype = C.c_int
-    lib.rtc_render_multi_rgb8.argtypes = [vp, C.POINTER(ff.RtcCamera), C.c_int32, vp, C.POINTER(RtcStatsC)]
-    lib.rtc_multi_set_band_rows.restype = C.c_int
-    lib.rtc_multi_set_band_rows.argtypes = [vp, C.c_uint32]
     rng = np.random.default_rng(77)
     cam0, world = cases.SMALL_CASES["nested_glass"]()
     flat = ff.flatten(world)

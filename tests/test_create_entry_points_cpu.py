@@ -2,12 +2,12 @@
 pairs from two different groups (bump records, background, cones, a NULL handle) -- answers the return code and the rtc_last_error()
 text recorded in tests/golden/create_entry_points.json, so the order of the checks cannot move unnoticed.  The table holds only faults
 that are answered before the device is looked for (create_cases.py): it gives the same answers with and without a GPU."""
-import ctypes as C
 import json
 import os
 
 import create_cases as cc
 import foreign_flattener as ff
+from raytracer_challenge_amd.cabi import load
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "raytracer_challenge_amd", "csrc", "librtc_amd.so")
@@ -20,7 +20,7 @@ def test_every_fault_and_pair_answers_as_recorded():
     flat = ff.flatten(cc.small_world())
     desc = flat.desc()
     assert desc.n_lights == 2 and desc.n_materials == 2 and desc.n_pattern_nodes >= 1
-    got = cc.answers(cc.bind(C.CDLL(LIB)), desc)
+    got = cc.answers(load(LIB), desc)
     assert sorted(got) == sorted(golden["rows"])
     # 12 entry points x (NULL desc, NULL out); cones through 6 of them, a background through 4, bump records through 2
     n_single = 12 * 2 + 6 * 3 + 4 * 2 + 2 * 3

@@ -18,13 +18,6 @@ vp = C.c_void_p
 FUEL = 2
 
 
-def bind(lib):
-    cc.bind(bm.bind(lib))
-    lib.rtc_render.restype, lib.rtc_render.argtypes = C.c_int, [vp, C.POINTER(ff.RtcCamera), C.c_int32, vp, C.c_uint64, C.c_uint64, vp, vp, vp]
-    lib.rtc_render_multi.restype, lib.rtc_render_multi.argtypes = C.c_int, [vp, C.POINTER(ff.RtcCamera), C.c_int32, vp, vp]
-    return lib
-
-
 class Created:
     """What one creation call gives: the frame's bits and, for a scene, its kernel builds on the pinned path and its device bytes."""
 
@@ -62,7 +55,7 @@ def fixtures():
 @pytest.mark.parametrize("path", ["1", "4"])
 def test_empty_extras_are_rtc_scene_create(hip, path, monkeypatch):
     monkeypatch.setenv("RTC_KERNEL", path)
-    lib = bind(hip.lib)
+    lib = hip.lib
     cam, flat, desc, unlit, lights = fixtures()
     want = Created(lib, "rtc_scene_create", path, cam, desc)
     assert np.isfinite(want.bits.view(np.float64)).all() and want.bits.view(np.float64).max() > 0.0 and want.device_bytes > 0
@@ -86,7 +79,7 @@ def test_empty_extras_are_rtc_scene_create(hip, path, monkeypatch):
 @pytest.mark.parametrize("path", ["1", "4"])
 def test_open_cone_on_either_light_list_is_no_cone(hip, path, monkeypatch):
     monkeypatch.setenv("RTC_KERNEL", path)
-    lib = bind(hip.lib)
+    lib = hip.lib
     cam, flat, desc, unlit, lights = fixtures()
     want = Created(lib, "rtc_scene_create", path, cam, desc)
     cones = (cc.RtcLightCone * 1)(cc.RtcLightCone(0, 0, (C.c_double * 3)(0.0, -1.0, 0.0), -1.0, -1.0))

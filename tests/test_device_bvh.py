@@ -1,7 +1,6 @@
 """SURVEY §8f rank 2, second half: the mesh accelerator's tree built ON THE DEVICE (RTC_DEVICE_BVH=1: linear BVH, csrc/bvh_device.hip)
 with the host's binned-SAH build as the checker.  The accelerator is results-neutral, so the same scene rendered through either tree
 must give the same pixels and primary-hit records, bit for bit — and both must match the oracle."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -15,10 +14,6 @@ pytestmark = pytest.mark.gpu
 
 def built_on_device(hip, nw):
     lib = hip.lib
-    lib.rtw_world_scene.restype = C.c_void_p
-    lib.rtw_world_scene.argtypes = [C.c_void_p, C.c_int]
-    lib.rtc_scene_bvh_built_on_device.restype = C.c_int
-    lib.rtc_scene_bvh_built_on_device.argtypes = [C.c_void_p]
     return lib.rtc_scene_bvh_built_on_device(lib.rtw_world_scene(nw.handle, 0))
 
 

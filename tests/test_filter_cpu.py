@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import foreign_flattener as ff
+from raytracer_challenge_amd.cabi import load
 from raytracer_challenge_amd import scenes
 from raytracer_challenge_amd.backend import Backend, FilterC, RtwError, SamplingC
 from raytracer_challenge_amd.image import Image
@@ -111,19 +112,10 @@ def same_bits(a, b):
     return a.shape == b.shape and bool(np.all(nan | (bits(a) == bits(b))))
 
 
-def bind_filter(lib):
-    lib.rtc_filter_frame.restype = C.c_int
-    lib.rtc_filter_frame.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp]
-    lib.rtc_last_error.restype = C.c_char_p
-    return lib
-
-
 @pytest.fixture(scope="module")
 def host():
     """librtc_amd.so without a device: loading it and the host-only entry points need none."""
-    be = Backend(LIB)
-    bind_filter(be.lib)
-    return be
+    return Backend(LIB)
 
 
 @pytest.fixture(scope="module")
@@ -161,10 +153,10 @@ def test_the_filters_positions_are_the_rays_positions(host):
     the normalisation, the quotient and x + fx: a few ulp of 8, under 1e-14.  The restated rule fed with THOSE positions must give
     rtc_filter_frame's frame; a tent's weight moves by at most |dfx| / r, so 1e-12 covers it, while a position from another hash, draw
     or cell is off by about the width of a cell and moves a pixel of these random colours by about 1e-1."""
-    from test_sampled_camera_cpu import bind_rays, c_rays
-    lib = bind_rays(host.lib)
+    from test_sampled_camera_cpu import c_rays
+    lib = host.lib
     hsize, vsize = 8, 4
-    rc = ff.RtcCamera()
+    rc = ff.RtcCameraC()
     rc.hsize, rc.vsize, rc.half_width, rc.half_height, rc.pixel_size = hsize, vsize, 0.0, 0.0, 2.0 ** -6
     for j in range(16):
         rc.transform_inv[j] = 1.0 if j % 5 == 0 else 0.0
@@ -293,10 +285,6 @@ def test_validation_through_c(host):
     assert lib.rtc_filter_frame(None, 3, 2, C.byref(spc), C.byref(fl), samples.ctypes.data, None) == 1
     # the render entry points validate before they touch a device
     rc = ff.make_camera(scenes.cover(9, 5)[0])
-    lib.rtc_render_filtered.restype = C.c_int
-    lib.rtc_render_filtered.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_uint32, C.c_uint32, vp, vp]
-    lib.rtc_render_filtered_rgb8.restype = C.c_int
-    lib.rtc_render_filtered_rgb8.argtypes = [vp, vp, vp, vp, C.c_int32, vp, vp]
     assert lib.rtc_render_filtered(None, C.byref(rc), C.byref(spc), C.byref(fl), 5, 0, 5, out.ctypes.data, None) == 1   # NULL scene
     assert lib.rtc_render_filtered_rgb8(None, C.byref(rc), C.byref(spc), C.byref(fl), 5, out.ctypes.data, None) == 1
     assert lib.rtc_render_filtered_rgb8(None, None, C.byref(spc), C.byref(fl), 5, out.ctypes.data, None) == 1
@@ -340,7 +328,7 @@ def test_libraries_without_the_entry_points_refuse(emu, orc):
 
 
 def test_exports_and_rust_mirror():
-    lib = C.CDLL(LIB)
+    lib = load(LIB)
     names = ("rtc_render_filtered", "rtc_render_filtered_rgb8", "rtc_filter_frame")
     for name in names:
         assert hasattr(lib, name), name

@@ -22,20 +22,6 @@ PATHS = ["1", "4"]
 vp = C.c_void_p
 
 
-def bind(lib):
-    lib.rtc_last_error.restype = C.c_char_p
-    lib.rtw_world_scene.restype, lib.rtw_world_scene.argtypes = vp, [vp, C.c_int]
-    cam, sp, fl, st = C.POINTER(ff.RtcCamera), C.POINTER(SamplingC), C.POINTER(FilterC), C.POINTER(RtcStatsC)
-    for name, args in (("rtc_render_filtered", [vp, cam, sp, fl, C.c_int32, C.c_uint32, C.c_uint32, vp, st]),
-                       ("rtc_render_filtered_rgb8", [vp, cam, sp, fl, C.c_int32, vp, st]),
-                       ("rtc_quantize", [vp, vp, C.c_uint64, vp])):
-        getattr(lib, name).restype = C.c_int
-        getattr(lib, name).argtypes = args
-    lib.rtc_scene_path_info.restype = None
-    lib.rtc_scene_path_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    return lib
-
-
 def filtered(lib, scene, cam, sp, flt, fuel, row_first=0, n_rows=None, stats=None):
     """rtc_render_filtered through C: the whole frame or a row range."""
     rc, spc, flc = ff.make_camera(cam), SamplingC.of(sp), FilterC.of(flt)
@@ -151,7 +137,7 @@ def test_box_of_half_a_pixel_is_rtc_render_sampled(hip, path, monkeypatch):
 def test_partitions_change_no_bit(hip, path, monkeypatch, capfd):
     monkeypatch.setenv("RTC_KERNEL", path)
     monkeypatch.delenv("RTC_SAMPLED_MAX_RAYS", raising=False)
-    lib = bind(hip.lib)
+    lib = hip.lib
     name, (w, h), sp, flt = MITCHELL_CASE
     cam, world = getattr(scenes, name)(w, h)
     nw = hip.build_world(world)
@@ -200,7 +186,7 @@ def test_partitions_change_no_bit(hip, path, monkeypatch, capfd):
 def test_stats_count_the_traced_rays(hip, path, monkeypatch):
     monkeypatch.setenv("RTC_KERNEL", path)
     monkeypatch.delenv("RTC_SAMPLED_MAX_RAYS", raising=False)
-    lib = bind(hip.lib)
+    lib = hip.lib
     name, (w, h), sp, flt = MITCHELL_CASE
     cam, world = getattr(scenes, name)(w, h)
     nw = hip.build_world(world)
@@ -224,7 +210,7 @@ def test_stats_count_the_traced_rays(hip, path, monkeypatch):
 # ---- 7. path choice -----------------------------------------------------------------------------------------------------------------
 def test_filtered_launches_choose_their_path(hip, monkeypatch):
     monkeypatch.delenv("RTC_KERNEL", raising=False)
-    lib = bind(hip.lib)
+    lib = hip.lib
     cam, world = scenes.chapter11_glass_air_bubble(64, 32)
     nw = hip.build_world(world)
     scene = lib.rtw_world_scene(nw.handle, 0)

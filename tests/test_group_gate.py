@@ -101,8 +101,6 @@ def test_the_gate_decides_like_the_reference_on_adversarial_rays(emu):
     EPSILON.  100 000 rays; one wrong answer would mean a margin is too small."""
     import ctypes as C
     lib = emu.lib
-    lib.rtc_emu_group_box_hit.restype = C.c_int
-    lib.rtc_emu_group_box_hit.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
     wrong = 0
     n_hit = 0
     for lo, hi, o, d in gate_rays(100000, seed=11):   # (the generator this test had, now shared with the device's probe)

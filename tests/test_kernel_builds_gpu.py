@@ -160,12 +160,8 @@ def test_lds_resident_scene_on_several_devices(hip, tmp_path):
     n_dev = int(hip.lib.rtc_device_count())
     if n_dev < 2:
         pytest.skip("needs two devices")
-    lib = bm.bind(hip.lib)
+    lib = hip.lib
     vp = C.c_void_p
-    from raytracer_challenge_amd.device import RtcStatsC
-    lib.rtc_multi_create.restype, lib.rtc_multi_create.argtypes = C.c_int, [C.POINTER(ff.RtcSceneDesc), C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
-    lib.rtc_multi_destroy.restype, lib.rtc_multi_destroy.argtypes = None, [vp]
-    lib.rtc_render_multi.restype, lib.rtc_render_multi.argtypes = C.c_int, [vp, C.POINTER(ff.RtcCamera), C.c_int32, vp, C.POINTER(RtcStatsC)]
     entry = bm.BY_NAME["grid_mesh_bvh"]
     cam, world = entry.make(tmp_path)
     k, want = lds_report(hip, world)

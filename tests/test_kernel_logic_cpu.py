@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import raytracer_challenge_amd as rt
+from raytracer_challenge_amd.cabi import load
 from raytracer_challenge_amd import scenes
 from raytracer_challenge_amd.scene import Color, Element, GroupKind, Material, Matrix, Pattern, PointLight, ShapeArgs, Vector, World, Camera
 import cases
@@ -48,8 +49,6 @@ def test_parallel_bvh_build_equals_serial(emu, orc, monkeypatch, tmp_path):
     cam, world = scenes.synthetic_mesh(obj, nx=160, nz=160, hsize=64, vsize=36)   # 50 562 triangles: two levels of threads
     idx = np.arange(0, cam.hsize * cam.vsize, 7, dtype=np.uint64)
     lib = emu.lib
-    lib.rtw_world_scene.restype = C.c_void_p
-    lib.rtw_world_scene.argtypes = [C.c_void_p, C.c_int]
     out = {}
     for threads in ("1", "4"):
         monkeypatch.setenv("RTC_BUILD_THREADS", threads)
@@ -70,11 +69,6 @@ def test_wavefront_path_really_runs_in_the_emulator(emu, monkeypatch):
     from raytracer_challenge_amd.device import RtcCameraC, RtcStatsC
     monkeypatch.setenv("RTC_KERNEL", "4")
     lib = emu.lib
-    lib.rtw_world_scene.restype = C.c_void_p
-    lib.rtw_world_scene.argtypes = [C.c_void_p, C.c_int]
-    lib.rtc_render_rows_device.restype = C.c_int
-    lib.rtc_render_rows_device.argtypes = [C.c_void_p, C.POINTER(RtcCameraC), C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(RtcStatsC),
-                                           C.c_int, C.c_int]
     for (cam, world), fuel in ((scenes.synthetic_analytic(hsize=96, vsize=54), 5), (cases.nested_glass(), 8)):
         nw = emu.build_world(world)
         scene = lib.rtw_world_scene(nw.handle, 0)
@@ -146,12 +140,11 @@ def declared(header, prefix):
 
 
 def test_library_exports_every_declared_symbol():
-    lib = C.CDLL(os.path.join(ROOT, "raytracer_challenge_amd", "csrc", "librtc_amd.so"))
+    lib = load(os.path.join(ROOT, "raytracer_challenge_amd", "csrc", "librtc_amd.so"))
     names = declared("rtc.h", "rtc") + declared("rtw.h", "rtw")
     assert len(names) >= 28, names
     missing = [n for n in names if not hasattr(lib, n)]
     assert not missing, missing
-    lib.rtw_backend.restype = C.c_char_p
     assert lib.rtw_backend() == b"hip"
 
 
@@ -169,7 +162,6 @@ def test_host_errors_and_flatten(emu):
     nw = b.build_world(world)
     assert nw.primitive_count == 243
     counts = (C.c_uint32 * 8)()
-    b.lib.rtw_world_flatten_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     assert b.lib.rtw_world_flatten_counts(nw.handle, counts) == 0
     n_nodes, n_prims, n_xforms, n_limits, n_tris, n_materials, n_pats, n_lights = list(counts)
     assert (n_nodes, n_prims, n_xforms, n_tris, n_lights) == (244, 243, 4, 240, 2) and n_materials == 2
@@ -190,7 +182,6 @@ def test_csg_subtrees_beyond_the_per_lane_buffer(emu, orc):
 def test_no_device_fails_loudly():
     """Without a GPU the product must refuse to compute (no CPU fallback).  Skipped when a device is present."""
     b = rt.Backend(os.path.join(ROOT, "raytracer_challenge_amd", "csrc", "librtc_amd.so"))
-    b.lib.rtc_device_count.restype = C.c_int
     if b.lib.rtc_device_count() > 0:
         pytest.skip("a HIP device is present")
     cam, world = scenes.default_world()
@@ -201,16 +192,13 @@ def test_no_device_fails_loudly():
 def test_cabi_argument_validation_without_a_device():
     """Entry points reject bad arguments with RTC_ERR_INVALID (1) and a message before they touch a device: NULL scenes,
     marker slots outside 0..7, NULL descriptors."""
-    lib = C.CDLL(os.path.join(ROOT, "raytracer_challenge_amd", "csrc", "librtc_amd.so"))
-    lib.rtc_last_error.restype = C.c_char_p
+    lib = load(os.path.join(ROOT, "raytracer_challenge_amd", "csrc", "librtc_amd.so"))
     for fn, args in (("rtc_scene_record", (None, 0)), ("rtc_scene_wait", (None, 3)), ("rtc_scene_check", (None,)), ("rtc_scene_sync", (None,)),
                      ("rtc_scene_create", (None, 0, None)), ("rtc_render", (None, None, 5, None, 0, 0, None, None, None))):
         f = getattr(lib, fn)
-        f.restype = C.c_int
         assert f(*args) == 1, fn
         assert lib.rtc_last_error(), fn
     ms = C.c_double(0)
-    lib.rtc_scene_elapsed_ms.restype = C.c_int
     assert lib.rtc_scene_elapsed_ms(None, 0, 9, C.byref(ms)) == 1
 
 

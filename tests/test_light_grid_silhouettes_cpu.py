@@ -29,7 +29,7 @@ RATIO_BOUND = 0.5 * (MEASURED_RATIO + 1.0)
 @pytest.fixture(scope="module")
 def lib():
     """librtc_amd.so without a device: loading it and the host-only entry points need none."""
-    return lg.bind(Backend(LIB).lib)
+    return Backend(LIB).lib
 
 
 @pytest.fixture(scope="module")

@@ -67,11 +67,9 @@ def test_band_gather_matches_single_rank(tmp_path, world_size, vsize, band_rows)
 
 def test_band_rows_owned_matches_the_python_partition():
     """rtc_band_rows_owned (host arithmetic of the product library: callable without a GPU) against parallel.rows_of."""
-    import ctypes as C
+    from raytracer_challenge_amd.cabi import load
     from raytracer_challenge_amd.parallel import rows_of, max_rows
-    lib = C.CDLL(os.path.join(ROOT, "raytracer_challenge_amd", "csrc", "librtc_amd.so"))
-    lib.rtc_band_rows_owned.restype = C.c_uint64
-    lib.rtc_band_rows_owned.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]
+    lib = load(os.path.join(ROOT, "raytracer_challenge_amd", "csrc", "librtc_amd.so"))
     for vsize in (1, 7, 8, 9, 25, 1080, 2160, 2161):
         for band in (1, 3, 8, 32):
             for n in (1, 2, 3, 4, 8):

@@ -40,8 +40,6 @@ def parse(be, path, transform=None, material=None):
 
 
 def flat_desc(be, nw):
-    be.lib.rtw_world_flatten_desc.restype = C.c_int
-    be.lib.rtw_world_flatten_desc.argtypes = [C.c_void_p, C.POINTER(ff.RtcSceneDesc)]
     d = ff.RtcSceneDesc()
     assert be.lib.rtw_world_flatten_desc(nw.handle, C.byref(d)) == 0, be._err()
     return d

@@ -14,6 +14,7 @@ import ext_cases as ec
 import oracle_lib
 from oracle_ext_lib import MUTANTS, mutant, oracle_ext
 from parity import RGB_TOL, rgb_error
+from raytracer_challenge_amd.cabi import load
 from raytracer_challenge_amd import scenes
 from raytracer_challenge_amd.scene import AreaLight, Background, Color, Cone, Matrix, Pattern, PointLight, Vector, World
 from raytracer_challenge_amd.texture import Texture, UvPattern
@@ -84,8 +85,8 @@ def test_sample_positions_bit_for_bit(ext):
 
 def test_spot_factor_bit_for_bit(ext):
     import ctypes as C
-    from test_spot_lights_cpu import LIB, bind_spot, lib_spot_factor, shadow_dir, spot_cos, spot_factor, unit_axis
-    lib = bind_spot(C.CDLL(LIB))
+    from test_spot_lights_cpu import LIB, lib_spot_factor, shadow_dir, spot_cos, spot_factor, unit_axis
+    lib = load(LIB)
 
     def check(axis, ci, co, light, point):
         want = spot_factor(axis, ci, co, light, point)
@@ -268,8 +269,8 @@ def test_bump_rule_bit_for_bit(orc, ext):
     point sets: three kinds, magnitudes 1e-3..1e3, identity / scale / shear / translation, amplitudes 0..10, octaves 1, 3, 8 and 64, RIPPLE
     at r == 0, g == 0, g == 1 and on the y axis, NaN and infinite points, amplitude 0 on normals one rounding off 1."""
     import ctypes as C
-    from test_bump_cpu import LIB, bind_bump, lib_normal, restated_normal
-    lib = bind_bump(C.CDLL(LIB))
+    from test_bump_cpu import LIB, lib_normal, restated_normal
+    lib = load(LIB)
     seen = {}
     for why, kind, octaves, a, f, m, X, n in bump_rule_cases():
         got = ext.bump_normal(kind, octaves, a, f, m, X, n)
@@ -285,7 +286,6 @@ def test_bump_rule_bit_for_bit(orc, ext):
 def test_bump_limits_are_the_products(ext):
     import ctypes as C
     lib = ext.lib
-    lib.rtw_shape.restype = C.c_void_p
     e = lib.rtw_shape(0, (C.c_double * 16)(*Matrix.id().flat()), None, 1, None, 0)
     assert e
     assert lib.rtw_element_set_bump(None, 2, 0, 0.1, 1.0) != 0 and "NULL" in ext._err()

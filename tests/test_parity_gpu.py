@@ -218,9 +218,9 @@ def test_hip_wavefront_allocation_failure_inside_a_chunked_launch(hip, monkeypat
     import ctypes as C
     from raytracer_challenge_amd.device import RtcStatsC
     from raytracer_challenge_amd.scene import Filter, Sampling
-    from test_filter_gpu import bind as bind_filtered, filtered
-    from test_sampled_camera_gpu import bind as bind_sampled, bits, sampled
-    lib = bind_filtered(bind_sampled(hip.lib))
+    from test_filter_gpu import filtered
+    from test_sampled_camera_gpu import bits, sampled
+    lib = hip.lib
     cam, world = scenes.chapter11_glass_air_bubble(16, 16)
     sp, box = Sampling(side=2), Filter.box(0.5)
     monkeypatch.setenv("RTC_SAMPLED_MAX_RAYS", "256")    # a row is 16 pixels x 4 rays: 4 rows per chunk, 4 chunks (the box has no halo)

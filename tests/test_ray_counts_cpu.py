@@ -11,6 +11,7 @@ import bump_cases as bc
 import ext_cases as ec
 import ray_counts as rc
 from oracle_ext_lib import oracle_ext
+from raytracer_challenge_amd.cabi import load
 from raytracer_challenge_amd import scenes
 from raytracer_challenge_amd.scene import (AreaLight, Background, Bump, Camera, Color, Element, Material, Matrix, Pattern, PointLight, ShapeArgs, SpotLight, Vector,
                                            World)
@@ -171,9 +172,8 @@ def test_a_hard_cone_sends_shadow_rays_to_the_lit_samples_only(ext):
     plane, rays straight down at a grid of points: the expected number is the count of f != 0 from the product's own rtc_spot_factor at
     each over_point, which the oracle's restated factor must agree with."""
     import os
-    import ctypes as C
-    from test_spot_lights_cpu import bind_spot, lib_spot_factor
-    lib = bind_spot(C.CDLL(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "raytracer_challenge_amd", "csrc", "librtc_amd.so")))
+    from test_spot_lights_cpu import lib_spot_factor
+    lib = load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "raytracer_challenge_amd", "csrc", "librtc_amd.so"))
     origin, axis, angle = (0.5, 4.0, -0.25), (0.2, -1.0, 0.1), 0.4
     points = [(0.37 * i - 2.9, 0.41 * j - 2.7) for i in range(16) for j in range(14)]
     factors = []

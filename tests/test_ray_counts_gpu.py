@@ -138,7 +138,6 @@ def test_rgb8_rows_and_bands(hip, ext, path, monkeypatch):
     n = cam.hsize * cam.vsize
     rc.assert_counts(rc.rgb8_stats(hip, nw, cam, 5), want_of("rgb8", lambda: rc.expected(ext.ray_counts(nwo, cam, 5), n)), "rtc_render_rgb8 path " + path)
     out = torch.empty(n * 3, dtype=torch.float64, device="cuda")
-    hip.lib.rtc_band_rows_owned.restype, hip.lib.rtc_band_rows_owned.argtypes = C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]
     for band, part, owned in ((1, 1, [1, 4, 7, 10, 13]), (4, 0, [0, 1, 2, 3, 12, 13])):
         rows = rc.band_rows_of(cam.vsize, band, part, 3)
         assert rows == owned and len(rows) == hip.lib.rtc_band_rows_owned(cam.vsize, band, part, 3)
@@ -152,9 +151,6 @@ def test_rtc_render_multi_sums_its_replicas(hip, orc, path, monkeypatch):
     """Two replicas on one device, each with the bands it owns: the sum is the frame's count, once."""
     monkeypatch.setenv("RTC_KERNEL", path)
     lib = hip.lib
-    lib.rtc_multi_create.restype, lib.rtc_multi_create.argtypes = C.c_int, [vp, C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
-    lib.rtc_multi_destroy.restype, lib.rtc_multi_destroy.argtypes = None, [vp]
-    lib.rtc_render_multi.restype, lib.rtc_render_multi.argtypes = C.c_int, [vp, vp, C.c_int32, vp, vp]
     cam, world = glass_scene()
     desc = ff.flatten(world).desc()
     m, devs = vp(), (C.c_int * 2)(0, 0)

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import foreign_flattener as ff
+from raytracer_challenge_amd.cabi import load
 from raytracer_challenge_amd import scenes
 from raytracer_challenge_amd.backend import Backend, RtwError, SamplingC
 from raytracer_challenge_amd.scene import Camera, Sampling, Vector
@@ -37,7 +38,7 @@ def subpixel(sp: Sampling, i: int, k: int):
     return (float(sx) + jx) / float(n), (float(sy) + jy) / float(n)
 
 
-def sample_ray(rc: ff.RtcCamera, sp: Sampling, i: int, k: int):
+def sample_ray(rc: ff.RtcCameraC, sp: Sampling, i: int, k: int):
     """{o, d} of sample k of pixel i; every step one f64 operation (Python floats), left to right as the header states them."""
     m = list(rc.transform_inv)
     x, y = i % rc.hsize, i // rc.hsize
@@ -71,7 +72,7 @@ def sample_ray(rc: ff.RtcCamera, sp: Sampling, i: int, k: int):
     return o + [d[0] / mag, d[1] / mag, d[2] / mag]
 
 
-def sample_rays(rc: ff.RtcCamera, sp: Sampling, pixels) -> np.ndarray:
+def sample_rays(rc: ff.RtcCameraC, sp: Sampling, pixels) -> np.ndarray:
     return np.array([[sample_ray(rc, sp, int(i), k) for k in range(sp.samples)] for i in pixels], dtype=np.float64).reshape(len(pixels), sp.samples, 6)
 
 
@@ -96,13 +97,6 @@ def rotated_camera():
     return Camera.new(9, 7, 1.1, Camera.transform(Vector.point(1.0, 2.0, -5.0), Vector.point(0.3, 0.5, 0.0), Vector.vector(0.1, 1.0, 0.2)))
 
 
-def bind_rays(lib):
-    lib.rtc_camera_rays.restype = C.c_int
-    lib.rtc_camera_rays.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_uint64, vp]
-    lib.rtc_last_error.restype = C.c_char_p
-    return lib
-
-
 def c_rays(lib, scene, rc, spc, n, idx=None, first=0):
     """rtc_camera_rays's status and rays for a raw SamplingC."""
     N = max(1, spc.side * spc.side) if spc.side <= 16 else 1
@@ -115,9 +109,7 @@ def c_rays(lib, scene, rc, spc, n, idx=None, first=0):
 @pytest.fixture(scope="module")
 def host():
     """librtc_amd.so without a device: loading it and the host-only entry points need none."""
-    be = Backend(LIB)
-    bind_rays(be.lib)
-    return be
+    return Backend(LIB)
 
 
 @pytest.fixture(scope="module")
@@ -270,10 +262,6 @@ def test_validation_through_c(host):
                        ("rtc_render_sampled_bands_device", (None, C.byref(rc), C.byref(spc), 5, 8, 0, 1, 1, out.ctypes.data, None, 0, 1)),
                        ("rtc_render_multi_sampled", (None, C.byref(rc), C.byref(spc), 5, out.ctypes.data, None))):
         fn = getattr(lib, name)
-        fn.restype = C.c_int
-        fn.argtypes = [vp, vp, vp, C.c_int32] + {"rtc_render_sampled": [vp, C.c_uint64, C.c_uint64, vp, vp], "rtc_render_sampled_rgb8": [vp, vp],
-                                                 "rtc_render_sampled_bands_device": [C.c_uint32] * 4 + [vp, vp, C.c_int, C.c_int],
-                                                 "rtc_render_multi_sampled": [vp, vp]}[name]
         assert fn(*args) == 1, name   # NULL scene
 
 
@@ -309,7 +297,7 @@ def test_libraries_without_the_entry_points_refuse(emu, orc):
 
 
 def test_exports_and_rust_mirror():
-    lib = C.CDLL(LIB)
+    lib = load(LIB)
     for name in ("rtc_render_sampled", "rtc_render_sampled_rgb8", "rtc_render_sampled_bands_device", "rtc_render_multi_sampled", "rtc_camera_rays"):
         assert hasattr(lib, name), name
     h = open(os.path.join(ROOT, "include", "rtc.h")).read()

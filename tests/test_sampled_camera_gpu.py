@@ -25,24 +25,6 @@ PATHS = ["1", "4"]
 vp = C.c_void_p
 
 
-def bind(lib):
-    lib.rtc_last_error.restype = C.c_char_p
-    lib.rtw_world_scene.restype, lib.rtw_world_scene.argtypes = vp, [vp, C.c_int]
-    cam, sp, st = C.POINTER(ff.RtcCamera), C.POINTER(SamplingC), C.POINTER(RtcStatsC)
-    for name, args in (("rtc_render", [vp, cam, C.c_int32, vp, C.c_uint64, C.c_uint64, vp, vp, st]),
-                       ("rtc_render_sampled", [vp, cam, sp, C.c_int32, vp, C.c_uint64, C.c_uint64, vp, st]),
-                       ("rtc_render_sampled_rgb8", [vp, cam, sp, C.c_int32, vp, st]),
-                       ("rtc_render_multi_sampled", [vp, cam, sp, C.c_int32, vp, st]),
-                       ("rtc_multi_create", [C.POINTER(ff.RtcSceneDesc), C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]),
-                       ("rtc_quantize", [vp, vp, C.c_uint64, vp])):
-        getattr(lib, name).restype = C.c_int
-        getattr(lib, name).argtypes = args
-    lib.rtc_multi_destroy.restype, lib.rtc_multi_destroy.argtypes = None, [vp]
-    lib.rtc_scene_path_info.restype = None
-    lib.rtc_scene_path_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    return lib
-
-
 def resized(cam, w, h):
     return Camera.new(w, h, cam.field_of_view, cam.transform_matrix)
 
@@ -154,7 +136,7 @@ def test_pixels_are_the_mean_of_their_rays(hip, path, name, monkeypatch):
 @pytest.mark.parametrize("path", PATHS)
 def test_one_centre_sample_is_rtc_render_and_counters(hip, path, monkeypatch):
     monkeypatch.setenv("RTC_KERNEL", path)
-    lib = bind(hip.lib)
+    lib = hip.lib
     cam, world = scenes.chapter11_glass_air_bubble(40, 24)
     nw = hip.build_world(world)
     scene = lib.rtw_world_scene(nw.handle, 0)
@@ -176,7 +158,7 @@ def test_one_centre_sample_is_rtc_render_and_counters(hip, path, monkeypatch):
 @pytest.mark.parametrize("path", PATHS)
 def test_chunks_change_no_bit(hip, path, monkeypatch):
     monkeypatch.setenv("RTC_KERNEL", path)
-    lib = bind(hip.lib)
+    lib = hip.lib
     cam, world = scenes.chapter11_glass_air_bubble(37, 19)
     nw = hip.build_world(world)
     scene = lib.rtw_world_scene(nw.handle, 0)
@@ -200,7 +182,7 @@ def test_chunks_change_no_bit(hip, path, monkeypatch):
 def test_partitions_and_layers_change_no_bit(hip, path, monkeypatch):
     import torch
     monkeypatch.setenv("RTC_KERNEL", path)
-    lib = bind(hip.lib)
+    lib = hip.lib
     world = mirror_world()
     cam = Camera.new(40, 24, 1.0, Camera.transform(Vector.point(0.0, 3.0, -7.0), Vector.point(0.0, 0.7, 0.0), Vector.vector(0.0, 1.0, 0.0)))
     sp = Sampling(side=2, jitter=True, seed=21, lens_radius=0.1, focal_distance=7.0)
@@ -274,7 +256,7 @@ def test_the_focal_plane_is_sharp(hip, path, monkeypatch):
 # ---- 7. path choice -----------------------------------------------------------------------------------------------------------------
 def test_sampled_row_launches_choose_their_path(hip, monkeypatch):
     monkeypatch.delenv("RTC_KERNEL", raising=False)
-    lib = bind(hip.lib)
+    lib = hip.lib
     cam, world = scenes.chapter11_glass_air_bubble(64, 32)
     nw = hip.build_world(world)
     scene = lib.rtw_world_scene(nw.handle, 0)

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import foreign_flattener as ff
+from raytracer_challenge_amd.cabi import load
 from raytracer_challenge_amd import scenes
 from raytracer_challenge_amd.backend import Backend, RtwError, SamplingC, ShutterC
 from raytracer_challenge_amd.image import Image
@@ -75,25 +76,10 @@ def deal(poses: np.ndarray, K: int):
     return order, offsets
 
 
-def bind(lib):
-    lib.rtc_last_error.restype = C.c_char_p
-    lib.rtc_shutter_deal.restype = C.c_int
-    lib.rtc_shutter_deal.argtypes = [vp, C.c_uint64, C.c_uint32, vp, vp, vp, C.c_uint64, C.c_uint64, vp, vp]
-    lib.rtc_render_shutter.restype = C.c_int
-    lib.rtc_render_shutter.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_int32, vp, C.c_uint64, C.c_uint64, vp, vp]
-    lib.rtc_render_shutter_rgb8.restype = C.c_int
-    lib.rtc_render_shutter_rgb8.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_int32, vp, vp]
-    lib.rtc_shutter_draw_pose.restype = C.c_uint32
-    lib.rtc_shutter_draw_pose.argtypes = [C.c_double, C.c_uint32]
-    return lib
-
-
 @pytest.fixture(scope="module")
 def host():
     """librtc_amd.so without a device: loading it and the host-only entry points need none."""
-    be = Backend(LIB)
-    bind(be.lib)
-    return be
+    return Backend(LIB)
 
 
 # ---- the rule ----------------------------------------------------------------------------------------------------------------------
@@ -237,7 +223,7 @@ def test_every_limit_through_c_without_a_device(host):
 
     # the render entry points: the shutter's own numbers before anything else, then the arrays; no device is touched
     cam = Camera.new(37, 19, 1.0, Matrix.id())
-    cams = (ff.RtcCamera * 3)(*[ff.make_camera(cam)] * 3)
+    cams = (ff.RtcCameraC * 3)(*[ff.make_camera(cam)] * 3)
     scenes_null = (vp * 3)()      # three NULL entries
     rgb = np.zeros((7, 3))
     rgb8 = np.zeros(703 * 3, dtype=np.uint8)
@@ -259,10 +245,10 @@ def test_every_limit_through_c_without_a_device(host):
     assert code == INVALID and b"NULL argument" in err
     code, err = render_code()
     assert code == INVALID and b"NULL scene" in err                                # NULL entries
-    odd = (ff.RtcCamera * 3)(ff.make_camera(cam), ff.make_camera(Camera.new(37, 20, 1.0, Matrix.id())), ff.make_camera(cam))
+    odd = (ff.RtcCameraC * 3)(ff.make_camera(cam), ff.make_camera(Camera.new(37, 20, 1.0, Matrix.id())), ff.make_camera(cam))
     code, err = render_code(cams_p=odd)
     assert code == INVALID and b"hsize or vsize differ" in err
-    odd = (ff.RtcCamera * 3)(ff.make_camera(cam), ff.make_camera(cam), ff.make_camera(Camera.new(36, 19, 1.0, Matrix.id())))
+    odd = (ff.RtcCameraC * 3)(ff.make_camera(cam), ff.make_camera(cam), ff.make_camera(Camera.new(36, 19, 1.0, Matrix.id())))
     code, err = render_code(cams_p=odd)
     assert code == INVALID and b"hsize or vsize differ" in err
     assert lib.rtc_render_shutter_rgb8(scenes_null, cams, 3, C.byref(ShutterC(1, 0)), C.byref(SamplingC(3, 0, 0, 0.0, 1.0)), 5, None, None) == INVALID
@@ -307,7 +293,7 @@ def test_libraries_without_the_entry_points_refuse(orc):
 
 
 def test_exports_and_mirrors():
-    lib = C.CDLL(LIB)
+    lib = load(LIB)
     names = ("rtc_render_shutter", "rtc_render_shutter_rgb8", "rtc_shutter_deal")
     for name in names + ("rtc_shutter_draw_pose",):
         assert hasattr(lib, name), name

@@ -12,25 +12,15 @@ import pytest
 import ext_cases
 from raytracer_challenge_amd import scenes
 from raytracer_challenge_amd.backend import HIT_DTYPE
-from raytracer_challenge_amd.device import RtcStatsC
+from raytracer_challenge_amd.device import RtcCameraC, RtcStatsC
 from raytracer_challenge_amd.image import Image
 from raytracer_challenge_amd.scene import Camera, Color, Element, Material, Matrix, Pattern, PointLight, Sampling, ShapeArgs, Shutter, Vector, World
 from test_sampled_camera_cpu import samples_mean
-from test_shutter_cpu import BIG_DEALS, FRAME, LIST7, big_deal_case, bind as bind_shutter, check_dealing_properties, poses_np, poses_of
+from test_shutter_cpu import BIG_DEALS, FRAME, LIST7, big_deal_case, check_dealing_properties, poses_np, poses_of
 
 pytestmark = pytest.mark.gpu
 PATHS = ["1", "4"]
 vp = C.c_void_p
-
-
-def bind(lib):
-    bind_shutter(lib)
-    lib.rtw_world_scene.restype, lib.rtw_world_scene.argtypes = vp, [vp, C.c_int]
-    lib.rtc_trace_rays.restype = C.c_int
-    lib.rtc_trace_rays.argtypes = [vp, vp, C.c_uint64, C.c_int32, vp, vp, C.POINTER(RtcStatsC)]
-    lib.rtc_quantize.restype = C.c_int
-    lib.rtc_quantize.argtypes = [vp, vp, C.c_uint64, vp]
-    return lib
 
 
 def bits(a):
@@ -166,7 +156,7 @@ def general(hip):
 @pytest.mark.parametrize("path", PATHS)
 def test_a_frame_is_the_mean_of_its_samples_each_in_its_pose(hip, path, monkeypatch):
     monkeypatch.setenv("RTC_KERNEL", path)
-    lib = bind(hip.lib)
+    lib = hip.lib
     cams, nws = general(hip)
     sp, sh = Sampling(side=3, jitter=True, seed=29), Shutter()
     pixels = np.arange(FRAME[0] * FRAME[1], dtype=np.uint64)
@@ -199,7 +189,7 @@ def test_a_frame_across_a_three_level_dealing(hip, path, monkeypatch):
     520 .. 1 031 -- gets its base from the third level, which no offset shows."""
     monkeypatch.setenv("RTC_KERNEL", path)
     monkeypatch.delenv("RTC_SAMPLED_MAX_RAYS", raising=False)
-    lib = bind(hip.lib)
+    lib = hip.lib
     W, H, K = 128, 129, 64
     cam, world = scenes.chapter11_glass_air_bubble(W, H)
     nw, twin = hip.build_world(world), hip.build_world(scenes.chapter11_glass_air_bubble(W, H)[1])
@@ -230,7 +220,7 @@ def test_a_frame_across_a_three_level_dealing(hip, path, monkeypatch):
 @pytest.mark.parametrize("path", PATHS)
 def test_chunks_quantiser_and_counters(hip, path, monkeypatch):
     monkeypatch.setenv("RTC_KERNEL", path)
-    lib = bind(hip.lib)
+    lib = hip.lib
     cams, nws = general(hip)
     sp, sh = Sampling(side=3, jitter=True, seed=29), Shutter()
     whole = hip.render_shutter(nws, cams, sp, sh, 5)
@@ -247,8 +237,7 @@ def test_chunks_quantiser_and_counters(hip, path, monkeypatch):
     assert st7.pixels == 7 and st7.rays_primary == 63
     # quantised on the device
     scene_p = (vp * 3)(*[lib.rtw_world_scene(nw.handle, 0) for nw in nws])
-    cams_c = ((C.c_double * 21) * 3)()
-    lib.rtw_make_camera.restype, lib.rtw_make_camera.argtypes = C.c_int, [vp, vp]
+    cams_c = (RtcCameraC * 3)()
     for p, cam in enumerate(cams):
         cc = hip.camera_c(cam)
         assert lib.rtw_make_camera(C.byref(cc), C.byref(cams_c[p])) == 0
@@ -283,7 +272,7 @@ def test_a_scene_with_every_extension_goes_through(hip, path, monkeypatch):
     for sh in (Shutter(), Shutter(hashed=False)):
         assert np.array_equal(bits(hip.render_shutter([nw, twin], [cam, cam], sp, sh, 5)), bits(want))
     # and over two different cameras it is the definition
-    lib = bind(hip.lib)
+    lib = hip.lib
     cam2 = Camera.new(24, 16, 1.0, Camera.transform(Vector.point(0.5, 2.6, -7.0), Vector.point(-0.2, 0.8, 0.0), Vector.vector(0.0, 1.0, 0.0)))
     got = hip.render_shutter([nw, twin], [cam, cam2], sp, Shutter(), 5)
     assert np.array_equal(bits(got), bits(expected_frame(hip, lib, [nw, twin], [cam, cam2], sp, Shutter(), 5, np.arange(24 * 16, dtype=np.uint64))))
@@ -324,7 +313,7 @@ def test_a_crossing_sphere_leaves_the_mean_of_its_still_frames(hip):
     worlds = [World([light], [Element.sphere(ShapeArgs(transform=Matrix.translation(-2.0 + 4.0 * p / (K - 1), 0.0, 0.0), material=white))]) for p in range(K)]
     nws = [hip.build_world(w) for w in worlds]
     sp = Sampling(side=4, jitter=True, seed=99)
-    lib = bind(hip.lib)
+    lib = hip.lib
     rays = hip.camera_rays(cam, sp)
     still = np.stack([trace(lib, nw, rays, 5)[:, 0].reshape(-1, N) for nw in nws])     # [K, pixels, N], channel 0
     still_frames = np.stack([hip.render_sampled(nw, cam, sp, 5)[:, 0] for nw in nws])

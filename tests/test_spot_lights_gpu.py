@@ -10,49 +10,23 @@ import numpy as np
 import pytest
 
 import foreign_flattener as ff
+from foreign_flattener import render_scene
 from raytracer_challenge_amd import scenes
-from raytracer_challenge_amd.device import RtcStatsC
 from raytracer_challenge_amd.image import Image
 from raytracer_challenge_amd.scene import (EPSILON, Adaptive, AreaLight, Camera, Color, Cone, Element, Filter, Material, Matrix, Pattern, PointLight, Sampling,
                                            ShapeArgs, SpotLight, Vector, World)
 from test_area_lights_cpu import sample_positions
-from test_spot_lights_cpu import (RtcLightCone, bind_spot, cone_c, lib_spot_factor, partition_classes, partition_fixture, partition_lights)
+from test_spot_lights_cpu import (RtcLightCone, cone_c, lib_spot_factor, partition_classes, partition_fixture, partition_lights)
 
 pytestmark = pytest.mark.gpu
 PATHS = ["1", "4"]
 vp = C.c_void_p
 DOWN = Vector.vector(0.0, -1.0, 0.0)
-HIT = [("t", "<f8"), ("prim", "<i4"), ("push_idx", "<i4")]
-
-
-def bind(lib):
-    bind_spot(lib)
-    for name, args in (("rtc_scene_create_ext", [C.POINTER(ff.RtcSceneDesc), vp, C.c_int, C.POINTER(vp)]),
-                       ("rtc_render", [vp, C.POINTER(ff.RtcCamera), C.c_int32, vp, C.c_uint64, C.c_uint64, vp, vp, C.POINTER(RtcStatsC)]),
-                       ("rtc_render_hit_digest", [vp, C.POINTER(ff.RtcCamera), C.c_int32, vp, C.c_uint64, C.c_uint64, vp]),
-                       ("rtc_render_multi", [vp, C.POINTER(ff.RtcCamera), C.c_int32, vp, C.POINTER(RtcStatsC)])):
-        getattr(lib, name).restype = C.c_int
-        getattr(lib, name).argtypes = args
-    lib.rtw_world_scene.restype, lib.rtw_world_scene.argtypes = vp, [vp, C.c_int]
-    lib.rtc_scene_destroy.restype, lib.rtc_scene_destroy.argtypes = None, [vp]
-    lib.rtc_multi_destroy.restype, lib.rtc_multi_destroy.argtypes = None, [vp]
-    return lib
-
-
-def render_scene(lib, scene, cam, fuel):
-    """(rgb, primary hits, hit-tree digests, stats) of an rtc_scene."""
-    rc = ff.make_camera(cam)
-    n = cam.hsize * cam.vsize
-    rgb, hits, dig = np.empty((n, 3)), np.empty(n, dtype=HIT), np.empty(n, dtype=np.uint64)
-    st = RtcStatsC()
-    assert lib.rtc_render(scene, C.byref(rc), fuel, None, 0, n, rgb.ctypes.data, hits.ctypes.data, C.byref(st)) == 0, lib.rtc_last_error()
-    assert lib.rtc_render_hit_digest(scene, C.byref(rc), fuel, None, 0, n, dig.ctypes.data) == 0, lib.rtc_last_error()
-    return rgb, hits, dig, st
 
 
 def render_world(hip, world, cam, fuel):
     """The same through the Python layer: SpotLight / AreaLight(cone=) -> rtw -> rtc_scene_create_ext2."""
-    lib = bind(hip.lib)
+    lib = hip.lib
     nw = hip.build_world(world)
     scene = lib.rtw_world_scene(nw.handle, 0)
     assert scene, hip._err()
@@ -152,7 +126,7 @@ def test_hard_edge_partitions_the_frame(hip, orc, path, monkeypatch):
 @pytest.mark.parametrize("path", PATHS)
 def test_smooth_band_against_the_oracle_ray_by_ray(hip, orc, path, monkeypatch):
     monkeypatch.setenv("RTC_KERNEL", path)
-    lib = bind(hip.lib)
+    lib = hip.lib
     mat = Material(pattern=Pattern.plain(Color(0.9, 0.8, 0.7)), ambient=0.1, diffuse=0.8, specular=0.0)
     els = [Element.plane(ShapeArgs(material=mat)), Element.sphere(ShapeArgs(transform=Matrix.translation(0.9, 1.5, 0.3) * Matrix.scaling(0.4, 0.4, 0.4)))]
     inten, pos, axis = Color(1.0, 0.9, 0.8), Vector.point(0.5, 4.0, -0.25), Vector.vector(0.2, -2.0, 0.1)
@@ -216,7 +190,7 @@ def spot_world():
 @pytest.mark.parametrize("path", PATHS)
 def test_create_ext2_multi_and_zero_cones(hip, path, monkeypatch):
     monkeypatch.setenv("RTC_KERNEL", path)
-    lib = bind(hip.lib)
+    lib = hip.lib
     cam, world = spot_world()
     want = render_world(hip, world, cam, 5)
     flat = ff.flatten(World([PointLight(l.intensity, l.origin) for l in world.lights], world.elements))

@@ -17,12 +17,10 @@ from raytracer_challenge_amd.scene import (AreaLight, Background, Color, Element
                                            World)
 from test_background_cpu import BG_CUBE, background_points
 from test_background_gpu import background_colors, render_world
-from test_sampled_camera_gpu import bind as bind_sampled, sampled
-from test_texture_filter_cpu import (LINEAR, LINEAR_KINDS, LINEAR_WRAP, LINEAR_WRAP_U, NEAREST, SIZES, SURFACES, SURFACE_FRAME, HostTexture, bind_sample,
-                                     floor_ties, linear, seeded, uv_set)
+from test_sampled_camera_gpu import sampled
+from test_texture_filter_cpu import (LINEAR, LINEAR_KINDS, LINEAR_WRAP, LINEAR_WRAP_U, NEAREST, SIZES, SURFACES, SURFACE_FRAME, HostTexture, floor_ties, linear, seeded, uv_set)
 from test_texture_map_cpu import near_threshold, uv_map
-from test_texture_map_gpu import (CASES, MAPS, T_PATTERN, RtcSceneExt, UvFlat, bind_ext, cam, flat_world, mapped, points, seeded_texture,
-                                  shading_world)
+from test_texture_map_gpu import (CASES, MAPS, T_PATTERN, RtcSceneExt, UvFlat, cam, flat_world, mapped, points, seeded_texture, shading_world)
 from wf_level_classes import trace_rays
 
 pytestmark = pytest.mark.gpu
@@ -37,7 +35,7 @@ def bits(a):
 
 def host_colours(lib, face, uv):
     """rtc_texture_sample of a UvPattern image record at each (u, v)."""
-    t = HostTexture(bind_sample(lib), face.texture.rgb)
+    t = HostTexture(lib, face.texture.rgb)
     code = face.kind_code()
     return np.array([t.sample(code, float(u), float(v)) for u, v in uv])
 
@@ -97,7 +95,7 @@ def test_skybox_faces_and_seams_are_rtc_texture_sample(hip):
     p = background_points(BG_CUBE, dirs)
     seen = set()
     want = np.empty_like(got)
-    samplers = [HostTexture(bind_sample(hip.lib), f.texture.rgb) for f in faces]
+    samplers = [HostTexture(hip.lib, f.texture.rgb) for f in faces]
     for i, q in enumerate(p):
         face, u, v = uv_map(MAPS["cube"], *identity_point(q))
         seen.add(face)
@@ -144,7 +142,7 @@ def test_linear_render_is_rtc_texture_sample_at_the_pattern_space_point(hip, orc
     pts, hit = points(hip, orc, shape, transform, T_PATTERN, c, path)
     faces = [linear(seeded_texture(11 + k), kind) for k in range(6 if mapping == "cube" else 1)]
     rgb, _ = hip.render(hip.build_world(flat_world(shape, transform, mapped(mapping, faces))), c, 5)
-    samplers = [HostTexture(bind_sample(hip.lib), f.texture.rgb) for f in faces]
+    samplers = [HostTexture(hip.lib, f.texture.rgb) for f in faces]
     want = np.zeros_like(pts)
     tie = np.zeros(len(pts), dtype=bool)
     uvs = {}
@@ -260,7 +258,7 @@ def linear_flatten(world):
 
 
 def test_linear_showcase_identical_everywhere(hip, monkeypatch):
-    lib = bind_sampled(bind_ext(hip.lib))
+    lib = hip.lib
     c, world = scenes.texture_showcase_linear(64, 48)
     near = scenes.texture_showcase(64, 48)[1]
     sp = Sampling(side=2, jitter=True, seed=9)
@@ -312,7 +310,7 @@ def test_linear_showcase_identical_everywhere(hip, monkeypatch):
 
 # ---- 5. creation on the device path -------------------------------------------------------------------------------------------------
 def test_creation_limits_and_device_bytes(hip):
-    lib = bm.bind(bind_ext(hip.lib))
+    lib = hip.lib
     tex = seeded_texture(3, 4, 3)
     world = flat_world("plane", Matrix.id(), Pattern.texture_map(Matrix.id(), "planar", UvPattern.image(tex)))
 

@@ -10,6 +10,7 @@ import pytest
 
 from raytracer_challenge_amd import Texture, UvPattern, read_ppm
 from raytracer_challenge_amd.backend import RtwError, _UvFaceC
+from raytracer_challenge_amd.cabi import RtcSceneDesc
 from raytracer_challenge_amd.image import ppm_text
 from raytracer_challenge_amd.scene import Color, Element, Material, Matrix, Pattern, PointLight, ShapeArgs, Vector, World
 from test_shim_layout import c_struct, rust_struct
@@ -339,14 +340,10 @@ def test_emulator_loads_and_names_the_missing_entry_point():
 def test_flatten_helpers_refuse_uv_worlds(lib):
     from raytracer_challenge_amd import hip_backend
     nw = hip_backend().build_world(uv_world())
-    lib.rtw_world_flatten_counts.restype = C.c_int
-    lib.rtw_world_flatten_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     counts = (C.c_uint32 * 8)()
     assert lib.rtw_world_flatten_counts(nw.handle, counts) != 0
     assert "texture-mapped" in lib.rtw_last_error().decode()
-    lib.rtw_world_flatten_desc.restype = C.c_int
-    lib.rtw_world_flatten_desc.argtypes = [C.c_void_p, C.c_void_p]
-    desc = (C.c_char * 512)()
+    desc = RtcSceneDesc()
     assert lib.rtw_world_flatten_desc(nw.handle, desc) != 0
     assert "texture-mapped" in lib.rtw_last_error().decode()
 

@@ -10,11 +10,12 @@ import pytest
 
 import foreign_flattener as ff
 from parity import assert_parity, oracle_reference
+from raytracer_challenge_amd.cabi import RtcSceneExt, RtcTexture, RtcUvPattern
 from raytracer_challenge_amd import Texture, UvPattern, scenes
 from raytracer_challenge_amd.image import Image
 from raytracer_challenge_amd.scene import (AreaLight, Camera, Color, Element, GroupKind, Material, Matrix, Noise, Pattern, PointLight,
                                            ShapeArgs, Vector, World)
-from test_area_lights_gpu import RtcLightEx, bind, ex_lights, render_scene
+from test_area_lights_gpu import ex_lights, render_scene
 from test_texture_map_cpu import near_threshold, uv_map, uv_select
 
 pytestmark = pytest.mark.gpu
@@ -22,28 +23,6 @@ PATHS = ["1", "4"]
 vp = C.c_void_p
 MAPS = {"planar": 0, "spherical": 1, "cylindrical": 2, "cube": 3}
 KINDS = {"checkers": 0, "align_check": 1, "image": 2}
-
-
-class RtcUvPattern(C.Structure):
-    _fields_ = [("kind", C.c_int32), ("texture", C.c_int32), ("width", C.c_double), ("height", C.c_double), ("child", C.c_int32 * 5), ("_pad", C.c_int32)]
-
-
-class RtcTexture(C.Structure):
-    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("rgb", C.c_void_p)]
-
-
-class RtcSceneExt(C.Structure):
-    _fields_ = [("n_lights", C.c_uint32), ("lights", C.POINTER(RtcLightEx)), ("n_uv_patterns", C.c_uint32), ("uv_patterns", C.POINTER(RtcUvPattern)),
-                ("n_textures", C.c_uint32), ("textures", C.POINTER(RtcTexture))]
-
-
-def bind_ext(lib):
-    bind(lib)
-    lib.rtc_scene_create_ext.restype = C.c_int
-    lib.rtc_scene_create_ext.argtypes = [C.POINTER(ff.RtcSceneDesc), C.POINTER(RtcSceneExt), C.c_int, C.POINTER(vp)]
-    lib.rtc_multi_create_ext.restype = C.c_int
-    lib.rtc_multi_create_ext.argtypes = [C.POINTER(ff.RtcSceneDesc), C.POINTER(RtcSceneExt), C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
-    return lib
 
 
 class UvFlat(ff.Flat):
@@ -274,7 +253,7 @@ def test_one_colour_textures_shade_like_plain(hip, orc, path, monkeypatch):
 
 # ---- 5. entry points and paths ------------------------------------------------------------------------------------------------------
 def test_showcase_1080p_identical_everywhere(hip, monkeypatch):
-    lib = bind_ext(hip.lib)
+    lib = hip.lib
     c, world = scenes.texture_showcase(1920, 1080)
     frames = []
     for path in PATHS:
@@ -311,7 +290,7 @@ def test_showcase_1080p_identical_everywhere(hip, monkeypatch):
 @pytest.mark.parametrize("path", PATHS)
 def test_create_ext_without_uv_is_create(hip, path, monkeypatch):
     monkeypatch.setenv("RTC_KERNEL", path)
-    lib = bind_ext(hip.lib)
+    lib = hip.lib
     for name in ("chapter11_title", "chapter14_hexagon"):
         c, world = getattr(scenes, name)(160, 90)
         flat = ff.flatten(world)
@@ -341,7 +320,7 @@ def test_create_ext_without_uv_is_create(hip, path, monkeypatch):
 
 # ---- 6. validation ------------------------------------------------------------------------------------------------------------------
 def test_texture_validation(hip):
-    lib = bind_ext(hip.lib)
+    lib = hip.lib
     P = Pattern.plain
     tex = seeded_texture(3, 4, 3)
     faces = [UvPattern.checkers(2, 2, P(Color.white()), P(Color.black()))] * 3 + [UvPattern.image(tex)] * 3

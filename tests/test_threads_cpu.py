@@ -8,6 +8,7 @@ import threading
 
 import create_cases as cc
 import foreign_flattener as ff
+from raytracer_challenge_amd.cabi import load
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "raytracer_challenge_amd", "csrc", "librtc_amd.so")
@@ -16,19 +17,8 @@ JOIN_S = 60.0
 
 
 def bound():
-    lib = cc.bind(C.CDLL(LIB))   # (a CDLL call releases the GIL: the two threads are inside the library at the same time)
+    lib = load(LIB)   # (a CDLL call releases the GIL: the two threads are inside the library at the same time)
     vp, d = C.c_void_p, C.c_double
-    lib.rtw_last_error.restype = C.c_char_p
-    lib.rtw_pattern_plain.restype, lib.rtw_pattern_plain.argtypes = vp, [d, d, d]
-    lib.rtw_pattern_jitter.restype, lib.rtw_pattern_jitter.argtypes = vp, [C.c_int, C.c_int, d, C.c_uint64, vp]
-    lib.rtw_pattern_mixture.restype, lib.rtw_pattern_mixture.argtypes = vp, [C.c_int, vp, vp, vp]
-    lib.rtw_pattern_release.restype, lib.rtw_pattern_release.argtypes = None, [vp]
-    lib.rtw_texture_create.restype, lib.rtw_texture_create.argtypes = vp, [C.c_uint32, C.c_uint32, vp]
-    lib.rtw_world_create.restype, lib.rtw_world_create.argtypes = vp, []
-    lib.rtw_world_add_element.restype, lib.rtw_world_add_element.argtypes = C.c_int, [vp, vp]
-    lib.rtw_world_release.restype, lib.rtw_world_release.argtypes = None, [vp]
-    lib.rtc_band_rows_owned.restype, lib.rtc_band_rows_owned.argtypes = C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]
-    lib.rtc_background_point.restype, lib.rtc_background_point.argtypes = C.c_int, [C.c_int32, vp, vp]
     return lib
 
 

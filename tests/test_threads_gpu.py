@@ -299,7 +299,6 @@ def test_creation_and_destruction_beside_rendering(hip, tmp_path_factory):
     ends in (1, 4), and the device's live-scene count is back where it started.  MI355X: under 0.1 s."""
     tmp = tmp_path_factory.mktemp("threads")
     lib = hip.lib
-    lib.rtc_scene_bvh_built_on_device.restype, lib.rtc_scene_bvh_built_on_device.argtypes = C.c_int, [C.c_void_p]
     with bm.environment(RTC_KERNEL=None, RTC_NO_KOPS=None, RTC_KOPS_GROUPS=None, RTC_WF_LDS=None, RTC_FIRST_GUESS=None, RTC_DEVICE_BVH=None, RTC_DEVICE_BVH_MIN="64"):
         small, large = bm.camera(), bm.camera(h=192, v=128)
         jobs = [  # (label, camera(s), world, built on the device)
@@ -377,7 +376,7 @@ def chunked_jobs(hip):
     """[(name, call)]: one chunked entry point each on scenes of its own; call() makes the C call into fresh numpy buffers and returns
     {pixels, rays_primary, ...}.  Everything a call needs is made here, on the calling thread."""
     from test_filter_gpu import MITCHELL_CASE
-    sl, al, fl, hl = hip._sampled_lib(), hip._adaptive_lib(), hip._filter_lib(), hip._shutter_lib()
+    sl = al = fl = hl = hip.lib
     keep, jobs = [], []
 
     def scene(world):
@@ -387,46 +386,46 @@ def chunked_jobs(hip):
 
     def sampled():
         cam, world = scenes.chapter11_glass_air_bubble(37, 19)
-        s, rc, sp, n = scene(world), hip._rtc_camera(sl, cam), SamplingC.of(Sampling(side=3, jitter=True, seed=5)), 37 * 19
+        s, rc, sp, n = scene(world), hip._rtc_camera(cam), SamplingC.of(Sampling(side=3, jitter=True, seed=5)), 37 * 19
 
         def call():
             rgb, st = np.full((n, 3), np.nan), RtcStatsC()
-            ok(sl, sl.rtc_render_sampled(s, C.byref(rc), C.byref(sp), 5, None, 0, n, rgb.ctypes.data, C.addressof(st)))
+            ok(sl, sl.rtc_render_sampled(s, C.byref(rc), C.byref(sp), 5, None, 0, n, rgb.ctypes.data, C.byref(st)))
             return {"rgb": rgb, "rays_primary": int(st.rays_primary)}
         return call
 
     def filtered(name, size, sampling, flt):
         cam, world = getattr(scenes, name)(*size)
-        s, rc, sp, fc, n = scene(world), hip._rtc_camera(fl, cam), SamplingC.of(sampling), FilterC.of(flt), size[0] * size[1]
+        s, rc, sp, fc, n = scene(world), hip._rtc_camera(cam), SamplingC.of(sampling), FilterC.of(flt), size[0] * size[1]
 
         def call():
             rgb, st = np.full((n, 3), np.nan), RtcStatsC()
-            ok(fl, fl.rtc_render_filtered(s, C.byref(rc), C.byref(sp), C.byref(fc), 5, 0, size[1], rgb.ctypes.data, C.addressof(st)))
+            ok(fl, fl.rtc_render_filtered(s, C.byref(rc), C.byref(sp), C.byref(fc), 5, 0, size[1], rgb.ctypes.data, C.byref(st)))
             return {"rgb": rgb, "rays_primary": int(st.rays_primary)}
         return call
 
     def adaptive():
         cam, world = scenes.texture_showcase(24, 16)   # (test_adaptive_gpu.KINDS: flat regions and edges at this threshold)
         ad = AdaptiveC.of(Adaptive(Sampling(), Sampling(side=3, jitter=True, seed=6), 0.3, 8))
-        s, rc, n = scene(world), hip._rtc_camera(al, cam), 24 * 16
+        s, rc, n = scene(world), hip._rtc_camera(cam), 24 * 16
 
         def call():
             rgb, mask, n_ref, st = np.full((n, 3), np.nan), np.full(n, 7, dtype=np.uint8), C.c_uint64(1 << 63), RtcStatsC()
-            ok(al, al.rtc_render_adaptive(s, C.byref(rc), C.byref(ad), 5, rgb.ctypes.data, mask.ctypes.data, C.byref(n_ref), C.addressof(st)))
+            ok(al, al.rtc_render_adaptive(s, C.byref(rc), C.byref(ad), 5, rgb.ctypes.data, mask.ctypes.data, C.byref(n_ref), C.byref(st)))
             return {"rgb": rgb, "mask": mask, "n_refined": int(n_ref.value), "rays_primary": int(st.rays_primary)}
         return call
 
     def shutter():
         poses = scenes.motion_showcase(37, 19, 3)
         K, n = len(poses), 37 * 19
-        ss, cams = (C.c_void_p * K)(*[scene(w) for _, w in poses]), ((C.c_double * 21) * K)()
+        ss, cams = (C.c_void_p * K)(*[scene(w) for _, w in poses]), (RtcCameraC * K)()
         for p, (cam, _) in enumerate(poses):
-            cams[p] = hip._rtc_camera(hl, cam)
+            cams[p] = hip._rtc_camera(cam)
         sp, sh = SamplingC.of(Sampling(side=3, jitter=True, seed=29)), ShutterC.of(Shutter())
 
         def call():
             rgb, st = np.full((n, 3), np.nan), RtcStatsC()
-            ok(hl, hl.rtc_render_shutter(ss, cams, K, C.byref(sh), C.byref(sp), 5, None, 0, n, rgb.ctypes.data, C.addressof(st)))
+            ok(hl, hl.rtc_render_shutter(ss, cams, K, C.byref(sh), C.byref(sp), 5, None, 0, n, rgb.ctypes.data, C.byref(st)))
             return {"rgb": rgb, "rays_primary": int(st.rays_primary)}
         return call
 
@@ -470,11 +469,8 @@ def test_rtc_multi_beside_plain_scenes(hip, tmp_path_factory):
     multiple of the band); two threads render scenes of their own.  The multi frame is the one-device frame of the same descriptor, as
     in test_cabi_desc.test_hip_render_multi_random_partitions.  MI355X: 0.1 s."""
     tmp = tmp_path_factory.mktemp("threads")
-    lib = cc.bind(hip.lib)
+    lib = hip.lib
     vp = C.c_void_p
-    lib.rtc_render_multi.restype, lib.rtc_render_multi.argtypes = C.c_int, [vp, vp, C.c_int32, vp, vp]
-    lib.rtc_render_multi_rgb8.restype, lib.rtc_render_multi_rgb8.argtypes = C.c_int, [vp, vp, C.c_int32, vp, vp]
-    lib.rtc_multi_set_band_rows.restype, lib.rtc_multi_set_band_rows.argtypes = C.c_int, [vp, C.c_uint32]
     with bm.switched("default", 4):
         others = [Owned(hip, tmp, "ops12"), Owned(hip, tmp, "csg")]
         cam0, world = cases.SMALL_CASES["nested_glass"]()
@@ -523,8 +519,7 @@ def test_errors_belong_to_the_calling_thread(hip, tmp_path_factory):
     twelve times: rtc_last_error() returns B's text after every frame, never A's, and the frames are B's solo frames.  (The CPU twin,
     test_threads_cpu.py, fails with `thread_local` taken off the error strings.)  MI355X: under 0.1 s."""
     tmp = tmp_path_factory.mktemp("threads")
-    lib = hip._filter_lib()
-    hip._sampled_lib()
+    lib = hip.lib
     with bm.switched("default", 1):
         a, b = Owned(hip, tmp, "csg"), Owned(hip, tmp, "planes7")
     try:
@@ -534,7 +529,7 @@ def test_errors_belong_to_the_calling_thread(hip, tmp_path_factory):
         A_CALLS = 1000 * ROUNDS   # (a refusal takes microseconds: this many last as long as B's frames do)
         n = a.cam.hsize * a.cam.vsize
         a_scene, b_scene = bm.scene_of(hip, a.nw), bm.scene_of(hip, b.nw)
-        a_cam, b_cam = hip._rtc_camera(lib, a.cam), hip._rtc_camera(lib, b.cam)
+        a_cam, b_cam = hip._rtc_camera(a.cam), hip._rtc_camera(b.cam)
         sp, zero, box = SamplingC.of(Sampling(side=2)), SamplingC.of(Sampling(side=1)), FilterC.of(Filter.tent(1.5))
         zero.side = 0
         b_solo = hip.render(b.nw, b.cam, FUEL)
@@ -542,7 +537,7 @@ def test_errors_belong_to_the_calling_thread(hip, tmp_path_factory):
 
         def a_body(out):
             rgb = np.empty((n, 3))
-            rc_cam = C.cast(a_cam, C.POINTER(RtcCameraC))
+            rc_cam = C.pointer(a_cam)
             for i in range(A_CALLS):
                 if i % 3 == 0:
                     code, want = lib.rtc_render(a_scene, rc_cam, 17, None, 0, n, rgb.ctypes.data, None, None), (2, FUEL_TEXT)

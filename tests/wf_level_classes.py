@@ -21,12 +21,11 @@ import numpy as np
 import wf_shade_queues as q
 from parity import assert_parity
 from raytracer_challenge_amd import scenes
-from raytracer_challenge_amd.device import RtcStatsC
+from raytracer_challenge_amd.cabi import HIT_DTYPE, RtcStatsC
 from raytracer_challenge_amd.scene import Camera, Color, Element, Material, Matrix, Pattern, PointLight, ShapeArgs, Vector, World
 
 CAMERAS = q.CAMERAS
 FUELS = (0, 1, 2, 5, 16)
-HIT = [("t", "<f8"), ("prim", "<i4"), ("push_idx", "<i4")]
 
 
 def _base():
@@ -131,17 +130,13 @@ def trace_rays(backend, world, rays, fuel, path, monkeypatch):
     """(rgb, hits, stats, the scene's error state afterwards) of include/rtc.h rtc_trace_rays on device path `path`, a fresh scene."""
     lib = backend.lib
     vp = C.c_void_p
-    lib.rtw_world_scene.restype, lib.rtw_world_scene.argtypes = vp, [vp, C.c_int]
-    lib.rtc_trace_rays.restype, lib.rtc_trace_rays.argtypes = C.c_int, [vp, vp, C.c_uint64, C.c_int32, vp, vp, C.POINTER(RtcStatsC)]
-    lib.rtc_scene_check.restype, lib.rtc_scene_check.argtypes = C.c_int, [vp]
-    lib.rtc_last_error.restype = C.c_char_p
     monkeypatch.setenv("RTC_KERNEL", path)
     nw = backend.build_world(world)
     scene = lib.rtw_world_scene(nw.handle, 0)
     assert scene, backend._err()
     rays = np.ascontiguousarray(rays, dtype=np.float64)
     n = len(rays)
-    rgb, hits, st = np.empty((n, 3)), np.empty(n, dtype=HIT), RtcStatsC()
+    rgb, hits, st = np.empty((n, 3)), np.empty(n, dtype=HIT_DTYPE), RtcStatsC()
     assert lib.rtc_trace_rays(scene, rays.ctypes.data, n, fuel, rgb.ctypes.data, hits.ctypes.data, C.byref(st)) == 0, lib.rtc_last_error()
     check = lib.rtc_scene_check(scene)
     out = (rgb.copy(), hits.copy(), st.as_dict(), check)
